@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — GANMF training steps/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -25,19 +25,24 @@ replicated tensors are reduce-scattered over RCCL every step (Adam on the rank's
 all-gathered: DESIGN.md section 6); `value` counts the 128-row minibatch
 updates all ranks processed per second (= N x synchronous global steps/s).
 
-Protocol: W untimed warm-up steps, then the K-step region FIVE times; every repeat is exactly K steps between a
-barrier + synchronize on both sides and is timed by hipEvents on the library's own stream (ganmf_stream_timer) and by the host's
-wall clock.  `value` = N * K / the MEDIAN event time (MAX over ranks per repeat); `timing` carries all five samples, their spread,
-the wall-clock median and the per-call overhead.  With --gpus N > 1 (or GANMF_BENCH_FORCE_COMM=1 on one GPU) the line also carries
-`parallelism` (per replicated tensor: collective time and exposed join-wait time per step; RCCL's own world size; rows/s) and
-`configs3_sharded` (BASELINE.json configs[3]: one 25 000 x 50 000 shard per rank at emb_dim 32 and 1024, same protocol).
+Protocol: W untimed warm-up steps, then ONE timed region of exactly K steps between a barrier + synchronize on both sides, timed by
+hipEvents on the library's own stream (ganmf_stream_timer) and by the host's wall clock.  `value` = N * K / its event time (MAX over
+ranks), `ms_per_step` = event time / K.  That is all a plain run measures.  --dump-outputs DIR then writes what the timed steps
+returned and left behind (per-update losses, every parameter tensor) as float32 DIR/<name>.npy; inputs are seeded, so two builds
+compare output for output.
 
-SURVEY 8(d)'s full report: the reference runs its discriminator passes and its generator passes as separate loops (GANRec/GANMF.py:176-189
+--full adds everything below, measured after the timed region.  SURVEY 8(d): the K-step region four more times, `timing` carrying all
+five samples, their median and spread, the wall-clock median and the per-call overhead.  With --gpus N > 1 (or
+GANMF_BENCH_FORCE_COMM=1 on one GPU) the line also carries `parallelism` (per replicated tensor: collective time and exposed join-wait
+time per step; RCCL's own world size; rows/s; the replica check) and `configs3_sharded` (BASELINE.json configs[3]: one 25 000 x 50 000
+shard per rank at emb_dim 32 and 1024, same protocol).
+
+SURVEY 8(d)'s full report (--full): the reference runs its discriminator passes and its generator passes as separate loops (GANRec/GANMF.py:176-189
 vs 191-203), so beside `value` (whole-epoch steps/s: D and G passes as fit() issues them) the line carries `d_steps_per_s` and `g_steps_per_s`
 (D-only / G-only ganmf_train_epoch calls over the same slices, event-timed, median of five, right after the timed region) and
 `cpu_baseline.value_1thread` beside the all-threads figure.
 
-Extra objects on the JSON line: `roofline` (dominant DEVICE FUNCTION of the step = gemm_bf16k_mfma<false, true, 3, false>, the 16-wave split-bf16 GEMM of
+Extra objects on the --full JSON line: `roofline` (dominant DEVICE FUNCTION of the step = gemm_bf16k_mfma<false, true, 3, false>, the 16-wave split-bf16 GEMM of
 gemm_bf16k.hpp with a K-major B -- fp32 in, fp32-accurate, priced against the fp32 MFMA peak -- over ALL of its launch classes: `frac` = sum of
 algorithmic FLOPs / sum of launch durations; `frac_best_class` = its best class alone); `roofline_fused_adam` = the HBM-bound launch of the two fused-Adam weight-gradient GEMMs; HIP-event timed on the
 library's stream in a profiled repeat of the same steps (at least 96) right after the timed region — events
@@ -69,17 +74,29 @@ C2 = dict(U=6040, N=3706, k=250, e=992, B=128, density=0.035,
 def run_steps(eng, perm, B, n_steps):
     """EXACTLY n_steps updates: ceil(n/2) D updates and floor(n/2) G updates, in chunks of full batches -- each chunk one
     ganmf_train_epoch call of c D updates followed by c G updates over the same slices (the call fit() makes); an odd
-    n_steps ends with one call that runs a single D update (d_steps=1, g_steps=0)."""
+    n_steps ends with one call that runs a single D update (d_steps=1, g_steps=0).  Returns what the calls returned: the
+    (D losses, G losses) pair of every call, in order."""
     per_call = (len(perm) // B)
     half = n_steps // 2
     done = 0
+    losses = []
     while done < half:
         c = min(per_call, half - done)
-        eng.train_epoch(perm[:c * B], 1, 1)
+        losses.append(eng.train_epoch(perm[:c * B], 1, 1))
         done += c
     if n_steps % 2:
-        eng.train_epoch(perm[:B], 1, 0)
-    return n_steps
+        losses.append(eng.train_epoch(perm[:B], 1, 0))
+    return losses
+
+
+def dump_outputs(path, eng, losses):
+    """--dump-outputs: what the timed path handed its caller, as float32 .npy files -- the per-update losses of the last timed region
+    (d_loss, g_loss: one value per D / G update, in order) and every parameter tensor after its last step (39 MB at configs[1])."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "d_loss.npy"), np.concatenate([d for d, _ in losses]).astype(np.float32))
+    np.save(os.path.join(path, "g_loss.npy"), np.concatenate([g for _, g in losses] + [np.zeros(0, np.float32)]).astype(np.float32))
+    for name, tid in (("We", 0), ("be", 1), ("Wd", 2), ("bd", 3), ("U", 100), ("V", 101)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(eng.get_tensor(tid), dtype=np.float32))
 
 
 def run_pass_steps(eng, perm, B, n_steps, kind):
@@ -404,10 +421,14 @@ def extra_workload(w, e, world, rank, local_rank, steps, warmup, sync, torch, di
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)      # (>= 200 timed steps, median of five repeats)
+    ap.add_argument("--steps", type=int, default=200)      # (>= 200 timed steps; --full: median of five repeats)
     ap.add_argument("--warmup", type=int, default=96)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the repeats, the D / G pass rates, roofline and kernel tables, the scoring GEMM, the CPU "
+                         "baseline and, data-parallel, the collectives, the replica check and configs[3]")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the losses and parameters of the timed steps to DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0)      # (--full)
+    ap.add_argument("--no-cpu-baseline", action="store_true")      # (--full)
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -476,7 +497,8 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- side measurement first: the generator / scoring GEMM (every rank runs it, rank 0 reports it).  ~20 ms of sustained GPU
+    # ---- side measurement first: the generator / scoring GEMM (every rank runs it, rank 0 reports it under --full; a plain run makes the
+    # same launches as its pre-heat only).  ~20 ms of sustained GPU
     # work right before the warm-up: the timed region then starts at the clocks a training run holds -- a short K would
     # otherwise be timed on the power-management ramp of a GPU that has just been handed its first kernels (20 steps: 2.83 ms
     # cold against 2.66 ms after 96 warm-up steps and 2.60 ms in a tight loop, tools/epoch_overhead.py)
@@ -523,19 +545,20 @@ def main():
     perm = np.random.RandomState(1337 + rank).permutation(w["U"]).astype(np.int32)
     if warmup:
         run_steps(eng, perm, w["B"], warmup)
-    # ---- the timed region, REPEATS times (hipEvent timing, median of 5).  Every repeat is EXACTLY `steps` steps,
-    # bracketed by the barrier + synchronize the contract asks for; its duration is read twice: hipEvents on the library's own
-    # stream (the time the device spent on the K steps, host gaps between the blocking ganmf_train_epoch calls included) and the
-    # host's wall clock around the same calls.  `value` is formed from the MEDIAN event time (MAX over ranks per repeat);
-    # the wall-clock median and the difference per call (launch + drain latency of a blocking call) are reported beside it.
+    # ---- the timed region: EXACTLY `steps` steps, bracketed by the barrier + synchronize the contract asks for; its duration is read
+    # twice: hipEvents on the library's own stream (the time the device spent on the K steps, host gaps between the blocking
+    # ganmf_train_epoch calls included) and the host's wall clock around the same calls.  `value` and `ms_per_step` are formed from
+    # the event time of the first region (MAX over ranks); --full times REPEATS - 1 more regions right after it (median
+    # of 5) and reports their samples, spread and median in `timing`, with the wall clock and the difference per call (launch + drain
+    # latency of a blocking call).
     calls_per_repeat = (steps // 2 + (len(perm) // w["B"]) - 1) // max(len(perm) // w["B"], 1) + (steps % 2)
-    ev_s, wall_s = [], []
     done = steps
-    for _ in range(REPEATS):
+
+    def timed_region():
         sync()
         t0 = time.perf_counter()
         eng.timer_start()
-        done = run_steps(eng, perm, w["B"], steps)      # blocking: returns after the stream drained
+        losses = run_steps(eng, perm, w["B"], steps)      # blocking: returns after the stream drained
         ev = eng.timer_stop() * 1e-3
         sync()
         wl = time.perf_counter() - t0
@@ -543,57 +566,87 @@ def main():
             t = torch.tensor([ev, wl], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             ev, wl = float(t[0].item()), float(t[1].item())
-        ev_s.append(ev)
-        wall_s.append(wl)
-    el = float(np.median(ev_s))
-    timing = {"repeats": REPEATS, "clock": "hipEvents on the library's stream around the K steps (median; MAX over ranks per repeat)",
-              "value_samples": [round(world * done / t, 2) for t in ev_s],
-              "value_spread": round((max(ev_s) - min(ev_s)) / el, 4),
-              "value_wall_clock_median": round(world * done / float(np.median(wall_s)), 2),
+        return ev, wl, losses
+    el, wall, losses = timed_region()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, losses)
+    ev_s, wall_s = [el], [wall]
+    if args.full:
+        for _ in range(REPEATS - 1):
+            ev, wl, _ = timed_region()
+            ev_s.append(ev)
+            wall_s.append(wl)
+    timing = {"repeats": len(ev_s), "clock": "hipEvents on the library's stream around the K steps (MAX over ranks per repeat); "
+                                             "`value` = the first repeat",
+              "value_wall_clock": round(world * done / wall, 2),
               "calls_per_repeat": int(max(calls_per_repeat, 1)),
               "per_call_overhead_us": round(float(np.median(np.array(wall_s) - np.array(ev_s))) / max(calls_per_repeat, 1) * 1e6, 1)}
+    if args.full:
+        med = float(np.median(ev_s))
+        timing.update({"value_samples": [round(world * done / t, 2) for t in ev_s], "value_median": round(world * done / med, 2),
+                       "value_spread": round((max(ev_s) - min(ev_s)) / med, 4),
+                       "value_wall_clock_median": round(world * done / float(np.median(wall_s)), 2)})
 
     if e32 is not None:
         e32.close()
-    # ---- profiled repeat (HIP events around every launch, on the library's stream) --------------
-    # ---- the two passes timed apart (D-steps/s, G-steps/s beside the whole-epoch rate): K/2 updates of one kind per repeat, as calls of
-    # their own over the same slices, same clock and protocol as the timed region
-    # (at least one whole pass over the shard per repeat, as the reference's loops run them: a 10-update call would mostly time its own set-up)
-    half = max(steps // 2, len(perm) // w["B"], 1)
-    split_rate, split_samples = {}, {}
-    for kind in ("D", "G"):
-        evs = []
-        for _ in range(REPEATS):
-            sync()
-            eng.timer_start()
-            run_pass_steps(eng, perm, w["B"], half, kind)
-            ev = eng.timer_stop() * 1e-3
-            sync()
-            if world > 1:
-                t = torch.tensor([ev], dtype=torch.float64)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                ev = float(t.item())
-            evs.append(ev)
-        split_rate[kind] = world * half / float(np.median(evs))
-        split_samples[kind] = [round(world * half / t, 2) for t in evs]
-    # ---- profiled repeats (HIP events around every launch, on the library's stream), D passes and G passes apart so that a launch class is a
-    # (step kind, class) pair -- the discriminator step's decode and the generator step's are different kernels
-    prof_steps = max(steps, 96) // 2      # (at least 48 launches per class: a short K alone averages over too few)
-    eng.profile(True)
-    run_pass_steps(eng, perm, w["B"], prof_steps, "D")
-    prof_d = eng.profile_read()
-    eng.profile(True)                     # (clears the records)
-    run_pass_steps(eng, perm, w["B"], prof_steps, "G")
-    prof_g = eng.profile_read()
-    eng.profile(False)
-    prof = prof_d + prof_g
-
-    # ---- data-parallel runs verify themselves: replicas bitwise equal after all of the above, RCCL's world = the launcher's ----
-    check = replica_check(eng, world, dist) if (world > 1 or force_comm) else None
-    failed_checks = [] if check is None or replicas_ok(check) else ["configs[1]"]
-
     out = None
     if rank == 0:
+        out = {
+            "metric": "GANMF training steps/sec", "value": round(world * done / el, 2), "unit": "steps/s",
+            "n_gpus": world, "steps": done, "warmup": warmup, "ms_per_step": round(el / done * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "GANMF --user, MovieLens-1M shape %dx%d per GPU, k=%d, emb_dim=%d, batch=%d/GPU, "
+                                   "tuned hyper-parameters (BASELINE.json configs[1])" % (w["U"], w["N"], w["k"], w["e"], w["B"]),
+                       "step": "one 128-row minibatch update (D or G), K/2 D then K/2 G",
+                       "arithmetic": "float32 tensors throughout; the K loops of the step's GEMMs run the fp32-accurate split-bf16 loop "
+                                     "(3 exact bf16 pieces per operand, 6 piece products on v_mfma_f32_32x32x16_bf16, fp32 accumulate) in "
+                                     "16-wave workgroups (gemm_bf16k.hpp) or, for the two fused-Adam weight-gradient GEMMs, 4-wave "
+                                     "workgroups; gUb + gV on the fp32 MFMA",
+                       "launches": "D-step 6, G-step 8, plus per pass: two launches in front of a discriminator pass (the CSR rows of all its full minibatches -- that launch also writes lr_t of every step of the pass -- and their generated rows: the generator is frozen during the pass) and two around a generator pass (the embeddings of the scheduled rows advanced to their step, ONE all-rows Adam over U behind the pass instead of one per step: with g_reg = 0 a row is read once and has a gradient once per pass) (dE + d_coef, gWd + gWe, gUb + gV share a launch; the generator step: generator GEMM + CSR rows, encode, its slab sum, decode on 64 x 32 tiles unsplit, dE, its slab sum, dF unsplit, gUb + gV)",
+                       "global_steps_per_s": round(done / el, 2), "rows_per_s": round(world * done * w["B"] / el, 1),
+                       "parallelism": "dp%d (users sharded row-wise; RCCL reduce-scatter of the D and V gradients, Adam on the rank's "
+                                      "slice, all-gather of the parameters)" % world},
+            "timing": timing, "reference_derived_steps_per_s": 84.0,
+        }
+    failed_checks = []
+    if args.full:
+        # ---- the two passes timed apart (D-steps/s, G-steps/s beside the whole-epoch rate): K/2 updates of one kind per repeat, as calls of
+        # their own over the same slices, same clock and protocol as the timed region
+        # (at least one whole pass over the shard per repeat, as the reference's loops run them: a 10-update call would mostly time its own set-up)
+        half = max(steps // 2, len(perm) // w["B"], 1)
+        split_rate, split_samples = {}, {}
+        for kind in ("D", "G"):
+            evs = []
+            for _ in range(REPEATS):
+                sync()
+                eng.timer_start()
+                run_pass_steps(eng, perm, w["B"], half, kind)
+                ev = eng.timer_stop() * 1e-3
+                sync()
+                if world > 1:
+                    t = torch.tensor([ev], dtype=torch.float64)
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                    ev = float(t.item())
+                evs.append(ev)
+            split_rate[kind] = world * half / float(np.median(evs))
+            split_samples[kind] = [round(world * half / t, 2) for t in evs]
+        # ---- profiled repeats (HIP events around every launch, on the library's stream), D passes and G passes apart so that a launch class is a
+        # (step kind, class) pair -- the discriminator step's decode and the generator step's are different kernels
+        prof_steps = max(steps, 96) // 2      # (at least 48 launches per class: a short K alone averages over too few)
+        eng.profile(True)
+        run_pass_steps(eng, perm, w["B"], prof_steps, "D")
+        prof_d = eng.profile_read()
+        eng.profile(True)                     # (clears the records)
+        run_pass_steps(eng, perm, w["B"], prof_steps, "G")
+        prof_g = eng.profile_read()
+        eng.profile(False)
+        prof = prof_d + prof_g
+
+        # ---- data-parallel runs verify themselves: replicas bitwise equal after all of the above, RCCL's world = the launcher's ----
+        check = replica_check(eng, world, dist) if (world > 1 or force_comm) else None
+        failed_checks = [] if check is None or replicas_ok(check) else ["configs[1]"]
+
+    if args.full and rank == 0:
         # Dominant DEVICE FUNCTION of the step = the symbol with the most kernel time: gemm_bf16k_mfma<false, true, 3, false> (encode of both
         # steps, decode of the discriminator step); `roofline.frac` covers all of its launches, `frac_best_class` the best class alone,
         # `frac_time_weighted` every class of the 16-wave GEMM family.  The fused-Adam weight-gradient launch, HBM-bound, has its own object.
@@ -612,22 +665,7 @@ def main():
         # products of weight >= 2^-16 accumulated in fp32 (fp32-accurate: tests/test_gpu_mfma_modes.py); `achieved`
         # counts the ALGORITHMIC 2MNK flops against the fp32 MFMA roof (the dtype of operands and result); the
         # executed bf16 flops (6x) against the bf16 roof and the plain fp32-MFMA kernel are reported beside it.
-        scoring = scoring_pre
-        out = {
-            "metric": "GANMF training steps/sec", "value": round(world * done / el, 2), "unit": "steps/s",
-            "n_gpus": world, "steps": done, "warmup": warmup, "ms_per_step": round(el / done * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "GANMF --user, MovieLens-1M shape %dx%d per GPU, k=%d, emb_dim=%d, batch=%d/GPU, "
-                                   "tuned hyper-parameters (BASELINE.json configs[1])" % (w["U"], w["N"], w["k"], w["e"], w["B"]),
-                       "step": "one 128-row minibatch update (D or G), K/2 D then K/2 G",
-                       "arithmetic": "float32 tensors throughout; the K loops of the step's GEMMs run the fp32-accurate split-bf16 loop "
-                                     "(3 exact bf16 pieces per operand, 6 piece products on v_mfma_f32_32x32x16_bf16, fp32 accumulate) in "
-                                     "16-wave workgroups (gemm_bf16k.hpp) or, for the two fused-Adam weight-gradient GEMMs, 4-wave "
-                                     "workgroups; gUb + gV on the fp32 MFMA",
-                       "launches": "D-step 6, G-step 8, plus per pass: two launches in front of a discriminator pass (the CSR rows of all its full minibatches -- that launch also writes lr_t of every step of the pass -- and their generated rows: the generator is frozen during the pass) and two around a generator pass (the embeddings of the scheduled rows advanced to their step, ONE all-rows Adam over U behind the pass instead of one per step: with g_reg = 0 a row is read once and has a gradient once per pass) (dE + d_coef, gWd + gWe, gUb + gV share a launch; the generator step: generator GEMM + CSR rows, encode, its slab sum, decode on 64 x 32 tiles unsplit, dE, its slab sum, dF unsplit, gUb + gV)",
-                       "global_steps_per_s": round(done / el, 2), "rows_per_s": round(world * done * w["B"] / el, 1),
-                       "parallelism": "dp%d (users sharded row-wise; RCCL reduce-scatter of the D and V gradients, Adam on the rank's "
-                                      "slice, all-gather of the parameters)" % world},
+        out.update({
             "d_steps_per_s": round(split_rate["D"], 2), "g_steps_per_s": round(split_rate["G"], 2),
             "pass_rates": {"protocol": "max(K/2, one pass over the shard) = %d updates of one kind per repeat as D-only / G-only ganmf_train_epoch calls over the same slices, hipEvent-timed, "
                                        "median of %d, right after the timed region (the reference's two loops, GANRec/GANMF.py:176-189 / 191-203)" % (half, REPEATS),
@@ -635,9 +673,8 @@ def main():
                            "harmonic_mean_steps_per_s": round(2.0 / (1.0 / split_rate["D"] + 1.0 / split_rate["G"]), 2),
                            "kernel_us_per_step": {"D": round(sum(p["ms"] for p in prof_d) * 1e3 / max(prof_steps, 1), 2),
                                                   "G": round(sum(p["ms"] for p in prof_g) * 1e3 / max(prof_steps, 1), 2)}},
-            "timing": timing, "roofline": roofline, "roofline_fused_adam": roofline_fused, "scoring_gemm": scoring, "kernels": kernels,
-            "reference_derived_steps_per_s": 84.0,
-        }
+            "roofline": roofline, "roofline_fused_adam": roofline_fused, "scoring_gemm": scoring_pre, "kernels": kernels,
+        })
         if world > 1 or force_comm:
             out["parallelism"] = parallelism_object(eng, prof, world, 2 * prof_steps, world * done * w["B"] / el)
             out["parallelism"].update(check)
@@ -647,7 +684,7 @@ def main():
     # ---- N > 1: the configuration BASELINE.md defines the >= 6x target on -- configs[3], 200 000 x 50 000 users x items sharded
     # 25 000 rows per GPU -- at the paper's default emb_dim = 32 and at 1024, beside the configs[1] line above (weak scaling: every
     # rank holds one shard at every N).  GANMF_BENCH_FORCE_COMM=1 rehearses the same code on one GPU (one-rank RCCL communicator).
-    if (world > 1 or force_comm) and os.environ.get("GANMF_BENCH_SKIP_C4") != "1":
+    if args.full and (world > 1 or force_comm) and os.environ.get("GANMF_BENCH_SKIP_C4") != "1":
         extra = []
         for e4 in (32, 1024):
             try:

@@ -214,3 +214,30 @@ def test_replica_check_over_gloo_world_2(tmp_path, capfd, diverge):
     if diverge:
         assert isinstance(checks[0]["crc32c"]["Wd"], list) and len(set(checks[0]["crc32c"]["Wd"])) == 2
         assert all(isinstance(checks[0]["crc32c"][n], str) for n in ("We", "be", "bd", "V"))
+
+
+def test_run_steps_and_dump_outputs(tmp_path):
+    """run_steps issues EXACTLY n updates (ceil(n/2) D, floor(n/2) G) and returns every call's losses; --dump-outputs writes them, in order,
+    and every parameter tensor as float32 DIR/<name>.npy."""
+    import numpy as np
+    b = _bench()
+
+    class Eng(object):
+        def __init__(self):
+            self.calls = 0
+
+        def train_epoch(self, perm, d, g):
+            n = len(perm) // 4
+            self.calls += 1
+            return np.arange(d * n, dtype=np.float32) + 100 * self.calls, -np.arange(g * n, dtype=np.float32) - 100 * self.calls
+
+        def get_tensor(self, tid):
+            return np.full((2, 3), tid, dtype=np.float32)
+    eng = Eng()
+    losses = b.run_steps(eng, np.arange(12, dtype=np.int32), 4, 9)      # 3 slices per call: D+G calls of 3 and 1 slices, then one D update
+    assert [(len(d), len(g)) for d, g in losses] == [(3, 3), (1, 1), (1, 0)]
+    b.dump_outputs(str(tmp_path / "out"), eng, losses)
+    got = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    assert set(got) == {"d_loss", "g_loss", "We", "be", "Wd", "bd", "U", "V"} and all(a.dtype == np.float32 for a in got.values())
+    assert got["d_loss"].tolist() == [100, 101, 102, 200, 300] and got["g_loss"].tolist() == [-100, -101, -102, -200]
+    assert got["V"].shape == (2, 3) and (got["V"] == 101).all() and (got["bd"] == 3).all()

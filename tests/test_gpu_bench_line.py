@@ -1,5 +1,6 @@
-"""`python bench.py` on the GPU: ONE JSON line on stdout carrying the driver's contract keys, SURVEY 8(d)'s full report (D / G pass rates, the one-thread CPU
-figure) and a `roofline` object whose `frac` is the dominant device function over all of its launch classes -- checked for internal consistency, not for speed."""
+"""`python bench.py` on the GPU: ONE JSON line on stdout carrying the driver's contract keys; with --full also SURVEY 8(d)'s full report (D / G pass rates,
+the one-thread CPU figure) and a `roofline` object whose `frac` is the dominant device function over all of its launch classes -- checked for internal
+consistency, not for speed.  A plain run measures the headline alone and --dump-outputs writes what its timed steps computed."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_contract_and_consistency():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "4", "--cpu-seconds", "1.5"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "4", "--cpu-seconds", "1.5"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -43,3 +44,29 @@ def test_bench_line_contract_and_consistency():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "steps/s" and c["value"] > 0 and c["cores"] >= 1 and c["value_1thread"] > 0
     assert {k["step"] for k in d["kernels"]} == {"D", "G"}
+    assert len(d["timing"]["value_samples"]) == 5 and d["timing"]["value_samples"][0] == d["value"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run: exactly K timed steps, the contract keys and nothing measured beside them; --dump-outputs DIR: the per-update losses of
+    those K steps and every parameter tensor after them, float32, finite, within 64 MB."""
+    import numpy as np
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "13", "--warmup", "4", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, "stdout must carry exactly one line"
+    d = json.loads(lines[0])
+    for key, val in (("metric", "GANMF training steps/sec"), ("unit", "steps/s"), ("n_gpus", 1), ("steps", 13), ("warmup", 4), ("higher_is_better", True),
+                     ("dtype", "f32")):
+        assert d[key] == val, (key, d[key])
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 1e3 / d["value"]) < 1e-3 * d["ms_per_step"] + 1e-4
+    assert d["timing"]["repeats"] == 1
+    assert not {"roofline", "kernels", "scoring_gemm", "cpu_baseline", "d_steps_per_s", "pass_rates", "parallelism"} & set(d)
+    files = {f: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    shapes = {"d_loss.npy": (7,), "g_loss.npy": (6,), "We.npy": (3706, 992), "be.npy": (1, 992), "Wd.npy": (992, 3706), "bd.npy": (1, 3706),
+              "U.npy": (6040, 250), "V.npy": (3706, 250)}
+    assert {f: a.shape for f, a in files.items()} == shapes
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20

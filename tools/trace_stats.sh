@@ -1,10 +1,10 @@
 #!/bin/bash
-# rocprofv3 kernel statistics (EVERY kernel, tagged by the library's profiler or not) of one python tool run on the GPU box.
-# usage: tools/trace_stats.sh <tag> <tool.py> [args...]      -> gpurun_out/<tag>/stats.txt (top 16 kernels by total time)
+# rocprofv3 kernel statistics (EVERY kernel, tagged by the library's profiler or not) of one python tool run on the GPU.
+# usage: tools/trace_stats.sh <tag> <tool.py> [args...]      -> $PROFILE_OUT/<tag>/stats.txt, default profile_out/ (top 16 kernels by total time)
 set -eu
 R="$(cd "$(dirname "$0")/.." && pwd)"
 TAG="$1"; shift
-O="$R/gpurun_out/$TAG"
+O="${PROFILE_OUT:-$R/profile_out}/$TAG"
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -- python3 "$R/$1" "${@:2}" > "$O/log" 2>&1

@@ -7,7 +7,7 @@ TAG="$1"; FIRST="${2:-60}"; COUNT="${3:-2}"; ANCHOR="${4:-de_dcoef_kernel}"
 O="$R/gpurun_out/$TAG"
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d "$O" -- python3 "$R/bench.py" --no-cpu-baseline --steps 64 --warmup 32 > "$O/log" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$O" -- python3 "$R/bench.py" --full --no-cpu-baseline --steps 64 --warmup 32 > "$O/log" 2>&1
 cd "$R"
 python3 tools/timeline.py "$(ls $O/*/*kernel_trace.csv | head -1)" "$FIRST" "$COUNT" "$ANCHOR" > "$O/timeline.txt"
 find "$O" -name "*trace.csv" -delete
