@@ -355,14 +355,46 @@ int ganmf_comm_abort(ganmf_handle* h) {
 
 int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data,
                       int64_t n_rows, int64_t n_cols) {
-  if (!h || !indptr || (!indices && indptr[n_rows] > 0)) return fail(-1, "ganmf_set_urm_csr: null argument");
+  if (!h || !indptr || ((!indices || !data) && indptr[n_rows] > 0)) return fail(-1, "ganmf_set_urm_csr: null argument");
   if (n_rows != h->U || n_cols != h->N) return fail(-1, "ganmf_set_urm_csr: shape %lldx%lld != handle %dx%d", (long long)n_rows, (long long)n_cols, h->U, h->N);
-  const int64_t nnz = indptr[n_rows];
+  int64_t nnz = indptr[n_rows];
   if (indptr[0] != 0 || nnz < 0) return fail(-1, "ganmf_set_urm_csr: bad indptr");
   for (int64_t r = 0; r < n_rows; ++r)
     if (indptr[r + 1] < indptr[r]) return fail(-1, "ganmf_set_urm_csr: indptr not monotone at row %lld", (long long)r);
   for (int64_t j = 0; j < nnz; ++j)
     if (indices[j] < 0 || indices[j] >= n_cols) return fail(-1, "ganmf_set_urm_csr: column index %d out of range at %lld", indices[j], (long long)j);
+  // Canonical form, as scipy's sum_duplicates() + sort_indices() leave it: every row's columns strictly ascending, the entries of a
+  // repeated (row, column) summed in stored order, explicit zeros kept.  The reference feeds URM_train[uids].toarray() -- which sums
+  // duplicates -- whatever form the matrix has; the device paths need the canonical one (densify_rows scatters one store per entry,
+  // csr_quad binary-searches a row).  A canonical input is uploaded as it is.
+  std::vector<int64_t> c_indptr;
+  std::vector<int> c_indices;
+  std::vector<float> c_data;
+  bool canonical = true;
+  for (int64_t r = 0; r < n_rows && canonical; ++r)
+    for (int64_t j = indptr[r] + 1; j < indptr[r + 1]; ++j)
+      if (indices[j] <= indices[j - 1]) { canonical = false; break; }
+  if (!canonical) {
+    c_indptr.assign((size_t)n_rows + 1, 0);
+    c_indices.reserve((size_t)nnz);
+    c_data.reserve((size_t)nnz);
+    std::vector<int64_t> order;
+    for (int64_t r = 0; r < n_rows; ++r) {
+      order.resize((size_t)(indptr[r + 1] - indptr[r]));
+      for (size_t i = 0; i < order.size(); ++i) order[i] = indptr[r] + (int64_t)i;
+      std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return indices[a] < indices[b]; });
+      for (size_t i = 0; i < order.size(); ++i) {
+        const int64_t j = order[i];
+        if (i > 0 && indices[j] == c_indices.back()) c_data.back() += data[j];
+        else { c_indices.push_back(indices[j]); c_data.push_back(data[j]); }
+      }
+      c_indptr[(size_t)r + 1] = (int64_t)c_indices.size();
+    }
+    indptr = c_indptr.data();
+    indices = c_indices.data();
+    data = c_data.data();
+    nnz = (int64_t)c_indices.size();
+  }
   HIP_TRY(hipSetDevice(h->dev));
   if (h->indptr) { hipFree(h->indptr); hipFree(h->indices); hipFree(h->data); h->indptr = nullptr; }
   HIP_TRY(hipMalloc((void**)&h->indptr, (n_rows + 1) * sizeof(long long)));
@@ -389,6 +421,9 @@ int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* ind
   const double flops_saved = 4.0 * (double)h->B * (double)h->N * (double)h->e;
   h->sparse_d = h->cfg.model == GANMF_MODEL_GANMF && force != 0 &&
                 (force_d >= 0 ? force_d != 0 : (density < 0.005 && flops_saved >= 2.0e9));
+  if (h->debug_plan)      // (tests assert on the path the planner took, not only on the numbers it produced)
+    fprintf(stderr, "[ganmf urm] set_urm_csr %lldx%lld nnz=%lld%s density %.5f -> sparse_g %d sparse_d %d\n", (long long)n_rows,
+            (long long)n_cols, (long long)nnz, canonical ? "" : " (made canonical)", density, (int)h->sparse_g, (int)h->sparse_d);
   hipFree(h->csc_colptr); hipFree(h->csc_rowidx); hipFree(h->csc_val);
   h->csc_colptr = nullptr; h->csc_rowidx = nullptr; h->csc_val = nullptr;
   if (h->sparse_d) {      // counting sort by column; rows ascend inside a column because the CSR rows are walked in order

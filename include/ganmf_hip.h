@@ -111,7 +111,10 @@ int ganmf_comm_abort(ganmf_handle* h);
 
 /* Replaces the per-minibatch host work `URM_train[uids].toarray()` + feed_dict upload
  * (GANMF.py:183-187,198-201): the CSR matrix (training orientation, this handle's rows) is
- * uploaded ONCE and minibatch rows are expanded on the device. */
+ * uploaded ONCE and minibatch rows are expanded on the device.  Any scipy CSR is accepted, as the reference accepts
+ * it: rows whose column indices are unsorted or repeated are made canonical on the host before the upload (columns
+ * ascending, the values of a repeated (row, column) summed in stored order, explicit zeros kept -- scipy's
+ * sum_duplicates() + sort_indices()), so the device sees what URM_train[uids].toarray() would give. */
 int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices,
                       const float* data, int64_t n_rows, int64_t n_cols);
 
