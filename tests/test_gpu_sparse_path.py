@@ -15,6 +15,7 @@ import scipy.sparse as sps
 
 from ganmf_amd.dist import shard_bounds
 from oracle.ganmf_oracle import DisGANMFOracle, GANMFOracle
+from tests.helpers_grad import _abs_d_bounds, _abs_g_bounds, _rowwise
 from tests.test_gpu_dist_local import _run_ranks
 from tests.test_gpu_multi_launch import _run_staged
 
@@ -231,57 +232,6 @@ def test_sparse_random_config(seed, monkeypatch, capfd):
 
 
 # -- 3: gradients of one step, row by row ---------------------------------------------------------------------------------------
-def _abs_d_bounds(o, uids, X):
-    """Per element, the fp64 sum of |terms| behind each discriminator gradient (the GEMM chain encode -> decode -> dR -> dE -> gW
-    with every operand replaced by its absolute value; hinge coefficients at their largest): what a rounding error of that element
-    is proportional to."""
-    p = {n: np.abs(v) for n, v in o.p.items()}
-    N = X.shape[1]
-    s = 2.0 / (X.shape[0] * N)
-    g = {n: np.zeros_like(p[n]) for n in o.D_NAMES}
-    Fa = p["U"][uids] @ p["V"].T
-    for inp, c in ((np.abs(X), 1.0 + float(o.m)), (Fa, 1.0)):
-        Ea = inp @ p["We"] + p["be"]
-        dRa = (c * s) * (Ea @ p["Wd"] + p["bd"] + inp)
-        g["Wd"] += Ea.T @ dRa
-        g["bd"] += dRa.sum(axis=0)
-        dEa = dRa @ p["Wd"].T
-        g["We"] += inp.T @ dEa
-        g["be"] += dEa.sum(axis=0)
-    for n in o.D_NAMES:
-        g[n] += abs(float(o.d_reg)) * p[n]
-    return g
-
-
-def _abs_g_bounds(o, uids, X):
-    p = {n: np.abs(v) for n, v in o.p.items()}
-    B, N = X.shape
-    a = float(o.alpha)
-    Ub = p["U"][uids]
-    Fa = Ub @ p["V"].T
-    Era = np.abs(X) @ p["We"] + p["be"]
-    Efa = Fa @ p["We"] + p["be"]
-    dRa = ((1.0 - a) * 2.0 / (B * N)) * (Efa @ p["Wd"] + p["bd"] + Fa)
-    dEa = dRa @ p["Wd"].T + (a * 2.0 / (B * o.e)) * (Efa + Era)
-    dFa = dEa @ p["We"].T + dRa
-    gU = abs(float(o.g_reg)) * p["U"]
-    gU[uids] += dFa @ p["V"]
-    return {"U": gU, "V": dFa.T @ Ub + abs(float(o.g_reg)) * p["V"]}
-
-
-def _rowwise(got, ref, bound, what, tol=2e-5):
-    """max |got - ref| of every row over the largest bound of that row; a row whose bound is 0 must be exactly 0."""
-    got = np.asarray(got, np.float64).reshape(np.shape(ref))
-    if got.ndim == 1:      # a bias vector: every element is its own row
-        got, ref, bound = got[:, None], ref[:, None], bound[:, None]
-    d = np.abs(got - ref).max(axis=1)
-    b = bound.max(axis=1)
-    zero = b == 0
-    assert np.all(d[zero] == 0), (what, np.flatnonzero(zero & (d != 0))[:8])
-    r = d[~zero] / b[~zero]
-    assert r.size == 0 or r.max() <= tol, (what, "row", int(np.flatnonzero(~zero)[np.argmax(r)]), float(r.max()))
-
-
 @pytest.mark.parametrize("mode", ["sparse_g", "sparse_gd"])
 @pytest.mark.parametrize("e", [37, 1030])
 def test_one_step_gradients_row_by_row(mode, e, monkeypatch, capfd):
