@@ -338,6 +338,33 @@ class GANMF(BaseRecommender):
         return self.engine.evaluate(np.asarray(user_id_array).reshape(-1), cutoffs, disc, ideal_cum,
                                     transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
 
+    def evaluate_full_on_device(self, evaluator_key, urm_test_sorted, gains, ratings, item_weights, user_id_array, cutoffs,
+                                disc, ideal_cum, remove_seen_flag=True, counts=None):
+        """The reference's full metric row for EvaluatorHoldoutFast(full_metrics=True) (ganmf_evaluate_full): returns the
+        [len(cutoffs), 13] float64 sums of ganmf_amd._lib.EVAL_FULL_METRICS and adds the per-item counts of the lists into
+        `counts` ([len(cutoffs), n_items] int64), or None when the device route does not apply (as evaluate_on_device).
+        `ratings`: float32 per stored test entry; `item_weights`: the (novelty, popularity) pair of
+        ganmf_amd.evaluation.popularity_weights, uploaded again whenever their values change."""
+        from . import _lib as L
+        self._require_engine()
+        cutoffs = list(cutoffs)
+        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or not (1 <= max(cutoffs) <= min(self._DEVICE_TOPK_MAX, self.n_items)):
+            return None
+        if min(cutoffs) < 1:
+            return None
+        held = getattr(self, "_test_on_device", None)
+        if held is None or held[0] != evaluator_key or held[1] is not self.engine or len(held) < 3:
+            self.engine.set_test(urm_test_sorted, gains)
+            self.engine.set_test_ratings(ratings)
+            self._test_on_device = (evaluator_key, self.engine, True)
+        held = getattr(self, "_weights_on_device", None)
+        if (held is None or held[1] is not self.engine or not all(np.array_equal(a, b) for a, b in zip(held[0], item_weights))):
+            self.engine.set_eval_item_weights(*item_weights)
+            self._weights_on_device = (tuple(np.array(w, dtype=np.float64) for w in item_weights), self.engine)
+        sums, _ = self.engine.evaluate_full(np.asarray(user_id_array).reshape(-1), cutoffs, disc, ideal_cum,
+                                            transposed=(self.mode == 'item'), remove_seen=remove_seen_flag, counts=counts)
+        return sums
+
     def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None,
                   remove_top_pop_flag=False, remove_CustomItems_flag=False, return_scores=False):
         device_ok = (not return_scores and not remove_top_pop_flag

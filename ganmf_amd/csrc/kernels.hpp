@@ -1015,13 +1015,21 @@ __global__ __launch_bounds__(64 * UIDG_GROUPS) void dis_uid_grad_kernel(const fl
 // One workgroup per score row.  The row is staged in LDS when it fits (lds_cap floats), otherwise the
 // selection works in place on the (private) score buffer.  k rounds of a block-wide arg-max with
 // removal; ties go to the smaller item id; exhausted rows (everything -inf) yield -1.
-__global__ __launch_bounds__(256) void mask_topk_kernel(float* __restrict__ scores, int ld, int W,
-                                                        const int* __restrict__ row_ids,
-                                                        const long long* __restrict__ seen_indptr,
-                                                        const int* __restrict__ seen_indices, int k, int lds_cap,
-                                                        int* __restrict__ out_items, float* __restrict__ out_vals,
-                                                        const unsigned char* __restrict__ item_mask,
-                                                        const long long* __restrict__ cold_indptr) {
+// kRmse (ganmf_evaluate_full): between the masking and the first selection round -- the in-place path overwrites every picked
+// item with -inf -- the row's RMSE over the user's test items (Base/Evaluation/metrics.py:634 rmse on the score row that
+// recommend(..., return_scores=True) returns): squared fp32 errors of the finite ones, summed in a fixed order, NaN without any.
+struct RmseP {
+  const long long* t_indptr;   // test matrix, evaluation orientation (ganmf_set_test_csr)
+  const int* t_indices;
+  const float* t_rating;       // rating per stored entry (ganmf_set_test_ratings)
+  float* out;                  // [n] per score row
+};
+template <bool kRmse>
+__device__ __forceinline__ void mask_topk_body(float* __restrict__ scores, int ld, int W, const int* __restrict__ row_ids,
+                                               const long long* __restrict__ seen_indptr, const int* __restrict__ seen_indices,
+                                               int k, int lds_cap, int* __restrict__ out_items, float* __restrict__ out_vals,
+                                               const unsigned char* __restrict__ item_mask,
+                                               const long long* __restrict__ cold_indptr, const RmseP rp) {
   extern __shared__ __attribute__((aligned(16))) float srow[];
   __shared__ float wv[4];
   __shared__ int wi[4];
@@ -1044,6 +1052,31 @@ __global__ __launch_bounds__(256) void mask_topk_kernel(float* __restrict__ scor
     for (long long j = s + tid; j < e; j += 256) row[seen_indices[j]] = -INFINITY;
   }
   __syncthreads();
+  if (kRmse) {
+    __shared__ double rs[4];
+    __shared__ int rc[4];
+    const int u = row_ids[r];
+    const long long s = rp.t_indptr[u], e = rp.t_indptr[u + 1];
+    double sq = 0.0;
+    int cnt = 0;
+    for (long long j = s + tid; j < e; j += 256) {
+      const float d = row[rp.t_indices[j]] - rp.t_rating[j];
+      const float d2 = d * d;
+      if (isfinite(d2)) { sq += (double)d2; ++cnt; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      sq += __shfl_xor(sq, o);
+      cnt += __shfl_xor(cnt, o);
+    }
+    if (lane == 0) { rs[wave] = sq; rc[wave] = cnt; }
+    __syncthreads();
+    if (tid == 0) {
+      const double t = ((rs[0] + rs[1]) + rs[2]) + rs[3];
+      const int c = rc[0] + rc[1] + rc[2] + rc[3];
+      rp.out[r] = c > 0 ? (float)sqrt(t / (double)c) : NAN;
+    }
+  }
   for (int t = 0; t < k; ++t) {
     float bv = -INFINITY;
     int bi = 0x7fffffff;
@@ -1070,6 +1103,26 @@ __global__ __launch_bounds__(256) void mask_topk_kernel(float* __restrict__ scor
     }
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(256) void mask_topk_kernel(float* __restrict__ scores, int ld, int W,
+                                                        const int* __restrict__ row_ids,
+                                                        const long long* __restrict__ seen_indptr,
+                                                        const int* __restrict__ seen_indices, int k, int lds_cap,
+                                                        int* __restrict__ out_items, float* __restrict__ out_vals,
+                                                        const unsigned char* __restrict__ item_mask,
+                                                        const long long* __restrict__ cold_indptr) {
+  mask_topk_body<false>(scores, ld, W, row_ids, seen_indptr, seen_indices, k, lds_cap, out_items, out_vals, item_mask,
+                        cold_indptr, RmseP{});
+}
+__global__ __launch_bounds__(256) void mask_topk_rmse_kernel(float* __restrict__ scores, int ld, int W,
+                                                             const int* __restrict__ row_ids,
+                                                             const long long* __restrict__ seen_indptr,
+                                                             const int* __restrict__ seen_indices, int k, int lds_cap,
+                                                             int* __restrict__ out_items, float* __restrict__ out_vals,
+                                                             const unsigned char* __restrict__ item_mask,
+                                                             const long long* __restrict__ cold_indptr, const RmseP rp) {
+  mask_topk_body<true>(scores, ld, W, row_ids, seen_indptr, seen_indices, k, lds_cap, out_items, out_vals, item_mask,
+                       cold_indptr, rp);
 }
 
 // ganmf_scores under a score filter (ganmf_set_score_filter): one workgroup per score row, same rule as mask_topk_kernel
@@ -1111,24 +1164,79 @@ struct EvalP {
   double* partials;            // [gridDim.x][ncut][EVAL_METRICS]
 };
 
-__global__ __launch_bounds__(256) void eval_topk_kernel(const EvalP p) {
+// ganmf_evaluate_full adds, per cut-off, the user's fp32 RMSE (mask_topk_rmse_kernel), the sums of two per-item weights over
+// the list -- novelty -log2(pop/sum(pop))/len(pop) (0 where pop = 0) and pop/max(pop), formed on the host in float64 as
+// metrics.py forms them (Novelty / AveragePopularity) -- and whether the list is non-empty (Coverage_User), plus the per-item
+// recommendation counts of the count-based metrics (Coverage_Item, Gini, Shannon, Herfindahl, MeanInterList).  Counts are
+// integer atomics (exact in any order): each list position goes to the bin of the smallest cut-off that contains it, a
+// workgroup's bins live in an LDS histogram [ncut][W] when it fits, and the flush adds the prefix over the cut-offs in
+// ascending order -- one global add per non-zero (cut-off, item).  Too wide for LDS: one global add per (position, cut-off).
+constexpr int EVAL_FULL_METRICS = 13;   // EVAL_METRICS, then RMSE, NOVELTY, AVERAGE_POPULARITY, NON_EMPTY (lists)
+constexpr size_t EVAL_COUNTS_LDS_BYTES = 128 * 1024;   // largest LDS histogram (of the CU's 160 KiB)
+struct EvalFullP {
+  const float* rmse;           // [n] per evaluated row, NaN when no test item has a finite error
+  const double* w_nov;         // [W] novelty term per item
+  const double* w_pop;         // [W] normalised popularity per item
+  unsigned* counts;            // [ncut][W] global, zeroed by the caller
+  int W;
+  int lds_counts;              // 1: dynamic LDS of ncut * W unsigned
+  int order[EVAL_MAX_CUTOFFS]; // cut-off indices by ascending cut-off (ties: lower index first)
+};
+
+template <bool kFull>
+__device__ __forceinline__ void eval_topk_body(const EvalP& p, const EvalFullP& f) {
+  constexpr int NM = kFull ? EVAL_FULL_METRICS : EVAL_METRICS;
   __shared__ double red[256];
   const int u = blockIdx.x * 256 + threadIdx.x;
   const bool live = u < p.n;
   long long t0 = 0, t1 = 0;
   if (live) { const int r = p.ids[u]; t0 = p.t_indptr[r]; t1 = p.t_indptr[r + 1]; }
   const double n_test = (double)(t1 - t0);
+  if (kFull) {
+    extern __shared__ unsigned hist[];
+    const int nbin = p.ncut * f.W;
+    if (f.lds_counts) {
+      for (int i = threadIdx.x; i < nbin; i += 256) hist[i] = 0u;
+      __syncthreads();
+    }
+    if (live) {
+      for (int i = 0; i < p.K; ++i) {
+        const int it = p.items[(size_t)u * p.K + i];
+        if (it < 0) continue;
+        if (f.lds_counts) {
+          int b = 0;                              // first cut-off (ascending) that contains position i
+          while (b < p.ncut && i >= p.cutoffs[f.order[b]]) ++b;
+          if (b < p.ncut) atomicAdd(&hist[b * f.W + it], 1u);
+        } else {
+          for (int ci = 0; ci < p.ncut; ++ci)
+            if (i < p.cutoffs[ci]) atomicAdd(&f.counts[(size_t)ci * f.W + it], 1u);
+        }
+      }
+    }
+    if (f.lds_counts) {
+      __syncthreads();
+      for (int x = threadIdx.x; x < f.W; x += 256) {
+        unsigned run = 0u;
+        for (int b = 0; b < p.ncut; ++b) {
+          run += hist[b * f.W + x];
+          if (run) atomicAdd(&f.counts[(size_t)f.order[b] * f.W + x], run);
+        }
+      }
+    }
+  }
   for (int ci = 0; ci < p.ncut; ++ci) {
     const int c = p.cutoffs[ci];
-    double m[EVAL_METRICS];
+    double m[NM];
 #pragma unroll
-    for (int q = 0; q < EVAL_METRICS; ++q) m[q] = 0.0;
+    for (int q = 0; q < NM; ++q) m[q] = 0.0;
     if (live) {
       double hits = 0.0, nneg = 0.0, len = 0.0, pairs = 0.0, ap = 0.0, arhr = 0.0, dcg = 0.0, rr = 0.0;
+      double nov = 0.0, pop = 0.0;
       for (int i = 0; i < c && i < p.K; ++i) {
         const int it = p.items[(size_t)u * p.K + i];
         if (it < 0) continue;
         len += 1.0;
+        if (kFull) { nov += f.w_nov[it]; pop += f.w_pop[it]; }
         long long lo = t0, hi = t1;          // first stored index >= it
         while (lo < hi) {
           const long long mid = (lo + hi) >> 1;
@@ -1160,19 +1268,28 @@ __global__ __launch_bounds__(256) void eval_topk_kernel(const EvalP p) {
       }
       m[7] = hits;
       m[8] = arhr;
+      if (kFull) {
+        m[9] = (double)f.rmse[u];
+        m[10] = nov;
+        m[11] = len > 0.0 ? pop / len : 0.0;
+        m[12] = len > 0.0 ? 1.0 : 0.0;
+      }
     }
 #pragma unroll
-    for (int q = 0; q < EVAL_METRICS; ++q) {
+    for (int q = 0; q < NM; ++q) {
       red[threadIdx.x] = m[q];
       __syncthreads();
       for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
         __syncthreads();
       }
-      if (threadIdx.x == 0) p.partials[((size_t)blockIdx.x * p.ncut + ci) * EVAL_METRICS + q] = red[0];
+      if (threadIdx.x == 0) p.partials[((size_t)blockIdx.x * p.ncut + ci) * NM + q] = red[0];
       __syncthreads();
     }
   }
 }
+
+__global__ __launch_bounds__(256) void eval_topk_kernel(const EvalP p) { eval_topk_body<false>(p, EvalFullP{}); }
+__global__ __launch_bounds__(256) void eval_topk_full_kernel(const EvalP p, const EvalFullP f) { eval_topk_body<true>(p, f); }
 
 }  // namespace ganmf

@@ -179,8 +179,9 @@ int ganmf_set_seen_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* in
 
 // scores -> seen mask -> top-`cutoff` of the rows `ids`, left on the device in h->topk_items / h->topk_vals ([n, cutoff]);
 // *ids_dev_out = the uploaded ids.  Shared by ganmf_recommend and ganmf_evaluate.
+// rmse != nullptr (ganmf_evaluate_full): the selection kernel also writes each row's RMSE over its test items (mask_topk_rmse_kernel).
 static int recommend_device(ganmf_handle* h, const char* who, const int32_t* ids, int64_t n, int transposed, int32_t cutoff,
-                            int remove_seen, int** ids_dev_out) {
+                            int remove_seen, int** ids_dev_out, const RmseP* rmse = nullptr) {
   if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
   if (cutoff < 1 || cutoff > W || cutoff > GANMF_RECOMMEND_MAX_CUTOFF)
@@ -207,6 +208,16 @@ static int recommend_device(ganmf_handle* h, const char* who, const int32_t* ids
   TRY(scores_device(h, ids_dev, n, transposed, &od, &Wd, &ldw));
   const int lds_cap = 32768;   // floats: 128 KiB of the CU's 160 KiB
   const size_t shmem = Wd <= lds_cap ? (size_t)Wd * sizeof(float) : 0;
+  if (rmse) {
+    if (shmem > 48 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mask_topk_rmse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    GANMF_LAUNCH(mask_topk_rmse_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev,
+                 remove_seen ? h->seen_indptr : (const long long*)nullptr, h->seen_indices, (int)cutoff, lds_cap,
+                 h->topk_items, h->topk_vals, fmask, fcold, *rmse);
+    HIP_TRY(hipGetLastError());
+    if (ids_dev_out) *ids_dev_out = ids_dev;
+    return 0;
+  }
   if (shmem > 48 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mask_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   GANMF_LAUNCH(mask_topk_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev,
@@ -233,6 +244,7 @@ int ganmf_set_test_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* in
   HIP_TRY(hipStreamSynchronize(h->st));
   hipFree(h->test_indptr); hipFree(h->test_indices); hipFree(h->test_gain);
   h->test_indptr = nullptr; h->test_indices = nullptr; h->test_gain = nullptr; h->test_rows = h->test_cols = 0;
+  hipFree(h->test_rating); h->test_rating = nullptr; h->test_rating_ok = false; h->test_nnz = nnz;
   HIP_TRY(hipMalloc((void**)&h->test_indptr, (size_t)(n_rows + 1) * sizeof(long long)));
   HIP_TRY(hipMalloc((void**)&h->test_indices, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int)));
   HIP_TRY(hipMalloc((void**)&h->test_gain, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
@@ -287,6 +299,107 @@ int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transpose
   for (int i = 0; i < n_cutoffs * EVAL_METRICS; ++i) sums[i] = 0.0;
   for (int b = 0; b < grid; ++b)      // block order: reproducible
     for (int i = 0; i < n_cutoffs * EVAL_METRICS; ++i) sums[i] += part[(size_t)b * n_cutoffs * EVAL_METRICS + i];
+  return 0;
+}
+
+int ganmf_set_test_ratings(ganmf_handle* h, const float* ratings, int64_t nnz) {
+  if (!h || (nnz > 0 && !ratings)) return fail(-1, "ganmf_set_test_ratings: null argument");
+  if (!h->test_indptr) return fail(-1, "ganmf_set_test_ratings: needs ganmf_set_test_csr first");
+  if (nnz != h->test_nnz) return fail(-1, "ganmf_set_test_ratings: %lld ratings for a test matrix of %lld entries", (long long)nnz, (long long)h->test_nnz);
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(h->test_rating); h->test_rating = nullptr; h->test_rating_ok = false;
+  HIP_TRY(hipMalloc((void**)&h->test_rating, (size_t)std::max<int64_t>(nnz, 1) * sizeof(float)));
+  if (nnz > 0) HIP_TRY(hipMemcpy(h->test_rating, ratings, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
+  h->test_rating_ok = true;
+  return 0;
+}
+
+int ganmf_set_eval_item_weights(ganmf_handle* h, const double* novelty, const double* popularity, int64_t width) {
+  if (!h || !novelty || !popularity) return fail(-1, "ganmf_set_eval_item_weights: null argument");
+  if (width < 1 || width > std::max(h->U, h->N)) return fail(-1, "ganmf_set_eval_item_weights: width %lld out of range", (long long)width);
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(h->eval_w); h->eval_w = nullptr; h->eval_w_width = 0;
+  HIP_TRY(hipMalloc((void**)&h->eval_w, (size_t)2 * width * sizeof(double)));
+  HIP_TRY(hipMemcpy(h->eval_w, novelty, (size_t)width * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->eval_w + width, popularity, (size_t)width * sizeof(double), hipMemcpyHostToDevice));
+  h->eval_w_width = width;
+  return 0;
+}
+
+int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
+                        int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts) {
+  if (!h || !ids || !cutoffs || !disc || !ideal_cum || !sums || !counts) return fail(-1, "ganmf_evaluate_full: null argument");
+  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "ganmf_evaluate_full: 1..%d cut-offs per call", GANMF_EVAL_MAX_CUTOFFS);
+  if (n < 1 || n > (1 << 30)) return fail(-1, "ganmf_evaluate_full: n out of range");
+  const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
+  if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
+    return fail(-1, "ganmf_evaluate_full: needs ganmf_set_test_csr with a %d x %d matrix", limit, W);
+  if (!h->test_rating_ok) return fail(-1, "ganmf_evaluate_full: needs ganmf_set_test_ratings for the current test matrix");
+  if (h->eval_w_width != W) return fail(-1, "ganmf_evaluate_full: needs ganmf_set_eval_item_weights of width %d", W);
+  int K = 0;
+  for (int i = 0; i < n_cutoffs; ++i) {
+    if (cutoffs[i] < 1) return fail(-1, "ganmf_evaluate_full: cut-off %d", cutoffs[i]);
+    K = std::max(K, (int)cutoffs[i]);
+  }
+  HIP_TRY(hipSetDevice(h->dev));
+  if ((size_t)n > h->eval_rmse_cap) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    hipFree(h->eval_rmse); h->eval_rmse = nullptr; h->eval_rmse_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h->eval_rmse, (size_t)n * sizeof(float)));
+    h->eval_rmse_cap = (size_t)n;
+  }
+  const size_t n_counts = (size_t)n_cutoffs * W;
+  if (n_counts > h->eval_counts_cap) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    hipFree(h->eval_counts); h->eval_counts = nullptr; h->eval_counts_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h->eval_counts, n_counts * sizeof(unsigned)));
+    h->eval_counts_cap = n_counts;
+  }
+  const RmseP rp{h->test_indptr, h->test_indices, h->test_rating, h->eval_rmse};
+  int* ids_dev = nullptr;
+  TRY(recommend_device(h, "ganmf_evaluate_full", ids, n, transposed, K, remove_seen, &ids_dev, &rp));
+  const int grid = (int)((n + 255) / 256);
+  const size_t n_part = (size_t)grid * n_cutoffs * EVAL_FULL_METRICS;
+  const size_t need = (size_t)K + (size_t)n * K + n_part;
+  if (need > h->eval_cap) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    hipFree(h->eval_buf); h->eval_buf = nullptr; h->eval_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h->eval_buf, need * sizeof(double)));
+    h->eval_cap = need;
+  }
+  double* d_disc = h->eval_buf;
+  double* d_ideal = d_disc + K;
+  double* d_part = d_ideal + (size_t)n * K;
+  HIP_TRY(hipMemcpyAsync(d_disc, disc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->st));
+  HIP_TRY(hipMemcpyAsync(d_ideal, ideal_cum, (size_t)n * K * sizeof(double), hipMemcpyHostToDevice, h->st));
+  HIP_TRY(hipMemsetAsync(h->eval_counts, 0, n_counts * sizeof(unsigned), h->st));
+  EvalP p{};
+  p.items = h->topk_items; p.K = K; p.n = (int)n; p.ids = ids_dev;
+  p.t_indptr = h->test_indptr; p.t_indices = h->test_indices; p.t_gain = h->test_gain;
+  p.disc = d_disc; p.ideal_cum = d_ideal; p.ncut = n_cutoffs; p.partials = d_part;
+  for (int i = 0; i < n_cutoffs; ++i) p.cutoffs[i] = cutoffs[i];
+  EvalFullP f{};
+  f.rmse = h->eval_rmse; f.w_nov = h->eval_w; f.w_pop = h->eval_w + W; f.counts = h->eval_counts; f.W = W;
+  for (int i = 0; i < n_cutoffs; ++i) f.order[i] = i;
+  std::stable_sort(f.order, f.order + n_cutoffs, [&](int a, int b) { return cutoffs[a] < cutoffs[b]; });
+  const size_t hist_bytes = n_counts * sizeof(unsigned);
+  f.lds_counts = hist_bytes <= EVAL_COUNTS_LDS_BYTES ? 1 : 0;
+  const size_t shmem = f.lds_counts ? hist_bytes : 0;
+  if (shmem > 48 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_topk_full_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  GANMF_LAUNCH(eval_topk_full_kernel, dim3(grid), dim3(256), shmem, h->st, p, f);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> part(n_part);
+  std::vector<unsigned> cnt(n_counts);
+  HIP_TRY(hipMemcpyAsync(part.data(), d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(cnt.data(), h->eval_counts, n_counts * sizeof(unsigned), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  for (int i = 0; i < n_cutoffs * EVAL_FULL_METRICS; ++i) sums[i] = 0.0;
+  for (int b = 0; b < grid; ++b)      // block order: reproducible
+    for (int i = 0; i < n_cutoffs * EVAL_FULL_METRICS; ++i) sums[i] += part[(size_t)b * n_cutoffs * EVAL_FULL_METRICS + i];
+  for (size_t i = 0; i < n_counts; ++i) counts[i] += (int64_t)cnt[i];
   return 0;
 }
 

@@ -160,6 +160,17 @@ struct ganmf_handle {
   int64_t test_rows = 0, test_cols = 0;
   double* eval_buf = nullptr;      // disc | ideal_cum | block partials
   size_t eval_cap = 0;
+  // ganmf_evaluate_full(): rating per stored test entry (dropped by every ganmf_set_test_csr), the two per-item weights of the
+  // evaluation width, and work buffers (per-row RMSE, [n_cutoffs, W] counts)
+  int64_t test_nnz = 0;
+  float* test_rating = nullptr;
+  bool test_rating_ok = false;
+  double* eval_w = nullptr;        // novelty | popularity, eval_w_width each
+  int64_t eval_w_width = 0;
+  float* eval_rmse = nullptr;
+  size_t eval_rmse_cap = 0;
+  unsigned* eval_counts = nullptr;
+  size_t eval_counts_cap = 0;
   // scoring scratch
   int* sc_ids = nullptr;
   size_t sc_ids_cap = 0;

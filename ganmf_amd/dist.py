@@ -430,6 +430,16 @@ class ShardedEngine(object):
         self._sync_master()
         return self.master.evaluate(ids, cutoffs, disc, ideal_cum, transposed, remove_seen)
 
+    def set_test_ratings(self, ratings):
+        self.master.set_test_ratings(ratings)
+
+    def set_eval_item_weights(self, novelty, popularity):
+        self.master.set_eval_item_weights(novelty, popularity)
+
+    def evaluate_full(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True, counts=None):
+        self._sync_master()
+        return self.master.evaluate_full(ids, cutoffs, disc, ideal_cum, transposed, remove_seen, counts)
+
     def snapshot_best(self):
         self._sync_master()
         self.master.snapshot_best()

@@ -183,6 +183,43 @@ class Engine:
                     "ganmf_evaluate")
         return out
 
+    def set_test_ratings(self, ratings):
+        """float32 rating of every stored entry of the set_test() matrix, in its order (RMSE of evaluate_full)"""
+        r = np.ascontiguousarray(ratings, dtype=np.float32).ravel()
+        L.check(self.lib.ganmf_set_test_ratings(self.h, _f32p(r), r.size), "ganmf_set_test_ratings")
+
+    def set_eval_item_weights(self, novelty, popularity):
+        """per-item novelty term and normalised popularity of the evaluation width (ganmf_amd.evaluation.popularity_weights)"""
+        nov = np.ascontiguousarray(novelty, dtype=np.float64).ravel()
+        pop = np.ascontiguousarray(popularity, dtype=np.float64).ravel()
+        assert nov.size == pop.size
+        dp = C.POINTER(C.c_double)
+        L.check(self.lib.ganmf_set_eval_item_weights(self.h, nov.ctypes.data_as(dp), pop.ctypes.data_as(dp), nov.size),
+                "ganmf_set_eval_item_weights")
+
+    def evaluate_full(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True, counts=None):
+        """evaluate() plus RMSE, NOVELTY, AVERAGE_POPULARITY and non-empty-list sums (L.EVAL_FULL_METRICS, [len(cutoffs), 13]
+        float64) and the per-item counts of the lists cut at each cut-off, ADDED into `counts` ([len(cutoffs), width] int64,
+        a new zero array when None).  Returns (sums, counts)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
+        K = int(cut.max())
+        width = self.num_users if transposed else self.num_items
+        disc = np.ascontiguousarray(disc, dtype=np.float64).ravel()
+        ideal = np.ascontiguousarray(ideal_cum, dtype=np.float64)
+        assert disc.size >= K and ideal.shape == (ids.size, K)
+        if counts is None:
+            counts = np.zeros((cut.size, width), dtype=np.int64)
+        assert counts.dtype == np.int64 and counts.shape == (cut.size, width) and counts.flags.c_contiguous
+        out = np.zeros((cut.size, len(L.EVAL_FULL_METRICS)), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        if ids.size:
+            L.check(self.lib.ganmf_evaluate_full(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), _i32p(cut),
+                                                 cut.size, disc.ctypes.data_as(dp), ideal.ctypes.data_as(dp),
+                                                 out.ctypes.data_as(dp), counts.ctypes.data_as(C.POINTER(C.c_int64))),
+                    "ganmf_evaluate_full")
+        return out, counts
+
     def snapshot_best(self):
         L.check(self.lib.ganmf_snapshot_best(self.h), "ganmf_snapshot_best")
 

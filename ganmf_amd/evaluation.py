@@ -1,6 +1,10 @@
 """Hold-out evaluation -- the consumer of the scores (protocol of Base/Evaluation/Evaluator.py:214-414 with the
-accuracy metrics of Base/Evaluation/metrics.py).  The GANMF callers read `results_dic[cutoff][metric]` (early stopping:
-cut-off 5, Utils_.py:64); the reference's beyond-accuracy metrics (novelty, diversity, coverage) are out of scope.
+metrics of Base/Evaluation/metrics.py).  The GANMF callers read `results_dic[cutoff][metric]` (early stopping:
+cut-off 5, Utils_.py:64).
+
+By default both evaluators return the eleven accuracy values of METRICS.  With `full_metrics=True` they return the
+reference's whole row, FULL_METRICS in the reference's key order (Evaluator.py:20-40; DIVERSITY_SIMILARITY, which the
+reference adds only for a `diversity_object`, and ignore_items / ignore_users are not supported).
 
 Metric definitions (one user, a ranked list `L` cut at c, test items `T` with ratings `w`, hit flags `h_i = [L_i in T]`):
   PRECISION = sum(h)/|L|      PRECISION_RECALL_MIN_DEN = sum(h)/min(|T|,|L|)      RECALL = sum(h)/|T|
@@ -10,8 +14,14 @@ Metric definitions (one user, a ranked list `L` cut at c, test items `T` with ra
   NDCG = DCG(L)/DCG(best |L| of T),  DCG = sum_i (2^{w_i}-1)/ln(i+1)
   RMSE over the test items whose score is finite (seen items carry -inf and do not count)
 Every user contributes the same weight; values are means over the evaluated users; F1 is formed from the means.
+Beyond accuracy (full_metrics; `pop` = per-item nnz of recommender.get_URM_train() at evaluation time, count_c[i] = number of
+evaluated users with i in L; `beyond_accuracy_metrics` finishes them for every route, metrics.py:30-551):
+  NOVELTY = mean over users of sum_{i in L, pop_i > 0} -log2(pop_i/sum(pop))/len(pop)
+  AVERAGE_POPULARITY = mean over users of mean_{i in L} pop_i/max(pop)  (an empty list adds 0)
+  COVERAGE_ITEM = share of items with count_c > 0;  COVERAGE_USER = users with a non-empty L / rows of URM_test
+  DIVERSITY_GINI, SHANNON_ENTROPY (over the non-zero counts), DIVERSITY_HERFINDAHL, DIVERSITY_MEAN_INTER_LIST from count_c
 
-`RankedListMetrics` computes all of them for one list in one pass over the hit positions.  Where the reference's
+`RankedListMetrics` computes the accuracy values for one list in one pass over the hit positions.  Where the reference's
 evaluator works in float32 (hit counts divided in float32, the DCG sums, and therefore its running sums) this one
 does too, so that the two agree to the last digits on the reference's golden outputs (tests/test_evaluator.py)."""
 import itertools
@@ -21,6 +31,9 @@ import scipy.sparse as sps
 
 METRICS = ("ROC_AUC", "PRECISION", "PRECISION_RECALL_MIN_DEN", "RECALL", "MAP", "MRR", "NDCG", "F1",
            "HIT_RATE", "ARHR", "RMSE")
+BEYOND_ACCURACY = ("NOVELTY", "AVERAGE_POPULARITY", "DIVERSITY_MEAN_INTER_LIST", "DIVERSITY_HERFINDAHL", "COVERAGE_ITEM",
+                   "COVERAGE_USER", "DIVERSITY_GINI", "SHANNON_ENTROPY")
+FULL_METRICS = METRICS + BEYOND_ACCURACY
 _SUMMED = tuple(m for m in METRICS if m != "F1")
 
 
@@ -31,6 +44,86 @@ def get_result_string(results_run, n_decimals=7):
         fields = "".join("%s: %.*f, " % (name, n_decimals, value) for name, value in per_metric.items())
         lines.append("CUTOFF: %s - %s\n" % (cutoff, fields))
     return "".join(lines)
+
+
+def item_popularity(URM_train):
+    """Per-column nnz of URM_train with explicit zeros dropped (metrics.py Novelty / AveragePopularity __init__: CSC,
+    eliminate_zeros, ediff1d of indptr), counted straight from the stored entries without building the CSC copy."""
+    URM_train = sps.csr_matrix(URM_train)
+    return np.bincount(URM_train.indices[URM_train.data != 0], minlength=URM_train.shape[1])
+
+
+def _train_matrix(recommender_object):
+    """URM_train of the recommender at evaluation time (Evaluator.py:250); read in place where the recommender keeps it,
+    since get_URM_train() is a copy of that attribute"""
+    held = getattr(recommender_object, "URM_train", None)
+    return held if sps.issparse(held) else recommender_object.get_URM_train()
+
+
+def popularity_weights(pop):
+    """(novelty term, normalised popularity) per item in float64, as metrics.py forms them: -log2(pop/sum(pop))/len(pop)
+    (0 where pop = 0: Novelty drops zero probabilities) and pop/max(pop).  The evaluators only gather and add these."""
+    pop = np.asarray(pop)
+    probability = pop / pop.sum()
+    novelty = np.zeros(len(pop), dtype=np.float64)
+    nz = probability != 0
+    novelty[nz] = -np.log2(probability[nz]) / len(pop)
+    return novelty, pop / pop.max()
+
+
+def beyond_accuracy_metrics(counts, novelty_sum, popularity_sum, n_nonempty, n_eval, cutoff, n_items, n_users):
+    """The eight beyond-accuracy values of one cut-off in float64, from the per-item recommendation counts `counts`
+    ([n_items], summed over all evaluated users) and the sums over the users of the novelty terms, of the mean normalised
+    popularity of each list and of the non-empty lists.  Verbatim metrics.py get_metric_value."""
+    counts = np.asarray(counts, dtype=np.float64)
+    out = {}
+    out["NOVELTY"] = novelty_sum / n_eval if n_eval else 0.0
+    out["AVERAGE_POPULARITY"] = popularity_sum / n_eval if n_eval else 0.0
+    # Diversity_MeanInterList (:536-551): the cut-off itself, not the list length
+    if n_eval == 0:
+        out["DIVERSITY_MEAN_INTER_LIST"] = 1.0
+    else:
+        cooccurrences_cumulative = np.sum(counts ** 2) - n_eval * cutoff
+        all_user_couples_count = n_eval ** 2 - n_eval
+        diversity_cumulative = all_user_couples_count - cooccurrences_cumulative / cutoff
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["DIVERSITY_MEAN_INTER_LIST"] = diversity_cumulative / all_user_couples_count
+    # Diversity_Herfindahl (:210-224)
+    if counts.sum() != 0:
+        out["DIVERSITY_HERFINDAHL"] = 1 - np.sum((counts / counts.sum()) ** 2)
+    else:
+        out["DIVERSITY_HERFINDAHL"] = np.nan
+    out["COVERAGE_ITEM"] = (counts > 0).sum() / n_items                       # Coverage_Item (:45-46)
+    out["COVERAGE_USER"] = n_nonempty / n_users                               # Coverage_User (:72-73)
+    nonzero = counts[counts != 0]
+    # Gini_Diversity (:160-178)
+    n = len(nonzero)
+    srt = np.sort(nonzero)
+    index = np.arange(1, n + 1)
+    out["DIVERSITY_GINI"] = 2 * np.sum((n + 1 - index) / (n + 1) * srt / np.sum(srt))
+    # Shannon_Entropy (:260-280)
+    probability = nonzero / nonzero.sum()
+    out["SHANNON_ENTROPY"] = -np.sum(probability * np.log2(probability))
+    return {k: float(v) for k, v in out.items()}
+
+
+class _FullSums(object):
+    """Per cut-off: the [n_items] recommendation counts and the three per-user sums of the beyond-accuracy metrics."""
+
+    def __init__(self, cutoffs, n_items):
+        self.counts = {c: np.zeros(n_items, dtype=np.int64) for c in cutoffs}
+        self.novelty = dict.fromkeys(cutoffs, 0.0)
+        self.popularity = dict.fromkeys(cutoffs, 0.0)
+        self.nonempty = dict.fromkeys(cutoffs, 0)
+
+    def rows(self, results, n_eval, cutoffs, n_items, n_users):
+        """results[c] in the reference's key order: the accuracy values as given, then the beyond-accuracy ones"""
+        for c in cutoffs:
+            row = {m: results[c][m] for m in METRICS}
+            row.update(beyond_accuracy_metrics(self.counts[c], self.novelty[c], self.popularity[c], self.nonempty[c], n_eval, c,
+                                               n_items, n_users))
+            results[c] = row
+        return results
 
 
 class RankedListMetrics(object):
@@ -111,13 +204,14 @@ def _finish(sums, n_eval, cutoffs):
 class EvaluatorHoldout(object):
     EVALUATOR_NAME = "EvaluatorHoldout"
 
-    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True):
+    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
         if isinstance(URM_test_list, list):
             raise ValueError("List of URM_test not supported")
         self.cutoff_list = list(cutoff_list)
         self.max_cutoff = max(self.cutoff_list)
         self.minRatingsPerUser = minRatingsPerUser
         self.exclude_seen = exclude_seen
+        self.full_metrics = bool(full_metrics)
         self.URM_test = sps.csr_matrix(URM_test_list)
         self.n_users, self.n_items = self.URM_test.shape
         n_ratings = np.ediff1d(self.URM_test.indptr)
@@ -134,6 +228,9 @@ class EvaluatorHoldout(object):
         `recommender.recommend(..., return_scores=True)` (Evaluator.py:237-277)."""
         block_size = min(1000, int(1e8 / self.n_items))
         sums = {c: dict.fromkeys(_SUMMED, 0.0) for c in self.cutoff_list}
+        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
+        if full is not None:
+            w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(recommender_object)))
         users = np.asarray(self.usersToEvaluate, dtype=np.int64)
         for lo in range(0, len(users), max(block_size, 1)):
             batch = users[lo:lo + block_size]
@@ -151,12 +248,21 @@ class EvaluatorHoldout(object):
                     for name, value in scorer(hit, gain, c).items():
                         acc[name] += value
                     acc["RMSE"] += user_rmse
+                    if full is not None:
+                        listed = np.asarray(recommended[:c], dtype=np.int64)
+                        if len(listed) > 0:
+                            full.counts[c][listed] += 1
+                            full.novelty[c] += np.sum(w_novelty[listed])
+                            full.popularity[c] += np.sum(w_popularity[listed]) / len(listed)
+                            full.nonempty[c] += 1
         n_eval = len(users)
         if n_eval == 0:
             print("WARNING: No users had a sufficient number of relevant items")
             results = {c: dict.fromkeys(METRICS, 0.0) for c in self.cutoff_list}
         else:
             results = _finish(sums, n_eval, self.cutoff_list)
+        if full is not None:
+            results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
         return results, get_result_string(results)
 
 
@@ -168,12 +274,14 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
     top-`max_cutoff` ids of each user — `recommender.recommend_topk(...)` when the recommender has it (device
     selection, include/ganmf_hip.h: ganmf_recommend), else `recommend(..., return_scores=False)` — and computes
     the ranking metrics for a whole block of users at once.  Sums are float64 (the per-user functions above
-    follow the reference's float32 sums); the two agree to ~1e-6 relative.  RMSE needs every score of every
-    user and is reported as NaN here; SURVEY §8(f) row 1."""
+    follow the reference's float32 sums); the two agree to ~1e-6 relative.  RMSE needs every score and is reported
+    as NaN here unless `full_metrics=True`: then the device route forms it inside the selection
+    kernel (ganmf_evaluate_full) and the host route takes ids and scores from `recommend(..., return_scores=True)`."""
     EVALUATOR_NAME = "EvaluatorHoldoutFast"
 
-    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True):
-        super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen)
+    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
+        super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen,
+                         full_metrics=full_metrics)
         K = self.max_cutoff
         self._users = np.asarray(self.usersToEvaluate, dtype=np.int64)
         self._n_test = np.ediff1d(self.URM_test.indptr)[self._users].astype(np.int64)
@@ -194,7 +302,10 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
         self._test_sorted = self.URM_test.tocsr().copy()
         self._test_sorted.sort_indices()
         self._test_gain = np.power(2.0, self._test_sorted.data.astype(np.float32)).astype(np.float64) - 1.0
+        self._test_rating = np.ascontiguousarray(self._test_sorted.data, dtype=np.float32)    # RMSE on the device (full_metrics)
         self.use_device_metrics = True
+        # users per call of every route; None: the defaults of evaluateRecommender (tests force several blocks)
+        self._block_size = None
         # identifies THIS evaluator's test matrix on the device (never reused, unlike id(): CPython hands the id of a freed
         # evaluator to the next one, and a recommender keyed on it would score the new evaluator against the old test matrix)
         self._device_token = next(_DEVICE_TOKENS)
@@ -210,21 +321,74 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
             out[i, :len(l)] = l
         return out
 
+    def _topk_and_rmse(self, rec, batch):
+        """full_metrics host route: the ids of recommend(..., return_scores=True) and the sum of the users' RMSE"""
+        K = self.max_cutoff
+        lists, scores = rec.recommend(batch, remove_seen_flag=self.exclude_seen, cutoff=K, remove_top_pop_flag=False,
+                                      remove_CustomItems_flag=False, return_scores=True)
+        out = np.full((len(batch), K), -1, dtype=np.int64)
+        rmse_sum = 0.0
+        for i, (l, u) in enumerate(zip(lists, batch)):
+            out[i, :len(l)] = l
+            rmse_sum += rmse_on_test_items(scores[i], self.get_user_relevant_items(u), self.get_user_test_ratings(u))
+        return out, rmse_sum
+
+    def _device_full(self, rec, n_eval, block):
+        """ganmf_evaluate_full over all user blocks: ([n_cutoffs, 13] sums, [n_cutoffs, n_items] counts), or None when
+        the recommender declines the device route"""
+        weights = popularity_weights(item_popularity(_train_matrix(rec)))
+        counts = np.zeros((len(self.cutoff_list), self.n_items), dtype=np.int64)
+        dev = None
+        for start in range(0, n_eval, block):
+            sl = slice(start, min(start + block, n_eval))
+            part = rec.evaluate_full_on_device(self._device_token, self._test_sorted, self._test_gain, self._test_rating,
+                                               weights, self._users[sl], self.cutoff_list, self._disc, self._ideal_cum[sl],
+                                               remove_seen_flag=self.exclude_seen, counts=counts)
+            if part is None:
+                return None
+            dev = part if dev is None else dev + part
+        return dev, counts
+
     def evaluateRecommender(self, recommender_object):
         K = self.max_cutoff
-        block_size = max(1, min(4096, int(1e8 / self.n_items)))
+        block_size = self._block_size or max(1, min(4096, int(1e8 / self.n_items)))
         names = _SUMMED
         sums = {c: {m: 0.0 for m in names} for c in self.cutoff_list}
         n_eval = len(self._users)
+        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         inv_rank = 1.0 / np.arange(1, K + 1, dtype=np.float64)
-        if self.use_device_metrics and n_eval > 0 and hasattr(recommender_object, "evaluate_on_device"):
+        if (full is not None and self.use_device_metrics and n_eval > 0
+                and hasattr(recommender_object, "evaluate_full_on_device")):
+            # the whole row on the device: per cut-off 13 sums and the per-item counts come back, added up over the user blocks
+            try:
+                got = self._device_full(recommender_object, n_eval, self._block_size or max(1, int(1e8 / self.n_items)))
+            except MemoryError:
+                got = None
+            if got is not None:
+                from ._lib import EVAL_FULL_METRICS
+                dev, counts = got
+                col = {name: i for i, name in enumerate(EVAL_FULL_METRICS)}
+                for ci, c in enumerate(self.cutoff_list):
+                    for name in _SUMMED:
+                        sums[c][name] = float(dev[ci, col[name]])
+                    full.counts[c] = counts[ci]
+                    full.novelty[c] = float(dev[ci, col["NOVELTY"]])
+                    full.popularity[c] = float(dev[ci, col["AVERAGE_POPULARITY"]])
+                    full.nonempty[c] = int(round(dev[ci, col["NON_EMPTY"]]))
+                results = _finish(sums, n_eval, self.cutoff_list)
+                for c in self.cutoff_list:
+                    results[c] = {m: float(v) for m, v in results[c].items()}
+                results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
+                return results, get_result_string(results)
+        if full is None and self.use_device_metrics and n_eval > 0 and hasattr(recommender_object, "evaluate_on_device"):
             # everything on the device: scores, seen mask, top-k AND the metric sums (only len(cutoffs) x 9 doubles come back)
             # in user blocks: the device forms a [block, n_items] score matrix (+ block x K doubles) per call, the same cap as
             # the host routes; the [cutoffs, 9] partial sums are added here in block order.  Out of device memory -> host route.
             dev = None
+            step = self._block_size or max(1, int(1e8 / self.n_items))
             try:
-                for start in range(0, n_eval, max(1, int(1e8 / self.n_items))):
-                    sl = slice(start, min(start + max(1, int(1e8 / self.n_items)), n_eval))
+                for start in range(0, n_eval, step):
+                    sl = slice(start, min(start + step, n_eval))
                     part = recommender_object.evaluate_on_device(self._device_token, self._test_sorted, self._test_gain,
                                                                  self._users[sl], self.cutoff_list, self._disc,
                                                                  self._ideal_cum[sl], remove_seen_flag=self.exclude_seen)
@@ -244,10 +408,15 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
                     results[c] = {m: float(v) for m, v in results[c].items()}
                     results[c]["RMSE"] = float("nan")
                 return results, get_result_string(results)
+        if full is not None:
+            w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(recommender_object)))
         for start in range(0, n_eval, block_size):
             sl = slice(start, min(start + block_size, n_eval))
             batch = self._users[sl]
-            items = self._topk(recommender_object, batch)
+            if full is not None:
+                items, rmse_sum = self._topk_and_rmse(recommender_object, batch)
+            else:
+                items = self._topk(recommender_object, batch)
             assert items.shape == (len(batch), K)
             valid = items >= 0
             safe = np.where(valid, items, 0)
@@ -284,12 +453,23 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
                 r["MRR"] += np.where(hits > 0, inv_rank[first], 0.0).sum()
                 p_at_k = rel * np.cumsum(rel, axis=1) * inv_rank[:c]
                 r["MAP"] += np.where(len_c > 0, p_at_k.sum(axis=1) / np.maximum(np.minimum(n_test, len_c), 1.0), 0.0).sum()
+                if full is not None:
+                    r["RMSE"] += rmse_sum
+                    listed = valid[:, :c]
+                    full.counts[c] += np.bincount(items[:, :c][listed], minlength=self.n_items)
+                    full.novelty[c] += (w_novelty[safe[:, :c]] * listed).sum()
+                    pop_sum = (w_popularity[safe[:, :c]] * listed).sum(axis=1)
+                    full.popularity[c] += np.where(len_c > 0, pop_sum / nz, 0.0).sum()
+                    full.nonempty[c] += int((len_c > 0).sum())
         if n_eval > 0:
             results = _finish(sums, n_eval, self.cutoff_list)
             for c in self.cutoff_list:
                 results[c] = {m: float(v) for m, v in results[c].items()}
-                results[c]["RMSE"] = float("nan")
+                if full is None:
+                    results[c]["RMSE"] = float("nan")
         else:
             results = {c: dict.fromkeys(METRICS, 0.0) for c in self.cutoff_list}
             print("WARNING: No users had a sufficient number of relevant items")
+        if full is not None:
+            results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
         return results, get_result_string(results)

@@ -237,6 +237,29 @@ int ganmf_set_test_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* in
 int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
                    int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums);
 
+/* The reference's full metric row on the device (Base/Evaluation/Evaluator.py:262-335 with every metric object that
+ * create_empty_metrics_dict builds, Evaluator.py:43-84, except DIVERSITY_SIMILARITY; no ignore_items / ignore_users).
+ * ganmf_set_test_ratings: the rating (float32) of every stored entry of the matrix ganmf_set_test_csr holds, in its order;
+ *   each ganmf_set_test_csr drops them.  Needed by RMSE (metrics.py:634 rmse).
+ * ganmf_set_eval_item_weights: two per-item vectors of the evaluation width, formed by the caller in float64 from the
+ *   per-column nnz `pop` of URM_train (evaluation orientation, zeros eliminated; Evaluator.py:250):
+ *   novelty[i] = -log2(pop[i] / sum(pop)) / len(pop), 0 where pop[i] = 0 (metrics.py:298-347 Novelty),
+ *   popularity[i] = pop[i] / max(pop) (metrics.py:355-398 AveragePopularity).  The device only gathers and adds them.
+ * ganmf_evaluate_full: ganmf_evaluate's ranking and lookups, and in the same selection kernel -- after the seen mask and the
+ *   score filter, before the first selection round -- each row's fp32 RMSE over its test items (NaN when no error is finite).
+ *   sums[n_cutoffs, GANMF_EVAL_FULL_METRICS] (overwritten): ganmf_evaluate's nine sums, then the sums over the n users of
+ *     RMSE, NOVELTY (novelty summed over the list cut at c), AVERAGE_POPULARITY (mean popularity of a non-empty list, else 0)
+ *     and the number of non-empty lists (Coverage_User).
+ *   counts[n_cutoffs, W] (ADDED into): times each item appears in the lists cut at each cut-off -- what Coverage_Item,
+ *     Gini_Diversity, Shannon_Entropy, Diversity_Herfindahl and Diversity_MeanInterList count (metrics.py:30-280,465-551);
+ *     the host finishes those from the counts summed over all its calls.
+ *   Same limits as ganmf_evaluate; also needs both uploads above for the current test matrix and width. */
+#define GANMF_EVAL_FULL_METRICS 13
+int ganmf_set_test_ratings(ganmf_handle* h, const float* ratings, int64_t nnz);
+int ganmf_set_eval_item_weights(ganmf_handle* h, const double* novelty, const double* popularity, int64_t width);
+int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
+                        int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts);
+
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch);
