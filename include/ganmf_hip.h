@@ -123,13 +123,20 @@ int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* ind
  * Data-parallel handles (communicator attached, world_size > 1): the Adam moments (GANMF_SLOT_ADAM_M / _V) of the
  * REPLICATED tensors (item_embeddings and every discriminator tensor) live sharded over the ranks -- rank r updates
  * slice r only -- so these two slots are rejected (-1) for them; parameters and the best snapshot are whole and identical
- * on every rank, and user_embeddings (rank-owned rows) is whole in every slot. */
+ * on every rank, and user_embeddings (rank-owned rows) is whole in every slot.
+ * Guarantee (single-GPU handle; tests/test_gpu_warm_start.py): GANMF_SLOT_PARAM + GANMF_SLOT_ADAM_M + GANMF_SLOT_ADAM_V of every
+ * tensor id, together with the four powers of ganmf_get_adam_powers, are the COMPLETE training state.  A fresh handle of the same
+ * configuration and URM that is given them continues the run they were read from bit for bit (losses, tensors, moments, scores),
+ * and writing a handle's own exported state back into it changes nothing: whatever else a handle keeps (the live side of the
+ * item_embeddings double buffer, cached operand copies, lr_t tables, per-pass arenas) is derived from them. */
 int ganmf_set_tensor(ganmf_handle* h, int tensor_id, int slot, const float* host, int64_t n);
 int ganmf_get_tensor(ganmf_handle* h, int tensor_id, int slot, float* host, int64_t n);
 int ganmf_tensor_shape(ganmf_handle* h, int tensor_id, int64_t* rows, int64_t* cols);
 
 /* Adam beta-power accumulators of the two optimizers (AdamOptimizer._finish): 4 floats
- * {b1p_D, b2p_D, b1p_G, b2p_G}; exposed for save/restore and tests. */
+ * {b1p_D, b2p_D, b1p_G, b2p_G} -- in this order: a discriminator step advances the first pair, a generator step the second;
+ * exposed for save/restore and tests.  Part of the complete training state (see ganmf_set_tensor): lr_t of the next step is
+ * formed from them, nothing else remembers the step count. */
 int ganmf_get_adam_powers(ganmf_handle* h, float out4[4]);
 int ganmf_set_adam_powers(ganmf_handle* h, const float in4[4]);
 
@@ -198,7 +205,8 @@ int ganmf_recommend(ganmf_handle* h, const int32_t* ids, int64_t n, int transpos
 int ganmf_set_score_filter(ganmf_handle* h, const int32_t* items, int64_t n_items, int mask_cold_rows);
 
 /* Replaces save_current_model / load_model (GANMF.py:249-255, Utils_.py:292-294): device-side
- * copies of all trainable tensors to / from their `best` twins. */
+ * copies of all trainable tensors to / from their `best` twins.  As the reference's load_model restores variables only,
+ * ganmf_restore_best overwrites GANMF_SLOT_PARAM only: the Adam moments and the beta powers are left untouched and run on. */
 int ganmf_snapshot_best(ganmf_handle* h);
 int ganmf_restore_best(ganmf_handle* h);
 

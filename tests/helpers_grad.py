@@ -5,7 +5,8 @@
 * _rowwise / row_ratio / allowed: each row of a gradient is held to its own bound, not to the tensor's largest element (one wrong
   row of a rarely rated item, or of one user, must fail).
 * grad_from_m: the gradient of one step read from SLOT_ADAM_M after a step from zero moments (m = (1 - beta1) g).
-* plan_lines / forms: the kernel forms a run took, from the GANMF_DEBUG_PLAN lines and the class names of Engine.profile_read()."""
+* plan_lines / forms: the kernel forms a run took, from the GANMF_DEBUG_PLAN lines and the class names of Engine.profile_read().
+* adam_powers_after / set_state: a warm training state (parameters, both moments, the four beta powers) loaded into an oracle."""
 import re
 
 import numpy as np
@@ -176,10 +177,13 @@ def grad_from_m(m):
 
 class MomentBounds:
     """|terms| bounds of the Adam moments after T updates, composed from the per-step gradient bounds B_t:
-    m: sum_t (1 - b1) b1^(T - t) B_t;   v: sum_t (1 - b2) b2^(T - t) 2 |g_t| B_t."""
+    m: sum_t (1 - b1) b1^(T - t) B_t;   v: sum_t (1 - b2) b2^(T - t) 2 |g_t| B_t.
+    m0 / v0 (name -> array, a warm start): the magnitudes of the initial moments enter as |m0| b1^T and |v0| b2^T, decayed like
+    every term behind them; without them the bounds are those of a start from zero moments."""
 
-    def __init__(self):
-        self.m, self.v = {}, {}
+    def __init__(self, m0=None, v0=None):
+        self.m = {n: np.abs(np.asarray(a, np.float64)) for n, a in (m0 or {}).items()}
+        self.v = {n: np.abs(np.asarray(a, np.float64)) for n, a in (v0 or {}).items()}
 
     def add(self, name, g, bound):
         g, bound = np.abs(np.asarray(g, np.float64)), np.asarray(bound, np.float64)
@@ -187,6 +191,26 @@ class MomentBounds:
         v = self.v.get(name, 0.0)
         self.m[name] = BETA1 * m + (1.0 - BETA1) * bound
         self.v[name] = BETA2 * v + (1.0 - BETA2) * 2.0 * g * bound
+
+
+# -- a warm training state -------------------------------------------------------------------------------------------------------
+def adam_powers_after(t):
+    """(beta1_power, beta2_power) after t optimizer steps, formed in fp32 by repeated multiplication as _Adam.finish forms them"""
+    b1, b2 = np.float32(BETA1), np.float32(BETA2)
+    p1, p2 = b1, b2
+    for _ in range(t):
+        p1, p2 = np.float32(p1 * b1), np.float32(p2 * b2)
+    return p1, p2
+
+
+def set_state(o, params, m, v, powers):
+    """Loads fp32 parameters, Adam moments (name -> array, any shape of the right size) and powers = (b1p_D, b2p_D, b1p_G, b2p_G)
+    into an oracle, widened to its dtype: the _Adam attributes it already has (slots[name] = (m, v), b1p, b2p)."""
+    o.set_params(**{n: np.asarray(a).reshape(o.p[n].shape) for n, a in params.items()})
+    for opt, names, (b1p, b2p) in ((o.opt_d, o.D_NAMES, powers[:2]), (o.opt_g, o.G_NAMES, powers[2:])):
+        for n in names:
+            opt.slots[n] = tuple(np.array(np.asarray(a).reshape(o.p[n].shape), dtype=o.dtype) for a in (m[n], v[n]))
+        opt.b1p, opt.b2p = opt.dt(b1p), opt.dt(b2p)
 
 
 # -- route probe -----------------------------------------------------------------------------------------------------------------
@@ -217,6 +241,14 @@ def plan_lines(text):
             out.append(dict(tag=tag.strip(), M=int(M), N=int(N), K=int(K), batch=int(batch), tile=int(tile), ring=int(ring),
                             kg=int(kg), nsplit=int(nsplit), mode=mode, rest=rest.strip()))
     return out
+
+
+_URM_PLAN = re.compile(r"\[ganmf urm\] set_urm_csr .*-> sparse_g (\d) sparse_d (\d)")
+
+
+def urm_paths(text):
+    """(sparse_g, sparse_d) of every URM upload of a GANMF_DEBUG_PLAN run"""
+    return [(int(a), int(b)) for a, b in _URM_PLAN.findall(text)]
 
 
 def forms(plans, classes):

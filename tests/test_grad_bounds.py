@@ -150,3 +150,44 @@ def test_adam_first_step_is_blind_to_gradient_scale():
     assert (a >= 0.11).any() and np.median(d / lr) <= 1e-4
     # ... while the rule sees it at once
     _fails(1.5 * g, g, GANMF[5]["We"], GANMF[6]["We"], "1.5 g")
+
+
+def test_moment_bounds_initial_magnitude():
+    """A warm start: |m0| and |v0| enter decayed by b1^T and b2^T; without them the bounds are those from zero moments."""
+    from tests.helpers_grad import MomentBounds
+    rng = np.random.RandomState(0)
+    g = [rng.randn(3, 4) for _ in range(5)]
+    b = [np.abs(rng.randn(3, 4)) for _ in range(5)]
+    m0, v0 = rng.randn(3, 4), np.abs(rng.randn(3, 4))
+    cold, cold2, warm = MomentBounds(), MomentBounds(None, None), MomentBounds({"w": m0}, {"w": v0})
+    for gi, bi in zip(g, b):
+        for mb in (cold, cold2, warm):
+            mb.add("w", gi, bi)
+    np.testing.assert_array_equal(cold.m["w"], cold2.m["w"])
+    np.testing.assert_array_equal(cold.v["w"], cold2.v["w"])
+    np.testing.assert_allclose(warm.m["w"] - cold.m["w"], np.abs(m0) * 0.9 ** 5, rtol=1e-9)
+    np.testing.assert_allclose(warm.v["w"] - cold.v["w"], v0 * 0.999 ** 5, rtol=1e-9)
+
+
+def test_set_state_loads_an_oracle():
+    """set_state: fp32 values widened to the oracle's dtype and reshaped to its variables; powers in the order {D, D, G, G},
+    formed by adam_powers_after as _Adam.finish forms them."""
+    from tests.helpers_grad import adam_powers_after, set_state
+    o = GANMFOracle(6, 5, 2, 3, dtype=np.float64)
+    rng = np.random.RandomState(1)
+    p = {n: rng.randn(*a.shape).astype(np.float32) for n, a in o.p.items()}
+    m = {n: rng.randn(1, a.size).astype(np.float32) for n, a in o.p.items()}
+    v = {n: np.abs(rng.randn(a.size)).astype(np.float32) for n, a in o.p.items()}
+    opt = _Adam(1e-3, np.float32)
+    for _ in range(7):
+        opt.finish()
+    assert adam_powers_after(7) == (opt.b1p, opt.b2p) and adam_powers_after(0) == (np.float32(0.9), np.float32(0.999))
+    pw = adam_powers_after(7) + adam_powers_after(2)
+    set_state(o, p, m, v, pw)
+    for n in o.p:
+        slots = (o.opt_d if n in o.D_NAMES else o.opt_g).slots[n]
+        assert o.p[n].dtype == np.float64 and slots[0].shape == o.p[n].shape and slots[1].dtype == np.float64
+        np.testing.assert_array_equal(o.p[n], p[n].astype(np.float64))
+        np.testing.assert_array_equal(slots[0].ravel(), m[n].ravel().astype(np.float64))
+        np.testing.assert_array_equal(slots[1].ravel(), v[n].ravel().astype(np.float64))
+    assert (o.opt_d.b1p, o.opt_d.b2p, o.opt_g.b1p, o.opt_g.b2p) == tuple(np.float64(x) for x in pw)
