@@ -365,6 +365,78 @@ class GANMF(BaseRecommender):
                                             transposed=(self.mode == 'item'), remove_seen=remove_seen_flag, counts=counts)
         return sums
 
+    # ---- per-user candidate lists (Base/Evaluation/Evaluator.py:419-590, EvaluatorNegativeItemSample) ----------------
+    @property
+    def honours_items_to_compute(self):
+        """whether `recommend(..., items_to_compute=...)` restricts the ranking: only under the MF contract (the reference's GANMF
+        accepts the argument and ignores it, GANMF.py:285-292)"""
+        return self.score_contract == "mf"
+
+    def _candidates_on_device(self, candidates_csr, key=None):
+        """uploads the candidate matrix unless the engine already holds the one of this `key` (an evaluator's device token)"""
+        held = getattr(self, "_cand_on_device", None)
+        if key is None or held is None or held[0] != key or held[1] is not self.engine:
+            m = sps.csr_matrix(candidates_csr)
+            if m.shape != (self.n_users, self.n_items):
+                raise ValueError("candidates must be a %d x %d matrix, given %r" % (self.n_users, self.n_items, m.shape))
+            self.engine.set_candidates(m)
+            self._cand_on_device = (key, self.engine)
+
+    def recommend_candidates(self, user_id_array, candidates_csr, cutoff, remove_seen_flag=True, candidates_key=None):
+        """Top-`cutoff` item ids of every user AMONG THAT USER'S OWN CANDIDATES, the stored entries of row `user` of
+        `candidates_csr` (users x items, e.g. EvaluatorNegativeItemSample.URM_items_to_rank): an [n, cutoff] int32 array, -1 padded
+        where a user has fewer unmasked candidates; ties go to the smaller item id.  Candidate scoring, seen-item mask and
+        selection run in one HIP kernel (ganmf_recommend_candidates); no full-width score row is formed.  This is an explicit
+        API, not the reference's `recommend`: it restricts to the candidates under either score contract (the cold-user mask
+        stays the contract's).  `candidates_key`: a token that names this candidate matrix (an evaluator's device token); calls
+        with the same token reuse the matrix the device already holds instead of uploading it again.  A cut-off above
+        _lib.RECOMMEND_MAX_CUTOFF or a requested user with more than _lib.CANDIDATES_MAX_PER_ROW candidates is an error
+        (ValueError / GanmfError)."""
+        self._require_engine()
+        ids = np.atleast_1d(np.asarray(user_id_array)).reshape(-1)
+        if not 1 <= cutoff <= self.n_items:
+            raise ValueError("recommend_candidates: cutoff %r outside [1, %d]" % (cutoff, self.n_items))
+        self._candidates_on_device(candidates_csr, key=candidates_key)
+        items, _ = self.engine.recommend_candidates(ids, cutoff, transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
+        return items
+
+    def evaluate_candidates_on_device(self, evaluator_key, urm_test_sorted, gains, candidates_csr, user_id_array, cutoffs, disc,
+                                      ideal_cum, remove_seen_flag=True, ratings=None, item_weights=None, counts=None):
+        """Metric sums for EvaluatorNegativeItemSampleFast without leaving the device (ganmf_evaluate_candidates): every user
+        ranked among the stored entries of its row of `candidates_csr`.  `ratings` None: [len(cutoffs), 9] float64 in the order
+        of ganmf_amd._lib.EVAL_METRICS; `ratings` and `item_weights` given (full row): the [len(cutoffs), 13] sums of
+        EVAL_FULL_METRICS, the lists' per-item counts added into `counts`.  The test and candidate matrices are uploaded once
+        per evaluator (`evaluator_key`).
+        Returns None -- the evaluator then takes another route -- under score_contract="ganmf" (the reference's GANMF ignores
+        items_to_compute, so the reference's evaluator around it ranks the whole catalogue), for cut-offs the device selection
+        does not take, and when a requested user has more than _lib.CANDIDATES_MAX_PER_ROW candidates."""
+        self._require_engine()
+        if self.score_contract != "mf":
+            return None
+        cutoffs = list(cutoffs)
+        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or min(cutoffs) < 1 or max(cutoffs) > min(L.RECOMMEND_MAX_CUTOFF, self.n_items):
+            return None
+        ids = np.asarray(user_id_array).reshape(-1)
+        per_row = np.ediff1d(candidates_csr.indptr)
+        if len(ids) and per_row[ids].max() > L.CANDIDATES_MAX_PER_ROW:
+            return None
+        full = ratings is not None
+        held = getattr(self, "_test_on_device", None)
+        if held is None or held[0] != evaluator_key or held[1] is not self.engine or (full and len(held) < 3):
+            self.engine.set_test(urm_test_sorted, gains)
+            if full:
+                self.engine.set_test_ratings(ratings)
+            self._test_on_device = (evaluator_key, self.engine, True) if full else (evaluator_key, self.engine)
+        if full:
+            held = getattr(self, "_weights_on_device", None)
+            if (held is None or held[1] is not self.engine or not all(np.array_equal(a, b) for a, b in zip(held[0], item_weights))):
+                self.engine.set_eval_item_weights(*item_weights)
+                self._weights_on_device = (tuple(np.array(w, dtype=np.float64) for w in item_weights), self.engine)
+        self._candidates_on_device(candidates_csr, key=evaluator_key)
+        got = self.engine.evaluate_candidates(ids, cutoffs, disc, ideal_cum, transposed=(self.mode == 'item'),
+                                              remove_seen=remove_seen_flag, counts=counts, full=full)
+        return got[0] if full else got
+
     def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None,
                   remove_top_pop_flag=False, remove_CustomItems_flag=False, return_scores=False):
         device_ok = (not return_scores and not remove_top_pop_flag

@@ -19,13 +19,15 @@ EVAL_MAX_CUTOFFS = 8
 # ganmf_evaluate_full's sums per cut-off (GANMF_EVAL_FULL_METRICS): NON_EMPTY = number of non-empty lists
 EVAL_FULL_METRICS = EVAL_METRICS + ("RMSE", "NOVELTY", "AVERAGE_POPULARITY", "NON_EMPTY")
 PROF_MAX = 48
+RECOMMEND_MAX_CUTOFF = 1024        # include/ganmf_hip.h GANMF_RECOMMEND_MAX_CUTOFF
+CANDIDATES_MAX_PER_ROW = 8192     # include/ganmf_hip.h GANMF_CANDIDATES_MAX_PER_ROW
 
 # every exported symbol of include/ganmf_hip.h (checked by tests/test_abi.py)
 SYMBOLS = [
     "ganmf_create", "ganmf_destroy", "ganmf_comm_unique_id", "ganmf_comm_init", "ganmf_comm_init_local", "ganmf_comm_abort", "ganmf_comm_info", "ganmf_set_urm_csr",
     "ganmf_set_tensor", "ganmf_get_tensor", "ganmf_tensor_shape", "ganmf_get_adam_powers",
     "ganmf_set_adam_powers", "ganmf_train_epoch", "ganmf_train_epoch_ragged", "ganmf_train_step", "ganmf_scores",
-    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
+    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
     "ganmf_bench_scores", "ganmf_gemm_f32", "ganmf_crc32c", "ganmf_device_count", "ganmf_abi_version", "ganmf_last_error",
 ]
 
@@ -103,6 +105,10 @@ def load_library():
         "ganmf_set_eval_item_weights": (C.c_int, [vp, P(C.c_double), P(C.c_double), i64]),
         "ganmf_evaluate_full": (C.c_int, [vp, P(C.c_int32), i64, C.c_int, C.c_int, P(C.c_int32), i32, P(C.c_double),
                                           P(C.c_double), P(C.c_double), P(C.c_int64)]),
+        "ganmf_set_candidates_csr": (C.c_int, [vp, P(C.c_int64), P(C.c_int32), i64, i64]),
+        "ganmf_recommend_candidates": (C.c_int, [vp, P(C.c_int32), i64, C.c_int, i32, C.c_int, P(C.c_int32), f32p]),
+        "ganmf_evaluate_candidates": (C.c_int, [vp, P(C.c_int32), i64, C.c_int, C.c_int, P(C.c_int32), i32, P(C.c_double),
+                                                P(C.c_double), P(C.c_double), P(C.c_int64)]),
         "ganmf_crc32c": (C.c_uint32, [C.c_uint32, vp, C.c_uint64]),
         "ganmf_snapshot_best": (C.c_int, [vp]),
         "ganmf_restore_best": (C.c_int, [vp]),

@@ -39,6 +39,7 @@
 #include "gemm_persist.hpp"
 #include "gemm_bf16p.hpp"
 #include "kernels.hpp"
+#include "cand_topk.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)

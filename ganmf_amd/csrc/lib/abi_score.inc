@@ -228,6 +228,118 @@ static int recommend_device(ganmf_handle* h, const char* who, const int32_t* ids
   return 0;
 }
 
+int ganmf_set_candidates_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols) {
+  if (!h) return fail(-1, "null handle");
+  if (indptr) {        // validate before the held matrix is touched
+    if (n_rows < 1 || n_cols < 1) return fail(-1, "ganmf_set_candidates_csr: empty matrix");
+    if (indptr[0] != 0 || indptr[n_rows] < 0 || (indptr[n_rows] > 0 && !indices)) return fail(-1, "ganmf_set_candidates_csr: bad indptr");
+    for (int64_t r = 0; r < n_rows; ++r)
+      if (indptr[r + 1] < indptr[r]) return fail(-1, "ganmf_set_candidates_csr: indptr not monotone at row %lld", (long long)r);
+    for (int64_t j = 0; j < indptr[n_rows]; ++j)
+      if (indices[j] < 0 || indices[j] >= n_cols) return fail(-1, "ganmf_set_candidates_csr: column index %d out of range", indices[j]);
+  }
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(h->cand_indptr); hipFree(h->cand_indices);
+  h->cand_indptr = nullptr; h->cand_indices = nullptr; h->cand_rows = h->cand_cols = 0;
+  h->cand_indptr_host.clear();
+  if (!indptr) return 0;
+  // canonical rows (columns ascending, a repeated column kept once), as ganmf_set_urm_csr makes the training matrix canonical
+  std::vector<long long> ip((size_t)n_rows + 1, 0);
+  std::vector<int> ix;
+  ix.reserve((size_t)indptr[n_rows]);
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const size_t at = ix.size();
+    ix.insert(ix.end(), indices + indptr[r], indices + indptr[r + 1]);
+    std::sort(ix.begin() + at, ix.end());
+    ix.erase(std::unique(ix.begin() + at, ix.end()), ix.end());
+    ip[(size_t)r + 1] = (long long)ix.size();
+  }
+  HIP_TRY(hipMalloc((void**)&h->cand_indptr, ip.size() * sizeof(long long)));
+  HIP_TRY(hipMalloc((void**)&h->cand_indices, std::max<size_t>(ix.size(), 1) * sizeof(int)));
+  HIP_TRY(hipMemcpy(h->cand_indptr, ip.data(), ip.size() * sizeof(long long), hipMemcpyHostToDevice));
+  if (!ix.empty()) HIP_TRY(hipMemcpy(h->cand_indices, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice));
+  h->cand_indptr_host.swap(ip);
+  h->cand_rows = n_rows; h->cand_cols = n_cols;     // set last: a failed upload leaves "no candidate matrix"
+  return 0;
+}
+
+// candidate scores -> masks -> top-`cutoff` of the rows `ids` among their own candidates (cand_topk.hpp), left on the device in
+// h->topk_items / h->topk_vals ([n, cutoff]) as recommend_device leaves them.  Every check runs before anything is enqueued.
+static int candidates_device(ganmf_handle* h, const char* who, const int32_t* ids, int64_t n, int transposed, int32_t cutoff,
+                             int remove_seen, int** ids_dev_out, const RmseP* rmse = nullptr) {
+  if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
+  const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
+  if (!h->cand_indptr) return fail(-1, "%s: no candidate matrix (ganmf_set_candidates_csr)", who);
+  if (h->cand_rows != limit || h->cand_cols != W)
+    return fail(-1, "%s: the candidate matrix is %lld x %lld, transposed = %d needs %d x %d", who, (long long)h->cand_rows,
+                (long long)h->cand_cols, transposed, limit, W);
+  if (cutoff < 1 || cutoff > W || cutoff > GANMF_RECOMMEND_MAX_CUTOFF)
+    return fail(-1, "%s: cutoff %d out of range [1,%d]", who, cutoff, std::min(W, GANMF_RECOMMEND_MAX_CUTOFF));
+  long long longest = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= limit) return fail(-1, "%s: id %d out of range [0,%d)", who, ids[i], limit);
+    const long long len = h->cand_indptr_host[(size_t)ids[i] + 1] - h->cand_indptr_host[(size_t)ids[i]];
+    if (len > CAND_MAX_PER_ROW)
+      return fail(-1, "%s: row %d has %lld candidates, at most %d (GANMF_CANDIDATES_MAX_PER_ROW)", who, ids[i], len, CAND_MAX_PER_ROW);
+    longest = std::max(longest, len);
+  }
+  if (remove_seen && (!h->seen_indptr || h->seen_rows != limit || h->seen_cols != W))
+    return fail(-1, "%s: remove_seen needs ganmf_set_seen_csr with a %d x %d matrix", who, limit, W);
+  const unsigned char* fmask; const long long* fcold;
+  TRY(score_filter_args(h, who, W, limit, &fmask, &fcold));
+  Tensor& rowsT = transposed ? h->V : h->Ue;
+  Tensor& colsT = transposed ? h->Ue : h->V;
+  CandP p{};
+  p.cap = round_up((int)std::max<long long>(longest, 1), 64);
+  const size_t shmem = ((size_t)2 * p.cap + (h->ldk > CAND_REG_LD ? (size_t)h->ldk : 0)) * sizeof(float);
+  if (shmem > 144 * 1024) return fail(-1, "%s: %d factors beside %lld candidates do not fit one workgroup's LDS", who, h->k, longest);
+  HIP_TRY(hipSetDevice(h->dev));
+  int* ids_dev = nullptr;
+  TRY(upload_ids(h, ids, n, &ids_dev));
+  const size_t need = (size_t)n * cutoff;
+  if (need > h->topk_cap) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    hipFree(h->topk_items); hipFree(h->topk_vals);
+    h->topk_items = nullptr; h->topk_vals = nullptr; h->topk_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h->topk_items, need * sizeof(int)));
+    HIP_TRY(hipMalloc((void**)&h->topk_vals, need * sizeof(float)));
+    h->topk_cap = need;
+  }
+  p.rows = rowsT.p; p.cols = colsT.p; p.ld = h->ldk; p.k = h->k; p.ids = ids_dev;
+  p.c_indptr = h->cand_indptr; p.c_indices = h->cand_indices;
+  p.seen_indptr = remove_seen ? h->seen_indptr : nullptr; p.seen_indices = h->seen_indices;
+  p.item_mask = fmask; p.cold_indptr = fcold; p.cutoff = cutoff;
+  p.out_items = h->topk_items; p.out_vals = h->topk_vals;
+  if (rmse) {
+    if (shmem > 48 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(cand_topk_rmse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    GANMF_LAUNCH(cand_topk_rmse_kernel, dim3((int)n), dim3(256), shmem, h->st, p, *rmse);
+  } else {
+    if (shmem > 48 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(cand_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    GANMF_LAUNCH(cand_topk_kernel, dim3((int)n), dim3(256), shmem, h->st, p);
+  }
+  HIP_TRY(hipGetLastError());
+  if (ids_dev_out) *ids_dev_out = ids_dev;
+  return 0;
+}
+
+int ganmf_recommend_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t cutoff, int remove_seen,
+                               int32_t* out_items, float* out_scores) {
+  if (!h || !ids || !out_items) return fail(-1, "ganmf_recommend_candidates: null argument");
+  int rc = candidates_device(h, "ganmf_recommend_candidates", ids, n, transposed, cutoff, remove_seen, nullptr);
+  if (rc == 0) {
+    const size_t need = (size_t)n * cutoff;
+    hipError_t e = hipMemcpyAsync(out_items, h->topk_items, need * sizeof(int), hipMemcpyDeviceToHost, h->st);
+    if (e == hipSuccess && out_scores) e = hipMemcpyAsync(out_scores, h->topk_vals, need * sizeof(float), hipMemcpyDeviceToHost, h->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+    if (e != hipSuccess) rc = fail(-2, "ganmf_recommend_candidates: %s", hipGetErrorString(e));
+    hipStreamSynchronize(h->st);
+  }
+  return rc;
+}
+
 int ganmf_set_test_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const double* gains, int64_t n_rows,
                        int64_t n_cols) {
   if (!h || !indptr || (!indices && indptr[n_rows] > 0) || (!gains && indptr[n_rows] > 0)) return fail(-1, "ganmf_set_test_csr: null argument");
@@ -258,20 +370,23 @@ int ganmf_set_test_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* in
   return 0;
 }
 
-int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
-                   int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums) {
-  if (!h || !ids || !cutoffs || !disc || !ideal_cum || !sums) return fail(-1, "ganmf_evaluate: null argument");
-  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "ganmf_evaluate: 1..%d cut-offs per call", GANMF_EVAL_MAX_CUTOFFS);
+// ganmf_evaluate (cand = false: full-width ranking, recommend_device) and the nine-sum form of ganmf_evaluate_candidates (cand = true:
+// each row's own candidate list, candidates_device); everything after the ranking is shared
+static int evaluate_impl(ganmf_handle* h, const char* who, bool cand, const int32_t* ids, int64_t n, int transposed, int remove_seen,
+                         const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums) {
+  if (!h || !ids || !cutoffs || !disc || !ideal_cum || !sums) return fail(-1, "%s: null argument", who);
+  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
   if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
-    return fail(-1, "ganmf_evaluate: needs ganmf_set_test_csr with a %d x %d matrix", limit, W);
+    return fail(-1, "%s: needs ganmf_set_test_csr with a %d x %d matrix", who, limit, W);
   int K = 0;
   for (int i = 0; i < n_cutoffs; ++i) {
-    if (cutoffs[i] < 1) return fail(-1, "ganmf_evaluate: cut-off %d", cutoffs[i]);
+    if (cutoffs[i] < 1) return fail(-1, "%s: cut-off %d", who, cutoffs[i]);
     K = std::max(K, (int)cutoffs[i]);
   }
   int* ids_dev = nullptr;
-  TRY(recommend_device(h, "ganmf_evaluate", ids, n, transposed, K, remove_seen, &ids_dev));
+  if (cand) TRY(candidates_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
+  else TRY(recommend_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
   const int grid = (int)((n + 255) / 256);
   const size_t n_part = (size_t)grid * n_cutoffs * EVAL_METRICS;
   const size_t need = (size_t)K + (size_t)n * K + n_part;
@@ -302,6 +417,11 @@ int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transpose
   return 0;
 }
 
+int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
+                   int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums) {
+  return evaluate_impl(h, "ganmf_evaluate", false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums);
+}
+
 int ganmf_set_test_ratings(ganmf_handle* h, const float* ratings, int64_t nnz) {
   if (!h || (nnz > 0 && !ratings)) return fail(-1, "ganmf_set_test_ratings: null argument");
   if (!h->test_indptr) return fail(-1, "ganmf_set_test_ratings: needs ganmf_set_test_csr first");
@@ -328,19 +448,21 @@ int ganmf_set_eval_item_weights(ganmf_handle* h, const double* novelty, const do
   return 0;
 }
 
-int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
-                        int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts) {
-  if (!h || !ids || !cutoffs || !disc || !ideal_cum || !sums || !counts) return fail(-1, "ganmf_evaluate_full: null argument");
-  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "ganmf_evaluate_full: 1..%d cut-offs per call", GANMF_EVAL_MAX_CUTOFFS);
-  if (n < 1 || n > (1 << 30)) return fail(-1, "ganmf_evaluate_full: n out of range");
+// ganmf_evaluate_full (cand = false) and the 13-sum form of ganmf_evaluate_candidates (cand = true), as evaluate_impl
+static int evaluate_full_impl(ganmf_handle* h, const char* who, bool cand, const int32_t* ids, int64_t n, int transposed, int remove_seen,
+                              const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums,
+                              int64_t* counts) {
+  if (!h || !ids || !cutoffs || !disc || !ideal_cum || !sums || !counts) return fail(-1, "%s: null argument", who);
+  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
+  if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
   if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
-    return fail(-1, "ganmf_evaluate_full: needs ganmf_set_test_csr with a %d x %d matrix", limit, W);
-  if (!h->test_rating_ok) return fail(-1, "ganmf_evaluate_full: needs ganmf_set_test_ratings for the current test matrix");
-  if (h->eval_w_width != W) return fail(-1, "ganmf_evaluate_full: needs ganmf_set_eval_item_weights of width %d", W);
+    return fail(-1, "%s: needs ganmf_set_test_csr with a %d x %d matrix", who, limit, W);
+  if (!h->test_rating_ok) return fail(-1, "%s: needs ganmf_set_test_ratings for the current test matrix", who);
+  if (h->eval_w_width != W) return fail(-1, "%s: needs ganmf_set_eval_item_weights of width %d", who, W);
   int K = 0;
   for (int i = 0; i < n_cutoffs; ++i) {
-    if (cutoffs[i] < 1) return fail(-1, "ganmf_evaluate_full: cut-off %d", cutoffs[i]);
+    if (cutoffs[i] < 1) return fail(-1, "%s: cut-off %d", who, cutoffs[i]);
     K = std::max(K, (int)cutoffs[i]);
   }
   HIP_TRY(hipSetDevice(h->dev));
@@ -359,7 +481,8 @@ int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int tran
   }
   const RmseP rp{h->test_indptr, h->test_indices, h->test_rating, h->eval_rmse};
   int* ids_dev = nullptr;
-  TRY(recommend_device(h, "ganmf_evaluate_full", ids, n, transposed, K, remove_seen, &ids_dev, &rp));
+  if (cand) TRY(candidates_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev, &rp));
+  else TRY(recommend_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev, &rp));
   const int grid = (int)((n + 255) / 256);
   const size_t n_part = (size_t)grid * n_cutoffs * EVAL_FULL_METRICS;
   const size_t need = (size_t)K + (size_t)n * K + n_part;
@@ -401,6 +524,19 @@ int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int tran
     for (int i = 0; i < n_cutoffs * EVAL_FULL_METRICS; ++i) sums[i] += part[(size_t)b * n_cutoffs * EVAL_FULL_METRICS + i];
   for (size_t i = 0; i < n_counts; ++i) counts[i] += (int64_t)cnt[i];
   return 0;
+}
+
+int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
+                        int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts) {
+  return evaluate_full_impl(h, "ganmf_evaluate_full", false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums,
+                            counts);
+}
+
+int ganmf_evaluate_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
+                              int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts) {
+  const char* who = "ganmf_evaluate_candidates";
+  if (!counts) return evaluate_impl(h, who, true, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums);
+  return evaluate_full_impl(h, who, true, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums, counts);
 }
 
 int ganmf_recommend(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t cutoff, int remove_seen,

@@ -171,6 +171,12 @@ struct ganmf_handle {
   size_t eval_rmse_cap = 0;
   unsigned* eval_counts = nullptr;
   size_t eval_counts_cap = 0;
+  // ganmf_set_candidates_csr: per-row candidate lists (evaluation orientation, rows sorted and unique) for cand_topk_kernel;
+  // the host keeps the row pointers to size a launch's LDS and to refuse a row over GANMF_CANDIDATES_MAX_PER_ROW without launching
+  long long* cand_indptr = nullptr;
+  int* cand_indices = nullptr;
+  std::vector<long long> cand_indptr_host;
+  int64_t cand_rows = 0, cand_cols = 0;
   // scoring scratch
   int* sc_ids = nullptr;
   size_t sc_ids_cap = 0;

@@ -440,6 +440,17 @@ class ShardedEngine(object):
         self._sync_master()
         return self.master.evaluate_full(ids, cutoffs, disc, ideal_cum, transposed, remove_seen, counts)
 
+    def set_candidates(self, candidates_csr):
+        self.master.set_candidates(candidates_csr)
+
+    def recommend_candidates(self, ids, cutoff, transposed=False, remove_seen=True):
+        self._sync_master()
+        return self.master.recommend_candidates(ids, cutoff, transposed, remove_seen)
+
+    def evaluate_candidates(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True, counts=None, full=False):
+        self._sync_master()
+        return self.master.evaluate_candidates(ids, cutoffs, disc, ideal_cum, transposed, remove_seen, counts, full)
+
     def snapshot_best(self):
         self._sync_master()
         self.master.snapshot_best()

@@ -220,6 +220,52 @@ class Engine:
                     "ganmf_evaluate_full")
         return out, counts
 
+    def set_candidates(self, candidates_csr):
+        """Per-row candidate lists in evaluation orientation (ganmf_set_candidates_csr): the stored entries of a scipy matrix,
+        in any order and with repeats (the library sorts and de-duplicates the rows); None drops the held matrix."""
+        if candidates_csr is None:
+            L.check(self.lib.ganmf_set_candidates_csr(self.h, None, None, 0, 0), "ganmf_set_candidates_csr")
+            return
+        m = candidates_csr.tocsr()
+        indptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(m.indices, dtype=np.int32)
+        L.check(self.lib.ganmf_set_candidates_csr(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices),
+                                                  m.shape[0], m.shape[1]), "ganmf_set_candidates_csr")
+
+    def recommend_candidates(self, ids, cutoff, transposed=False, remove_seen=True):
+        """device top-k of every row among its own candidates: (items [n, cutoff] int32 with -1 padding, scores [n, cutoff])"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        items = np.empty((ids.size, cutoff), dtype=np.int32)
+        vals = np.empty((ids.size, cutoff), dtype=np.float32)
+        if ids.size:
+            L.check(self.lib.ganmf_recommend_candidates(self.h, _i32p(ids), ids.size, int(transposed), int(cutoff), int(remove_seen),
+                                                        _i32p(items), _f32p(vals)), "ganmf_recommend_candidates")
+        return items, vals
+
+    def evaluate_candidates(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True, counts=None, full=False):
+        """evaluate() / evaluate_full() with every row ranked among its own candidates (ganmf_evaluate_candidates).  full=False:
+        the [len(cutoffs), 9] sums.  full=True: (the [len(cutoffs), 13] sums, `counts` with the lists' per-item counts added)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
+        K = int(cut.max())
+        width = self.num_users if transposed else self.num_items
+        disc = np.ascontiguousarray(disc, dtype=np.float64).ravel()
+        ideal = np.ascontiguousarray(ideal_cum, dtype=np.float64)
+        assert disc.size >= K and ideal.shape == (ids.size, K)
+        cp = None
+        if full:
+            if counts is None:
+                counts = np.zeros((cut.size, width), dtype=np.int64)
+            assert counts.dtype == np.int64 and counts.shape == (cut.size, width) and counts.flags.c_contiguous
+            cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
+        out = np.zeros((cut.size, len(L.EVAL_FULL_METRICS if full else L.EVAL_METRICS)), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        if ids.size:
+            L.check(self.lib.ganmf_evaluate_candidates(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), _i32p(cut),
+                                                       cut.size, disc.ctypes.data_as(dp), ideal.ctypes.data_as(dp),
+                                                       out.ctypes.data_as(dp), cp), "ganmf_evaluate_candidates")
+        return (out, counts) if full else out
+
     def snapshot_best(self):
         L.check(self.lib.ganmf_snapshot_best(self.h), "ganmf_snapshot_best")
 

@@ -1,4 +1,5 @@
-"""Hold-out evaluation -- the consumer of the scores (protocol of Base/Evaluation/Evaluator.py:214-414 with the
+"""Hold-out and negative-sample evaluation -- the consumers of the scores (protocols of Base/Evaluation/Evaluator.py:214-414,
+EvaluatorHoldout*, and :419-590, EvaluatorNegativeItemSample*: each user ranked among its own candidates; with the
 metrics of Base/Evaluation/metrics.py).  The GANMF callers read `results_dic[cutoff][metric]` (early stopping:
 cut-off 5, Utils_.py:64).
 
@@ -229,6 +230,7 @@ class EvaluatorHoldout(object):
         block_size = min(1000, int(1e8 / self.n_items))
         sums = {c: dict.fromkeys(_SUMMED, 0.0) for c in self.cutoff_list}
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
+        w_novelty = w_popularity = None
         if full is not None:
             w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(recommender_object)))
         users = np.asarray(self.usersToEvaluate, dtype=np.int64)
@@ -239,23 +241,29 @@ class EvaluatorHoldout(object):
                 remove_CustomItems_flag=False, return_scores=True)
             assert len(rec_lists) == len(batch) and scores_batch.shape == (len(batch), self.n_items)
             for user, recommended, score_row in zip(batch, rec_lists, scores_batch):
-                test_items, test_ratings = self.get_user_relevant_items(user), self.get_user_test_ratings(user)
-                scorer = RankedListMetrics(test_items, test_ratings, self.max_cutoff)
-                hit, gain = scorer.match(recommended)
-                user_rmse = rmse_on_test_items(score_row, test_items, test_ratings)
-                for c in self.cutoff_list:
-                    acc = sums[c]
-                    for name, value in scorer(hit, gain, c).items():
-                        acc[name] += value
-                    acc["RMSE"] += user_rmse
-                    if full is not None:
-                        listed = np.asarray(recommended[:c], dtype=np.int64)
-                        if len(listed) > 0:
-                            full.counts[c][listed] += 1
-                            full.novelty[c] += np.sum(w_novelty[listed])
-                            full.popularity[c] += np.sum(w_popularity[listed]) / len(listed)
-                            full.nonempty[c] += 1
-        n_eval = len(users)
+                self._add_user(sums, full, user, recommended, score_row, w_novelty, w_popularity)
+        return self._finish_users(sums, full, len(users))
+
+    def _add_user(self, sums, full, user, recommended, score_row, w_novelty, w_popularity):
+        """one user's ranked list and score row into the running sums of every cut-off (Evaluator.py:280-335)"""
+        test_items, test_ratings = self.get_user_relevant_items(user), self.get_user_test_ratings(user)
+        scorer = RankedListMetrics(test_items, test_ratings, self.max_cutoff)
+        hit, gain = scorer.match(recommended)
+        user_rmse = rmse_on_test_items(score_row, test_items, test_ratings)
+        for c in self.cutoff_list:
+            acc = sums[c]
+            for name, value in scorer(hit, gain, c).items():
+                acc[name] += value
+            acc["RMSE"] += user_rmse
+            if full is not None:
+                listed = np.asarray(recommended[:c], dtype=np.int64)
+                if len(listed) > 0:
+                    full.counts[c][listed] += 1
+                    full.novelty[c] += np.sum(w_novelty[listed])
+                    full.popularity[c] += np.sum(w_popularity[listed]) / len(listed)
+                    full.nonempty[c] += 1
+
+    def _finish_users(self, sums, full, n_eval):
         if n_eval == 0:
             print("WARNING: No users had a sufficient number of relevant items")
             results = {c: dict.fromkeys(METRICS, 0.0) for c in self.cutoff_list}
@@ -350,13 +358,10 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
         return dev, counts
 
     def evaluateRecommender(self, recommender_object):
-        K = self.max_cutoff
         block_size = self._block_size or max(1, min(4096, int(1e8 / self.n_items)))
-        names = _SUMMED
-        sums = {c: {m: 0.0 for m in names} for c in self.cutoff_list}
+        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
         n_eval = len(self._users)
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
-        inv_rank = 1.0 / np.arange(1, K + 1, dtype=np.float64)
         if (full is not None and self.use_device_metrics and n_eval > 0
                 and hasattr(recommender_object, "evaluate_full_on_device")):
             # the whole row on the device: per cut-off 13 sums and the per-item counts come back, added up over the user blocks
@@ -365,21 +370,7 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
             except MemoryError:
                 got = None
             if got is not None:
-                from ._lib import EVAL_FULL_METRICS
-                dev, counts = got
-                col = {name: i for i, name in enumerate(EVAL_FULL_METRICS)}
-                for ci, c in enumerate(self.cutoff_list):
-                    for name in _SUMMED:
-                        sums[c][name] = float(dev[ci, col[name]])
-                    full.counts[c] = counts[ci]
-                    full.novelty[c] = float(dev[ci, col["NOVELTY"]])
-                    full.popularity[c] = float(dev[ci, col["AVERAGE_POPULARITY"]])
-                    full.nonempty[c] = int(round(dev[ci, col["NON_EMPTY"]]))
-                results = _finish(sums, n_eval, self.cutoff_list)
-                for c in self.cutoff_list:
-                    results[c] = {m: float(v) for m, v in results[c].items()}
-                results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
-                return results, get_result_string(results)
+                return self._from_device_full(sums, full, got[0], got[1], n_eval)
         if full is None and self.use_device_metrics and n_eval > 0 and hasattr(recommender_object, "evaluate_on_device"):
             # everything on the device: scores, seen mask, top-k AND the metric sums (only len(cutoffs) x 9 doubles come back)
             # in user blocks: the device forms a [block, n_items] score matrix (+ block x K doubles) per call, the same cap as
@@ -399,68 +390,101 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
             except MemoryError:
                 dev = None
             if dev is not None:
-                from ._lib import EVAL_METRICS
-                for ci, c in enumerate(self.cutoff_list):
-                    for mi, name in enumerate(EVAL_METRICS):
-                        sums[c][name] = float(dev[ci, mi])
-                results = _finish(sums, n_eval, self.cutoff_list)
-                for c in self.cutoff_list:
-                    results[c] = {m: float(v) for m, v in results[c].items()}
-                    results[c]["RMSE"] = float("nan")
-                return results, get_result_string(results)
+                return self._from_device(sums, dev, n_eval)
+        w_novelty = w_popularity = None
         if full is not None:
             w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(recommender_object)))
         for start in range(0, n_eval, block_size):
             sl = slice(start, min(start + block_size, n_eval))
             batch = self._users[sl]
+            rmse_sum = 0.0
             if full is not None:
                 items, rmse_sum = self._topk_and_rmse(recommender_object, batch)
             else:
                 items = self._topk(recommender_object, batch)
-            assert items.shape == (len(batch), K)
-            valid = items >= 0
-            safe = np.where(valid, items, 0)
-            rows = np.repeat(np.arange(len(batch)), K)
-            rel_block, gain_block = self._rel[batch], self._gain[batch]
-            is_rel = np.asarray(rel_block[rows, safe.ravel()]).reshape(len(batch), K) > 0
-            is_rel &= valid
-            gain = np.asarray(gain_block[rows, safe.ravel()]).reshape(len(batch), K) * is_rel
-            n_test = self._n_test[sl].astype(np.float64)
-            length = valid.sum(axis=1)
-            for c in self.cutoff_list:
-                r = sums[c]
-                rel = is_rel[:, :c].astype(np.float64)
-                neg = (valid[:, :c] & ~is_rel[:, :c]).astype(np.float64)
-                len_c = np.minimum(length, c).astype(np.float64)
-                hits = rel.sum(axis=1)
-                nneg = neg.sum(axis=1)
-                # AUC over the list: for each hit, the negatives ranked after it (metrics.py roc_auc)
-                neg_after = nneg[:, None] - np.cumsum(neg, axis=1)
-                pairs = (rel * neg_after).sum(axis=1)
-                auc = np.where(nneg == 0, 1.0, np.where(hits > 0, pairs / np.maximum(hits * nneg, 1.0), 0.0))
-                nz = np.maximum(len_c, 1.0)
-                r["ROC_AUC"] += auc.sum()
-                r["PRECISION"] += np.where(len_c > 0, hits / nz, 0.0).sum()
-                r["PRECISION_RECALL_MIN_DEN"] += np.where(len_c > 0, hits / np.maximum(np.minimum(n_test, len_c), 1.0), 0.0).sum()
-                r["RECALL"] += (hits / n_test).sum()
-                dcg_rank = (gain[:, :c] * self._disc[:c]).sum(axis=1)
-                li = np.maximum(len_c.astype(np.int64) - 1, 0)
-                ideal = self._ideal_cum[sl][np.arange(len(batch)), li]
-                r["NDCG"] += np.where(dcg_rank > 0, dcg_rank / np.where(ideal > 0, ideal, 1.0), 0.0).sum()
-                r["HIT_RATE"] += hits.sum()
-                r["ARHR"] += (rel * inv_rank[:c]).sum()
-                first = np.argmax(rel > 0, axis=1)
-                r["MRR"] += np.where(hits > 0, inv_rank[first], 0.0).sum()
-                p_at_k = rel * np.cumsum(rel, axis=1) * inv_rank[:c]
-                r["MAP"] += np.where(len_c > 0, p_at_k.sum(axis=1) / np.maximum(np.minimum(n_test, len_c), 1.0), 0.0).sum()
-                if full is not None:
-                    r["RMSE"] += rmse_sum
-                    listed = valid[:, :c]
-                    full.counts[c] += np.bincount(items[:, :c][listed], minlength=self.n_items)
-                    full.novelty[c] += (w_novelty[safe[:, :c]] * listed).sum()
-                    pop_sum = (w_popularity[safe[:, :c]] * listed).sum(axis=1)
-                    full.popularity[c] += np.where(len_c > 0, pop_sum / nz, 0.0).sum()
-                    full.nonempty[c] += int((len_c > 0).sum())
+            self._add_block(sums, full, items, sl, rmse_sum, w_novelty, w_popularity)
+        return self._finish_blocks(sums, full, n_eval)
+
+    def _from_device_full(self, sums, full, dev, counts, n_eval):
+        """results from the [n_cutoffs, 13] device sums and the [n_cutoffs, n_items] counts of a full-row device route"""
+        from ._lib import EVAL_FULL_METRICS
+        col = {name: i for i, name in enumerate(EVAL_FULL_METRICS)}
+        for ci, c in enumerate(self.cutoff_list):
+            for name in _SUMMED:
+                sums[c][name] = float(dev[ci, col[name]])
+            full.counts[c] = counts[ci]
+            full.novelty[c] = float(dev[ci, col["NOVELTY"]])
+            full.popularity[c] = float(dev[ci, col["AVERAGE_POPULARITY"]])
+            full.nonempty[c] = int(round(dev[ci, col["NON_EMPTY"]]))
+        results = _finish(sums, n_eval, self.cutoff_list)
+        for c in self.cutoff_list:
+            results[c] = {m: float(v) for m, v in results[c].items()}
+        results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
+        return results, get_result_string(results)
+
+    def _from_device(self, sums, dev, n_eval):
+        """results from the [n_cutoffs, 9] device sums of a nine-metric device route (RMSE is NaN there)"""
+        from ._lib import EVAL_METRICS
+        for ci, c in enumerate(self.cutoff_list):
+            for mi, name in enumerate(EVAL_METRICS):
+                sums[c][name] = float(dev[ci, mi])
+        results = _finish(sums, n_eval, self.cutoff_list)
+        for c in self.cutoff_list:
+            results[c] = {m: float(v) for m, v in results[c].items()}
+            results[c]["RMSE"] = float("nan")
+        return results, get_result_string(results)
+
+    def _add_block(self, sums, full, items, sl, rmse_sum, w_novelty, w_popularity):
+        """the ranked ids [len(block), K] (-1 padded) of the users self._users[sl] into the float64 sums of every cut-off"""
+        K = self.max_cutoff
+        batch = self._users[sl]
+        inv_rank = 1.0 / np.arange(1, K + 1, dtype=np.float64)
+        assert items.shape == (len(batch), K)
+        valid = items >= 0
+        safe = np.where(valid, items, 0)
+        rows = np.repeat(np.arange(len(batch)), K)
+        rel_block, gain_block = self._rel[batch], self._gain[batch]
+        is_rel = np.asarray(rel_block[rows, safe.ravel()]).reshape(len(batch), K) > 0
+        is_rel &= valid
+        gain = np.asarray(gain_block[rows, safe.ravel()]).reshape(len(batch), K) * is_rel
+        n_test = self._n_test[sl].astype(np.float64)
+        length = valid.sum(axis=1)
+        for c in self.cutoff_list:
+            r = sums[c]
+            rel = is_rel[:, :c].astype(np.float64)
+            neg = (valid[:, :c] & ~is_rel[:, :c]).astype(np.float64)
+            len_c = np.minimum(length, c).astype(np.float64)
+            hits = rel.sum(axis=1)
+            nneg = neg.sum(axis=1)
+            # AUC over the list: for each hit, the negatives ranked after it (metrics.py roc_auc)
+            neg_after = nneg[:, None] - np.cumsum(neg, axis=1)
+            pairs = (rel * neg_after).sum(axis=1)
+            auc = np.where(nneg == 0, 1.0, np.where(hits > 0, pairs / np.maximum(hits * nneg, 1.0), 0.0))
+            nz = np.maximum(len_c, 1.0)
+            r["ROC_AUC"] += auc.sum()
+            r["PRECISION"] += np.where(len_c > 0, hits / nz, 0.0).sum()
+            r["PRECISION_RECALL_MIN_DEN"] += np.where(len_c > 0, hits / np.maximum(np.minimum(n_test, len_c), 1.0), 0.0).sum()
+            r["RECALL"] += (hits / n_test).sum()
+            dcg_rank = (gain[:, :c] * self._disc[:c]).sum(axis=1)
+            li = np.maximum(len_c.astype(np.int64) - 1, 0)
+            ideal = self._ideal_cum[sl][np.arange(len(batch)), li]
+            r["NDCG"] += np.where(dcg_rank > 0, dcg_rank / np.where(ideal > 0, ideal, 1.0), 0.0).sum()
+            r["HIT_RATE"] += hits.sum()
+            r["ARHR"] += (rel * inv_rank[:c]).sum()
+            first = np.argmax(rel > 0, axis=1)
+            r["MRR"] += np.where(hits > 0, inv_rank[first], 0.0).sum()
+            p_at_k = rel * np.cumsum(rel, axis=1) * inv_rank[:c]
+            r["MAP"] += np.where(len_c > 0, p_at_k.sum(axis=1) / np.maximum(np.minimum(n_test, len_c), 1.0), 0.0).sum()
+            if full is not None:
+                r["RMSE"] += rmse_sum
+                listed = valid[:, :c]
+                full.counts[c] += np.bincount(items[:, :c][listed], minlength=self.n_items)
+                full.novelty[c] += (w_novelty[safe[:, :c]] * listed).sum()
+                pop_sum = (w_popularity[safe[:, :c]] * listed).sum(axis=1)
+                full.popularity[c] += np.where(len_c > 0, pop_sum / nz, 0.0).sum()
+                full.nonempty[c] += int((len_c > 0).sum())
+
+    def _finish_blocks(self, sums, full, n_eval):
         if n_eval > 0:
             results = _finish(sums, n_eval, self.cutoff_list)
             for c in self.cutoff_list:
@@ -473,3 +497,157 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
         if full is not None:
             results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
         return results, get_result_string(results)
+
+
+def items_to_rank(URM_test, URM_test_negative):
+    """URM_items_to_rank of the reference (Evaluator.py:450-452): test items + negative items of every user, binarised, an item
+    stored in both matrices kept once, explicit zeros dropped; rows sorted."""
+    m = sps.csr_matrix(sps.csr_matrix(URM_test).astype(bool)) + sps.csr_matrix(sps.csr_matrix(URM_test_negative).astype(bool))
+    m = sps.csr_matrix(m)
+    m.eliminate_zeros()
+    m.sort_indices()
+    m.data = np.ones_like(m.data)
+    return m
+
+
+class EvaluatorNegativeItemSample(EvaluatorHoldout):
+    """The reference's negative-sample protocol (Evaluator.py:419-590) in its own order: every evaluated user's test items are
+    ranked only against that user's candidates `URM_items_to_rank` = URM_test + URM_test_negative ("leave-one-out + N sampled
+    negatives"), through ONE `recommend(user, items_to_compute=candidates, return_scores=True)` call per user, with the
+    reference's float32 per-user sums.
+
+    What "only against the candidates" means is the recommender's business, as in the reference: a recommender that honours
+    `items_to_compute` (the MF contract, Base/BaseMatrixFactorizationRecommender.py:113-119; GANMF(score_contract="mf")) scores
+    every other item -inf; the reference's own GANMF ignores `items_to_compute` (GANMF.py:285-292; the default
+    score_contract="ganmf" here), and this evaluator around it ranks the whole catalogue, exactly as the reference's does."""
+    EVALUATOR_NAME = "EvaluatorNegativeItemSample"
+
+    def __init__(self, URM_test_list, URM_test_negative, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
+        super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen,
+                         full_metrics=full_metrics)
+        self.URM_items_to_rank = items_to_rank(self.URM_test, URM_test_negative)
+        if self.URM_items_to_rank.shape != self.URM_test.shape:
+            raise ValueError("URM_test_negative must have the shape of URM_test")
+
+    def _get_user_specific_items_to_compute(self, user_id):
+        m = self.URM_items_to_rank
+        return m.indices[m.indptr[user_id]:m.indptr[user_id + 1]]
+
+    def evaluateRecommender(self, recommender_object):
+        sums = {c: dict.fromkeys(_SUMMED, 0.0) for c in self.cutoff_list}
+        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
+        w_novelty = w_popularity = None
+        if full is not None:
+            w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(recommender_object)))
+        for user in self.usersToEvaluate:
+            rec_lists, scores = recommender_object.recommend(
+                np.atleast_1d(user), remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
+                items_to_compute=self._get_user_specific_items_to_compute(user), remove_CustomItems_flag=False,
+                return_scores=True)
+            assert len(rec_lists) == 1 and scores.shape == (1, self.n_items)
+            self._add_user(sums, full, user, rec_lists[0], scores[0], w_novelty, w_popularity)
+        return self._finish_users(sums, full, len(self.usersToEvaluate))
+
+
+class EvaluatorNegativeItemSampleFast(EvaluatorHoldoutFast):
+    """EvaluatorNegativeItemSample's protocol and result dictionaries, consuming only the top-`max_cutoff` ids of every user, with
+    the float64 sums and the finishing code of EvaluatorHoldoutFast.  Routes, in this order:
+
+      device   `recommender.evaluate_candidates_on_device(...)` (ganmf_evaluate_candidates: candidate scoring, masks, top-k and the
+               metric sums in HIP kernels; only the sums, and the counts of a full row, come back), in user blocks;
+      blocks   `recommender.recommend_candidates(users, candidates, cutoff, ...)` -> [n, cutoff] ids (ganmf_recommend_candidates),
+               metrics on the host (nine-metric rows: RMSE, which needs the scores, is NaN as in EvaluatorHoldoutFast); a
+               ValueError / RuntimeError from it (limits of the block-wise API) sends the remaining blocks to the next route;
+      users    one `recommend(user, items_to_compute=candidates, ...)` per user, as the reference-order class calls it.
+
+    Contracts.  The result is what EvaluatorNegativeItemSample returns for the same recommender.  A recommender that ignores
+    `items_to_compute` -- the reference's GANMF (GANMF.py:285-292) and GANMF here under the default score_contract="ganmf" --
+    is ranked over the whole catalogue by the reference's evaluator; such a recommender says so (`honours_items_to_compute` is
+    False), declines the device route (None), and this class then evaluates it exactly as EvaluatorHoldoutFast does (full-width
+    routes).  Under score_contract="mf" the candidate kernel is used."""
+    EVALUATOR_NAME = "EvaluatorNegativeItemSampleFast"
+
+    def __init__(self, URM_test_list, URM_test_negative, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
+        super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen,
+                         full_metrics=full_metrics)
+        self.URM_items_to_rank = items_to_rank(self.URM_test, URM_test_negative)
+        if self.URM_items_to_rank.shape != self.URM_test.shape:
+            raise ValueError("URM_test_negative must have the shape of URM_test")
+
+    def _get_user_specific_items_to_compute(self, user_id):
+        m = self.URM_items_to_rank
+        return m.indices[m.indptr[user_id]:m.indptr[user_id + 1]]
+
+    def _device_candidates(self, rec, n_eval, block):
+        """sums (and counts) of evaluate_candidates_on_device over all user blocks, or None when the recommender declines"""
+        full = self.full_metrics
+        weights = popularity_weights(item_popularity(_train_matrix(rec))) if full else None
+        counts = np.zeros((len(self.cutoff_list), self.n_items), dtype=np.int64) if full else None
+        dev = None
+        for start in range(0, n_eval, block):
+            sl = slice(start, min(start + block, n_eval))
+            part = rec.evaluate_candidates_on_device(self._device_token, self._test_sorted, self._test_gain, self.URM_items_to_rank,
+                                                     self._users[sl], self.cutoff_list, self._disc, self._ideal_cum[sl],
+                                                     remove_seen_flag=self.exclude_seen,
+                                                     ratings=self._test_rating if full else None, item_weights=weights, counts=counts)
+            if part is None:
+                return None
+            dev = part if dev is None else dev + part
+        return dev, counts
+
+    def _per_user(self, rec, batch, with_scores):
+        """ids [len(batch), K] (-1 padded) from one recommend(user, items_to_compute=...) per user, and the users' RMSE sum"""
+        K = self.max_cutoff
+        out = np.full((len(batch), K), -1, dtype=np.int64)
+        rmse_sum = 0.0
+        for i, u in enumerate(batch):
+            got = rec.recommend(np.atleast_1d(u), remove_seen_flag=self.exclude_seen, cutoff=K, remove_top_pop_flag=False,
+                                items_to_compute=self._get_user_specific_items_to_compute(u), remove_CustomItems_flag=False,
+                                return_scores=with_scores)
+            lists, scores = got if with_scores else (got, None)
+            out[i, :len(lists[0])] = lists[0]
+            if with_scores:
+                rmse_sum += float(rmse_on_test_items(scores[0], self.get_user_relevant_items(u), self.get_user_test_ratings(u)))
+        return out, rmse_sum
+
+    def evaluateRecommender(self, recommender_object):
+        rec = recommender_object
+        K = self.max_cutoff
+        n_eval = len(self._users)
+        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
+        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
+        # users per call: the device route holds block x K doubles and two ints per candidate, no score matrix
+        block_size = self._block_size or 4096
+        if self.use_device_metrics and n_eval > 0 and hasattr(rec, "evaluate_candidates_on_device"):
+            try:
+                got = self._device_candidates(rec, n_eval, self._block_size or 65536)
+            except MemoryError:
+                got = None
+            if got is not None:
+                if full is not None:
+                    return self._from_device_full(sums, full, got[0], got[1], n_eval)
+                return self._from_device(sums, got[0], n_eval)
+        if not getattr(rec, "honours_items_to_compute", True):
+            # the reference's evaluator around this recommender ranks the whole catalogue: the full-width routes
+            return super().evaluateRecommender(rec)
+        w_novelty = w_popularity = None
+        if full is not None:
+            w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(rec)))
+        by_block = full is None and hasattr(rec, "recommend_candidates")
+        for start in range(0, n_eval, block_size):
+            sl = slice(start, min(start + block_size, n_eval))
+            batch = self._users[sl]
+            rmse_sum = 0.0
+            items = None
+            if by_block:
+                try:
+                    items = np.asarray(rec.recommend_candidates(batch, self.URM_items_to_rank, K, remove_seen_flag=self.exclude_seen,
+                                                                candidates_key=self._device_token), dtype=np.int64)
+                except (ValueError, RuntimeError):
+                    # beyond what the block-wise API takes (a cut-off or a candidate list over its limits): this block and the
+                    # ones after it go user by user, as the full row does
+                    by_block = False
+            if items is None:
+                items, rmse_sum = self._per_user(rec, batch, with_scores=full is not None)
+            self._add_block(sums, full, items, sl, rmse_sum, w_novelty, w_popularity)
+        return self._finish_blocks(sums, full, n_eval)

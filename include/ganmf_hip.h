@@ -268,6 +268,35 @@ int ganmf_set_eval_item_weights(ganmf_handle* h, const double* novelty, const do
 int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
                         int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts);
 
+/* Negative-sample evaluation on the device (Base/Evaluation/Evaluator.py:419-590, EvaluatorNegativeItemSample): every user's test
+ * items are ranked only against that user's own candidate list, URM_test + URM_test_negative.  The reference forms a full-width score
+ * row per user and masks it down to the candidates; these entries gather the factor rows of the candidates and form only those dot
+ * products (ganmf_amd/csrc/cand_topk.hpp), so the [n, W] score matrix never exists.  They always restrict to the candidates -- the MF
+ * contract's items_to_compute rule (Base/BaseMatrixFactorizationRecommender.py:113-119), whatever score filter is set; the filter of
+ * ganmf_set_score_filter (item list, cold rows) applies on top of it.
+ * ganmf_set_candidates_csr: replaces URM_items_to_rank and _get_user_specific_items_to_compute (Evaluator.py:450-463).  The matrix
+ *   is in EVALUATION orientation like ganmf_set_seen_csr (n_rows / n_cols must match the id domain / score width of the `transposed`
+ *   it is used with); stored entries are the candidates, values do not matter.  Any CSR is accepted: rows are sorted and a repeated
+ *   column is kept once on the host before the upload (the reference's sum of two boolean matrices de-duplicates the same way).
+ *   indptr == NULL drops the held matrix.
+ * ganmf_recommend_candidates: replaces the per-user recommend(user, items_to_compute = candidates) call and the ranking inside it
+ *   (Evaluator.py:504-513, 527).  Arguments, outputs, tie rule (smaller item id) and -1 / -inf padding as ganmf_recommend; a row with
+ *   fewer than `cutoff` unmasked candidates is padded.  Scores are fp32 sums in a fixed order: the same bytes on every call and handle.
+ * ganmf_evaluate_candidates: replaces the metric loop Evaluator.py:496-564 (sums; the host divides as :586-599 does).  The ranking of
+ *   ganmf_recommend_candidates at the largest cut-off, then ganmf_evaluate's metric kernel (counts == NULL: sums[n_cutoffs, 9]) or
+ *   ganmf_evaluate_full's (counts != NULL: sums[n_cutoffs, 13] overwritten, counts[n_cutoffs, W] added into; needs
+ *   ganmf_set_test_ratings and ganmf_set_eval_item_weights like it; RMSE (Evaluator.py:528) over the test items that are candidates
+ *   with a finite score).  Same cut-off limits as those two calls.
+ * A row may hold at most GANMF_CANDIDATES_MAX_PER_ROW candidates (one workgroup's LDS holds a row's scores and ids).  Errors (-1, message
+ *   in ganmf_last_error, nothing enqueued, the handle usable as before): no candidate matrix set, its shape does not match
+ *   `transposed`, a requested row over the limit, and the argument errors of ganmf_recommend / ganmf_evaluate(_full). */
+#define GANMF_CANDIDATES_MAX_PER_ROW 8192
+int ganmf_set_candidates_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols);
+int ganmf_recommend_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t cutoff, int remove_seen,
+                               int32_t* out_items, float* out_scores);
+int ganmf_evaluate_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
+                              int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts);
+
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch);

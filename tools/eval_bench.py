@@ -1,5 +1,15 @@
 """Hold-out evaluation wall time on ML-1M shapes: reference-order evaluator (all score rows to the host, per-user
-python metrics) vs device top-k + block evaluator.  Usage: python tools/eval_bench.py"""
+python metrics) vs device top-k + block evaluator.  Usage: python tools/eval_bench.py
+
+    python tools/eval_bench.py --candidates N
+
+times instead the negative-sample protocol with N candidates per user (the test items included): ganmf_evaluate_candidates
+(candidate scoring + top-k + metric sums, one call for all users) against the full-width ganmf_evaluate of the same users (user
+blocks of 1e8 / n_items, as EvaluatorHoldoutFast calls it), alternating in one process, at two shapes with k = 250: ML-1M
+(6040 x 3706) and the configs[3] shard width (25 000 x 50 000).  Host wall time around calls that end in a stream synchronise;
+one JSON line per shape."""
+import argparse
+import json
 import os
 import sys
 import time
@@ -10,6 +20,62 @@ import scipy.sparse as sps
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ganmf_amd.GANMF import GANMF  # noqa: E402
 from ganmf_amd.evaluation import EvaluatorHoldout, EvaluatorHoldoutFast  # noqa: E402
+
+
+def candidates_bench(n_candidates, cutoffs=(5, 10), reps=7):
+    from ganmf_amd.engine import Engine
+    from ganmf_amd.evaluation import EvaluatorHoldoutFast
+    for name, (nu, ni) in (("ml1m", (6040, 3706)), ("configs3_shard", (25000, 50000))):
+        rng = np.random.RandomState(0)
+        k = 250
+        eng = Engine(nu, ni, k, 16, 32)
+        eng.set_tensor(100, rng.standard_normal((nu, k)).astype(np.float32))
+        eng.set_tensor(101, rng.standard_normal((ni, k)).astype(np.float32))
+        # per user: n_candidates distinct items, the first a test item (leave-one-out), 20 others seen
+        cols = np.argsort(rng.rand(nu, 2 * n_candidates + 40), axis=1)[:, :n_candidates + 20] * (ni // (2 * n_candidates + 40))
+        cols = (cols + rng.randint(0, ni // (2 * n_candidates + 40), size=cols.shape)).astype(np.int32)
+        rows = np.repeat(np.arange(nu), n_candidates)
+        cand = sps.csr_matrix((np.ones(nu * n_candidates, np.float32), (rows, cols[:, :n_candidates].ravel())), shape=(nu, ni))
+        test = sps.csr_matrix((np.ones(nu, np.float32), (np.arange(nu), cols[:, 0])), shape=(nu, ni))
+        seen = sps.csr_matrix((np.ones(nu * 20, np.float32), (np.repeat(np.arange(nu), 20), cols[:, n_candidates:].ravel())),
+                              shape=(nu, ni))
+        ev = EvaluatorHoldoutFast(test, list(cutoffs))
+        eng.set_seen(seen)
+        eng.set_test(ev._test_sorted, ev._test_gain)
+        eng.set_candidates(cand)
+        users = np.arange(nu)
+        block = max(1, int(1e8 / ni))
+
+        def full_width():
+            out = None
+            for lo in range(0, nu, block):
+                part = eng.evaluate(users[lo:lo + block], cutoffs, ev._disc, ev._ideal_cum[lo:lo + block])
+                out = part if out is None else out + part
+            return out
+
+        def candidates():
+            return eng.evaluate_candidates(users, cutoffs, ev._disc, ev._ideal_cum)
+
+        full_width(), candidates()                                   # warm-up: code objects, buffers, the split of V
+        t_full, t_cand = [], []
+        for _ in range(reps):                                        # alternating, every call ends in a stream synchronise
+            t0 = time.perf_counter(); full_width(); t_full.append(time.perf_counter() - t0)
+            t0 = time.perf_counter(); candidates(); t_cand.append(time.perf_counter() - t0)
+        f, c = float(np.median(t_full)) * 1e3, float(np.median(t_cand)) * 1e3
+        print(json.dumps({"shape": name, "users": nu, "items": ni, "k": k, "candidates_per_user": n_candidates,
+                          "cutoffs": list(cutoffs), "reps": reps, "full_width_evaluate_ms": round(f, 3),
+                          "candidates_evaluate_ms": round(c, 3), "full_over_candidates": round(f / c, 2),
+                          "full_width_ms_min_max": [round(min(t_full) * 1e3, 3), round(max(t_full) * 1e3, 3)],
+                          "candidates_ms_min_max": [round(min(t_cand) * 1e3, 3), round(max(t_cand) * 1e3, 3)]}), flush=True)
+        eng.close()
+
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--candidates", type=int, default=0, help="N candidates per user (test items included): time the candidate route")
+args = ap.parse_args()
+if args.candidates:
+    candidates_bench(args.candidates)
+    sys.exit(0)
 
 g = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 train = sps.load_npz(os.path.join(g, "Movielens1M_URM_train.npz")).tocsr()
