@@ -279,6 +279,16 @@ class GANMF(BaseRecommender):
         with self._item_filter(items_to_compute):
             return self.engine.scores(ids, transposed=(self.mode == 'item'))
 
+    def prediction_similarity(self, user_id_array=None, pool=None, return_matrix=False):
+        """Cosine similarity of the predictions of `user_id_array` (None: every user) among themselves -- the reference's collapse
+        study, AblationStudy.py:88-92,113-117: cosine_similarity(_compute_item_score(all users)), its np.mean and np.std -- formed on
+        the device from the unfiltered scores (no score filter under either contract: a -inf has no cosine).  Returns a dict: mean,
+        std (population), n, zero_rows; with pool=P also `pooled`, the [P, P] block means behind a heat-map; with
+        return_matrix=True also `matrix`, the [n, n] float32 similarities.  No host fallback."""
+        self._require_engine()
+        ids = np.arange(self.n_users) if user_id_array is None else np.asarray(user_id_array).reshape(-1)
+        return self.engine.score_similarity(ids, transposed=(self.mode == 'item'), pool=pool, return_matrix=return_matrix)
+
     def _item_filter(self, items_to_compute):
         """context (MF contract only): scores / recommend / evaluate restricted to `items_to_compute`; the cold-user mask stays on"""
         eng = self.engine

@@ -40,6 +40,7 @@
 #include "gemm_bf16p.hpp"
 #include "kernels.hpp"
 #include "cand_topk.hpp"
+#include "gram_stats.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)

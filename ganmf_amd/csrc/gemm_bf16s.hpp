@@ -173,7 +173,8 @@ struct Bf16sLds {      // floats of LDS one workgroup needs: the piece planes, o
 
 // (body = device function of (block index, blocks of this GEMM): one launch can carry more than one piece of work,
 // gemm_multi.hpp; `smem` is the launch's only LDS object, Bf16sLds<...>::DW floats)
-template <int BM, int BN, int BK, bool AKM, bool BKM, int NPIECE, bool F16 = false>
+// GRAM: the symmetric product of gram_stats.hpp, as in gemm_f32_body
+template <int BM, int BN, int BK, bool AKM, bool BKM, int NPIECE, bool F16 = false, bool GRAM = false>
 __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, const int nblk, float* __restrict__ smem) {
   static_assert(!F16 || NPIECE == 1, "fp16 pieces only in the single-piece (mixed precision) mode");
   const float sa = (F16 && p.a_scale != 0.f) ? p.a_scale : 1.f, sb = (F16 && p.b_scale != 0.f) ? p.b_scale : 1.f;
@@ -194,8 +195,9 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
   const int wr = wave >> 1, wc = wave & 1;
   const int li = lane & 31, lh = lane >> 5;
 
-  int tm, tn, sp, bz;
-  tile_coords(p, bid, nblk, tm, tn, sp, bz);
+  int tm, tn, sp = 0, bz = 0;
+  if constexpr (GRAM) gram_tile_coords(p, bid, nblk, tm, tn);
+  else tile_coords(p, bid, nblk, tm, tn, sp, bz);
   const int m0 = tm * BM, n0 = tn * BN;
   const int kbeg = sp * p.k_per_split;
   const int kend = min(p.K, kbeg + p.k_per_split);
@@ -332,6 +334,10 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
         for (int b = 0; b < TN; ++b) acc[a][b] *= un;
     }
   }
+  if constexpr (GRAM) {
+    static_assert(NPIECE == 3 && !F16 && !AKM && !BKM, "the symmetric product is an NT product in the exact three-way split");
+    gram_epilogue<BM, BN, TM, TN>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
+  } else
   gemm_epilogue<BM, BN, TM, TN, 1, AKM && BKM>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
 #ifdef GANMF_PERSIST_DIAG_BUILD
   if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }

@@ -163,6 +163,9 @@ enum GemmEpi : int {
   EPI_MUL_ACTGRAD = 6,     // C = acc * act'(aux[m,n]) from the layer OUTPUT aux   (DisGANMF backward)
   EPI_ADAM = 7,            // acc is the gradient: TF ApplyAdam on theta/m/v in place, nothing stored to C;
                            // sum(theta_old^2) -> sq_partials.  Never split along K.
+  EPI_GRAM_STATS = 8,      // C = A . A^T over the upper triangle of tiles (gram_stats.hpp): per tile the float64 sums of d = acc - 1 and
+                           // d^2 -> gram_partials; the tile and its mirror are stored only when C != nullptr.  Its own kernels only
+                           // (the bodies' GRAM instantiations); never split along K, gemm_dispatch rejects it.
 };
 
 constexpr float ADAM_B1 = 0.9f, ADAM_B2 = 0.999f, ADAM_EPS = 1e-8f;
@@ -232,6 +235,7 @@ struct EpiD {
   // geometry, piece q at planes + q * plane_stride -- the operand form of wgrad_stream.hpp (nullptr: no planes)
   unsigned short* planes;
   long long plane_stride;
+  double* gram_partials;   // EPI_GRAM_STATS: [tiles of the upper triangle][2] = (sum d, sum d^2) of each tile's in-range elements
 };
 
 // X[batch row m, column col .. col + 3] of the CSR rows of the batch (EpiD::csr_*): lower bound on the sorted column indices
@@ -524,6 +528,11 @@ __device__ inline void tile_coords(const GemmP& p, int bid, int nblk, int& tm, i
 // row = (reg&3) + 8*(reg>>2) + 4*(lane>>5), i.e. a lane owns a column.  `smem` must hold BM*BN floats and be idle.
 struct TileCoord { int tm, tn, sp, bz, m0, n0; };
 
+// EPI_GRAM_STATS (gram_stats.hpp, included behind the GEMM bodies): block id -> tile of the upper triangle, and the epilogue
+__device__ inline void gram_tile_coords(const GemmP& p, int bid, int nblk, int& tm, int& tn);
+template <int BM, int BN, int TM, int TN>
+__device__ inline void gram_epilogue(const GemmP& p, const f32x16 (&acc)[TM][TN], float* smem, const TileCoord& tc_);
+
 // KG > 1: the workgroup has KG groups of four waves that each hold a partial sum of the SAME tile (they split the
 // chunks of every K-tile between them, gemm_f32_mfma); group g stages its accumulators at smem + g * BM * BN and the row
 // pass adds the KG images in group order (fixed order: bitwise reproducible).
@@ -806,7 +815,8 @@ __device__ inline void gemm_epilogue(const GemmP& p, const f32x16 (&acc)[TM][TN]
 // profiles/README.md).  The partial sums meet in the epilogue through LDS.
 // The body is a device function of (block index, blocks of this GEMM) so that one launch can carry several independent
 // pieces of work (gemm_multi.hpp); `smem` is the launch's only LDS object, NS ring slots of BM*BK + BN*BK floats.
-template <int BM, int BN, int BK, int NS, bool AKM, bool BKM, int KG = 1>
+// GRAM: the symmetric product of gram_stats.hpp -- the same K loop on the tiles of the upper triangle, behind EPI_GRAM_STATS.
+template <int BM, int BN, int BK, int NS, bool AKM, bool BKM, int KG = 1, bool GRAM = false>
 __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, const int nblk, float* __restrict__ smem) {
   constexpr int NTHR = 256 * KG;
   using SA = Stage<BM, BK, AKM, NTHR>;
@@ -825,8 +835,9 @@ __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, con
   const int wr = (wave >> 1) & 1, wc = wave & 1;
   const int li = lane & 31, lh = lane >> 5;
 
-  int tm, tn, sp, bz;
-  tile_coords(p, bid, nblk, tm, tn, sp, bz);
+  int tm, tn, sp = 0, bz = 0;
+  if constexpr (GRAM) gram_tile_coords(p, bid, nblk, tm, tn);
+  else tile_coords(p, bid, nblk, tm, tn, sp, bz);
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #define GANMF_GEMM_STAMP(i) do { if (p.stamps && tid == 0) p.stamps[(size_t)bid * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
@@ -957,6 +968,10 @@ __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, con
 
   GANMF_GEMM_STAMP(2);
   static_assert(KG * BM * BN <= NS * BUF, "the ring must hold the KG staged partial tiles");
+  if constexpr (GRAM) {
+    static_assert(KG == 1 && !AKM && !BKM, "the symmetric product is an NT product on one K group");
+    gram_epilogue<BM, BN, TM, TN>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
+  } else
   gemm_epilogue<BM, BN, TM, TN, KG, AKM && BKM>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
 #ifdef GANMF_PERSIST_DIAG_BUILD
   if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
@@ -1364,6 +1379,7 @@ inline hipError_t gemm_dispatch_bf16w(hipStream_t st, const GemmP& p, bool bkm, 
 
 inline hipError_t gemm_dispatch(hipStream_t st, const GemmP& p0, bool akm, bool bkm, const GemmPlan& pl) {
   if (p0.epi.kind == EPI_ADAM && !(akm && bkm)) return hipErrorInvalidValue;      // (the fused Adam row pass exists in the TN kernels only)
+  if (p0.epi.kind == EPI_GRAM_STATS) return hipErrorInvalidValue;                  // (gram_stats.hpp launches its own instantiations)
   if (pl.skinny) return gemm_dispatch_skinny(st, p0, bkm, pl.skinny);
   if (pl.skinny_n) return gemm_dispatch_skinny_n(st, p0, bkm);
   if (pl.wide32) return gemm_dispatch_bf16w(st, p0, bkm, pl.mode);

@@ -105,6 +105,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   h->g_rows_staged = std::max(0, std::min(2, tune_env_int("g_rows_staged", 1)));
   h->pair_kg = tune_env_int("pair_kg", 4) == 1 ? 1 : 4;
   h->wgrad_seam = tune_env_int("wgrad_seam", 0);
+  h->gram_arith = tune_env_int("gram", 1) == 0 ? 0 : 1;
   HIP_TRY(hipMalloc((void**)&h->seam_cnt, 2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(h->seam_cnt, 0, 2 * sizeof(unsigned long long)));
   if (h->tune.kg != 0 && h->tune.kg != 1 && h->tune.kg != 2 && h->tune.kg != 4) h->tune.kg = 0;
@@ -269,6 +270,7 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->slab); hipFree(h->rs); hipFree(h->scal); hipFree(h->sqp);
   hipFree(h->seen_indptr); hipFree(h->seen_indices); hipFree(h->item_mask); hipFree(h->topk_items); hipFree(h->topk_vals); hipFree(h->sc_ids);
   hipFree(h->colbuf); hipFree(h->parts_all); hipFree(h->sc_rows); hipFree(h->sc_out); hipFree(h->sc_pa); hipFree(h->sc_pb);
+  hipFree(h->sim_mat); hipFree(h->sim_pool); hipFree(h->sim_part); hipFree(h->sim_zero);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   if (h->st2) hipStreamSynchronize(h->st2);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);

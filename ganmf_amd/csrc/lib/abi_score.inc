@@ -592,3 +592,100 @@ int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters
   return 0;
 }
 
+// ---- ganmf_score_similarity (gram_stats.hpp) ---------------------------------------------------------------------------------
+constexpr int64_t SIM_MAX_ROWS = 1 << 22;      // 32 768 tile rows: the tiles of the upper triangle still fit a 1-D grid
+
+static int sim_grow(ganmf_handle* h, void** buf, size_t* cap, size_t need, size_t elem_bytes) {
+  if (need <= *cap) return 0;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(*buf); *buf = nullptr; *cap = 0;
+  HIP_TRY(hipMalloc(buf, need * elem_bytes));
+  *cap = need;
+  return 0;
+}
+
+int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t pool, double sums[4], float* pooled,
+                           float* matrix) {
+  const char* who = "ganmf_score_similarity";
+  if (!h || !ids || !sums) return fail(-1, "%s: null argument", who);
+  if (n < 1 || n > SIM_MAX_ROWS) return fail(-1, "%s: n out of range [1,%lld]", who, (long long)SIM_MAX_ROWS);
+  const int limit = transposed ? h->N : h->U;
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= limit) return fail(-1, "%s: id %d out of range [0,%d)", who, ids[i], limit);
+  if (pooled && (pool < 1 || pool > std::min<int64_t>(n, 1024)))
+    return fail(-1, "%s: pool %d out of range [1,%lld]", who, pool, (long long)std::min<int64_t>(n, 1024));
+  const int W = transposed ? h->U : h->N, ldw = round_up(W, LD_ALIGN), ldn = round_up((int)n, LD_ALIGN);
+  const bool want_mat = pooled != nullptr || matrix != nullptr;
+  const int nt = ((int)n + GRAM_TILE - 1) / GRAM_TILE;
+  const long long tiles = gram_row_start(nt, nt);
+  const size_t need_out = (size_t)n * ldw, need_mat = want_mat ? (size_t)n * ldn : 0, need_pool = pooled ? (size_t)pool * pool : 0;
+  HIP_TRY(hipSetDevice(h->dev));
+  {   // never more than a quarter of the free device memory for what this call adds to the handle (the rule of the pass buffers)
+    size_t grow = 0, free_b = 0, total_b = 0;
+    if (need_out > h->sc_out_cap) grow += (need_out - h->sc_out_cap) * sizeof(float);
+    if (need_mat > h->sim_mat_cap) grow += (need_mat - h->sim_mat_cap) * sizeof(float);
+    if (need_pool > h->sim_pool_cap) grow += (need_pool - h->sim_pool_cap) * sizeof(float);
+    if ((size_t)2 * tiles > h->sim_part_cap) grow += ((size_t)2 * tiles - h->sim_part_cap) * sizeof(double);
+    if (grow > 0 && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow > free_b / 4))
+      return fail(-1, "%s: %lld rows%s need %.1f MB more device memory, over a quarter of the %.1f MB free", who, (long long)n,
+                  want_mat ? " with their similarity matrix" : "", grow / 1048576.0, free_b / 1048576.0);
+  }
+  int* ids_dev = nullptr;
+  TRY(upload_ids(h, ids, n, &ids_dev));
+  TRY(sim_grow(h, (void**)&h->sim_mat, &h->sim_mat_cap, need_mat, sizeof(float)));
+  TRY(sim_grow(h, (void**)&h->sim_pool, &h->sim_pool_cap, need_pool, sizeof(float)));
+  TRY(sim_grow(h, (void**)&h->sim_part, &h->sim_part_cap, (size_t)2 * tiles, sizeof(double)));
+  TRY(sim_grow(h, (void**)&h->sim_zero, &h->sim_zero_cap, (size_t)n, sizeof(int)));
+  float* sd = nullptr; int Wd = 0, ldd = 0;
+  int rc = scores_device(h, ids_dev, n, transposed, &sd, &Wd, &ldd);      // unfiltered: a -inf has no cosine
+  if (rc) { hipStreamSynchronize(h->st); return rc; }
+  {
+    Scope s(h, T_SIM_AUX, 3.0 * n * W, 8.0 * n * ldw);
+    GANMF_LAUNCH(sim_normalize_kernel, dim3((int)n), dim3(256), 0, h->st, sd, ldd, Wd, h->sim_zero);
+    HIP_TRY(hipGetLastError());
+  }
+  {
+    GemmP g{};
+    g.A = sd; g.B = sd; g.lda = ldd; g.ldb = ldd;
+    g.C = want_mat ? h->sim_mat : nullptr; g.ldc = ldn;
+    g.M = (int)n; g.N = (int)n; g.K = Wd;
+    g.zero_page = h->zero_page;
+    g.nsplit = 1; g.k_per_split = round_up(Wd, GEMM_K_ALIGN); g.nbatch = 1;
+    g.tiles_m = nt; g.tiles_n = nt;
+    g.epi.kind = EPI_GRAM_STATS; g.epi.gram_partials = h->sim_part;
+    // (flops: the tiles that run, 2 * 128 * 128 * K each -- what the launch executes, against the MFMA roof)
+    Scope s(h, T_SIM_GRAM, 2.0 * tiles * GRAM_TILE * GRAM_TILE * Wd, 4.0 * n * ldw + (want_mat ? 4.0 * n * n : 0.0));
+    if (h->gram_arith == 1) GANMF_LAUNCH(gram_bf16x3_kernel, dim3((unsigned)tiles), dim3(256), 0, h->st, g);
+    else GANMF_LAUNCH(gram_f32_kernel, dim3((unsigned)tiles), dim3(256), 0, h->st, g);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<double> part((size_t)2 * tiles);
+  std::vector<int> zr((size_t)n);
+  hipError_t e = hipMemcpyAsync(part.data(), h->sim_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess) e = hipMemcpyAsync(zr.data(), h->sim_zero, zr.size() * sizeof(int), hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess && pooled) {
+    {
+      Scope s(h, T_SIM_AUX, (double)n * n, 4.0 * n * n);
+      GANMF_LAUNCH(sim_pool_kernel, dim3((unsigned)(pool * pool)), dim3(256), 0, h->st, h->sim_mat, ldn, (int)n, (int)pool, h->sim_pool);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(pooled, h->sim_pool, need_pool * sizeof(float), hipMemcpyDeviceToHost, h->st);
+  }
+  if (e == hipSuccess && matrix)
+    e = hipMemcpy2DAsync(matrix, (size_t)n * 4, h->sim_mat, (size_t)ldn * 4, (size_t)n * 4, n, hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+  if (e != hipSuccess) { hipStreamSynchronize(h->st); return fail(-2, "%s: %s", who, hipGetErrorString(e)); }
+  // finish: the tiles' pairs in tile order, an off-diagonal tile for its mirror image too
+  double s1 = 0.0, s2 = 0.0;
+  size_t t = 0;
+  for (int ti = 0; ti < nt; ++ti)
+    for (int tj = ti; tj < nt; ++tj, ++t) {
+      const double w = tj == ti ? 1.0 : 2.0;
+      s1 += w * part[2 * t]; s2 += w * part[2 * t + 1];
+    }
+  long long zeros = 0;
+  for (int64_t i = 0; i < n; ++i) zeros += zr[(size_t)i];
+  sums[0] = s1; sums[1] = s2; sums[2] = (double)zeros; sums[3] = (double)n;
+  return 0;
+}
+

@@ -40,7 +40,8 @@ int env_int(const char* name, int dflt) {
 // Product knobs, read when a handle is created: GANMF_MFMA, GANMF_MULTI, GANMF_X3KG, GANMF_SCORE_PRESPLIT, GANMF_SPARSE,
 // GANMF_SPARSE_D, GANMF_FORCE_COLLECTIVES, GANMF_LANE_EVENT_FENCE, GANMF_DEBUG_PLAN, and GANMF_TUNE = "key=value,..." with the
 // GEMM-plan overrides the kernel tests use to reach a variant at a small shape: tile (64 | 128), ring (2 | 3 | 4), kg (1 | 2 | 4),
-// nsplit, tile_order (0 | 1 | 2), persist (-1 auto | 0 | 1), score_product (ganmf_bench_scores times the whole product).
+// nsplit, tile_order (0 | 1 | 2), persist (-1 auto | 0 | 1), score_product (ganmf_bench_scores times the whole product),
+// gram (K loop of ganmf_score_similarity's Gram product: 1 exact three-way bf16 split, the default | 0 plain fp32 MFMA).
 // Everything else that ever selected a path -- the alternatives that were measured slower and that no planner picks -- is an
 // EXPERIMENT switch: read only by a library built with `make DIAG=1`, a constant in the product build.
 int tune_env_int(const char* key, int dflt) {
@@ -93,7 +94,7 @@ enum Tag : int {
   T_GEMM_GWD, T_RED_GWD, T_GEMM_GWE, T_RED_GWE, T_ADAM_D, T_GEMM_DF, T_RED_DF, T_GEMM_GUB, T_RED_GUB, T_GEMM_GV,
   T_RED_GV, T_ADAM_V, T_ADAM_U, T_MULTIRED, T_ALLREDUCE, T_SCORE_GEMM, T_RED_SCORE, T_DIS_FWD, T_RED_DIS_FWD, T_DIS_HEAD,
   T_DIS_GW, T_RED_DIS_GW, T_DIS_BWD, T_RED_DIS_BWD, T_FRONT, T_GWD_RED, T_PAIR, T_DE_DCOEF, T_WPAIR,
-  T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_COUNT
+  T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_SIM_GRAM, T_SIM_AUX, T_COUNT
 };
 const char* const kTagName[T_COUNT] = {
   "densify_rows+gather", "gemm_generator[B,k]x[N,k]^T", "reduce_generator", "gemm_encode[2B,N]x[N,e]",
@@ -108,7 +109,9 @@ const char* const kTagName[T_COUNT] = {
   // data-parallel step: reduce-scatter + all-gather of one replicated tensor (side lane), and the time the MAIN lane spent
   // waiting at the join in front of that tensor's next reader (the exposed part of the collective)
   "collective_We (reduce-scatter + all-gather)", "collective_Wd (reduce-scatter + all-gather)",
-  "collective_V (reduce-scatter + all-gather)", "join_wait_We (main lane)", "join_wait_Wd (main lane)", "join_wait_V (main lane)"};
+  "collective_V (reduce-scatter + all-gather)", "join_wait_We (main lane)", "join_wait_Wd (main lane)", "join_wait_V (main lane)",
+  // ganmf_score_similarity: the symmetric Gram product with its statistics, and the row normalisation / block means around it
+  "gram_similarity[n,W]x[n,W]^T + stats", "similarity_normalize / pool"};
 
 struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };
 

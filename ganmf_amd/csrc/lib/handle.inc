@@ -187,6 +187,13 @@ struct ganmf_handle {
   const float* sc_pb_src = nullptr;                 // what sc_pb holds: the planes of this parameter buffer ...
   long long sc_pb_version = -1, param_version = 0;  // ... as of this parameter version (bumped by training, set_tensor, restore_best)
   int sc_pb_rows = 0;
+  // ganmf_score_similarity (gram_stats.hpp): the similarity matrix [n, ld(n)] (only when the matrix or its block means are asked for), the
+  // block means, the per-tile (sum d, sum d^2) pairs and the zero-row flags; grown on demand.  The normalised rows live in sc_out.
+  float *sim_mat = nullptr, *sim_pool = nullptr;
+  double* sim_part = nullptr;
+  int* sim_zero = nullptr;
+  size_t sim_mat_cap = 0, sim_pool_cap = 0, sim_part_cap = 0, sim_zero_cap = 0;
+  int gram_arith = 1;                               // GANMF_TUNE gram: 1 (default, the faster one measured) the exact three-way bf16 split, 0 the plain fp32 MFMA body
   bool score_presplit = true;                       // GANMF_SCORE_PRESPLIT: many-tile scoring products on the pre-split persistent kernel
   // RCCL
   ncclComm_t comm = nullptr;

@@ -451,6 +451,10 @@ class ShardedEngine(object):
         self._sync_master()
         return self.master.evaluate_candidates(ids, cutoffs, disc, ideal_cum, transposed, remove_seen, counts, full)
 
+    def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
+        self._sync_master()
+        return self.master.score_similarity(ids, transposed, pool, return_matrix)
+
     def snapshot_best(self):
         self._sync_master()
         self.master.snapshot_best()

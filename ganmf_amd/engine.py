@@ -266,6 +266,34 @@ class Engine:
                                                        out.ctypes.data_as(dp), cp), "ganmf_evaluate_candidates")
         return (out, counts) if full else out
 
+    def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
+        """Cosine similarity of the (unfiltered) score rows `ids` among themselves, formed on the device (ganmf_score_similarity;
+        the computation under AblationStudy.py:88-92,113-117).  Returns a dict: mean and std (population, as np.mean / np.std of
+        the [n, n] matrix), n, zero_rows (rows of norm 0: similarity 0 with every row, themselves included), sum_d / sum_d2 (the
+        float64 sums of c - 1 and (c - 1)^2 the two are formed from); with pool=P also `pooled`, the [P, P] block means (row i in
+        bin i * P // n, 1 <= P <= min(n, 1024)); with return_matrix=True also `matrix`, the [n, n] float32 similarities."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        n = ids.size
+        sums = np.zeros(4, dtype=np.float64)
+        pooled = matrix = None
+        if pool is not None:      # (an invalid pool is refused by the library: give it a buffer it will not write)
+            p = int(pool)
+            pooled = np.empty((p, p) if 1 <= p <= min(n, 1024) else (1, 1), dtype=np.float32)
+        if return_matrix:
+            matrix = np.empty((n, n), dtype=np.float32)
+        L.check(self.lib.ganmf_score_similarity(self.h, _i32p(ids), n, int(transposed), int(pool) if pool is not None else 0,
+                                                sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                                _f32p(pooled) if pooled is not None else None,
+                                                _f32p(matrix) if matrix is not None else None), "ganmf_score_similarity")
+        md = sums[0] / (float(n) * n)
+        out = dict(mean=1.0 + md, std=float(np.sqrt(max(sums[1] / (float(n) * n) - md * md, 0.0))), n=n, zero_rows=int(sums[2]),
+                   sum_d=float(sums[0]), sum_d2=float(sums[1]))
+        if pooled is not None:
+            out["pooled"] = pooled
+        if matrix is not None:
+            out["matrix"] = matrix
+        return out
+
     def snapshot_best(self):
         L.check(self.lib.ganmf_snapshot_best(self.h), "ganmf_snapshot_best")
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GANMF_ABI_VERSION 1
+#define GANMF_ABI_VERSION 2
 
 typedef struct ganmf_handle ganmf_handle;
 
@@ -296,6 +296,28 @@ int ganmf_recommend_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, i
                                int32_t* out_items, float* out_scores);
 int ganmf_evaluate_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
                               int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts);
+
+/* Cosine similarity of the predictions on the device: the computation under the reference's collapse study
+ * (AblationStudy.py:88-92,113-117: cosine_similarity of all predictions, np.mean and np.std of the [users, users] matrix, and the
+ * matrix behind the heat-map).  For the requested rows ids[0..n) (transposed as in ganmf_scores):
+ *   s_i = the UNFILTERED score row i of ganmf_scores; s^_i = s_i / ||s_i||_2; c_ij = s^_i . s^_j for all n^2 ordered pairs.
+ *   Zero-row rule: a row of norm 0 stays all-zero (sklearn's normalize divides it by 1), so its similarity with every row, itself
+ *   included, is 0; such rows are counted in sums[2] and are part of the statistics, as in np.mean / np.std of the sklearn matrix.
+ *   No-filter rule: the filter of ganmf_set_score_filter is NOT applied, under either score contract -- a -inf has no cosine, and
+ *   the reference's GANMF has no filter.  The filter stays set for the calls that follow.
+ * sums = { sum d, sum d^2, number of zero rows, n } with d = c - 1 over the n^2 pairs, in float64: the caller forms
+ *   mean = 1 + sums[0] / n^2 and std = sqrt(sums[1] / n^2 - (sums[0] / n^2)^2), the population standard deviation of np.std.  (d is
+ *   summed instead of c because the statistic of interest is a collapsed model's, c ~ 1, where this form has no cancellation.)
+ * matrix != NULL: receives the [n, n] float32 similarities.  pooled != NULL: receives [pool, pool] block means of that matrix, row
+ *   i in bin floor(i * pool / n), 1 <= pool <= min(n, 1024) -- what a figure needs, instead of n^2 values over PCIe.  Both NULL:
+ *   statistics only, the matrix is never stored (`pool` is then ignored).
+ * The scores stay on the device; the symmetric product forms only the upper triangle of 128 x 128 tiles in fp32-accurate arithmetic
+ * (ganmf_amd/csrc/gram_stats.hpp), every sum runs in a fixed order without atomics: the same bytes on every call and handle.
+ * Parameters, Adam state and the score filter are not touched.  Errors (-1, message in ganmf_last_error, nothing enqueued, the
+ * handle usable as before): null ids / sums, n < 1, an id out of range, a bad pool, and a call whose buffers would take more than
+ * a quarter of the free device memory. */
+int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t pool, double sums[4], float* pooled,
+                           float* matrix);
 
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
