@@ -447,6 +447,43 @@ class GANMF(BaseRecommender):
                                               remove_seen=remove_seen_flag, counts=counts, full=full)
         return got[0] if full else got
 
+    def evaluate_groups_on_device(self, evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, disc, ideal_cum, group_of,
+                                  n_groups, remove_seen_flag=True, candidates_csr=None, per_user=False):
+        """Hold-out metrics per group of users without leaving the device (ganmf_evaluate_groups): (sums [n_groups, len(cutoffs), 9]
+        float64 in the order of ganmf_amd._lib.EVAL_METRICS, sizes [n_groups], the [n, len(cutoffs), 9] per-user values or None).
+        `group_of[i]` in [-1, n_groups) names the group of user_id_array[i] (-1: none).  `candidates_csr` None: the ranking of
+        evaluate_on_device; given: every user among its own candidates, as evaluate_candidates_on_device.  The test (and candidate)
+        matrix is uploaded once per evaluator (`evaluator_key`).  Returns None under the conditions of those two methods: cut-offs
+        the device selection does not take, more than _lib.EVAL_MAX_CUTOFFS of them, and on the candidate route also
+        score_contract != "mf" and a requested user with more than _lib.CANDIDATES_MAX_PER_ROW candidates; and for more than
+        _lib.EVAL_MAX_GROUPS groups."""
+        self._require_engine()
+        cutoffs = list(cutoffs)
+        cand = candidates_csr is not None
+        if cand and self.score_contract != "mf":
+            return None
+        top = min(L.RECOMMEND_MAX_CUTOFF if cand else self._DEVICE_TOPK_MAX, self.n_items)
+        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or min(cutoffs) < 1 or max(cutoffs) > top:
+            return None
+        if not 0 <= n_groups <= L.EVAL_MAX_GROUPS:
+            return None
+        ids = np.asarray(user_id_array).reshape(-1)
+        if cand and len(ids) and np.ediff1d(candidates_csr.indptr)[ids].max() > L.CANDIDATES_MAX_PER_ROW:
+            return None
+        held = getattr(self, "_test_on_device", None)
+        if held is None or held[0] != evaluator_key or held[1] is not self.engine:
+            self.engine.set_test(urm_test_sorted, gains)
+            self._test_on_device = (evaluator_key, self.engine)
+        if cand:
+            self._candidates_on_device(candidates_csr, key=evaluator_key)
+        return self.engine.evaluate_groups(ids, cutoffs, disc, ideal_cum, group_of, n_groups, transposed=(self.mode == 'item'),
+                                           remove_seen=remove_seen_flag, candidates=cand, per_user=per_user)
+
+    def activity_study(self, URM_test, bounds, cutoff=20, metric="MAP"):
+        """ganmf_amd.studies.activity_study(self, ...): the reference's user-activity study (MFLearned.py:80-145) on the device"""
+        from .studies import activity_study
+        return activity_study(self, URM_test, bounds, cutoff=cutoff, metric=metric)
+
     def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None,
                   remove_top_pop_flag=False, remove_CustomItems_flag=False, return_scores=False):
         device_ok = (not return_scores and not remove_top_pop_flag

@@ -1183,6 +1183,58 @@ struct EvalFullP {
   int order[EVAL_MAX_CUTOFFS]; // cut-off indices by ascending cut-off (ties: lower index first)
 };
 
+// One user's metric values at cut-off c, m[EVAL_METRICS] (m[EVAL_FULL_METRICS] when kFull), from row u of the top-K lists and the
+// user's test row [t0, t1).  The ONE place the per-user arithmetic lives: the summing kernels (eval_topk_body) and the per-user kernel
+// (eval_topk_users_kernel) both call it, so their values cannot drift apart.
+template <bool kFull>
+__device__ __forceinline__ void eval_user_metrics(const EvalP& p, const EvalFullP& f, int u, long long t0, long long t1, int c, double* m) {
+  const double n_test = (double)(t1 - t0);
+  double hits = 0.0, nneg = 0.0, len = 0.0, pairs = 0.0, ap = 0.0, arhr = 0.0, dcg = 0.0, rr = 0.0;
+  double nov = 0.0, pop = 0.0;
+  for (int i = 0; i < c && i < p.K; ++i) {
+    const int it = p.items[(size_t)u * p.K + i];
+    if (it < 0) continue;
+    len += 1.0;
+    if (kFull) { nov += f.w_nov[it]; pop += f.w_pop[it]; }
+    long long lo = t0, hi = t1;          // first stored index >= it
+    while (lo < hi) {
+      const long long mid = (lo + hi) >> 1;
+      if (p.t_indices[mid] < it) lo = mid + 1; else hi = mid;
+    }
+    const bool hit = lo < t1 && p.t_indices[lo] == it;
+    const double inv_rank = 1.0 / (double)(i + 1);
+    if (hit) {
+      hits += 1.0;
+      ap += hits * inv_rank;
+      arhr += inv_rank;
+      if (rr == 0.0) rr = inv_rank;
+      dcg += p.t_gain[lo] * p.disc[i];
+    } else {
+      nneg += 1.0;
+      pairs += hits;                     // every hit ranked before this miss is a correctly ordered pair
+    }
+  }
+  const double den = fmin(n_test, len);
+  m[0] = nneg == 0.0 ? 1.0 : (hits > 0.0 ? pairs / (hits * nneg) : 0.0);
+  m[1] = len > 0.0 ? hits / len : 0.0;
+  m[2] = len > 0.0 ? hits / fmax(den, 1.0) : 0.0;
+  m[3] = hits / n_test;
+  m[4] = len > 0.0 ? ap / fmax(den, 1.0) : 0.0;
+  m[5] = rr;
+  if (dcg > 0.0) {
+    const double ideal = p.ideal_cum[(size_t)u * p.K + (len > 0.0 ? (int)len - 1 : 0)];
+    m[6] = dcg / (ideal > 0.0 ? ideal : 1.0);
+  }
+  m[7] = hits;
+  m[8] = arhr;
+  if (kFull) {
+    m[9] = (double)f.rmse[u];
+    m[10] = nov;
+    m[11] = len > 0.0 ? pop / len : 0.0;
+    m[12] = len > 0.0 ? 1.0 : 0.0;
+  }
+}
+
 template <bool kFull>
 __device__ __forceinline__ void eval_topk_body(const EvalP& p, const EvalFullP& f) {
   constexpr int NM = kFull ? EVAL_FULL_METRICS : EVAL_METRICS;
@@ -1191,7 +1243,6 @@ __device__ __forceinline__ void eval_topk_body(const EvalP& p, const EvalFullP& 
   const bool live = u < p.n;
   long long t0 = 0, t1 = 0;
   if (live) { const int r = p.ids[u]; t0 = p.t_indptr[r]; t1 = p.t_indptr[r + 1]; }
-  const double n_test = (double)(t1 - t0);
   if (kFull) {
     extern __shared__ unsigned hist[];
     const int nbin = p.ncut * f.W;
@@ -1229,52 +1280,7 @@ __device__ __forceinline__ void eval_topk_body(const EvalP& p, const EvalFullP& 
     double m[NM];
 #pragma unroll
     for (int q = 0; q < NM; ++q) m[q] = 0.0;
-    if (live) {
-      double hits = 0.0, nneg = 0.0, len = 0.0, pairs = 0.0, ap = 0.0, arhr = 0.0, dcg = 0.0, rr = 0.0;
-      double nov = 0.0, pop = 0.0;
-      for (int i = 0; i < c && i < p.K; ++i) {
-        const int it = p.items[(size_t)u * p.K + i];
-        if (it < 0) continue;
-        len += 1.0;
-        if (kFull) { nov += f.w_nov[it]; pop += f.w_pop[it]; }
-        long long lo = t0, hi = t1;          // first stored index >= it
-        while (lo < hi) {
-          const long long mid = (lo + hi) >> 1;
-          if (p.t_indices[mid] < it) lo = mid + 1; else hi = mid;
-        }
-        const bool hit = lo < t1 && p.t_indices[lo] == it;
-        const double inv_rank = 1.0 / (double)(i + 1);
-        if (hit) {
-          hits += 1.0;
-          ap += hits * inv_rank;
-          arhr += inv_rank;
-          if (rr == 0.0) rr = inv_rank;
-          dcg += p.t_gain[lo] * p.disc[i];
-        } else {
-          nneg += 1.0;
-          pairs += hits;                     // every hit ranked before this miss is a correctly ordered pair
-        }
-      }
-      const double den = fmin(n_test, len);
-      m[0] = nneg == 0.0 ? 1.0 : (hits > 0.0 ? pairs / (hits * nneg) : 0.0);
-      m[1] = len > 0.0 ? hits / len : 0.0;
-      m[2] = len > 0.0 ? hits / fmax(den, 1.0) : 0.0;
-      m[3] = hits / n_test;
-      m[4] = len > 0.0 ? ap / fmax(den, 1.0) : 0.0;
-      m[5] = rr;
-      if (dcg > 0.0) {
-        const double ideal = p.ideal_cum[(size_t)u * p.K + (len > 0.0 ? (int)len - 1 : 0)];
-        m[6] = dcg / (ideal > 0.0 ? ideal : 1.0);
-      }
-      m[7] = hits;
-      m[8] = arhr;
-      if (kFull) {
-        m[9] = (double)f.rmse[u];
-        m[10] = nov;
-        m[11] = len > 0.0 ? pop / len : 0.0;
-        m[12] = len > 0.0 ? 1.0 : 0.0;
-      }
-    }
+    if (live) eval_user_metrics<kFull>(p, f, u, t0, t1, c, m);
 #pragma unroll
     for (int q = 0; q < NM; ++q) {
       red[threadIdx.x] = m[q];
@@ -1291,5 +1297,43 @@ __device__ __forceinline__ void eval_topk_body(const EvalP& p, const EvalFullP& 
 
 __global__ __launch_bounds__(256) void eval_topk_kernel(const EvalP p) { eval_topk_body<false>(p, EvalFullP{}); }
 __global__ __launch_bounds__(256) void eval_topk_full_kernel(const EvalP p, const EvalFullP f) { eval_topk_body<true>(p, f); }
+
+// Per-user values instead of sums (ganmf_evaluate_groups): thread u writes its user's EVAL_METRICS values of every cut-off to
+// out[u][ncut][EVAL_METRICS] (p.partials is not used).
+__global__ __launch_bounds__(256) void eval_topk_users_kernel(const EvalP p, double* __restrict__ out) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= p.n) return;
+  const int r = p.ids[u];
+  const long long t0 = p.t_indptr[r], t1 = p.t_indptr[r + 1];
+  for (int ci = 0; ci < p.ncut; ++ci) {
+    double m[EVAL_METRICS];
+#pragma unroll
+    for (int q = 0; q < EVAL_METRICS; ++q) m[q] = 0.0;
+    eval_user_metrics<false>(p, EvalFullP{}, u, t0, t1, p.cutoffs[ci], m);
+#pragma unroll
+    for (int q = 0; q < EVAL_METRICS; ++q) out[((size_t)u * p.ncut + ci) * EVAL_METRICS + q] = m[q];
+  }
+}
+
+// Sums of the per-user values over the members of each group, in a fixed order: workgroup (g, col) takes column col (one cut-off, one
+// metric) of group g, whose members are members[begin[g] .. begin[g + 1]) -- positions of the call's ids, ascending (the host's counting
+// sort).  Thread t adds members t, t + 256, ... in that order, then the 256 partial sums go through the LDS tree of eval_topk_body: no
+// floating-point atomics, the same bytes for the same membership on every call.  An empty group writes 0.
+constexpr int EVAL_MAX_GROUPS = 256;
+__global__ __launch_bounds__(256) void eval_group_sum_kernel(const double* __restrict__ vals, int ncol, const int* __restrict__ members,
+                                                             const int* __restrict__ begin, double* __restrict__ sums) {
+  __shared__ double red[256];
+  const int g = blockIdx.x, col = blockIdx.y;
+  const int b0 = begin[g], b1 = begin[g + 1];
+  double acc = 0.0;
+  for (int j = b0 + (int)threadIdx.x; j < b1; j += 256) acc += vals[(size_t)members[j] * ncol + col];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) sums[(size_t)g * ncol + col] = red[0];
+}
 
 }  // namespace ganmf

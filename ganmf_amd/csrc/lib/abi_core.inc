@@ -261,7 +261,7 @@ int ganmf_destroy(ganmf_handle* h) {
   if (h->stage_f) hipHostFree(h->stage_f);
   hipFree(h->test_indptr); hipFree(h->test_indices); hipFree(h->test_gain); hipFree(h->eval_buf);
   hipFree(h->cand_indptr); hipFree(h->cand_indices);
-  hipFree(h->test_rating); hipFree(h->eval_w); hipFree(h->eval_rmse); hipFree(h->eval_counts);
+  hipFree(h->test_rating); hipFree(h->eval_w); hipFree(h->eval_rmse); hipFree(h->eval_counts); hipFree(h->eval_grp);
   hipFree(h->XF_own); hipFree(h->XF_pass); hipFree(h->Ub_pass); hipFree(h->Ub_own); hipFree(h->Ub_sched); hipFree(h->lazy_tab);
   for (auto& ch : h->lazy_chunks) hipFree(ch.first);
   if (h->lazy_stage) hipHostFree(h->lazy_stage);

@@ -539,6 +539,98 @@ int ganmf_evaluate_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, in
   return evaluate_full_impl(h, who, true, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums, counts);
 }
 
+// ganmf_evaluate_groups: the ranking of ganmf_evaluate (candidates = 0) or ganmf_evaluate_candidates (candidates = 1), then every user's
+// own metric values (eval_topk_users_kernel) instead of their sum, and the sums of those values per group of users in a fixed order
+// (eval_group_sum_kernel).  Every argument check runs before anything is enqueued.
+static_assert(EVAL_MAX_GROUPS == GANMF_EVAL_MAX_GROUPS, "group limit of the kernels and of the header");
+int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, int candidates,
+                          const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum,
+                          const int32_t* group_of, int32_t n_groups, double* group_sums, int64_t* group_size, double* per_user) {
+  const char* who = "ganmf_evaluate_groups";
+  if (!h || !ids || !cutoffs || !disc || !ideal_cum) return fail(-1, "%s: null argument", who);
+  if (n_groups < 0 || n_groups > GANMF_EVAL_MAX_GROUPS) return fail(-1, "%s: %d groups, 0..%d per call", who, n_groups, GANMF_EVAL_MAX_GROUPS);
+  if (n_groups == 0 && !per_user) return fail(-1, "%s: neither groups nor per_user asked for", who);
+  if (n_groups > 0 && (!group_of || !group_sums || !group_size)) return fail(-1, "%s: null group argument", who);
+  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
+  if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
+  const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
+  if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
+    return fail(-1, "%s: needs ganmf_set_test_csr with a %d x %d matrix", who, limit, W);
+  int K = 0;
+  for (int i = 0; i < n_cutoffs; ++i) {
+    if (cutoffs[i] < 1) return fail(-1, "%s: cut-off %d", who, cutoffs[i]);
+    K = std::max(K, (int)cutoffs[i]);
+  }
+  // members of every group: positions of `ids`, ascending inside a group (counting sort) -- the order the sums are formed in
+  const int G = n_groups;
+  std::vector<int> begin((size_t)G + 1, 0), members;
+  if (G > 0) {
+    for (int64_t i = 0; i < n; ++i) {
+      if (group_of[i] < -1 || group_of[i] >= G)
+        return fail(-1, "%s: group_of[%lld] = %d out of range [-1,%d)", who, (long long)i, group_of[i], G);
+      if (group_of[i] >= 0) ++begin[(size_t)group_of[i] + 1];
+    }
+    for (int g = 0; g < G; ++g) begin[(size_t)g + 1] += begin[(size_t)g];
+    members.resize((size_t)std::max(begin[(size_t)G], 1));
+    std::vector<int> at(begin.begin(), begin.end() - 1);
+    for (int64_t i = 0; i < n; ++i)
+      if (group_of[i] >= 0) members[(size_t)at[(size_t)group_of[i]]++] = (int)i;
+  }
+  int* ids_dev = nullptr;
+  if (candidates) TRY(candidates_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
+  else TRY(recommend_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
+  const int ncol = n_cutoffs * EVAL_METRICS;
+  const size_t n_user = (size_t)n * ncol, n_sum = (size_t)G * ncol;
+  const size_t need = (size_t)K + (size_t)n * K + n_user + n_sum;
+  if (need > h->eval_cap) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    hipFree(h->eval_buf); h->eval_buf = nullptr; h->eval_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h->eval_buf, need * sizeof(double)));
+    h->eval_cap = need;
+  }
+  const size_t need_grp = G > 0 ? members.size() + begin.size() : 0;
+  if (need_grp > h->eval_grp_cap) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    hipFree(h->eval_grp); h->eval_grp = nullptr; h->eval_grp_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h->eval_grp, need_grp * sizeof(int)));
+    h->eval_grp_cap = need_grp;
+  }
+  double* d_disc = h->eval_buf;
+  double* d_ideal = d_disc + K;
+  double* d_user = d_ideal + (size_t)n * K;
+  double* d_sum = d_user + n_user;
+  HIP_TRY(hipMemcpyAsync(d_disc, disc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->st));
+  HIP_TRY(hipMemcpyAsync(d_ideal, ideal_cum, (size_t)n * K * sizeof(double), hipMemcpyHostToDevice, h->st));
+  EvalP p{};
+  p.items = h->topk_items; p.K = K; p.n = (int)n; p.ids = ids_dev;
+  p.t_indptr = h->test_indptr; p.t_indices = h->test_indices; p.t_gain = h->test_gain;
+  p.disc = d_disc; p.ideal_cum = d_ideal; p.ncut = n_cutoffs; p.partials = nullptr;
+  for (int i = 0; i < n_cutoffs; ++i) p.cutoffs[i] = cutoffs[i];
+  {
+    Scope s(h, T_EVAL_GROUPS, 0.0, 4.0 * n * K + 8.0 * n * K + 8.0 * n_user);
+    GANMF_LAUNCH(eval_topk_users_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, p, d_user);
+    HIP_TRY(hipGetLastError());
+  }
+  hipError_t e = hipSuccess;
+  if (G > 0) {
+    int* d_members = h->eval_grp;
+    int* d_begin = d_members + members.size();
+    e = hipMemcpyAsync(d_members, members.data(), members.size() * sizeof(int), hipMemcpyHostToDevice, h->st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_begin, begin.data(), begin.size() * sizeof(int), hipMemcpyHostToDevice, h->st);
+    if (e == hipSuccess) {
+      Scope s(h, T_EVAL_GROUPS, (double)begin[(size_t)G] * ncol, 12.0 * begin[(size_t)G] * ncol + 8.0 * n_sum);
+      GANMF_LAUNCH(eval_group_sum_kernel, dim3((unsigned)G, (unsigned)ncol), dim3(256), 0, h->st, d_user, ncol, d_members, d_begin, d_sum);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(group_sums, d_sum, n_sum * sizeof(double), hipMemcpyDeviceToHost, h->st);
+  }
+  if (e == hipSuccess && per_user) e = hipMemcpyAsync(per_user, d_user, n_user * sizeof(double), hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+  if (e != hipSuccess) { hipStreamSynchronize(h->st); return fail(-2, "%s: %s", who, hipGetErrorString(e)); }   // (members / begin are locals)
+  for (int g = 0; g < G; ++g) group_size[g] = (int64_t)(begin[(size_t)g + 1] - begin[(size_t)g]);
+  return 0;
+}
+
 int ganmf_recommend(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t cutoff, int remove_seen,
                     int32_t* out_items, float* out_scores) {
   if (!h || !ids || !out_items) return fail(-1, "ganmf_recommend: null argument");

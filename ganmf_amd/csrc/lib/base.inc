@@ -94,7 +94,7 @@ enum Tag : int {
   T_GEMM_GWD, T_RED_GWD, T_GEMM_GWE, T_RED_GWE, T_ADAM_D, T_GEMM_DF, T_RED_DF, T_GEMM_GUB, T_RED_GUB, T_GEMM_GV,
   T_RED_GV, T_ADAM_V, T_ADAM_U, T_MULTIRED, T_ALLREDUCE, T_SCORE_GEMM, T_RED_SCORE, T_DIS_FWD, T_RED_DIS_FWD, T_DIS_HEAD,
   T_DIS_GW, T_RED_DIS_GW, T_DIS_BWD, T_RED_DIS_BWD, T_FRONT, T_GWD_RED, T_PAIR, T_DE_DCOEF, T_WPAIR,
-  T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_SIM_GRAM, T_SIM_AUX, T_COUNT
+  T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_SIM_GRAM, T_SIM_AUX, T_EVAL_GROUPS, T_COUNT
 };
 const char* const kTagName[T_COUNT] = {
   "densify_rows+gather", "gemm_generator[B,k]x[N,k]^T", "reduce_generator", "gemm_encode[2B,N]x[N,e]",
@@ -111,7 +111,10 @@ const char* const kTagName[T_COUNT] = {
   "collective_We (reduce-scatter + all-gather)", "collective_Wd (reduce-scatter + all-gather)",
   "collective_V (reduce-scatter + all-gather)", "join_wait_We (main lane)", "join_wait_Wd (main lane)", "join_wait_V (main lane)",
   // ganmf_score_similarity: the symmetric Gram product with its statistics, and the row normalisation / block means around it
-  "gram_similarity[n,W]x[n,W]^T + stats", "similarity_normalize / pool"};
+  "gram_similarity[n,W]x[n,W]^T + stats", "similarity_normalize / pool",
+  // ganmf_evaluate_groups: the per-user metric values and their sums per group of users
+  "eval_groups: per-user metrics / group sums"};
+static_assert(T_COUNT <= GANMF_PROF_MAX, "ganmf_profile_read's callers size their buffer by GANMF_PROF_MAX");
 
 struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };
 

@@ -171,6 +171,9 @@ struct ganmf_handle {
   size_t eval_rmse_cap = 0;
   unsigned* eval_counts = nullptr;
   size_t eval_counts_cap = 0;
+  // ganmf_evaluate_groups(): members of every group | their begin offsets (the per-user values and the group sums live in eval_buf)
+  int* eval_grp = nullptr;
+  size_t eval_grp_cap = 0;
   // ganmf_set_candidates_csr: per-row candidate lists (evaluation orientation, rows sorted and unique) for cand_topk_kernel;
   // the host keeps the row pointers to size a launch's LDS and to refuse a row over GANMF_CANDIDATES_MAX_PER_ROW without launching
   long long* cand_indptr = nullptr;

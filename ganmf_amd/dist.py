@@ -451,6 +451,12 @@ class ShardedEngine(object):
         self._sync_master()
         return self.master.evaluate_candidates(ids, cutoffs, disc, ideal_cum, transposed, remove_seen, counts, full)
 
+    def evaluate_groups(self, ids, cutoffs, disc, ideal_cum, group_of, n_groups, transposed=False, remove_seen=True,
+                        candidates=False, per_user=False):
+        self._sync_master()
+        return self.master.evaluate_groups(ids, cutoffs, disc, ideal_cum, group_of, n_groups, transposed, remove_seen, candidates,
+                                           per_user)
+
     def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
         self._sync_master()
         return self.master.score_similarity(ids, transposed, pool, return_matrix)

@@ -266,6 +266,36 @@ class Engine:
                                                        out.ctypes.data_as(dp), cp), "ganmf_evaluate_candidates")
         return (out, counts) if full else out
 
+    def evaluate_groups(self, ids, cutoffs, disc, ideal_cum, group_of, n_groups, transposed=False, remove_seen=True,
+                        candidates=False, per_user=False):
+        """evaluate() (candidates=False) or evaluate_candidates() (candidates=True) per group of users (ganmf_evaluate_groups):
+        group_of[i] in [-1, n_groups) is the group of ids[i], -1 = in no group (None with n_groups = 0: per-user values only).
+        Returns (sums [n_groups, len(cutoffs), 9] float64 over each group's members, sizes [n_groups] int64, the
+        [len(ids), len(cutoffs), 9] per-user values in the order of `ids` when per_user=True, else None)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
+        K = int(cut.max())
+        disc = np.ascontiguousarray(disc, dtype=np.float64).ravel()
+        ideal = np.ascontiguousarray(ideal_cum, dtype=np.float64)
+        assert disc.size >= K and ideal.shape == (ids.size, K)
+        G = int(n_groups)
+        grp = None
+        if group_of is not None:
+            grp = np.ascontiguousarray(group_of, dtype=np.int32).ravel()
+            assert grp.size == ids.size
+        sums = np.zeros((max(G, 0), cut.size, len(L.EVAL_METRICS)), dtype=np.float64)
+        sizes = np.zeros(max(G, 0), dtype=np.int64)
+        users = np.zeros((ids.size, cut.size, len(L.EVAL_METRICS)), dtype=np.float64) if per_user else None
+        dp = C.POINTER(C.c_double)
+        if ids.size:
+            L.check(self.lib.ganmf_evaluate_groups(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), int(candidates),
+                                                   _i32p(cut), cut.size, disc.ctypes.data_as(dp), ideal.ctypes.data_as(dp),
+                                                   _i32p(grp) if grp is not None else None, G,
+                                                   sums.ctypes.data_as(dp) if G > 0 else None,
+                                                   sizes.ctypes.data_as(C.POINTER(C.c_int64)) if G > 0 else None,
+                                                   users.ctypes.data_as(dp) if users is not None else None), "ganmf_evaluate_groups")
+        return sums, sizes, users
+
     def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
         """Cosine similarity of the (unfiltered) score rows `ids` among themselves, formed on the device (ganmf_score_similarity;
         the computation under AblationStudy.py:88-92,113-117).  Returns a dict: mean and std (population, as np.mean / np.std of

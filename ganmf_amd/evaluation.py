@@ -131,9 +131,12 @@ class RankedListMetrics(object):
     """Accuracy metrics of one user's ranked list against that user's test items.
 
     `test_items` / `test_ratings`: the stored entries of the user's URM_test row.  `__call__(recommended, c)` returns a
-    dict over the metric names for the list cut at c."""
+    dict over the metric names for the list cut at c.  `dtype=np.float64`: the same values in float64 throughout, as
+    EvaluatorHoldoutFast and the device form them (only the ratings' powers of two and the logarithms stay float32, as everywhere)
+    -- the per-user values of `evaluateRecommenderByGroup`."""
 
-    def __init__(self, test_items, test_ratings, max_cutoff):
+    def __init__(self, test_items, test_ratings, max_cutoff, dtype=np.float32):
+        self._exact = np.dtype(dtype) == np.float64
         order = np.argsort(test_items, kind="stable")
         self._items = np.asarray(test_items)[order]
         self._ratings = np.asarray(test_ratings)[order]
@@ -142,6 +145,10 @@ class RankedListMetrics(object):
         self._ln_rank = np.log(np.arange(max_cutoff, dtype=np.float32) + 2)
         best_first = np.sort(np.asarray(test_ratings))[::-1][:max_cutoff]
         self._ideal_terms = (np.power(2, best_first.astype(np.float32)) - 1) / self._ln_rank[:best_first.shape[0]]
+        if self._exact:
+            self._disc = 1.0 / self._ln_rank.astype(np.float64)
+            self._ideal_cum = np.cumsum((np.power(2.0, best_first.astype(np.float32)).astype(np.float64) - 1.0)
+                                        * self._disc[:best_first.shape[0]])
 
     def match(self, recommended):
         """(hit flags, rating of each hit else 0) for the ranked ids."""
@@ -152,7 +159,35 @@ class RankedListMetrics(object):
         hit = self._items[slot] == recommended
         return hit, np.where(hit, self._ratings[slot], 0).astype(np.float32)
 
+    def _call_float64(self, hit, gain, c):
+        hit, gain = hit[:c], gain[:c]
+        n = int(hit.shape[0])
+        at = np.flatnonzero(hit)
+        n_hit = int(at.shape[0])
+        n_miss = n - n_hit
+        out = dict.fromkeys(_SUMMED, 0.0)
+        out["HIT_RATE"] = float(n_hit)
+        out["RECALL"] = n_hit / self.n_test if self.n_test else float("nan")
+        if n:
+            out["PRECISION"] = n_hit / n
+            out["PRECISION_RECALL_MIN_DEN"] = n_hit / max(min(self.n_test, n), 1)
+        if n_miss == 0:
+            out["ROC_AUC"] = 1.0
+        elif n_hit:
+            out["ROC_AUC"] = int(((n - 1 - at) - (n_hit - 1 - np.arange(n_hit))).sum()) / (n_hit * n_miss)
+        if n_hit:
+            rank = at + 1.0
+            out["MRR"] = float(1.0 / rank[0])
+            out["ARHR"] = float((1.0 / rank).sum())
+            out["MAP"] = float((np.arange(1, n_hit + 1, dtype=np.float64) / rank).sum()) / min(self.n_test, n)
+            dcg = float(((np.power(2.0, gain[at].astype(np.float32)).astype(np.float64) - 1.0) * self._disc[at]).sum())
+            if dcg > 0.0:
+                out["NDCG"] = dcg / float(self._ideal_cum[min(n, self._ideal_cum.shape[0]) - 1])
+        return out
+
     def __call__(self, hit, gain, c):
+        if self._exact:
+            return self._call_float64(hit, gain, c)
         hit, gain = hit[:c], gain[:c]
         n = int(hit.shape[0])
         at = np.flatnonzero(hit)                       # 0-based ranks of the hits
@@ -191,11 +226,11 @@ def rmse_on_test_items(score_row, test_items, test_ratings):
     return np.sqrt(np.sum(sq[usable]) / count) if count else np.nan
 
 
-def _finish(sums, n_eval, cutoffs):
+def _finish(sums, n_eval, cutoffs, names=_SUMMED):
     """Means over the evaluated users + F1 of the mean precision / recall (0 when both are 0)."""
     results = {}
     for c in cutoffs:
-        r = {name: sums[c][name] / n_eval for name in _SUMMED}
+        r = {name: sums[c][name] / n_eval for name in names}
         p, rc = r["PRECISION"], r["RECALL"]
         r["F1"] = 2 * (p * rc) / (p + rc) if p + rc != 0 else 0.0
         results[c] = r
@@ -243,6 +278,84 @@ class EvaluatorHoldout(object):
             for user, recommended, score_row in zip(batch, rec_lists, scores_batch):
                 self._add_user(sums, full, user, recommended, score_row, w_novelty, w_popularity)
         return self._finish_users(sums, full, len(users))
+
+    # ---- metrics per group of users ----------------------------------------------------------------------------------------
+    def evaluateRecommenderByGroup(self, recommender_object, user_groups, return_per_user=False):
+        """The accuracy metrics per group of users instead of over all of them (what the reference's user-activity study,
+        MFLearned.py:80-145, computes for MAP; also metrics per segment or fold, and per-user values for a significance test).
+        `user_groups`: one integer per row of URM_test, the user's group; -1 = in no group.  Users below minRatingsPerUser
+        are not evaluated whatever their group (`usersToEvaluate`, as in evaluateRecommender).
+        Returns {group: {cutoff: {metric: value}, "n_users": n}} for every group value >= 0 of `user_groups`: the nine values
+        of ganmf_amd._lib.EVAL_METRICS as means over the group's n evaluated users, and F1 from the group's mean precision
+        and recall as evaluateRecommender forms it; a group without evaluated users gets zeros.  RMSE and the
+        beyond-accuracy metrics are NOT part of the grouped row (`full_metrics` is ignored): RMSE needs every score, the
+        others are properties of a whole set of lists.  Per-user values are float64 (RankedListMetrics(dtype=np.float64)) on
+        every class and route.  `return_per_user=True`: (that dict, the [n_evaluated, n_cutoffs, 9] per-user values, the
+        evaluated user ids in the same order)."""
+        labels, group_idx = self._group_index(user_groups)
+        return self._finish_groups(labels, group_idx, self._per_user_host(recommender_object), return_per_user)
+
+    def _group_index(self, user_groups):
+        """(the group values >= 0 in ascending order, the index into them of every evaluated user or -1)"""
+        groups = np.asarray(user_groups).reshape(-1)
+        if groups.shape[0] != self.n_users or not np.issubdtype(groups.dtype, np.integer) or (len(groups) and groups.min() < -1):
+            raise ValueError("user_groups: one integer >= -1 per row of URM_test")
+        labels = np.unique(groups[groups >= 0])
+        of_eval = groups[np.asarray(self.usersToEvaluate, dtype=np.int64)]
+        return labels, np.where(of_eval >= 0, np.searchsorted(labels, of_eval), -1).astype(np.int64)
+
+    def _ranked_lists(self, recommender_object):
+        """the evaluated users' ranked lists in the order of usersToEvaluate, from the calls evaluateRecommender makes"""
+        block_size = max(min(1000, int(1e8 / self.n_items)), 1)
+        users = np.asarray(self.usersToEvaluate, dtype=np.int64)
+        for lo in range(0, len(users), block_size):
+            batch = users[lo:lo + block_size]
+            rec_lists, _ = recommender_object.recommend(
+                batch, remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
+                remove_CustomItems_flag=False, return_scores=True)
+            assert len(rec_lists) == len(batch)
+            for recommended in rec_lists:
+                yield recommended
+
+    def _per_user_host(self, recommender_object):
+        """[n_evaluated, n_cutoffs, 9] float64: every evaluated user's values in the order of ganmf_amd._lib.EVAL_METRICS"""
+        from ._lib import EVAL_METRICS
+        users = self.usersToEvaluate
+        vals = np.zeros((len(users), len(self.cutoff_list), len(EVAL_METRICS)), dtype=np.float64)
+        for i, recommended in enumerate(self._ranked_lists(recommender_object)):
+            user = users[i]
+            scorer = RankedListMetrics(self.get_user_relevant_items(user), self.get_user_test_ratings(user), self.max_cutoff,
+                                       dtype=np.float64)
+            hit, gain = scorer.match(np.asarray(recommended))
+            for ci, c in enumerate(self.cutoff_list):
+                row = scorer(hit, gain, c)
+                vals[i, ci] = [row[name] for name in EVAL_METRICS]
+        return vals
+
+    def _finish_groups(self, labels, group_idx, per_user, return_per_user, sums=None, sizes=None):
+        """the result of evaluateRecommenderByGroup from the per-user values, or from group sums / sizes formed elsewhere"""
+        from ._lib import EVAL_METRICS
+        if sums is None:
+            sums = np.zeros((len(labels), len(self.cutoff_list), len(EVAL_METRICS)), dtype=np.float64)
+            sizes = np.zeros(len(labels), dtype=np.int64)
+            for g in range(len(labels)):
+                member = group_idx == g
+                sizes[g] = int(member.sum())
+                sums[g] = per_user[member].sum(axis=0)
+        results = {}
+        for g, label in enumerate(labels):
+            n = int(sizes[g])
+            if n:
+                rows = _finish({c: dict(zip(EVAL_METRICS, sums[g, ci])) for ci, c in enumerate(self.cutoff_list)}, n,
+                               self.cutoff_list, names=EVAL_METRICS)
+                rows = {c: {m: float(v) for m, v in row.items()} for c, row in rows.items()}
+            else:
+                rows = {c: dict.fromkeys(EVAL_METRICS + ("F1",), 0.0) for c in self.cutoff_list}
+            rows["n_users"] = n
+            results[int(label)] = rows
+        if return_per_user:
+            return results, per_user, np.asarray(self.usersToEvaluate, dtype=np.int64)
+        return results
 
     def _add_user(self, sums, full, user, recommended, score_row, w_novelty, w_popularity):
         """one user's ranked list and score row into the running sums of every cut-off (Evaluator.py:280-335)"""
@@ -405,6 +518,50 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
             self._add_block(sums, full, items, sl, rmse_sum, w_novelty, w_popularity)
         return self._finish_blocks(sums, full, n_eval)
 
+    def _ranked_lists(self, recommender_object):
+        """the host route's lists: `_topk` in the blocks of evaluateRecommender"""
+        block_size = self._block_size or max(1, min(4096, int(1e8 / self.n_items)))
+        for start in range(0, len(self._users), block_size):
+            for row in self._topk(recommender_object, self._users[start:start + block_size]):
+                yield row[row >= 0]
+
+    def _device_groups(self, rec, labels, group_idx, per_user, block, candidates=None):
+        """(sums [G, C, 9], sizes [G], per-user values or None) of evaluate_groups_on_device over all user blocks, added in block
+        order; None when the recommender declines the device route"""
+        sums = sizes = None
+        users = []
+        for start in range(0, len(self._users), block):
+            sl = slice(start, min(start + block, len(self._users)))
+            part = rec.evaluate_groups_on_device(self._device_token, self._test_sorted, self._test_gain, self._users[sl],
+                                                 self.cutoff_list, self._disc, self._ideal_cum[sl], group_idx[sl], len(labels),
+                                                 remove_seen_flag=self.exclude_seen, candidates_csr=candidates, per_user=per_user)
+            if part is None:
+                return None
+            sums = part[0] if sums is None else sums + part[0]
+            sizes = part[1] if sizes is None else sizes + part[1]
+            users.append(part[2])
+        return sums, sizes, np.concatenate(users) if per_user else None
+
+    def _groups_on_device(self, rec, labels, group_idx, per_user, block, candidates=None):
+        """_device_groups where evaluateRecommender would take its device route, else None"""
+        if not (self.use_device_metrics and len(self._users) > 0 and hasattr(rec, "evaluate_groups_on_device")):
+            return None
+        try:
+            return self._device_groups(rec, labels, group_idx, per_user, block, candidates)
+        except MemoryError:
+            return None
+
+    def evaluateRecommenderByGroup(self, recommender_object, user_groups, return_per_user=False):
+        """EvaluatorHoldout.evaluateRecommenderByGroup; with a recommender that has `evaluate_groups_on_device`
+        (ganmf_evaluate_groups) ranking, per-user values and group sums stay on the device, and the host route is taken exactly
+        where evaluateRecommender takes it."""
+        labels, group_idx = self._group_index(user_groups)
+        got = self._groups_on_device(recommender_object, labels, group_idx, return_per_user,
+                                     self._block_size or max(1, int(1e8 / self.n_items)))
+        if got is not None:
+            return self._finish_groups(labels, group_idx, got[2], return_per_user, sums=got[0], sizes=got[1])
+        return self._finish_groups(labels, group_idx, self._per_user_host(recommender_object), return_per_user)
+
     def _from_device_full(self, sums, full, dev, counts, n_eval):
         """results from the [n_cutoffs, 13] device sums and the [n_cutoffs, n_items] counts of a full-row device route"""
         from ._lib import EVAL_FULL_METRICS
@@ -548,6 +705,15 @@ class EvaluatorNegativeItemSample(EvaluatorHoldout):
             self._add_user(sums, full, user, rec_lists[0], scores[0], w_novelty, w_popularity)
         return self._finish_users(sums, full, len(self.usersToEvaluate))
 
+    def _ranked_lists(self, recommender_object):
+        for user in self.usersToEvaluate:
+            rec_lists, _ = recommender_object.recommend(
+                np.atleast_1d(user), remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
+                items_to_compute=self._get_user_specific_items_to_compute(user), remove_CustomItems_flag=False,
+                return_scores=True)
+            assert len(rec_lists) == 1
+            yield rec_lists[0]
+
 
 class EvaluatorNegativeItemSampleFast(EvaluatorHoldoutFast):
     """EvaluatorNegativeItemSample's protocol and result dictionaries, consuming only the top-`max_cutoff` ids of every user, with
@@ -609,6 +775,45 @@ class EvaluatorNegativeItemSampleFast(EvaluatorHoldoutFast):
             if with_scores:
                 rmse_sum += float(rmse_on_test_items(scores[0], self.get_user_relevant_items(u), self.get_user_test_ratings(u)))
         return out, rmse_sum
+
+    def _ranked_lists(self, recommender_object):
+        """the host routes of evaluateRecommender: full width for a recommender that ignores items_to_compute, else blocks
+        through recommend_candidates while it takes them, then user by user"""
+        rec = recommender_object
+        if not getattr(rec, "honours_items_to_compute", True):
+            for row in super()._ranked_lists(rec):
+                yield row
+            return
+        by_block = hasattr(rec, "recommend_candidates")
+        block_size = self._block_size or 4096
+        for start in range(0, len(self._users), block_size):
+            batch = self._users[start:start + block_size]
+            items = None
+            if by_block:
+                try:
+                    items = np.asarray(rec.recommend_candidates(batch, self.URM_items_to_rank, self.max_cutoff,
+                                                                remove_seen_flag=self.exclude_seen,
+                                                                candidates_key=self._device_token), dtype=np.int64)
+                except (ValueError, RuntimeError):
+                    by_block = False
+            if items is None:
+                items, _ = self._per_user(rec, batch, with_scores=False)
+            for row in items:
+                yield row[row >= 0]
+
+    def evaluateRecommenderByGroup(self, recommender_object, user_groups, return_per_user=False):
+        """EvaluatorHoldout.evaluateRecommenderByGroup with every user ranked among its own candidates; the routes of
+        evaluateRecommender in its order (device candidates, full width for a recommender that ignores items_to_compute, blocks,
+        users)."""
+        rec = recommender_object
+        labels, group_idx = self._group_index(user_groups)
+        got = self._groups_on_device(rec, labels, group_idx, return_per_user, self._block_size or 65536,
+                                     candidates=self.URM_items_to_rank)
+        if got is not None:
+            return self._finish_groups(labels, group_idx, got[2], return_per_user, sums=got[0], sizes=got[1])
+        if not getattr(rec, "honours_items_to_compute", True):
+            return super().evaluateRecommenderByGroup(rec, user_groups, return_per_user=return_per_user)
+        return self._finish_groups(labels, group_idx, self._per_user_host(rec), return_per_user)
 
     def evaluateRecommender(self, recommender_object):
         rec = recommender_object

@@ -297,6 +297,28 @@ int ganmf_recommend_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, i
 int ganmf_evaluate_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
                               int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts);
 
+/* Hold-out metrics per user and per group of users on the device -- what the reference's user-activity study computes in a Python loop
+ * over a [users, items] score matrix (MFLearned.py:80-145: MAP@20 of every user, averaged per bucket of interaction counts), and what
+ * metrics per segment / fold or a significance test over users need.
+ * ganmf_evaluate_groups ranks the rows `ids` exactly as ganmf_evaluate does (candidates = 0: the full width, with the score filter and
+ *   the seen mask as set) or as ganmf_evaluate_candidates does (candidates = 1: each row among its own candidates); test matrix, `disc`,
+ *   `ideal_cum`, cut-off limits and tie rule are those calls'.  The per-user values are the ones those calls sum (one device function
+ *   forms them for all three).
+ *   group_of[i] in [-1, n_groups): the group of position i of `ids`; -1: ranked and written to per_user, counted in no group.
+ *   group_sums[n_groups, n_cutoffs, GANMF_EVAL_METRICS] (overwritten): the sums of the nine values over each group's members, float64,
+ *     added in a fixed order without floating-point atomics -- the same bytes on every call and handle.  group_size[n_groups]: the
+ *     member counts.  An empty group gets zeros.  0 <= n_groups <= GANMF_EVAL_MAX_GROUPS.
+ *   per_user: NULL, or [n, n_cutoffs, GANMF_EVAL_METRICS] float64 in position order.
+ *   group_of == NULL with n_groups == 0 is allowed when per_user != NULL (per-user values only).
+ * Only group_sums, group_size and per_user (if asked for) cross PCIe; the [n, W] score matrix never does.  Parameters, Adam state, the
+ * score filter and the held test / candidate / seen matrices are not modified.  Errors (-1, message in ganmf_last_error, nothing
+ * enqueued, the handle usable as before): every argument error of ganmf_evaluate / ganmf_evaluate_candidates, n_groups out of range,
+ * a group_of entry out of range, and a call that asks for neither groups nor per_user. */
+#define GANMF_EVAL_MAX_GROUPS 256
+int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, int candidates,
+                          const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum,
+                          const int32_t* group_of, int32_t n_groups, double* group_sums, int64_t* group_size, double* per_user);
+
 /* Cosine similarity of the predictions on the device: the computation under the reference's collapse study
  * (AblationStudy.py:88-92,113-117: cosine_similarity of all predictions, np.mean and np.std of the [users, users] matrix, and the
  * matrix behind the heat-map).  For the requested rows ids[0..n) (transposed as in ganmf_scores):

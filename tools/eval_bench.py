@@ -7,7 +7,15 @@ times instead the negative-sample protocol with N candidates per user (the test 
 (candidate scoring + top-k + metric sums, one call for all users) against the full-width ganmf_evaluate of the same users (user
 blocks of 1e8 / n_items, as EvaluatorHoldoutFast calls it), alternating in one process, at two shapes with k = 250: ML-1M
 (6040 x 3706) and the configs[3] shard width (25 000 x 50 000).  Host wall time around calls that end in a stream synchronise;
-one JSON line per shape."""
+one JSON line per shape.
+
+    python tools/eval_bench.py --groups 5
+
+times ganmf_evaluate_groups with that many groups (users dealt to them at random), without and with the per-user values coming
+back, beside ganmf_evaluate on the same handle and users, at the ML-1M shape (6040 x 3706, k = 250, cut-offs 5 / 10 / 20, one user
+block): the three alternate in one process after a warm-up of each, host wall time around calls that end in a stream synchronise,
+medians of `reps` calls in one JSON line; a second line gives the device time per kernel class of one profiled grouped call (a pass of
+its own, after the timed ones)."""
 import argparse
 import json
 import os
@@ -70,9 +78,53 @@ def candidates_bench(n_candidates, cutoffs=(5, 10), reps=7):
         eng.close()
 
 
+def groups_bench(n_groups, cutoffs=(5, 10, 20), reps=15):
+    from ganmf_amd.engine import Engine
+    from ganmf_amd.evaluation import EvaluatorHoldoutFast
+    nu, ni, k = 6040, 3706, 250
+    rng = np.random.RandomState(0)
+    eng = Engine(nu, ni, k, 16, 32)
+    eng.set_tensor(100, rng.standard_normal((nu, k)).astype(np.float32))
+    eng.set_tensor(101, rng.standard_normal((ni, k)).astype(np.float32))
+    seen = sps.random(nu, ni, density=0.04, format="csr", dtype=np.float32, random_state=1)
+    test = sps.random(nu, ni, density=0.005, format="csr", dtype=np.float32, random_state=2)
+    test.data[:] = rng.randint(1, 6, size=test.nnz)
+    ev = EvaluatorHoldoutFast(test, list(cutoffs))
+    eng.set_seen(seen)
+    eng.set_test(ev._test_sorted, ev._test_gain)
+    users = ev._users
+    group_of = rng.randint(0, n_groups, size=len(users))
+    calls = {"evaluate": lambda: eng.evaluate(users, cutoffs, ev._disc, ev._ideal_cum),
+             "groups": lambda: eng.evaluate_groups(users, cutoffs, ev._disc, ev._ideal_cum, group_of, n_groups),
+             "groups_per_user": lambda: eng.evaluate_groups(users, cutoffs, ev._disc, ev._ideal_cum, group_of, n_groups, per_user=True)}
+    for fn in calls.values():                                        # warm-up: code objects, buffers, the split of V
+        fn(), fn()
+    times = {name: [] for name in calls}
+    for _ in range(reps):                                            # alternating, every call ends in a stream synchronise
+        for name, fn in calls.items():
+            t0 = time.perf_counter(); fn(); times[name].append(time.perf_counter() - t0)
+    med = {name: float(np.median(t)) * 1e3 for name, t in times.items()}
+    sums, sizes, _ = calls["groups"]()
+    assert np.allclose(sums.sum(axis=0), calls["evaluate"](), rtol=1e-12, atol=1e-9) and sizes.sum() == len(users)
+    print(json.dumps({"shape": "ml1m", "users": int(len(users)), "items": ni, "k": k, "groups": n_groups, "cutoffs": list(cutoffs),
+                      "reps": reps, "evaluate_ms": round(med["evaluate"], 3), "groups_ms": round(med["groups"], 3),
+                      "groups_per_user_ms": round(med["groups_per_user"], 3),
+                      "groups_over_evaluate": round(med["groups"] / med["evaluate"], 3),
+                      "min_max_ms": {name: [round(min(t) * 1e3, 3), round(max(t) * 1e3, 3)] for name, t in times.items()}}), flush=True)
+    eng.profile(True)
+    calls["groups_per_user"]()
+    print(json.dumps({"profiled_call": "groups_per_user", "device_ms_by_class": {p["name"]: round(p["ms"], 4) for p in eng.profile_read()}}),
+          flush=True)
+    eng.close()
+
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--candidates", type=int, default=0, help="N candidates per user (test items included): time the candidate route")
+ap.add_argument("--groups", type=int, default=0, help="G groups: time ganmf_evaluate_groups beside ganmf_evaluate (ML-1M shape)")
 args = ap.parse_args()
+if args.groups:
+    groups_bench(args.groups)
+    sys.exit(0)
 if args.candidates:
     candidates_bench(args.candidates)
     sys.exit(0)
