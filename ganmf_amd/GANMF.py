@@ -5,6 +5,7 @@ as the reference, so it can stand in for `GANRec.GANMF.GANMF` under RecSysExp.py
 RunBestParameters.py.  Every number is produced by libganmf_hip.so (HIP kernels on gfx950)
 through the C ABI in include/ganmf_hip.h; this file holds only the epoch loop and bookkeeping.
 """
+import collections
 import os
 import pickle
 import time
@@ -17,6 +18,7 @@ from . import _lib as L
 from .base import BaseRecommender
 from .early_stopping import EarlyStoppingScheduler
 from .engine import Engine
+from .evaluation import _pad_lists
 
 try:  # progress bar is cosmetic (GANMF.py:170,234)
     import tqdm
@@ -38,6 +40,10 @@ class _TensorRef(object):
 
     def __init__(self, tid, name):
         self.tid, self.name = tid, name
+
+
+# the test matrix an engine holds for device evaluation: the evaluator's token, that engine, whether the ratings went up with it
+_TestOnDevice = collections.namedtuple("_TestOnDevice", "key engine has_ratings")
 
 
 class _SessionShim(object):
@@ -322,31 +328,53 @@ class GANMF(BaseRecommender):
             return items
         lists = self.recommend(ids, cutoff=cutoff, remove_seen_flag=remove_seen_flag, items_to_compute=items_to_compute,
                                return_scores=True)[0]
-        items = np.full((len(ids), cutoff), -1, dtype=np.int32)
-        for i, row in enumerate(lists):
-            items[i, :len(row)] = row
-        return items
+        return _pad_lists(lists, cutoff, dtype=np.int32)
+
+    def _prepare_device_evaluation(self, evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, max_cutoff, ratings=None,
+                                   item_weights=None, candidates_csr=None):
+        """What the four evaluate_*_on_device share.  None: the device route does not apply -- too many cut-offs, one outside
+        [1, min(max_cutoff, n_items)], and with `candidates_csr` also score_contract != "mf" or a requested user with more than
+        _lib.CANDIDATES_MAX_PER_ROW candidates.  Else (ids, cutoffs) as the engine takes them, and the engine holds the test
+        matrix (with `ratings` where given), the `item_weights` and the candidate matrix the call needs.
+        `evaluator_key`: a token the evaluator draws once from a process-wide counter (never id(): ids of freed objects are
+        reused), under which its test and candidate matrices are uploaded once; the engine is compared by identity through a
+        strong reference, so a rebuilt engine uploads again.  The item weights are uploaded again whenever their values change."""
+        self._require_engine()
+        cand = candidates_csr is not None
+        if cand and self.score_contract != "mf":
+            return None
+        cutoffs = list(cutoffs)
+        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or min(cutoffs) < 1 or max(cutoffs) > min(max_cutoff, self.n_items):
+            return None
+        ids = np.asarray(user_id_array).reshape(-1)
+        if cand and len(ids) and np.ediff1d(candidates_csr.indptr)[ids].max() > L.CANDIDATES_MAX_PER_ROW:
+            return None
+        held = getattr(self, "_test_on_device", None)
+        if (held is None or held.key != evaluator_key or held.engine is not self.engine
+                or (ratings is not None and not held.has_ratings)):
+            self.engine.set_test(urm_test_sorted, gains)
+            if ratings is not None:
+                self.engine.set_test_ratings(ratings)
+            self._test_on_device = _TestOnDevice(evaluator_key, self.engine, ratings is not None)
+        if item_weights is not None:
+            held = getattr(self, "_weights_on_device", None)
+            if (held is None or held[1] is not self.engine or not all(np.array_equal(a, b) for a, b in zip(held[0], item_weights))):
+                self.engine.set_eval_item_weights(*item_weights)
+                self._weights_on_device = (tuple(np.array(w, dtype=np.float64) for w in item_weights), self.engine)
+        if cand:
+            self._candidates_on_device(candidates_csr, key=evaluator_key)
+        return ids, cutoffs
 
     def evaluate_on_device(self, evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, disc, ideal_cum,
                            remove_seen_flag=True):
         """Hold-out metric sums for EvaluatorHoldoutFast without leaving the device (ganmf_evaluate): [len(cutoffs), 9]
         float64 in the order of ganmf_amd._lib.EVAL_METRICS, or None when the device route does not apply (cut-off beyond
         the device selection, too many cut-offs).  The test matrix is uploaded once per evaluator (`evaluator_key`)."""
-        from . import _lib as L
-        self._require_engine()
-        cutoffs = list(cutoffs)
-        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or not (1 <= max(cutoffs) <= min(self._DEVICE_TOPK_MAX, self.n_items)):
+        ready = self._prepare_device_evaluation(evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, self._DEVICE_TOPK_MAX)
+        if ready is None:
             return None
-        if min(cutoffs) < 1:
-            return None
-        # `evaluator_key`: a token the evaluator draws once from a process-wide counter (never id(): ids of freed objects are
-        # reused); the engine is compared by identity through a strong reference, so a rebuilt engine uploads again
-        held = getattr(self, "_test_on_device", None)
-        if held is None or held[0] != evaluator_key or held[1] is not self.engine:
-            self.engine.set_test(urm_test_sorted, gains)
-            self._test_on_device = (evaluator_key, self.engine)
-        return self.engine.evaluate(np.asarray(user_id_array).reshape(-1), cutoffs, disc, ideal_cum,
-                                    transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
+        return self.engine.evaluate(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
+                                    remove_seen=remove_seen_flag)
 
     def evaluate_full_on_device(self, evaluator_key, urm_test_sorted, gains, ratings, item_weights, user_id_array, cutoffs,
                                 disc, ideal_cum, remove_seen_flag=True, counts=None):
@@ -355,25 +383,12 @@ class GANMF(BaseRecommender):
         `counts` ([len(cutoffs), n_items] int64), or None when the device route does not apply (as evaluate_on_device).
         `ratings`: float32 per stored test entry; `item_weights`: the (novelty, popularity) pair of
         ganmf_amd.evaluation.popularity_weights, uploaded again whenever their values change."""
-        from . import _lib as L
-        self._require_engine()
-        cutoffs = list(cutoffs)
-        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or not (1 <= max(cutoffs) <= min(self._DEVICE_TOPK_MAX, self.n_items)):
+        ready = self._prepare_device_evaluation(evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, self._DEVICE_TOPK_MAX,
+                                                ratings=ratings, item_weights=item_weights)
+        if ready is None:
             return None
-        if min(cutoffs) < 1:
-            return None
-        held = getattr(self, "_test_on_device", None)
-        if held is None or held[0] != evaluator_key or held[1] is not self.engine or len(held) < 3:
-            self.engine.set_test(urm_test_sorted, gains)
-            self.engine.set_test_ratings(ratings)
-            self._test_on_device = (evaluator_key, self.engine, True)
-        held = getattr(self, "_weights_on_device", None)
-        if (held is None or held[1] is not self.engine or not all(np.array_equal(a, b) for a, b in zip(held[0], item_weights))):
-            self.engine.set_eval_item_weights(*item_weights)
-            self._weights_on_device = (tuple(np.array(w, dtype=np.float64) for w in item_weights), self.engine)
-        sums, _ = self.engine.evaluate_full(np.asarray(user_id_array).reshape(-1), cutoffs, disc, ideal_cum,
-                                            transposed=(self.mode == 'item'), remove_seen=remove_seen_flag, counts=counts)
-        return sums
+        return self.engine.evaluate_full(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
+                                         remove_seen=remove_seen_flag, counts=counts)[0]
 
     # ---- per-user candidate lists (Base/Evaluation/Evaluator.py:419-590, EvaluatorNegativeItemSample) ----------------
     @property
@@ -420,30 +435,13 @@ class GANMF(BaseRecommender):
         Returns None -- the evaluator then takes another route -- under score_contract="ganmf" (the reference's GANMF ignores
         items_to_compute, so the reference's evaluator around it ranks the whole catalogue), for cut-offs the device selection
         does not take, and when a requested user has more than _lib.CANDIDATES_MAX_PER_ROW candidates."""
-        self._require_engine()
-        if self.score_contract != "mf":
-            return None
-        cutoffs = list(cutoffs)
-        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or min(cutoffs) < 1 or max(cutoffs) > min(L.RECOMMEND_MAX_CUTOFF, self.n_items):
-            return None
-        ids = np.asarray(user_id_array).reshape(-1)
-        per_row = np.ediff1d(candidates_csr.indptr)
-        if len(ids) and per_row[ids].max() > L.CANDIDATES_MAX_PER_ROW:
-            return None
         full = ratings is not None
-        held = getattr(self, "_test_on_device", None)
-        if held is None or held[0] != evaluator_key or held[1] is not self.engine or (full and len(held) < 3):
-            self.engine.set_test(urm_test_sorted, gains)
-            if full:
-                self.engine.set_test_ratings(ratings)
-            self._test_on_device = (evaluator_key, self.engine, True) if full else (evaluator_key, self.engine)
-        if full:
-            held = getattr(self, "_weights_on_device", None)
-            if (held is None or held[1] is not self.engine or not all(np.array_equal(a, b) for a, b in zip(held[0], item_weights))):
-                self.engine.set_eval_item_weights(*item_weights)
-                self._weights_on_device = (tuple(np.array(w, dtype=np.float64) for w in item_weights), self.engine)
-        self._candidates_on_device(candidates_csr, key=evaluator_key)
-        got = self.engine.evaluate_candidates(ids, cutoffs, disc, ideal_cum, transposed=(self.mode == 'item'),
+        ready = self._prepare_device_evaluation(evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, L.RECOMMEND_MAX_CUTOFF,
+                                                ratings=ratings, item_weights=item_weights if full else None,
+                                                candidates_csr=candidates_csr)
+        if ready is None:
+            return None
+        got = self.engine.evaluate_candidates(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
                                               remove_seen=remove_seen_flag, counts=counts, full=full)
         return got[0] if full else got
 
@@ -458,25 +456,15 @@ class GANMF(BaseRecommender):
         score_contract != "mf" and a requested user with more than _lib.CANDIDATES_MAX_PER_ROW candidates; and for more than
         _lib.EVAL_MAX_GROUPS groups."""
         self._require_engine()
-        cutoffs = list(cutoffs)
         cand = candidates_csr is not None
-        if cand and self.score_contract != "mf":
-            return None
-        top = min(L.RECOMMEND_MAX_CUTOFF if cand else self._DEVICE_TOPK_MAX, self.n_items)
-        if not cutoffs or len(cutoffs) > L.EVAL_MAX_CUTOFFS or min(cutoffs) < 1 or max(cutoffs) > top:
-            return None
         if not 0 <= n_groups <= L.EVAL_MAX_GROUPS:
             return None
-        ids = np.asarray(user_id_array).reshape(-1)
-        if cand and len(ids) and np.ediff1d(candidates_csr.indptr)[ids].max() > L.CANDIDATES_MAX_PER_ROW:
+        ready = self._prepare_device_evaluation(evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs,
+                                                L.RECOMMEND_MAX_CUTOFF if cand else self._DEVICE_TOPK_MAX,
+                                                candidates_csr=candidates_csr)
+        if ready is None:
             return None
-        held = getattr(self, "_test_on_device", None)
-        if held is None or held[0] != evaluator_key or held[1] is not self.engine:
-            self.engine.set_test(urm_test_sorted, gains)
-            self._test_on_device = (evaluator_key, self.engine)
-        if cand:
-            self._candidates_on_device(candidates_csr, key=evaluator_key)
-        return self.engine.evaluate_groups(ids, cutoffs, disc, ideal_cum, group_of, n_groups, transposed=(self.mode == 'item'),
+        return self.engine.evaluate_groups(ready[0], ready[1], disc, ideal_cum, group_of, n_groups, transposed=(self.mode == 'item'),
                                            remove_seen=remove_seen_flag, candidates=cand, per_user=per_user)
 
     def activity_study(self, URM_test, bounds, cutoff=20, metric="MAP"):

@@ -1,5 +1,19 @@
 // abi_score.inc -- C ABI: scores, score filter, seen / test matrices, recommend, evaluate, scoring bench
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
+
+// A grow-on-demand buffer of the handle: at least `need` elements of `elem_bytes` behind *buf, *cap the elements it holds.  The stream
+// is drained before a buffer that enqueued work may still use is freed.  zeroed: through dalloc (float elements, zero-filled, at
+// least four of them, the device synchronised).  A failed allocation leaves a null pointer and cap 0.
+static int grow_device(ganmf_handle* h, void** buf, size_t* cap, size_t need, size_t elem_bytes, bool zeroed = false) {
+  if (need <= *cap) return 0;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(*buf); *buf = nullptr; *cap = 0;
+  if (zeroed) TRY(dalloc((float**)buf, need));
+  else HIP_TRY(hipMalloc(buf, need * elem_bytes));
+  *cap = need;
+  return 0;
+}
+
 // The scoring product itself: out[n, ldw] = rows[ids] . cols^T.  Many-tile shapes under the fp32-accurate default arithmetic take
 // the pre-split persistent kernel (gemm_bf16p.hpp): both factors are split ONCE into their three bf16 planes (the gather of the
 // scored rows rides in that pass), then one persistent launch; everything else goes through the planner (run_gemm).
@@ -11,16 +25,8 @@ static int score_product(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
   if (presplit) {
     const int mpad = round_up((int)n, BF16P_TILE), npad = round_up(W, BF16P_TILE), kp2 = round_up(h->k, BF16P_BK) / 2;
     const size_t need_a = (size_t)3 * mpad * kp2, need_b = (size_t)3 * npad * kp2;
-    if (need_a > h->sc_pa_cap) {
-      HIP_TRY(hipStreamSynchronize(h->st));
-      hipFree(h->sc_pa); h->sc_pa = nullptr; h->sc_pa_cap = 0;
-      HIP_TRY(hipMalloc((void**)&h->sc_pa, need_a * sizeof(unsigned))); h->sc_pa_cap = need_a;
-    }
-    if (need_b > h->sc_pb_cap) {
-      HIP_TRY(hipStreamSynchronize(h->st));
-      hipFree(h->sc_pb); h->sc_pb = nullptr; h->sc_pb_cap = 0;
-      HIP_TRY(hipMalloc((void**)&h->sc_pb, need_b * sizeof(unsigned))); h->sc_pb_cap = need_b;
-    }
+    TRY(grow_device(h, (void**)&h->sc_pa, &h->sc_pa_cap, need_a, sizeof(unsigned)));
+    TRY(grow_device(h, (void**)&h->sc_pb, &h->sc_pb_cap, need_b, sizeof(unsigned)));
     const double fl = gemm_flops((double)n, W, h->k);
     Scope s(h, T_SCORE_GEMM, fl, gemm_bytes((double)n, W, h->k));
     if (gemm_only) {      // (ganmf_bench_scores: operands prepared by the call before)
@@ -39,12 +45,7 @@ static int score_product(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
     HIP_TRY(gemm_bf16p_launch(h->st, h->sc_pa, mpad, h->sc_pb, npad, kp2, h->sc_out, ldw, (int)n, W));
     return 0;
   }
-  const size_t need_rows = (size_t)n * h->ldk;
-  if (need_rows > h->sc_rows_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->sc_rows); h->sc_rows = nullptr; h->sc_rows_cap = 0;
-    TRY(dalloc(&h->sc_rows, need_rows)); h->sc_rows_cap = need_rows;
-  }
+  TRY(grow_device(h, (void**)&h->sc_rows, &h->sc_rows_cap, (size_t)n * h->ldk, sizeof(float), true));
   if (!gemm_only) {
     const long long total = (long long)n * (h->ldk / 4);
     GANMF_LAUNCH(gather_rows_kernel, dim3((int)std::min<long long>(2048, (total + 255) / 256)), dim3(256), 0,
@@ -61,12 +62,7 @@ static int scores_device(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
                          int* ld_out) {
   Tensor& colsT = transposed ? h->Ue : h->V;   // the other factor
   const int W = colsT.rows, ldw = round_up(W, LD_ALIGN);
-  const size_t need_out = (size_t)n * ldw;
-  if (need_out > h->sc_out_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->sc_out); h->sc_out = nullptr; h->sc_out_cap = 0;
-    TRY(dalloc(&h->sc_out, need_out)); h->sc_out_cap = need_out;
-  }
+  TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
   TRY(score_product(h, ids_dev, n, transposed, W, ldw));
   *out_dev = h->sc_out; *width = W; *ld_out = ldw;
   return 0;
@@ -75,13 +71,7 @@ static int scores_device(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
 // device copy of an id list in the handle's reusable buffer (scores / recommend are called once per 1000-user
 // block by the evaluators: no allocation per call)
 static int upload_ids(ganmf_handle* h, const int32_t* ids, int64_t n, int** out) {
-  if ((size_t)n > h->sc_ids_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->sc_ids) hipFree(h->sc_ids);
-    h->sc_ids = nullptr; h->sc_ids_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->sc_ids, (size_t)n * sizeof(int)));
-    h->sc_ids_cap = (size_t)n;
-  }
+  TRY(grow_device(h, (void**)&h->sc_ids, &h->sc_ids_cap, (size_t)n, sizeof(int)));
   HIP_TRY(hipMemcpyAsync(h->sc_ids, ids, n * sizeof(int), hipMemcpyHostToDevice, h->st));
   *out = h->sc_ids;
   return 0;
@@ -123,11 +113,7 @@ int ganmf_set_score_filter(ganmf_handle* h, const int32_t* items, int64_t n_item
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   if (n_items > 0) {
-    if ((size_t)wmax > h->item_mask_cap) {
-      hipFree(h->item_mask); h->item_mask = nullptr; h->item_mask_cap = 0;
-      HIP_TRY(hipMalloc((void**)&h->item_mask, (size_t)wmax));
-      h->item_mask_cap = (size_t)wmax;
-    }
+    TRY(grow_device(h, (void**)&h->item_mask, &h->item_mask_cap, (size_t)wmax, 1));
     std::vector<unsigned char> m((size_t)wmax, 0);
     for (int64_t i = 0; i < n_items; ++i) m[(size_t)items[i]] = 1;
     HIP_TRY(hipMemcpy(h->item_mask, m.data(), m.size(), hipMemcpyHostToDevice));
@@ -158,14 +144,32 @@ int ganmf_scores(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed,
   return rc;
 }
 
+// The CSR arguments of a ganmf_set_*_csr entry, checked before that entry touches what it holds: monotone indptr, columns in
+// [0, n_cols); require_sorted_unique: columns ascending without repeats inside a row (the test matrix, searched by bisection).
+// (That entry has never refused an indptr that starts past 0 -- its rows still index the arrays it uploads -- and words its
+// column message with the row; both stay.)
+static int check_csr(const char* who, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols, bool refuse_empty,
+                     bool require_sorted_unique) {
+  if (refuse_empty && (n_rows < 1 || n_cols < 1)) return fail(-1, "%s: empty matrix", who);
+  const int64_t nnz = indptr[n_rows];
+  if (!require_sorted_unique && (indptr[0] != 0 || nnz < 0 || (nnz > 0 && !indices))) return fail(-1, "%s: bad indptr", who);
+  for (int64_t r = 0; r < n_rows; ++r)
+    if (indptr[r + 1] < indptr[r]) return fail(-1, "%s: indptr not monotone at row %lld", who, (long long)r);
+  for (int64_t r = 0; r < n_rows; ++r)
+    for (int64_t j = indptr[r]; j < indptr[r + 1]; ++j) {
+      if (indices[j] < 0 || indices[j] >= n_cols)
+        return require_sorted_unique ? fail(-1, "%s: column %d out of range in row %lld", who, indices[j], (long long)r)
+                                     : fail(-1, "%s: column index %d out of range", who, indices[j]);
+      if (require_sorted_unique && j > indptr[r] && indices[j] <= indices[j - 1])
+        return fail(-1, "%s: row %lld is not sorted / has duplicates", who, (long long)r);
+    }
+  return 0;
+}
+
 int ganmf_set_seen_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols) {
   if (!h || !indptr) return fail(-1, "ganmf_set_seen_csr: null argument");
+  TRY(check_csr("ganmf_set_seen_csr", indptr, indices, n_rows, n_cols, false, false));
   const int64_t nnz = indptr[n_rows];
-  if (indptr[0] != 0 || nnz < 0 || (nnz > 0 && !indices)) return fail(-1, "ganmf_set_seen_csr: bad indptr");
-  for (int64_t r = 0; r < n_rows; ++r)
-    if (indptr[r + 1] < indptr[r]) return fail(-1, "ganmf_set_seen_csr: indptr not monotone at row %lld", (long long)r);
-  for (int64_t j = 0; j < nnz; ++j)
-    if (indices[j] < 0 || indices[j] >= n_cols) return fail(-1, "ganmf_set_seen_csr: column index %d out of range", indices[j]);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   if (h->seen_indptr) { hipFree(h->seen_indptr); hipFree(h->seen_indices); h->seen_indptr = nullptr; h->seen_indices = nullptr; }
@@ -177,67 +181,108 @@ int ganmf_set_seen_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* in
   return 0;
 }
 
-// scores -> seen mask -> top-`cutoff` of the rows `ids`, left on the device in h->topk_items / h->topk_vals ([n, cutoff]);
-// *ids_dev_out = the uploaded ids.  Shared by ganmf_recommend and ganmf_evaluate.
-// rmse != nullptr (ganmf_evaluate_full): the selection kernel also writes each row's RMSE over its test items (mask_topk_rmse_kernel).
-static int recommend_device(ganmf_handle* h, const char* who, const int32_t* ids, int64_t n, int transposed, int32_t cutoff,
-                            int remove_seen, int** ids_dev_out, const RmseP* rmse = nullptr) {
+// a launch with `shmem` bytes of dynamic LDS: past the 48 KiB every kernel may ask for, the kernel has to be told first
+static int allow_lds(const void* kernel, size_t shmem) {
+  if (shmem > 48 * 1024) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  return 0;
+}
+
+// The ranking front of ganmf_recommend[_candidates] and of every ganmf_evaluate*: the top-`cutoff` of the rows `ids`, left on the
+// device in h->topk_items / h->topk_vals ([n, cutoff]); *ids_dev_out = the uploaded ids.  cand = false: full width, scores -> seen
+// mask -> selection (scores_device + mask_topk_kernel).  cand = true: each row among its own candidates (cand_topk.hpp), no score
+// row formed.  rmse != nullptr (the 13-sum evaluations): the selection kernel also writes each row's RMSE over its test items.
+// Every check runs before anything is enqueued.
+static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_t* ids, int64_t n, int transposed, int32_t cutoff,
+                       int remove_seen, int** ids_dev_out, const RmseP* rmse) {
   if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
+  if (cand && !h->cand_indptr) return fail(-1, "%s: no candidate matrix (ganmf_set_candidates_csr)", who);
+  if (cand && (h->cand_rows != limit || h->cand_cols != W))
+    return fail(-1, "%s: the candidate matrix is %lld x %lld, transposed = %d needs %d x %d", who, (long long)h->cand_rows,
+                (long long)h->cand_cols, transposed, limit, W);
   if (cutoff < 1 || cutoff > W || cutoff > GANMF_RECOMMEND_MAX_CUTOFF)
     return fail(-1, "%s: cutoff %d out of range [1,%d]", who, cutoff, std::min(W, GANMF_RECOMMEND_MAX_CUTOFF));
-  for (int64_t i = 0; i < n; ++i)
+  long long longest = 0;      // (candidate lists of the rows asked for)
+  for (int64_t i = 0; i < n; ++i) {
     if (ids[i] < 0 || ids[i] >= limit) return fail(-1, "%s: id %d out of range [0,%d)", who, ids[i], limit);
+    if (!cand) continue;
+    const long long len = h->cand_indptr_host[(size_t)ids[i] + 1] - h->cand_indptr_host[(size_t)ids[i]];
+    if (len > CAND_MAX_PER_ROW)
+      return fail(-1, "%s: row %d has %lld candidates, at most %d (GANMF_CANDIDATES_MAX_PER_ROW)", who, ids[i], len, CAND_MAX_PER_ROW);
+    longest = std::max(longest, len);
+  }
   if (remove_seen && (!h->seen_indptr || h->seen_rows != limit || h->seen_cols != W))
     return fail(-1, "%s: remove_seen needs ganmf_set_seen_csr with a %d x %d matrix", who, limit, W);
+  const unsigned char* fmask; const long long* fcold;
+  TRY(score_filter_args(h, who, W, limit, &fmask, &fcold));
+  const int cand_cap = round_up((int)std::max<long long>(longest, 1), 64);
+  const size_t cand_shmem = ((size_t)2 * cand_cap + (h->ldk > CAND_REG_LD ? (size_t)h->ldk : 0)) * sizeof(float);
+  if (cand && cand_shmem > 144 * 1024)
+    return fail(-1, "%s: %d factors beside %lld candidates do not fit one workgroup's LDS", who, h->k, longest);
   HIP_TRY(hipSetDevice(h->dev));
   int* ids_dev = nullptr;
   TRY(upload_ids(h, ids, n, &ids_dev));
-  const size_t need = (size_t)n * cutoff;
-  if (need > h->topk_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->topk_items); hipFree(h->topk_vals);
-    h->topk_items = nullptr; h->topk_vals = nullptr; h->topk_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->topk_items, need * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&h->topk_vals, need * sizeof(float)));
-    h->topk_cap = need;
+  {   // the two top-k buffers under their one cap: published once both hold n * cutoff
+    const size_t need = (size_t)n * cutoff;
+    size_t cap_items = h->topk_cap, cap_vals = h->topk_cap;
+    if (need > h->topk_cap) h->topk_cap = 0;
+    TRY(grow_device(h, (void**)&h->topk_items, &cap_items, need, sizeof(int)));
+    TRY(grow_device(h, (void**)&h->topk_vals, &cap_vals, need, sizeof(float)));
+    h->topk_cap = cap_items;
   }
-  const unsigned char* fmask; const long long* fcold;
-  TRY(score_filter_args(h, who, W, limit, &fmask, &fcold));
-  float* od = nullptr; int Wd = 0, ldw = 0;
-  TRY(scores_device(h, ids_dev, n, transposed, &od, &Wd, &ldw));
-  const int lds_cap = 32768;   // floats: 128 KiB of the CU's 160 KiB
-  const size_t shmem = Wd <= lds_cap ? (size_t)Wd * sizeof(float) : 0;
-  if (rmse) {
-    if (shmem > 48 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mask_topk_rmse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    GANMF_LAUNCH(mask_topk_rmse_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev,
-                 remove_seen ? h->seen_indptr : (const long long*)nullptr, h->seen_indices, (int)cutoff, lds_cap,
-                 h->topk_items, h->topk_vals, fmask, fcold, *rmse);
-    HIP_TRY(hipGetLastError());
-    if (ids_dev_out) *ids_dev_out = ids_dev;
-    return 0;
+  const long long* seen_indptr = remove_seen ? h->seen_indptr : nullptr;
+  if (cand) {
+    Tensor& rowsT = transposed ? h->V : h->Ue;
+    Tensor& colsT = transposed ? h->Ue : h->V;
+    CandP p{};
+    p.cap = cand_cap;
+    p.rows = rowsT.p; p.cols = colsT.p; p.ld = h->ldk; p.k = h->k; p.ids = ids_dev;
+    p.c_indptr = h->cand_indptr; p.c_indices = h->cand_indices;
+    p.seen_indptr = seen_indptr; p.seen_indices = h->seen_indices;
+    p.item_mask = fmask; p.cold_indptr = fcold; p.cutoff = cutoff;
+    p.out_items = h->topk_items; p.out_vals = h->topk_vals;
+    TRY(allow_lds(rmse ? reinterpret_cast<const void*>(cand_topk_rmse_kernel) : reinterpret_cast<const void*>(cand_topk_kernel), cand_shmem));
+    if (rmse) GANMF_LAUNCH(cand_topk_rmse_kernel, dim3((int)n), dim3(256), cand_shmem, h->st, p, *rmse);
+    else GANMF_LAUNCH(cand_topk_kernel, dim3((int)n), dim3(256), cand_shmem, h->st, p);
+  } else {
+    float* od = nullptr; int Wd = 0, ldw = 0;
+    TRY(scores_device(h, ids_dev, n, transposed, &od, &Wd, &ldw));
+    const int lds_cap = 32768;   // floats: 128 KiB of the CU's 160 KiB
+    const size_t shmem = Wd <= lds_cap ? (size_t)Wd * sizeof(float) : 0;
+    TRY(allow_lds(rmse ? reinterpret_cast<const void*>(mask_topk_rmse_kernel) : reinterpret_cast<const void*>(mask_topk_kernel), shmem));
+    if (rmse)
+      GANMF_LAUNCH(mask_topk_rmse_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev, seen_indptr, h->seen_indices,
+                   (int)cutoff, lds_cap, h->topk_items, h->topk_vals, fmask, fcold, *rmse);
+    else
+      GANMF_LAUNCH(mask_topk_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev, seen_indptr, h->seen_indices,
+                   (int)cutoff, lds_cap, h->topk_items, h->topk_vals, fmask, fcold);
   }
-  if (shmem > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mask_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  GANMF_LAUNCH(mask_topk_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev,
-                     remove_seen ? h->seen_indptr : (const long long*)nullptr, h->seen_indices, (int)cutoff, lds_cap,
-                     h->topk_items, h->topk_vals, fmask, fcold);
   HIP_TRY(hipGetLastError());
   if (ids_dev_out) *ids_dev_out = ids_dev;
   return 0;
 }
 
+// the [n, cutoff] lists rank_device left on the device, to the caller's arrays
+static int copy_topk(ganmf_handle* h, const char* who, int64_t n, int32_t cutoff, int32_t* out_items, float* out_scores) {
+  const size_t need = (size_t)n * cutoff;
+  hipError_t e = hipMemcpyAsync(out_items, h->topk_items, need * sizeof(int), hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess && out_scores) e = hipMemcpyAsync(out_scores, h->topk_vals, need * sizeof(float), hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+  return e == hipSuccess ? 0 : fail(-2, "%s: %s", who, hipGetErrorString(e));
+}
+
+int ganmf_recommend(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t cutoff, int remove_seen,
+                    int32_t* out_items, float* out_scores) {
+  if (!h || !ids || !out_items) return fail(-1, "ganmf_recommend: null argument");
+  int rc = rank_device(h, "ganmf_recommend", false, ids, n, transposed, cutoff, remove_seen, nullptr, nullptr);
+  if (rc == 0) rc = copy_topk(h, "ganmf_recommend", n, cutoff, out_items, out_scores);
+  hipStreamSynchronize(h->st);
+  return rc;
+}
+
 int ganmf_set_candidates_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols) {
   if (!h) return fail(-1, "null handle");
-  if (indptr) {        // validate before the held matrix is touched
-    if (n_rows < 1 || n_cols < 1) return fail(-1, "ganmf_set_candidates_csr: empty matrix");
-    if (indptr[0] != 0 || indptr[n_rows] < 0 || (indptr[n_rows] > 0 && !indices)) return fail(-1, "ganmf_set_candidates_csr: bad indptr");
-    for (int64_t r = 0; r < n_rows; ++r)
-      if (indptr[r + 1] < indptr[r]) return fail(-1, "ganmf_set_candidates_csr: indptr not monotone at row %lld", (long long)r);
-    for (int64_t j = 0; j < indptr[n_rows]; ++j)
-      if (indices[j] < 0 || indices[j] >= n_cols) return fail(-1, "ganmf_set_candidates_csr: column index %d out of range", indices[j]);
-  }
+  if (indptr) TRY(check_csr("ganmf_set_candidates_csr", indptr, indices, n_rows, n_cols, true, false));
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   hipFree(h->cand_indptr); hipFree(h->cand_indices);
@@ -264,94 +309,20 @@ int ganmf_set_candidates_csr(ganmf_handle* h, const int64_t* indptr, const int32
   return 0;
 }
 
-// candidate scores -> masks -> top-`cutoff` of the rows `ids` among their own candidates (cand_topk.hpp), left on the device in
-// h->topk_items / h->topk_vals ([n, cutoff]) as recommend_device leaves them.  Every check runs before anything is enqueued.
-static int candidates_device(ganmf_handle* h, const char* who, const int32_t* ids, int64_t n, int transposed, int32_t cutoff,
-                             int remove_seen, int** ids_dev_out, const RmseP* rmse = nullptr) {
-  if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
-  const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
-  if (!h->cand_indptr) return fail(-1, "%s: no candidate matrix (ganmf_set_candidates_csr)", who);
-  if (h->cand_rows != limit || h->cand_cols != W)
-    return fail(-1, "%s: the candidate matrix is %lld x %lld, transposed = %d needs %d x %d", who, (long long)h->cand_rows,
-                (long long)h->cand_cols, transposed, limit, W);
-  if (cutoff < 1 || cutoff > W || cutoff > GANMF_RECOMMEND_MAX_CUTOFF)
-    return fail(-1, "%s: cutoff %d out of range [1,%d]", who, cutoff, std::min(W, GANMF_RECOMMEND_MAX_CUTOFF));
-  long long longest = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    if (ids[i] < 0 || ids[i] >= limit) return fail(-1, "%s: id %d out of range [0,%d)", who, ids[i], limit);
-    const long long len = h->cand_indptr_host[(size_t)ids[i] + 1] - h->cand_indptr_host[(size_t)ids[i]];
-    if (len > CAND_MAX_PER_ROW)
-      return fail(-1, "%s: row %d has %lld candidates, at most %d (GANMF_CANDIDATES_MAX_PER_ROW)", who, ids[i], len, CAND_MAX_PER_ROW);
-    longest = std::max(longest, len);
-  }
-  if (remove_seen && (!h->seen_indptr || h->seen_rows != limit || h->seen_cols != W))
-    return fail(-1, "%s: remove_seen needs ganmf_set_seen_csr with a %d x %d matrix", who, limit, W);
-  const unsigned char* fmask; const long long* fcold;
-  TRY(score_filter_args(h, who, W, limit, &fmask, &fcold));
-  Tensor& rowsT = transposed ? h->V : h->Ue;
-  Tensor& colsT = transposed ? h->Ue : h->V;
-  CandP p{};
-  p.cap = round_up((int)std::max<long long>(longest, 1), 64);
-  const size_t shmem = ((size_t)2 * p.cap + (h->ldk > CAND_REG_LD ? (size_t)h->ldk : 0)) * sizeof(float);
-  if (shmem > 144 * 1024) return fail(-1, "%s: %d factors beside %lld candidates do not fit one workgroup's LDS", who, h->k, longest);
-  HIP_TRY(hipSetDevice(h->dev));
-  int* ids_dev = nullptr;
-  TRY(upload_ids(h, ids, n, &ids_dev));
-  const size_t need = (size_t)n * cutoff;
-  if (need > h->topk_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->topk_items); hipFree(h->topk_vals);
-    h->topk_items = nullptr; h->topk_vals = nullptr; h->topk_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->topk_items, need * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&h->topk_vals, need * sizeof(float)));
-    h->topk_cap = need;
-  }
-  p.rows = rowsT.p; p.cols = colsT.p; p.ld = h->ldk; p.k = h->k; p.ids = ids_dev;
-  p.c_indptr = h->cand_indptr; p.c_indices = h->cand_indices;
-  p.seen_indptr = remove_seen ? h->seen_indptr : nullptr; p.seen_indices = h->seen_indices;
-  p.item_mask = fmask; p.cold_indptr = fcold; p.cutoff = cutoff;
-  p.out_items = h->topk_items; p.out_vals = h->topk_vals;
-  if (rmse) {
-    if (shmem > 48 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(cand_topk_rmse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    GANMF_LAUNCH(cand_topk_rmse_kernel, dim3((int)n), dim3(256), shmem, h->st, p, *rmse);
-  } else {
-    if (shmem > 48 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(cand_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    GANMF_LAUNCH(cand_topk_kernel, dim3((int)n), dim3(256), shmem, h->st, p);
-  }
-  HIP_TRY(hipGetLastError());
-  if (ids_dev_out) *ids_dev_out = ids_dev;
-  return 0;
-}
-
 int ganmf_recommend_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t cutoff, int remove_seen,
                                int32_t* out_items, float* out_scores) {
   if (!h || !ids || !out_items) return fail(-1, "ganmf_recommend_candidates: null argument");
-  int rc = candidates_device(h, "ganmf_recommend_candidates", ids, n, transposed, cutoff, remove_seen, nullptr);
-  if (rc == 0) {
-    const size_t need = (size_t)n * cutoff;
-    hipError_t e = hipMemcpyAsync(out_items, h->topk_items, need * sizeof(int), hipMemcpyDeviceToHost, h->st);
-    if (e == hipSuccess && out_scores) e = hipMemcpyAsync(out_scores, h->topk_vals, need * sizeof(float), hipMemcpyDeviceToHost, h->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->st);
-    if (e != hipSuccess) rc = fail(-2, "ganmf_recommend_candidates: %s", hipGetErrorString(e));
-    hipStreamSynchronize(h->st);
-  }
+  int rc = rank_device(h, "ganmf_recommend_candidates", true, ids, n, transposed, cutoff, remove_seen, nullptr, nullptr);
+  if (rc == 0) rc = copy_topk(h, "ganmf_recommend_candidates", n, cutoff, out_items, out_scores);
+  hipStreamSynchronize(h->st);
   return rc;
 }
 
 int ganmf_set_test_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const double* gains, int64_t n_rows,
                        int64_t n_cols) {
   if (!h || !indptr || (!indices && indptr[n_rows] > 0) || (!gains && indptr[n_rows] > 0)) return fail(-1, "ganmf_set_test_csr: null argument");
-  if (n_rows < 1 || n_cols < 1) return fail(-1, "ganmf_set_test_csr: empty matrix");
+  TRY(check_csr("ganmf_set_test_csr", indptr, indices, n_rows, n_cols, true, true));
   const int64_t nnz = indptr[n_rows];
-  for (int64_t r = 0; r < n_rows; ++r) {
-    if (indptr[r + 1] < indptr[r]) return fail(-1, "ganmf_set_test_csr: indptr not monotone at row %lld", (long long)r);
-    for (int64_t j = indptr[r]; j < indptr[r + 1]; ++j) {
-      if (indices[j] < 0 || indices[j] >= n_cols) return fail(-1, "ganmf_set_test_csr: column %d out of range in row %lld", indices[j], (long long)r);
-      if (j > indptr[r] && indices[j] <= indices[j - 1]) return fail(-1, "ganmf_set_test_csr: row %lld is not sorted / has duplicates", (long long)r);
-    }
-  }
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   hipFree(h->test_indptr); hipFree(h->test_indices); hipFree(h->test_gain);
@@ -368,58 +339,6 @@ int ganmf_set_test_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* in
   }
   h->test_rows = n_rows; h->test_cols = n_cols;
   return 0;
-}
-
-// ganmf_evaluate (cand = false: full-width ranking, recommend_device) and the nine-sum form of ganmf_evaluate_candidates (cand = true:
-// each row's own candidate list, candidates_device); everything after the ranking is shared
-static int evaluate_impl(ganmf_handle* h, const char* who, bool cand, const int32_t* ids, int64_t n, int transposed, int remove_seen,
-                         const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums) {
-  if (!h || !ids || !cutoffs || !disc || !ideal_cum || !sums) return fail(-1, "%s: null argument", who);
-  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
-  const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
-  if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
-    return fail(-1, "%s: needs ganmf_set_test_csr with a %d x %d matrix", who, limit, W);
-  int K = 0;
-  for (int i = 0; i < n_cutoffs; ++i) {
-    if (cutoffs[i] < 1) return fail(-1, "%s: cut-off %d", who, cutoffs[i]);
-    K = std::max(K, (int)cutoffs[i]);
-  }
-  int* ids_dev = nullptr;
-  if (cand) TRY(candidates_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
-  else TRY(recommend_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
-  const int grid = (int)((n + 255) / 256);
-  const size_t n_part = (size_t)grid * n_cutoffs * EVAL_METRICS;
-  const size_t need = (size_t)K + (size_t)n * K + n_part;
-  if (need > h->eval_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->eval_buf); h->eval_buf = nullptr; h->eval_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->eval_buf, need * sizeof(double)));
-    h->eval_cap = need;
-  }
-  double* d_disc = h->eval_buf;
-  double* d_ideal = d_disc + K;
-  double* d_part = d_ideal + (size_t)n * K;
-  HIP_TRY(hipMemcpyAsync(d_disc, disc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->st));
-  HIP_TRY(hipMemcpyAsync(d_ideal, ideal_cum, (size_t)n * K * sizeof(double), hipMemcpyHostToDevice, h->st));
-  EvalP p{};
-  p.items = h->topk_items; p.K = K; p.n = (int)n; p.ids = ids_dev;
-  p.t_indptr = h->test_indptr; p.t_indices = h->test_indices; p.t_gain = h->test_gain;
-  p.disc = d_disc; p.ideal_cum = d_ideal; p.ncut = n_cutoffs; p.partials = d_part;
-  for (int i = 0; i < n_cutoffs; ++i) p.cutoffs[i] = cutoffs[i];
-  GANMF_LAUNCH(eval_topk_kernel, dim3(grid), dim3(256), 0, h->st, p);
-  HIP_TRY(hipGetLastError());
-  std::vector<double> part(n_part);
-  HIP_TRY(hipMemcpyAsync(part.data(), d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  for (int i = 0; i < n_cutoffs * EVAL_METRICS; ++i) sums[i] = 0.0;
-  for (int b = 0; b < grid; ++b)      // block order: reproducible
-    for (int i = 0; i < n_cutoffs * EVAL_METRICS; ++i) sums[i] += part[(size_t)b * n_cutoffs * EVAL_METRICS + i];
-  return 0;
-}
-
-int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
-                   int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums) {
-  return evaluate_impl(h, "ganmf_evaluate", false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums);
 }
 
 int ganmf_set_test_ratings(ganmf_handle* h, const float* ratings, int64_t nnz) {
@@ -448,95 +367,113 @@ int ganmf_set_eval_item_weights(ganmf_handle* h, const double* novelty, const do
   return 0;
 }
 
-// ganmf_evaluate_full (cand = false) and the 13-sum form of ganmf_evaluate_candidates (cand = true), as evaluate_impl
-static int evaluate_full_impl(ganmf_handle* h, const char* who, bool cand, const int32_t* ids, int64_t n, int transposed, int remove_seen,
-                              const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums,
-                              int64_t* counts) {
-  if (!h || !ids || !cutoffs || !disc || !ideal_cum || !sums || !counts) return fail(-1, "%s: null argument", who);
+// What every ganmf_evaluate* shares.  eval_prepare makes the argument checks, ranks the rows (rank_device, to the largest cut-off K)
+// and stages the metric kernels' inputs in h->eval_buf, laid out  disc [K] | ideal_cum [n, K] | tail [tail]  (the tail is the
+// caller's: block partials, or per-user values and group sums); `p` is ready but for p.partials.
+struct EvalCall { int K, W; double *d_disc, *d_ideal, *d_tail; EvalP p; };
+
+// full: the 13-sum form, which also needs the ratings and the item weights, and whose ranking writes every row's RMSE to h->eval_rmse
+static int eval_prepare(ganmf_handle* h, const char* who, bool cand, bool full, const int32_t* ids, int64_t n, int transposed,
+                        int remove_seen, const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum,
+                        size_t tail, EvalCall* c) {
+  if (!h || !ids || !cutoffs || !disc || !ideal_cum) return fail(-1, "%s: null argument", who);
   if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
   if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
   if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
     return fail(-1, "%s: needs ganmf_set_test_csr with a %d x %d matrix", who, limit, W);
-  if (!h->test_rating_ok) return fail(-1, "%s: needs ganmf_set_test_ratings for the current test matrix", who);
-  if (h->eval_w_width != W) return fail(-1, "%s: needs ganmf_set_eval_item_weights of width %d", who, W);
+  if (full && !h->test_rating_ok) return fail(-1, "%s: needs ganmf_set_test_ratings for the current test matrix", who);
+  if (full && h->eval_w_width != W) return fail(-1, "%s: needs ganmf_set_eval_item_weights of width %d", who, W);
   int K = 0;
   for (int i = 0; i < n_cutoffs; ++i) {
     if (cutoffs[i] < 1) return fail(-1, "%s: cut-off %d", who, cutoffs[i]);
     K = std::max(K, (int)cutoffs[i]);
   }
   HIP_TRY(hipSetDevice(h->dev));
-  if ((size_t)n > h->eval_rmse_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->eval_rmse); h->eval_rmse = nullptr; h->eval_rmse_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->eval_rmse, (size_t)n * sizeof(float)));
-    h->eval_rmse_cap = (size_t)n;
-  }
-  const size_t n_counts = (size_t)n_cutoffs * W;
-  if (n_counts > h->eval_counts_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->eval_counts); h->eval_counts = nullptr; h->eval_counts_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->eval_counts, n_counts * sizeof(unsigned)));
-    h->eval_counts_cap = n_counts;
+  if (full) {
+    TRY(grow_device(h, (void**)&h->eval_rmse, &h->eval_rmse_cap, (size_t)n, sizeof(float)));
+    TRY(grow_device(h, (void**)&h->eval_counts, &h->eval_counts_cap, (size_t)n_cutoffs * W, sizeof(unsigned)));
   }
   const RmseP rp{h->test_indptr, h->test_indices, h->test_rating, h->eval_rmse};
   int* ids_dev = nullptr;
-  if (cand) TRY(candidates_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev, &rp));
-  else TRY(recommend_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev, &rp));
-  const int grid = (int)((n + 255) / 256);
-  const size_t n_part = (size_t)grid * n_cutoffs * EVAL_FULL_METRICS;
-  const size_t need = (size_t)K + (size_t)n * K + n_part;
-  if (need > h->eval_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->eval_buf); h->eval_buf = nullptr; h->eval_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->eval_buf, need * sizeof(double)));
-    h->eval_cap = need;
-  }
-  double* d_disc = h->eval_buf;
-  double* d_ideal = d_disc + K;
-  double* d_part = d_ideal + (size_t)n * K;
-  HIP_TRY(hipMemcpyAsync(d_disc, disc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->st));
-  HIP_TRY(hipMemcpyAsync(d_ideal, ideal_cum, (size_t)n * K * sizeof(double), hipMemcpyHostToDevice, h->st));
-  HIP_TRY(hipMemsetAsync(h->eval_counts, 0, n_counts * sizeof(unsigned), h->st));
-  EvalP p{};
+  TRY(rank_device(h, who, cand, ids, n, transposed, K, remove_seen, &ids_dev, full ? &rp : nullptr));
+  TRY(grow_device(h, (void**)&h->eval_buf, &h->eval_cap, (size_t)K + (size_t)n * K + tail, sizeof(double)));
+  c->K = K; c->W = W;
+  c->d_disc = h->eval_buf;
+  c->d_ideal = c->d_disc + K;
+  c->d_tail = c->d_ideal + (size_t)n * K;
+  HIP_TRY(hipMemcpyAsync(c->d_disc, disc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->st));
+  HIP_TRY(hipMemcpyAsync(c->d_ideal, ideal_cum, (size_t)n * K * sizeof(double), hipMemcpyHostToDevice, h->st));
+  EvalP& p = c->p;
+  p = EvalP{};
   p.items = h->topk_items; p.K = K; p.n = (int)n; p.ids = ids_dev;
   p.t_indptr = h->test_indptr; p.t_indices = h->test_indices; p.t_gain = h->test_gain;
-  p.disc = d_disc; p.ideal_cum = d_ideal; p.ncut = n_cutoffs; p.partials = d_part;
+  p.disc = c->d_disc; p.ideal_cum = c->d_ideal; p.ncut = n_cutoffs; p.partials = nullptr;
   for (int i = 0; i < n_cutoffs; ++i) p.cutoffs[i] = cutoffs[i];
-  EvalFullP f{};
-  f.rmse = h->eval_rmse; f.w_nov = h->eval_w; f.w_pop = h->eval_w + W; f.counts = h->eval_counts; f.W = W;
-  for (int i = 0; i < n_cutoffs; ++i) f.order[i] = i;
-  std::stable_sort(f.order, f.order + n_cutoffs, [&](int a, int b) { return cutoffs[a] < cutoffs[b]; });
-  const size_t hist_bytes = n_counts * sizeof(unsigned);
-  f.lds_counts = hist_bytes <= EVAL_COUNTS_LDS_BYTES ? 1 : 0;
-  const size_t shmem = f.lds_counts ? hist_bytes : 0;
-  if (shmem > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_topk_full_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  GANMF_LAUNCH(eval_topk_full_kernel, dim3(grid), dim3(256), shmem, h->st, p, f);
+  return 0;
+}
+
+// sums[ncol] of the [grid, ncol] block partials: blocks ascending, one running sum per column (reproducible)
+static void sum_block_partials(const std::vector<double>& part, int grid, int ncol, double* sums) {
+  for (int i = 0; i < ncol; ++i) sums[i] = 0.0;
+  for (int b = 0; b < grid; ++b)
+    for (int i = 0; i < ncol; ++i) sums[i] += part[(size_t)b * ncol + i];
+}
+
+// ganmf_evaluate, ganmf_evaluate_full (cand = false: full-width ranking) and ganmf_evaluate_candidates (cand = true: each row's own
+// candidate list).  counts == nullptr: the nine sums of EVAL_METRICS per cut-off; given: the 13 of EVAL_FULL_METRICS, and the lists'
+// per-item counts added into `counts`.
+static int evaluate_device(ganmf_handle* h, const char* who, bool cand, const int32_t* ids, int64_t n, int transposed, int remove_seen,
+                           const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums,
+                           int64_t* counts) {
+  if (!sums) return fail(-1, "%s: null argument", who);
+  const bool full = counts != nullptr;
+  const int grid = (int)((n + 255) / 256), ncol = n_cutoffs * (full ? EVAL_FULL_METRICS : EVAL_METRICS);
+  const size_t n_part = (size_t)grid * ncol;
+  EvalCall c;
+  TRY(eval_prepare(h, who, cand, full, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, n_part, &c));
+  c.p.partials = c.d_tail;
+  const size_t n_counts = full ? (size_t)n_cutoffs * c.W : 0;
+  if (full) {
+    HIP_TRY(hipMemsetAsync(h->eval_counts, 0, n_counts * sizeof(unsigned), h->st));
+    EvalFullP f{};
+    f.rmse = h->eval_rmse; f.w_nov = h->eval_w; f.w_pop = h->eval_w + c.W; f.counts = h->eval_counts; f.W = c.W;
+    for (int i = 0; i < n_cutoffs; ++i) f.order[i] = i;
+    std::stable_sort(f.order, f.order + n_cutoffs, [&](int a, int b) { return cutoffs[a] < cutoffs[b]; });
+    const size_t hist_bytes = n_counts * sizeof(unsigned);
+    f.lds_counts = hist_bytes <= EVAL_COUNTS_LDS_BYTES ? 1 : 0;
+    const size_t shmem = f.lds_counts ? hist_bytes : 0;
+    TRY(allow_lds(reinterpret_cast<const void*>(eval_topk_full_kernel), shmem));
+    GANMF_LAUNCH(eval_topk_full_kernel, dim3(grid), dim3(256), shmem, h->st, c.p, f);
+  } else {
+    GANMF_LAUNCH(eval_topk_kernel, dim3(grid), dim3(256), 0, h->st, c.p);
+  }
   HIP_TRY(hipGetLastError());
   std::vector<double> part(n_part);
   std::vector<unsigned> cnt(n_counts);
-  HIP_TRY(hipMemcpyAsync(part.data(), d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(cnt.data(), h->eval_counts, n_counts * sizeof(unsigned), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(part.data(), c.d_tail, n_part * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  if (full) HIP_TRY(hipMemcpyAsync(cnt.data(), h->eval_counts, n_counts * sizeof(unsigned), hipMemcpyDeviceToHost, h->st));
   HIP_TRY(hipStreamSynchronize(h->st));
-  for (int i = 0; i < n_cutoffs * EVAL_FULL_METRICS; ++i) sums[i] = 0.0;
-  for (int b = 0; b < grid; ++b)      // block order: reproducible
-    for (int i = 0; i < n_cutoffs * EVAL_FULL_METRICS; ++i) sums[i] += part[(size_t)b * n_cutoffs * EVAL_FULL_METRICS + i];
+  sum_block_partials(part, grid, ncol, sums);
   for (size_t i = 0; i < n_counts; ++i) counts[i] += (int64_t)cnt[i];
   return 0;
 }
 
+int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
+                   int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums) {
+  return evaluate_device(h, "ganmf_evaluate", false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums, nullptr);
+}
+
 int ganmf_evaluate_full(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
                         int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts) {
-  return evaluate_full_impl(h, "ganmf_evaluate_full", false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums,
-                            counts);
+  if (!counts) return fail(-1, "ganmf_evaluate_full: null argument");
+  return evaluate_device(h, "ganmf_evaluate_full", false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums, counts);
 }
 
 int ganmf_evaluate_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, const int32_t* cutoffs,
                               int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums, int64_t* counts) {
-  const char* who = "ganmf_evaluate_candidates";
-  if (!counts) return evaluate_impl(h, who, true, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums);
-  return evaluate_full_impl(h, who, true, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums, counts);
+  return evaluate_device(h, "ganmf_evaluate_candidates", true, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, sums,
+                         counts);
 }
 
 // ganmf_evaluate_groups: the ranking of ganmf_evaluate (candidates = 0) or ganmf_evaluate_candidates (candidates = 1), then every user's
@@ -547,20 +484,9 @@ int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int tr
                           const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum,
                           const int32_t* group_of, int32_t n_groups, double* group_sums, int64_t* group_size, double* per_user) {
   const char* who = "ganmf_evaluate_groups";
-  if (!h || !ids || !cutoffs || !disc || !ideal_cum) return fail(-1, "%s: null argument", who);
   if (n_groups < 0 || n_groups > GANMF_EVAL_MAX_GROUPS) return fail(-1, "%s: %d groups, 0..%d per call", who, n_groups, GANMF_EVAL_MAX_GROUPS);
   if (n_groups == 0 && !per_user) return fail(-1, "%s: neither groups nor per_user asked for", who);
   if (n_groups > 0 && (!group_of || !group_sums || !group_size)) return fail(-1, "%s: null group argument", who);
-  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
-  if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
-  const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
-  if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
-    return fail(-1, "%s: needs ganmf_set_test_csr with a %d x %d matrix", who, limit, W);
-  int K = 0;
-  for (int i = 0; i < n_cutoffs; ++i) {
-    if (cutoffs[i] < 1) return fail(-1, "%s: cut-off %d", who, cutoffs[i]);
-    K = std::max(K, (int)cutoffs[i]);
-  }
   // members of every group: positions of `ids`, ascending inside a group (counting sort) -- the order the sums are formed in
   const int G = n_groups;
   std::vector<int> begin((size_t)G + 1, 0), members;
@@ -576,39 +502,16 @@ int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int tr
     for (int64_t i = 0; i < n; ++i)
       if (group_of[i] >= 0) members[(size_t)at[(size_t)group_of[i]]++] = (int)i;
   }
-  int* ids_dev = nullptr;
-  if (candidates) TRY(candidates_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
-  else TRY(recommend_device(h, who, ids, n, transposed, K, remove_seen, &ids_dev));
   const int ncol = n_cutoffs * EVAL_METRICS;
   const size_t n_user = (size_t)n * ncol, n_sum = (size_t)G * ncol;
-  const size_t need = (size_t)K + (size_t)n * K + n_user + n_sum;
-  if (need > h->eval_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->eval_buf); h->eval_buf = nullptr; h->eval_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->eval_buf, need * sizeof(double)));
-    h->eval_cap = need;
-  }
-  const size_t need_grp = G > 0 ? members.size() + begin.size() : 0;
-  if (need_grp > h->eval_grp_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->eval_grp); h->eval_grp = nullptr; h->eval_grp_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->eval_grp, need_grp * sizeof(int)));
-    h->eval_grp_cap = need_grp;
-  }
-  double* d_disc = h->eval_buf;
-  double* d_ideal = d_disc + K;
-  double* d_user = d_ideal + (size_t)n * K;
+  EvalCall c;
+  TRY(eval_prepare(h, who, candidates != 0, false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, n_user + n_sum, &c));
+  TRY(grow_device(h, (void**)&h->eval_grp, &h->eval_grp_cap, G > 0 ? members.size() + begin.size() : 0, sizeof(int)));
+  double* d_user = c.d_tail;
   double* d_sum = d_user + n_user;
-  HIP_TRY(hipMemcpyAsync(d_disc, disc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->st));
-  HIP_TRY(hipMemcpyAsync(d_ideal, ideal_cum, (size_t)n * K * sizeof(double), hipMemcpyHostToDevice, h->st));
-  EvalP p{};
-  p.items = h->topk_items; p.K = K; p.n = (int)n; p.ids = ids_dev;
-  p.t_indptr = h->test_indptr; p.t_indices = h->test_indices; p.t_gain = h->test_gain;
-  p.disc = d_disc; p.ideal_cum = d_ideal; p.ncut = n_cutoffs; p.partials = nullptr;
-  for (int i = 0; i < n_cutoffs; ++i) p.cutoffs[i] = cutoffs[i];
   {
-    Scope s(h, T_EVAL_GROUPS, 0.0, 4.0 * n * K + 8.0 * n * K + 8.0 * n_user);
-    GANMF_LAUNCH(eval_topk_users_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, p, d_user);
+    Scope s(h, T_EVAL_GROUPS, 0.0, 4.0 * n * c.K + 8.0 * n * c.K + 8.0 * n_user);
+    GANMF_LAUNCH(eval_topk_users_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, c.p, d_user);
     HIP_TRY(hipGetLastError());
   }
   hipError_t e = hipSuccess;
@@ -629,21 +532,6 @@ int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int tr
   if (e != hipSuccess) { hipStreamSynchronize(h->st); return fail(-2, "%s: %s", who, hipGetErrorString(e)); }   // (members / begin are locals)
   for (int g = 0; g < G; ++g) group_size[g] = (int64_t)(begin[(size_t)g + 1] - begin[(size_t)g]);
   return 0;
-}
-
-int ganmf_recommend(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t cutoff, int remove_seen,
-                    int32_t* out_items, float* out_scores) {
-  if (!h || !ids || !out_items) return fail(-1, "ganmf_recommend: null argument");
-  int rc = recommend_device(h, "ganmf_recommend", ids, n, transposed, cutoff, remove_seen, nullptr);
-  if (rc == 0) {
-    const size_t need = (size_t)n * cutoff;
-    hipError_t e = hipMemcpyAsync(out_items, h->topk_items, need * sizeof(int), hipMemcpyDeviceToHost, h->st);
-    if (e == hipSuccess && out_scores) e = hipMemcpyAsync(out_scores, h->topk_vals, need * sizeof(float), hipMemcpyDeviceToHost, h->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->st);
-    if (e != hipSuccess) rc = fail(-2, "ganmf_recommend: %s", hipGetErrorString(e));
-  }
-  hipStreamSynchronize(h->st);
-  return rc;
 }
 
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch) {
@@ -687,15 +575,6 @@ int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters
 // ---- ganmf_score_similarity (gram_stats.hpp) ---------------------------------------------------------------------------------
 constexpr int64_t SIM_MAX_ROWS = 1 << 22;      // 32 768 tile rows: the tiles of the upper triangle still fit a 1-D grid
 
-static int sim_grow(ganmf_handle* h, void** buf, size_t* cap, size_t need, size_t elem_bytes) {
-  if (need <= *cap) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(*buf); *buf = nullptr; *cap = 0;
-  HIP_TRY(hipMalloc(buf, need * elem_bytes));
-  *cap = need;
-  return 0;
-}
-
 int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t pool, double sums[4], float* pooled,
                            float* matrix) {
   const char* who = "ganmf_score_similarity";
@@ -724,10 +603,10 @@ int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int t
   }
   int* ids_dev = nullptr;
   TRY(upload_ids(h, ids, n, &ids_dev));
-  TRY(sim_grow(h, (void**)&h->sim_mat, &h->sim_mat_cap, need_mat, sizeof(float)));
-  TRY(sim_grow(h, (void**)&h->sim_pool, &h->sim_pool_cap, need_pool, sizeof(float)));
-  TRY(sim_grow(h, (void**)&h->sim_part, &h->sim_part_cap, (size_t)2 * tiles, sizeof(double)));
-  TRY(sim_grow(h, (void**)&h->sim_zero, &h->sim_zero_cap, (size_t)n, sizeof(int)));
+  TRY(grow_device(h, (void**)&h->sim_mat, &h->sim_mat_cap, need_mat, sizeof(float)));
+  TRY(grow_device(h, (void**)&h->sim_pool, &h->sim_pool_cap, need_pool, sizeof(float)));
+  TRY(grow_device(h, (void**)&h->sim_part, &h->sim_part_cap, (size_t)2 * tiles, sizeof(double)));
+  TRY(grow_device(h, (void**)&h->sim_zero, &h->sim_zero_cap, (size_t)n, sizeof(int)));
   float* sd = nullptr; int Wd = 0, ldd = 0;
   int rc = scores_device(h, ids_dev, n, transposed, &sd, &Wd, &ldd);      // unfiltered: a -inf has no cosine
   if (rc) { hipStreamSynchronize(h->st); return rc; }
@@ -780,4 +659,3 @@ int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int t
   sums[0] = s1; sums[1] = s2; sums[2] = (double)zeros; sums[3] = (double)n;
   return 0;
 }
-

@@ -14,6 +14,10 @@ def _i32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _f64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
 class Engine:
     def __init__(self, num_users, num_items, num_factors, emb_dim, batch_size, d_lr=1e-4, g_lr=1e-4, d_reg=0.0,
                  g_reg=0.0, m=1.0, recon_coefficient=1e-2, model=L.MODEL_GANMF, d_layers=1, d_act="linear",
@@ -162,25 +166,37 @@ class Engine:
         indices = np.ascontiguousarray(urm.indices, dtype=np.int32)
         g = np.ascontiguousarray(gains, dtype=np.float64)
         assert g.size == indices.size
-        dp = C.POINTER(C.c_double)
         L.check(self.lib.ganmf_set_test_csr(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices),
-                                            g.ctypes.data_as(dp), urm.shape[0], urm.shape[1]), "ganmf_set_test_csr")
+                                            _f64p(g), urm.shape[0], urm.shape[1]), "ganmf_set_test_csr")
 
-    def evaluate(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True):
-        """Sums over the users `ids` of the nine ranking metrics (L.EVAL_METRICS) per cut-off, formed on the device from
-        the device's own top-k lists: returns a [len(cutoffs), 9] float64 array."""
+    @staticmethod
+    def _eval_args(ids, cutoffs, disc, ideal_cum):
+        """the arguments every evaluate* shares as contiguous arrays (ids, cut-offs int32; disc, ideal_cum float64), the last two
+        checked to reach the largest cut-off"""
         ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
         cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
         K = int(cut.max())
         disc = np.ascontiguousarray(disc, dtype=np.float64).ravel()
         ideal = np.ascontiguousarray(ideal_cum, dtype=np.float64)
         assert disc.size >= K and ideal.shape == (ids.size, K)
+        return ids, cut, disc, ideal
+
+    def _counts_arg(self, counts, n_cutoffs, transposed):
+        """(`counts`, or a new zero array when None: [n_cutoffs, width] int64; its pointer)"""
+        width = self.num_users if transposed else self.num_items
+        if counts is None:
+            counts = np.zeros((n_cutoffs, width), dtype=np.int64)
+        assert counts.dtype == np.int64 and counts.shape == (n_cutoffs, width) and counts.flags.c_contiguous
+        return counts, counts.ctypes.data_as(C.POINTER(C.c_int64))
+
+    def evaluate(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True):
+        """Sums over the users `ids` of the nine ranking metrics (L.EVAL_METRICS) per cut-off, formed on the device from
+        the device's own top-k lists: returns a [len(cutoffs), 9] float64 array."""
+        ids, cut, disc, ideal = self._eval_args(ids, cutoffs, disc, ideal_cum)
         out = np.zeros((cut.size, len(L.EVAL_METRICS)), dtype=np.float64)
-        dp = C.POINTER(C.c_double)
         if ids.size:
             L.check(self.lib.ganmf_evaluate(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), _i32p(cut), cut.size,
-                                            disc.ctypes.data_as(dp), ideal.ctypes.data_as(dp), out.ctypes.data_as(dp)),
-                    "ganmf_evaluate")
+                                            _f64p(disc), _f64p(ideal), _f64p(out)), "ganmf_evaluate")
         return out
 
     def set_test_ratings(self, ratings):
@@ -193,31 +209,18 @@ class Engine:
         nov = np.ascontiguousarray(novelty, dtype=np.float64).ravel()
         pop = np.ascontiguousarray(popularity, dtype=np.float64).ravel()
         assert nov.size == pop.size
-        dp = C.POINTER(C.c_double)
-        L.check(self.lib.ganmf_set_eval_item_weights(self.h, nov.ctypes.data_as(dp), pop.ctypes.data_as(dp), nov.size),
-                "ganmf_set_eval_item_weights")
+        L.check(self.lib.ganmf_set_eval_item_weights(self.h, _f64p(nov), _f64p(pop), nov.size), "ganmf_set_eval_item_weights")
 
     def evaluate_full(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True, counts=None):
         """evaluate() plus RMSE, NOVELTY, AVERAGE_POPULARITY and non-empty-list sums (L.EVAL_FULL_METRICS, [len(cutoffs), 13]
         float64) and the per-item counts of the lists cut at each cut-off, ADDED into `counts` ([len(cutoffs), width] int64,
         a new zero array when None).  Returns (sums, counts)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
-        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
-        K = int(cut.max())
-        width = self.num_users if transposed else self.num_items
-        disc = np.ascontiguousarray(disc, dtype=np.float64).ravel()
-        ideal = np.ascontiguousarray(ideal_cum, dtype=np.float64)
-        assert disc.size >= K and ideal.shape == (ids.size, K)
-        if counts is None:
-            counts = np.zeros((cut.size, width), dtype=np.int64)
-        assert counts.dtype == np.int64 and counts.shape == (cut.size, width) and counts.flags.c_contiguous
+        ids, cut, disc, ideal = self._eval_args(ids, cutoffs, disc, ideal_cum)
+        counts, cp = self._counts_arg(counts, cut.size, transposed)
         out = np.zeros((cut.size, len(L.EVAL_FULL_METRICS)), dtype=np.float64)
-        dp = C.POINTER(C.c_double)
         if ids.size:
             L.check(self.lib.ganmf_evaluate_full(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), _i32p(cut),
-                                                 cut.size, disc.ctypes.data_as(dp), ideal.ctypes.data_as(dp),
-                                                 out.ctypes.data_as(dp), counts.ctypes.data_as(C.POINTER(C.c_int64))),
-                    "ganmf_evaluate_full")
+                                                 cut.size, _f64p(disc), _f64p(ideal), _f64p(out), cp), "ganmf_evaluate_full")
         return out, counts
 
     def set_candidates(self, candidates_csr):
@@ -245,25 +248,15 @@ class Engine:
     def evaluate_candidates(self, ids, cutoffs, disc, ideal_cum, transposed=False, remove_seen=True, counts=None, full=False):
         """evaluate() / evaluate_full() with every row ranked among its own candidates (ganmf_evaluate_candidates).  full=False:
         the [len(cutoffs), 9] sums.  full=True: (the [len(cutoffs), 13] sums, `counts` with the lists' per-item counts added)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
-        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
-        K = int(cut.max())
-        width = self.num_users if transposed else self.num_items
-        disc = np.ascontiguousarray(disc, dtype=np.float64).ravel()
-        ideal = np.ascontiguousarray(ideal_cum, dtype=np.float64)
-        assert disc.size >= K and ideal.shape == (ids.size, K)
+        ids, cut, disc, ideal = self._eval_args(ids, cutoffs, disc, ideal_cum)
         cp = None
         if full:
-            if counts is None:
-                counts = np.zeros((cut.size, width), dtype=np.int64)
-            assert counts.dtype == np.int64 and counts.shape == (cut.size, width) and counts.flags.c_contiguous
-            cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
+            counts, cp = self._counts_arg(counts, cut.size, transposed)
         out = np.zeros((cut.size, len(L.EVAL_FULL_METRICS if full else L.EVAL_METRICS)), dtype=np.float64)
-        dp = C.POINTER(C.c_double)
         if ids.size:
             L.check(self.lib.ganmf_evaluate_candidates(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), _i32p(cut),
-                                                       cut.size, disc.ctypes.data_as(dp), ideal.ctypes.data_as(dp),
-                                                       out.ctypes.data_as(dp), cp), "ganmf_evaluate_candidates")
+                                                       cut.size, _f64p(disc), _f64p(ideal), _f64p(out), cp),
+                    "ganmf_evaluate_candidates")
         return (out, counts) if full else out
 
     def evaluate_groups(self, ids, cutoffs, disc, ideal_cum, group_of, n_groups, transposed=False, remove_seen=True,
@@ -272,12 +265,7 @@ class Engine:
         group_of[i] in [-1, n_groups) is the group of ids[i], -1 = in no group (None with n_groups = 0: per-user values only).
         Returns (sums [n_groups, len(cutoffs), 9] float64 over each group's members, sizes [n_groups] int64, the
         [len(ids), len(cutoffs), 9] per-user values in the order of `ids` when per_user=True, else None)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
-        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
-        K = int(cut.max())
-        disc = np.ascontiguousarray(disc, dtype=np.float64).ravel()
-        ideal = np.ascontiguousarray(ideal_cum, dtype=np.float64)
-        assert disc.size >= K and ideal.shape == (ids.size, K)
+        ids, cut, disc, ideal = self._eval_args(ids, cutoffs, disc, ideal_cum)
         G = int(n_groups)
         grp = None
         if group_of is not None:
@@ -286,14 +274,13 @@ class Engine:
         sums = np.zeros((max(G, 0), cut.size, len(L.EVAL_METRICS)), dtype=np.float64)
         sizes = np.zeros(max(G, 0), dtype=np.int64)
         users = np.zeros((ids.size, cut.size, len(L.EVAL_METRICS)), dtype=np.float64) if per_user else None
-        dp = C.POINTER(C.c_double)
         if ids.size:
             L.check(self.lib.ganmf_evaluate_groups(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), int(candidates),
-                                                   _i32p(cut), cut.size, disc.ctypes.data_as(dp), ideal.ctypes.data_as(dp),
+                                                   _i32p(cut), cut.size, _f64p(disc), _f64p(ideal),
                                                    _i32p(grp) if grp is not None else None, G,
-                                                   sums.ctypes.data_as(dp) if G > 0 else None,
+                                                   _f64p(sums) if G > 0 else None,
                                                    sizes.ctypes.data_as(C.POINTER(C.c_int64)) if G > 0 else None,
-                                                   users.ctypes.data_as(dp) if users is not None else None), "ganmf_evaluate_groups")
+                                                   _f64p(users) if users is not None else None), "ganmf_evaluate_groups")
         return sums, sizes, users
 
     def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
@@ -312,7 +299,7 @@ class Engine:
         if return_matrix:
             matrix = np.empty((n, n), dtype=np.float32)
         L.check(self.lib.ganmf_score_similarity(self.h, _i32p(ids), n, int(transposed), int(pool) if pool is not None else 0,
-                                                sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                                _f64p(sums),
                                                 _f32p(pooled) if pooled is not None else None,
                                                 _f32p(matrix) if matrix is not None else None), "ganmf_score_similarity")
         md = sums[0] / (float(n) * n)

@@ -237,6 +237,22 @@ def _finish(sums, n_eval, cutoffs, names=_SUMMED):
     return results
 
 
+def _pad_lists(lists, K, dtype=np.int64):
+    """ragged ranked lists as an [n, K] array, -1 where a list is shorter than K"""
+    out = np.full((len(lists), K), -1, dtype=dtype)
+    for i, row in enumerate(lists):
+        out[i, :len(row)] = row
+    return out
+
+
+def _add_parts(a, b):
+    """the results of two consecutive user blocks of a device route as one: sums are added; of the groups route's (sums, sizes,
+    per-user values or None) the per-user values of the later block follow those of the earlier one"""
+    if isinstance(a, tuple):
+        return a[0] + b[0], a[1] + b[1], None if a[2] is None else np.concatenate([a[2], b[2]])
+    return a + b
+
+
 class EvaluatorHoldout(object):
     EVALUATOR_NAME = "EvaluatorHoldout"
 
@@ -259,6 +275,12 @@ class EvaluatorHoldout(object):
     def get_user_test_ratings(self, user_id):
         return self.URM_test.data[self.URM_test.indptr[user_id]:self.URM_test.indptr[user_id + 1]]
 
+    def _recommend(self, rec, users, return_scores, items_to_compute=None):
+        """the one `recommend` call of every host route (the keyword set of Evaluator.py:264-270)"""
+        restrict = {} if items_to_compute is None else {"items_to_compute": items_to_compute}
+        return rec.recommend(users, remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
+                             remove_CustomItems_flag=False, return_scores=return_scores, **restrict)
+
     def evaluateRecommender(self, recommender_object):
         """(results[cutoff][metric], text).  Users are scored in blocks of min(1000, 1e8/n_items) through
         `recommender.recommend(..., return_scores=True)` (Evaluator.py:237-277)."""
@@ -271,13 +293,11 @@ class EvaluatorHoldout(object):
         users = np.asarray(self.usersToEvaluate, dtype=np.int64)
         for lo in range(0, len(users), max(block_size, 1)):
             batch = users[lo:lo + block_size]
-            rec_lists, scores_batch = recommender_object.recommend(
-                batch, remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
-                remove_CustomItems_flag=False, return_scores=True)
+            rec_lists, scores_batch = self._recommend(recommender_object, batch, True)
             assert len(rec_lists) == len(batch) and scores_batch.shape == (len(batch), self.n_items)
             for user, recommended, score_row in zip(batch, rec_lists, scores_batch):
                 self._add_user(sums, full, user, recommended, score_row, w_novelty, w_popularity)
-        return self._finish_users(sums, full, len(users))
+        return self._finish_results(sums, full, len(users))
 
     # ---- metrics per group of users ----------------------------------------------------------------------------------------
     def evaluateRecommenderByGroup(self, recommender_object, user_groups, return_per_user=False):
@@ -310,9 +330,7 @@ class EvaluatorHoldout(object):
         users = np.asarray(self.usersToEvaluate, dtype=np.int64)
         for lo in range(0, len(users), block_size):
             batch = users[lo:lo + block_size]
-            rec_lists, _ = recommender_object.recommend(
-                batch, remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
-                remove_CustomItems_flag=False, return_scores=True)
+            rec_lists, _ = self._recommend(recommender_object, batch, True)
             assert len(rec_lists) == len(batch)
             for recommended in rec_lists:
                 yield recommended
@@ -376,12 +394,19 @@ class EvaluatorHoldout(object):
                     full.popularity[c] += np.sum(w_popularity[listed]) / len(listed)
                     full.nonempty[c] += 1
 
-    def _finish_users(self, sums, full, n_eval):
+    def _finish_results(self, sums, full, n_eval, rmse=True, as_float=False):
+        """(results, text) from the running sums.  rmse=False: the route did not compute it, NaN.  as_float: Python floats (the
+        reference-order classes return the float32 / float64 scalars their sums are made of)."""
         if n_eval == 0:
             print("WARNING: No users had a sufficient number of relevant items")
             results = {c: dict.fromkeys(METRICS, 0.0) for c in self.cutoff_list}
         else:
             results = _finish(sums, n_eval, self.cutoff_list)
+            for c in self.cutoff_list:
+                if as_float:
+                    results[c] = {m: float(v) for m, v in results[c].items()}
+                if not rmse:
+                    results[c]["RMSE"] = float("nan")
         if full is not None:
             results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
         return results, get_result_string(results)
@@ -431,165 +456,133 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
         # evaluator to the next one, and a recommender keyed on it would score the new evaluator against the old test matrix)
         self._device_token = next(_DEVICE_TOKENS)
 
+    # ---- users per call of every route: `_block_size` when set, else the route's own rule ---------------------------------------
+    def _host_block(self):
+        return self._block_size or max(1, min(4096, int(1e8 / self.n_items)))
+
+    def _device_block(self):
+        """the device forms a [block, n_items] score matrix (+ block x K doubles) per call: the cap of the host routes, unclipped"""
+        return self._block_size or max(1, int(1e8 / self.n_items))
+
     def _topk(self, rec, batch):
-        K = self.max_cutoff
         if hasattr(rec, "recommend_topk"):
-            return np.asarray(rec.recommend_topk(batch, K, remove_seen_flag=self.exclude_seen))
-        lists = rec.recommend(batch, remove_seen_flag=self.exclude_seen, cutoff=K, remove_top_pop_flag=False,
-                              remove_CustomItems_flag=False, return_scores=False)
-        out = np.full((len(batch), K), -1, dtype=np.int64)
-        for i, l in enumerate(lists):
-            out[i, :len(l)] = l
-        return out
+            return np.asarray(rec.recommend_topk(batch, self.max_cutoff, remove_seen_flag=self.exclude_seen))
+        return _pad_lists(self._recommend(rec, batch, False), self.max_cutoff)
 
     def _topk_and_rmse(self, rec, batch):
         """full_metrics host route: the ids of recommend(..., return_scores=True) and the sum of the users' RMSE"""
-        K = self.max_cutoff
-        lists, scores = rec.recommend(batch, remove_seen_flag=self.exclude_seen, cutoff=K, remove_top_pop_flag=False,
-                                      remove_CustomItems_flag=False, return_scores=True)
-        out = np.full((len(batch), K), -1, dtype=np.int64)
+        lists, scores = self._recommend(rec, batch, True)
         rmse_sum = 0.0
-        for i, (l, u) in enumerate(zip(lists, batch)):
-            out[i, :len(l)] = l
+        for i, u in enumerate(batch):
             rmse_sum += rmse_on_test_items(scores[i], self.get_user_relevant_items(u), self.get_user_test_ratings(u))
-        return out, rmse_sum
+        return _pad_lists(lists, self.max_cutoff), rmse_sum
 
-    def _device_full(self, rec, n_eval, block):
-        """ganmf_evaluate_full over all user blocks: ([n_cutoffs, 13] sums, [n_cutoffs, n_items] counts), or None when
-        the recommender declines the device route"""
-        weights = popularity_weights(item_popularity(_train_matrix(rec)))
-        counts = np.zeros((len(self.cutoff_list), self.n_items), dtype=np.int64)
-        dev = None
-        for start in range(0, n_eval, block):
-            sl = slice(start, min(start + block, n_eval))
-            part = rec.evaluate_full_on_device(self._device_token, self._test_sorted, self._test_gain, self._test_rating,
-                                               weights, self._users[sl], self.cutoff_list, self._disc, self._ideal_cum[sl],
-                                               remove_seen_flag=self.exclude_seen, counts=counts)
-            if part is None:
-                return None
-            dev = part if dev is None else dev + part
-        return dev, counts
+    def _device_route(self, rec, hook):
+        """whether the device route through `rec.<hook>` is open: asked for, somebody to evaluate, and the recommender has it"""
+        return self.use_device_metrics and len(self._users) > 0 and hasattr(rec, hook)
+
+    def _device_blocks(self, call, n, block):
+        """The one loop of every device route: `call(slice)` over the n evaluated users in blocks of `block`, the parts added in
+        block order (_add_parts).  None -- the caller then takes its host route for ALL users -- as soon as a block returns None
+        (the recommender declines) or the device runs out of memory."""
+        total = None
+        try:
+            for start in range(0, n, block):
+                part = call(slice(start, min(start + block, n)))
+                if part is None:
+                    return None
+                total = part if total is None else _add_parts(total, part)
+        except MemoryError:
+            return None
+        return total
+
+    def _device_sums(self, rec, call, block):
+        """A device route over all user blocks, finished: (results, text), or None when the host route is to be taken.
+        `call(slice, ratings, item_weights, counts)` returns one block's sums from the recommender's hook: nine per cut-off
+        (the three arguments None), or with full_metrics 13 per cut-off, the block's per-item counts added into `counts`."""
+        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
+        ratings = weights = counts = None
+        if full is not None:
+            ratings, weights = self._test_rating, popularity_weights(item_popularity(_train_matrix(rec)))
+            counts = np.zeros((len(self.cutoff_list), self.n_items), dtype=np.int64)
+        dev = self._device_blocks(lambda sl: call(sl, ratings, weights, counts), len(self._users), block)
+        return None if dev is None else self._from_device(dev, full, counts)
 
     def evaluateRecommender(self, recommender_object):
-        block_size = self._block_size or max(1, min(4096, int(1e8 / self.n_items)))
-        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
-        n_eval = len(self._users)
-        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
-        if (full is not None and self.use_device_metrics and n_eval > 0
-                and hasattr(recommender_object, "evaluate_full_on_device")):
-            # the whole row on the device: per cut-off 13 sums and the per-item counts come back, added up over the user blocks
-            try:
-                got = self._device_full(recommender_object, n_eval, self._block_size or max(1, int(1e8 / self.n_items)))
-            except MemoryError:
-                got = None
+        rec = recommender_object
+        if self._device_route(rec, "evaluate_full_on_device" if self.full_metrics else "evaluate_on_device"):
+            # everything on the device: scores, seen mask, top-k AND the metric sums (only the sums, and the counts of a full row,
+            # come back), added up over the user blocks
+            def call(sl, ratings, weights, counts):
+                if self.full_metrics:
+                    return rec.evaluate_full_on_device(self._device_token, self._test_sorted, self._test_gain, ratings, weights,
+                                                       self._users[sl], self.cutoff_list, self._disc, self._ideal_cum[sl],
+                                                       remove_seen_flag=self.exclude_seen, counts=counts)
+                return rec.evaluate_on_device(self._device_token, self._test_sorted, self._test_gain, self._users[sl],
+                                              self.cutoff_list, self._disc, self._ideal_cum[sl], remove_seen_flag=self.exclude_seen)
+            got = self._device_sums(rec, call, self._device_block())
             if got is not None:
-                return self._from_device_full(sums, full, got[0], got[1], n_eval)
-        if full is None and self.use_device_metrics and n_eval > 0 and hasattr(recommender_object, "evaluate_on_device"):
-            # everything on the device: scores, seen mask, top-k AND the metric sums (only len(cutoffs) x 9 doubles come back)
-            # in user blocks: the device forms a [block, n_items] score matrix (+ block x K doubles) per call, the same cap as
-            # the host routes; the [cutoffs, 9] partial sums are added here in block order.  Out of device memory -> host route.
-            dev = None
-            step = self._block_size or max(1, int(1e8 / self.n_items))
-            try:
-                for start in range(0, n_eval, step):
-                    sl = slice(start, min(start + step, n_eval))
-                    part = recommender_object.evaluate_on_device(self._device_token, self._test_sorted, self._test_gain,
-                                                                 self._users[sl], self.cutoff_list, self._disc,
-                                                                 self._ideal_cum[sl], remove_seen_flag=self.exclude_seen)
-                    if part is None:
-                        dev = None
-                        break
-                    dev = part if dev is None else dev + part
-            except MemoryError:
-                dev = None
-            if dev is not None:
-                return self._from_device(sums, dev, n_eval)
+                return got
+        n_eval = len(self._users)
+        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
+        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         w_novelty = w_popularity = None
         if full is not None:
-            w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(recommender_object)))
+            w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(rec)))
+        block_size = self._host_block()
         for start in range(0, n_eval, block_size):
             sl = slice(start, min(start + block_size, n_eval))
-            batch = self._users[sl]
             rmse_sum = 0.0
             if full is not None:
-                items, rmse_sum = self._topk_and_rmse(recommender_object, batch)
+                items, rmse_sum = self._topk_and_rmse(rec, self._users[sl])
             else:
-                items = self._topk(recommender_object, batch)
+                items = self._topk(rec, self._users[sl])
             self._add_block(sums, full, items, sl, rmse_sum, w_novelty, w_popularity)
-        return self._finish_blocks(sums, full, n_eval)
+        return self._finish_results(sums, full, n_eval, rmse=full is not None, as_float=True)
 
     def _ranked_lists(self, recommender_object):
         """the host route's lists: `_topk` in the blocks of evaluateRecommender"""
-        block_size = self._block_size or max(1, min(4096, int(1e8 / self.n_items)))
+        block_size = self._host_block()
         for start in range(0, len(self._users), block_size):
             for row in self._topk(recommender_object, self._users[start:start + block_size]):
                 yield row[row >= 0]
 
     def _device_groups(self, rec, labels, group_idx, per_user, block, candidates=None):
         """(sums [G, C, 9], sizes [G], per-user values or None) of evaluate_groups_on_device over all user blocks, added in block
-        order; None when the recommender declines the device route"""
-        sums = sizes = None
-        users = []
-        for start in range(0, len(self._users), block):
-            sl = slice(start, min(start + block, len(self._users)))
-            part = rec.evaluate_groups_on_device(self._device_token, self._test_sorted, self._test_gain, self._users[sl],
-                                                 self.cutoff_list, self._disc, self._ideal_cum[sl], group_idx[sl], len(labels),
-                                                 remove_seen_flag=self.exclude_seen, candidates_csr=candidates, per_user=per_user)
-            if part is None:
-                return None
-            sums = part[0] if sums is None else sums + part[0]
-            sizes = part[1] if sizes is None else sizes + part[1]
-            users.append(part[2])
-        return sums, sizes, np.concatenate(users) if per_user else None
-
-    def _groups_on_device(self, rec, labels, group_idx, per_user, block, candidates=None):
-        """_device_groups where evaluateRecommender would take its device route, else None"""
-        if not (self.use_device_metrics and len(self._users) > 0 and hasattr(rec, "evaluate_groups_on_device")):
-            return None
-        try:
-            return self._device_groups(rec, labels, group_idx, per_user, block, candidates)
-        except MemoryError:
-            return None
+        order; None when the recommender declines the device route or the device runs out of memory"""
+        return self._device_blocks(
+            lambda sl: rec.evaluate_groups_on_device(self._device_token, self._test_sorted, self._test_gain, self._users[sl],
+                                                     self.cutoff_list, self._disc, self._ideal_cum[sl], group_idx[sl], len(labels),
+                                                     remove_seen_flag=self.exclude_seen, candidates_csr=candidates, per_user=per_user),
+            len(self._users), block)
 
     def evaluateRecommenderByGroup(self, recommender_object, user_groups, return_per_user=False):
         """EvaluatorHoldout.evaluateRecommenderByGroup; with a recommender that has `evaluate_groups_on_device`
         (ganmf_evaluate_groups) ranking, per-user values and group sums stay on the device, and the host route is taken exactly
         where evaluateRecommender takes it."""
         labels, group_idx = self._group_index(user_groups)
-        got = self._groups_on_device(recommender_object, labels, group_idx, return_per_user,
-                                     self._block_size or max(1, int(1e8 / self.n_items)))
-        if got is not None:
-            return self._finish_groups(labels, group_idx, got[2], return_per_user, sums=got[0], sizes=got[1])
+        if self._device_route(recommender_object, "evaluate_groups_on_device"):
+            got = self._device_groups(recommender_object, labels, group_idx, return_per_user, self._device_block())
+            if got is not None:
+                return self._finish_groups(labels, group_idx, got[2], return_per_user, sums=got[0], sizes=got[1])
         return self._finish_groups(labels, group_idx, self._per_user_host(recommender_object), return_per_user)
 
-    def _from_device_full(self, sums, full, dev, counts, n_eval):
-        """results from the [n_cutoffs, 13] device sums and the [n_cutoffs, n_items] counts of a full-row device route"""
-        from ._lib import EVAL_FULL_METRICS
-        col = {name: i for i, name in enumerate(EVAL_FULL_METRICS)}
+    def _from_device(self, dev, full, counts):
+        """(results, text) from a device route's sums over all evaluated users: [n_cutoffs, 9] in the order of EVAL_METRICS (RMSE is
+        not computed there), or with `full` [n_cutoffs, 13] in the order of EVAL_FULL_METRICS beside the [n_cutoffs, n_items] counts"""
+        from ._lib import EVAL_FULL_METRICS, EVAL_METRICS
+        col = {name: i for i, name in enumerate(EVAL_METRICS if full is None else EVAL_FULL_METRICS)}
+        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
         for ci, c in enumerate(self.cutoff_list):
             for name in _SUMMED:
-                sums[c][name] = float(dev[ci, col[name]])
-            full.counts[c] = counts[ci]
-            full.novelty[c] = float(dev[ci, col["NOVELTY"]])
-            full.popularity[c] = float(dev[ci, col["AVERAGE_POPULARITY"]])
-            full.nonempty[c] = int(round(dev[ci, col["NON_EMPTY"]]))
-        results = _finish(sums, n_eval, self.cutoff_list)
-        for c in self.cutoff_list:
-            results[c] = {m: float(v) for m, v in results[c].items()}
-        results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
-        return results, get_result_string(results)
-
-    def _from_device(self, sums, dev, n_eval):
-        """results from the [n_cutoffs, 9] device sums of a nine-metric device route (RMSE is NaN there)"""
-        from ._lib import EVAL_METRICS
-        for ci, c in enumerate(self.cutoff_list):
-            for mi, name in enumerate(EVAL_METRICS):
-                sums[c][name] = float(dev[ci, mi])
-        results = _finish(sums, n_eval, self.cutoff_list)
-        for c in self.cutoff_list:
-            results[c] = {m: float(v) for m, v in results[c].items()}
-            results[c]["RMSE"] = float("nan")
-        return results, get_result_string(results)
+                if name in col:
+                    sums[c][name] = float(dev[ci, col[name]])
+            if full is not None:
+                full.counts[c] = counts[ci]
+                full.novelty[c] = float(dev[ci, col["NOVELTY"]])
+                full.popularity[c] = float(dev[ci, col["AVERAGE_POPULARITY"]])
+                full.nonempty[c] = int(round(dev[ci, col["NON_EMPTY"]]))
+        return self._finish_results(sums, full, len(self._users), rmse=full is not None, as_float=True)
 
     def _add_block(self, sums, full, items, sl, rmse_sum, w_novelty, w_popularity):
         """the ranked ids [len(block), K] (-1 padded) of the users self._users[sl] into the float64 sums of every cut-off"""
@@ -641,20 +634,6 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
                 full.popularity[c] += np.where(len_c > 0, pop_sum / nz, 0.0).sum()
                 full.nonempty[c] += int((len_c > 0).sum())
 
-    def _finish_blocks(self, sums, full, n_eval):
-        if n_eval > 0:
-            results = _finish(sums, n_eval, self.cutoff_list)
-            for c in self.cutoff_list:
-                results[c] = {m: float(v) for m, v in results[c].items()}
-                if full is None:
-                    results[c]["RMSE"] = float("nan")
-        else:
-            results = {c: dict.fromkeys(METRICS, 0.0) for c in self.cutoff_list}
-            print("WARNING: No users had a sufficient number of relevant items")
-        if full is not None:
-            results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
-        return results, get_result_string(results)
-
 
 def items_to_rank(URM_test, URM_test_negative):
     """URM_items_to_rank of the reference (Evaluator.py:450-452): test items + negative items of every user, binarised, an item
@@ -667,17 +646,8 @@ def items_to_rank(URM_test, URM_test_negative):
     return m
 
 
-class EvaluatorNegativeItemSample(EvaluatorHoldout):
-    """The reference's negative-sample protocol (Evaluator.py:419-590) in its own order: every evaluated user's test items are
-    ranked only against that user's candidates `URM_items_to_rank` = URM_test + URM_test_negative ("leave-one-out + N sampled
-    negatives"), through ONE `recommend(user, items_to_compute=candidates, return_scores=True)` call per user, with the
-    reference's float32 per-user sums.
-
-    What "only against the candidates" means is the recommender's business, as in the reference: a recommender that honours
-    `items_to_compute` (the MF contract, Base/BaseMatrixFactorizationRecommender.py:113-119; GANMF(score_contract="mf")) scores
-    every other item -inf; the reference's own GANMF ignores `items_to_compute` (GANMF.py:285-292; the default
-    score_contract="ganmf" here), and this evaluator around it ranks the whole catalogue, exactly as the reference's does."""
-    EVALUATOR_NAME = "EvaluatorNegativeItemSample"
+class _NegativeSample(object):
+    """What the two negative-sample evaluators add to their hold-out base: every user's candidates, `URM_items_to_rank`"""
 
     def __init__(self, URM_test_list, URM_test_negative, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
         super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen,
@@ -690,6 +660,23 @@ class EvaluatorNegativeItemSample(EvaluatorHoldout):
         m = self.URM_items_to_rank
         return m.indices[m.indptr[user_id]:m.indptr[user_id + 1]]
 
+    def _recommend_user(self, rec, user, return_scores):
+        """the reference's one call per user: recommend(user, items_to_compute=the user's candidates)"""
+        return self._recommend(rec, np.atleast_1d(user), return_scores, self._get_user_specific_items_to_compute(user))
+
+
+class EvaluatorNegativeItemSample(_NegativeSample, EvaluatorHoldout):
+    """The reference's negative-sample protocol (Evaluator.py:419-590) in its own order: every evaluated user's test items are
+    ranked only against that user's candidates `URM_items_to_rank` = URM_test + URM_test_negative ("leave-one-out + N sampled
+    negatives"), through ONE `recommend(user, items_to_compute=candidates, return_scores=True)` call per user, with the
+    reference's float32 per-user sums.
+
+    What "only against the candidates" means is the recommender's business, as in the reference: a recommender that honours
+    `items_to_compute` (the MF contract, Base/BaseMatrixFactorizationRecommender.py:113-119; GANMF(score_contract="mf")) scores
+    every other item -inf; the reference's own GANMF ignores `items_to_compute` (GANMF.py:285-292; the default
+    score_contract="ganmf" here), and this evaluator around it ranks the whole catalogue, exactly as the reference's does."""
+    EVALUATOR_NAME = "EvaluatorNegativeItemSample"
+
     def evaluateRecommender(self, recommender_object):
         sums = {c: dict.fromkeys(_SUMMED, 0.0) for c in self.cutoff_list}
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
@@ -697,25 +684,19 @@ class EvaluatorNegativeItemSample(EvaluatorHoldout):
         if full is not None:
             w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(recommender_object)))
         for user in self.usersToEvaluate:
-            rec_lists, scores = recommender_object.recommend(
-                np.atleast_1d(user), remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
-                items_to_compute=self._get_user_specific_items_to_compute(user), remove_CustomItems_flag=False,
-                return_scores=True)
+            rec_lists, scores = self._recommend_user(recommender_object, user, True)
             assert len(rec_lists) == 1 and scores.shape == (1, self.n_items)
             self._add_user(sums, full, user, rec_lists[0], scores[0], w_novelty, w_popularity)
-        return self._finish_users(sums, full, len(self.usersToEvaluate))
+        return self._finish_results(sums, full, len(self.usersToEvaluate))
 
     def _ranked_lists(self, recommender_object):
         for user in self.usersToEvaluate:
-            rec_lists, _ = recommender_object.recommend(
-                np.atleast_1d(user), remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
-                items_to_compute=self._get_user_specific_items_to_compute(user), remove_CustomItems_flag=False,
-                return_scores=True)
+            rec_lists, _ = self._recommend_user(recommender_object, user, True)
             assert len(rec_lists) == 1
             yield rec_lists[0]
 
 
-class EvaluatorNegativeItemSampleFast(EvaluatorHoldoutFast):
+class EvaluatorNegativeItemSampleFast(_NegativeSample, EvaluatorHoldoutFast):
     """EvaluatorNegativeItemSample's protocol and result dictionaries, consuming only the top-`max_cutoff` ids of every user, with
     the float64 sums and the finishing code of EvaluatorHoldoutFast.  Routes, in this order:
 
@@ -733,71 +714,55 @@ class EvaluatorNegativeItemSampleFast(EvaluatorHoldoutFast):
     routes).  Under score_contract="mf" the candidate kernel is used."""
     EVALUATOR_NAME = "EvaluatorNegativeItemSampleFast"
 
-    def __init__(self, URM_test_list, URM_test_negative, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
-        super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen,
-                         full_metrics=full_metrics)
-        self.URM_items_to_rank = items_to_rank(self.URM_test, URM_test_negative)
-        if self.URM_items_to_rank.shape != self.URM_test.shape:
-            raise ValueError("URM_test_negative must have the shape of URM_test")
+    # ---- users per call of the candidate routes (the device route holds block x K doubles and two ints per candidate, no score
+    # matrix) ------------------------------------------------------------------------------------------------------------------
+    def _candidate_host_block(self):
+        return self._block_size or 4096
 
-    def _get_user_specific_items_to_compute(self, user_id):
-        m = self.URM_items_to_rank
-        return m.indices[m.indptr[user_id]:m.indptr[user_id + 1]]
-
-    def _device_candidates(self, rec, n_eval, block):
-        """sums (and counts) of evaluate_candidates_on_device over all user blocks, or None when the recommender declines"""
-        full = self.full_metrics
-        weights = popularity_weights(item_popularity(_train_matrix(rec))) if full else None
-        counts = np.zeros((len(self.cutoff_list), self.n_items), dtype=np.int64) if full else None
-        dev = None
-        for start in range(0, n_eval, block):
-            sl = slice(start, min(start + block, n_eval))
-            part = rec.evaluate_candidates_on_device(self._device_token, self._test_sorted, self._test_gain, self.URM_items_to_rank,
-                                                     self._users[sl], self.cutoff_list, self._disc, self._ideal_cum[sl],
-                                                     remove_seen_flag=self.exclude_seen,
-                                                     ratings=self._test_rating if full else None, item_weights=weights, counts=counts)
-            if part is None:
-                return None
-            dev = part if dev is None else dev + part
-        return dev, counts
+    def _candidate_device_block(self):
+        return self._block_size or 65536
 
     def _per_user(self, rec, batch, with_scores):
         """ids [len(batch), K] (-1 padded) from one recommend(user, items_to_compute=...) per user, and the users' RMSE sum"""
-        K = self.max_cutoff
-        out = np.full((len(batch), K), -1, dtype=np.int64)
+        lists = []
         rmse_sum = 0.0
-        for i, u in enumerate(batch):
-            got = rec.recommend(np.atleast_1d(u), remove_seen_flag=self.exclude_seen, cutoff=K, remove_top_pop_flag=False,
-                                items_to_compute=self._get_user_specific_items_to_compute(u), remove_CustomItems_flag=False,
-                                return_scores=with_scores)
-            lists, scores = got if with_scores else (got, None)
-            out[i, :len(lists[0])] = lists[0]
+        for u in batch:
+            got = self._recommend_user(rec, u, with_scores)
+            user_lists, scores = got if with_scores else (got, None)
+            lists.append(user_lists[0])
             if with_scores:
                 rmse_sum += float(rmse_on_test_items(scores[0], self.get_user_relevant_items(u), self.get_user_test_ratings(u)))
-        return out, rmse_sum
+        return _pad_lists(lists, self.max_cutoff), rmse_sum
 
-    def _ranked_lists(self, recommender_object):
-        """the host routes of evaluateRecommender: full width for a recommender that ignores items_to_compute, else blocks
-        through recommend_candidates while it takes them, then user by user"""
-        rec = recommender_object
-        if not getattr(rec, "honours_items_to_compute", True):
-            for row in super()._ranked_lists(rec):
-                yield row
-            return
-        by_block = hasattr(rec, "recommend_candidates")
-        block_size = self._block_size or 4096
-        for start in range(0, len(self._users), block_size):
-            batch = self._users[start:start + block_size]
-            items = None
+    def _candidate_blocks(self, rec, with_scores):
+        """The host candidate routes: yields (slice of the evaluated users, their ids [len, K] -1 padded, their RMSE sum -- 0
+        without scores) block by block.  Blocks go through `rec.recommend_candidates` (ids only: not with_scores) while it takes
+        them; its first ValueError / RuntimeError (beyond what the block-wise API takes: a cut-off or a candidate list over its
+        limits) sends that block and every later one user by user, as the full row goes."""
+        by_block = not with_scores and hasattr(rec, "recommend_candidates")
+        n_eval, block_size = len(self._users), self._candidate_host_block()
+        for start in range(0, n_eval, block_size):
+            sl = slice(start, min(start + block_size, n_eval))
+            items, rmse_sum = None, 0.0
             if by_block:
                 try:
-                    items = np.asarray(rec.recommend_candidates(batch, self.URM_items_to_rank, self.max_cutoff,
+                    items = np.asarray(rec.recommend_candidates(self._users[sl], self.URM_items_to_rank, self.max_cutoff,
                                                                 remove_seen_flag=self.exclude_seen,
                                                                 candidates_key=self._device_token), dtype=np.int64)
                 except (ValueError, RuntimeError):
                     by_block = False
             if items is None:
-                items, _ = self._per_user(rec, batch, with_scores=False)
+                items, rmse_sum = self._per_user(rec, self._users[sl], with_scores)
+            yield sl, items, rmse_sum
+
+    def _ranked_lists(self, recommender_object):
+        """the host routes of evaluateRecommender: full width for a recommender that ignores items_to_compute, else the candidate
+        blocks"""
+        if not getattr(recommender_object, "honours_items_to_compute", True):
+            for row in super()._ranked_lists(recommender_object):
+                yield row
+            return
+        for _, items, _ in self._candidate_blocks(recommender_object, False):
             for row in items:
                 yield row[row >= 0]
 
@@ -807,52 +772,34 @@ class EvaluatorNegativeItemSampleFast(EvaluatorHoldoutFast):
         users)."""
         rec = recommender_object
         labels, group_idx = self._group_index(user_groups)
-        got = self._groups_on_device(rec, labels, group_idx, return_per_user, self._block_size or 65536,
-                                     candidates=self.URM_items_to_rank)
-        if got is not None:
-            return self._finish_groups(labels, group_idx, got[2], return_per_user, sums=got[0], sizes=got[1])
+        if self._device_route(rec, "evaluate_groups_on_device"):
+            got = self._device_groups(rec, labels, group_idx, return_per_user, self._candidate_device_block(),
+                                      candidates=self.URM_items_to_rank)
+            if got is not None:
+                return self._finish_groups(labels, group_idx, got[2], return_per_user, sums=got[0], sizes=got[1])
         if not getattr(rec, "honours_items_to_compute", True):
             return super().evaluateRecommenderByGroup(rec, user_groups, return_per_user=return_per_user)
         return self._finish_groups(labels, group_idx, self._per_user_host(rec), return_per_user)
 
     def evaluateRecommender(self, recommender_object):
         rec = recommender_object
-        K = self.max_cutoff
-        n_eval = len(self._users)
-        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
-        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
-        # users per call: the device route holds block x K doubles and two ints per candidate, no score matrix
-        block_size = self._block_size or 4096
-        if self.use_device_metrics and n_eval > 0 and hasattr(rec, "evaluate_candidates_on_device"):
-            try:
-                got = self._device_candidates(rec, n_eval, self._block_size or 65536)
-            except MemoryError:
-                got = None
+        if self._device_route(rec, "evaluate_candidates_on_device"):
+            got = self._device_sums(
+                rec, lambda sl, ratings, weights, counts: rec.evaluate_candidates_on_device(
+                    self._device_token, self._test_sorted, self._test_gain, self.URM_items_to_rank, self._users[sl], self.cutoff_list,
+                    self._disc, self._ideal_cum[sl], remove_seen_flag=self.exclude_seen, ratings=ratings, item_weights=weights,
+                    counts=counts),
+                self._candidate_device_block())
             if got is not None:
-                if full is not None:
-                    return self._from_device_full(sums, full, got[0], got[1], n_eval)
-                return self._from_device(sums, got[0], n_eval)
+                return got
         if not getattr(rec, "honours_items_to_compute", True):
             # the reference's evaluator around this recommender ranks the whole catalogue: the full-width routes
             return super().evaluateRecommender(rec)
+        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
+        full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         w_novelty = w_popularity = None
         if full is not None:
             w_novelty, w_popularity = popularity_weights(item_popularity(_train_matrix(rec)))
-        by_block = full is None and hasattr(rec, "recommend_candidates")
-        for start in range(0, n_eval, block_size):
-            sl = slice(start, min(start + block_size, n_eval))
-            batch = self._users[sl]
-            rmse_sum = 0.0
-            items = None
-            if by_block:
-                try:
-                    items = np.asarray(rec.recommend_candidates(batch, self.URM_items_to_rank, K, remove_seen_flag=self.exclude_seen,
-                                                                candidates_key=self._device_token), dtype=np.int64)
-                except (ValueError, RuntimeError):
-                    # beyond what the block-wise API takes (a cut-off or a candidate list over its limits): this block and the
-                    # ones after it go user by user, as the full row does
-                    by_block = False
-            if items is None:
-                items, rmse_sum = self._per_user(rec, batch, with_scores=full is not None)
+        for sl, items, rmse_sum in self._candidate_blocks(rec, with_scores=full is not None):
             self._add_block(sums, full, items, sl, rmse_sum, w_novelty, w_popularity)
-        return self._finish_blocks(sums, full, n_eval)
+        return self._finish_results(sums, full, len(self._users), rmse=full is not None, as_float=True)

@@ -66,7 +66,7 @@ def activity_study(model, URM_test, bounds, cutoff=20, metric="MAP"):
     per_user = np.full(test.shape[0], np.nan)
     sums, sizes = np.zeros(len(keys)), np.zeros(len(keys), dtype=np.int64)
     if len(ev._users):
-        got = ev._device_groups(model, keys, bucket[ev._users], True, max(1, int(1e8 / test.shape[1])))
+        got = ev._device_groups(model, keys, bucket[ev._users], True, ev._device_block())
         if got is None:
             raise RuntimeError("activity_study: cut-off %r is outside what the device route takes; there is no host route" % (cutoff,))
         sums, sizes = got[0][:, 0, col], got[1]
