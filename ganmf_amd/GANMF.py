@@ -6,6 +6,7 @@ RunBestParameters.py.  Every number is produced by libganmf_hip.so (HIP kernels 
 through the C ABI in include/ganmf_hip.h; this file holds only the epoch loop and bookkeeping.
 """
 import collections
+import contextlib
 import os
 import pickle
 import time
@@ -309,36 +310,54 @@ class GANMF(BaseRecommender):
                 return False
         return _Ctx()
 
+    @contextlib.contextmanager
+    def _ignored_items(self, remove_CustomItems_flag=False, remove_top_pop_flag=False):
+        """context: the union of `items_to_ignore_ID` and `filterTopPop_ItemsID`, each under its flag, is the engine's ignore list
+        (ganmf_set_items_to_ignore: -inf in everything that ranks, Base/BaseRecommender.py:80-86, 207-211) for the duration, and
+        cleared afterwards; nothing is set for an empty union"""
+        parts = []
+        if remove_CustomItems_flag:
+            parts.append(np.asarray(self.items_to_ignore_ID, dtype=np.int64).reshape(-1))
+        if remove_top_pop_flag:
+            parts.append(np.asarray(self.filterTopPop_ItemsID, dtype=np.int64).reshape(-1))
+        items = np.unique(np.concatenate(parts)) if parts else np.zeros(0, dtype=np.int64)
+        if len(items) == 0:
+            yield
+            return
+        self.engine.set_items_to_ignore(items)
+        try:
+            yield
+        finally:
+            self.engine.set_items_to_ignore(None)
+
     # ---- recommend (Base/BaseRecommender.py:155-247) ---------------------------------------------
     _DEVICE_TOPK_MAX = 256   # above this the k-round device selection loses to numpy's argpartition
 
-    def recommend_topk(self, user_id_array, cutoff, remove_seen_flag=True, items_to_compute=None):
+    def recommend_topk(self, user_id_array, cutoff, remove_seen_flag=True, items_to_compute=None, remove_CustomItems_flag=False,
+                       remove_top_pop_flag=False):
         """Top-`cutoff` item ids per user as an [n, cutoff] int32 array, -1 padded where a user has fewer
-        finite scores; scores, seen-item mask and selection all stay on the device (ganmf_recommend).
+        finite scores; scores, seen-item mask, the two remove_* filters and selection all stay on the device (ganmf_recommend).
         Cut-offs the device selection does not take (above _DEVICE_TOPK_MAX or above the item count) are ranked by
         the host route and padded the same way."""
         self._require_engine()
         ids = np.atleast_1d(np.asarray(user_id_array)).reshape(-1)
         if 1 <= cutoff <= min(self._DEVICE_TOPK_MAX, self.n_items):
-            if items_to_compute is None or self.score_contract != "mf":
-                items, _ = self.engine.recommend(ids, cutoff, transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
-            else:
-                with self._item_filter(items_to_compute):
+            with self._ignored_items(remove_CustomItems_flag, remove_top_pop_flag):
+                if items_to_compute is None or self.score_contract != "mf":
                     items, _ = self.engine.recommend(ids, cutoff, transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
+                else:
+                    with self._item_filter(items_to_compute):
+                        items, _ = self.engine.recommend(ids, cutoff, transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
             return items
         lists = self.recommend(ids, cutoff=cutoff, remove_seen_flag=remove_seen_flag, items_to_compute=items_to_compute,
+                               remove_top_pop_flag=remove_top_pop_flag, remove_CustomItems_flag=remove_CustomItems_flag,
                                return_scores=True)[0]
         return _pad_lists(lists, cutoff, dtype=np.int32)
 
-    def _prepare_device_evaluation(self, evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, max_cutoff, ratings=None,
-                                   item_weights=None, candidates_csr=None):
-        """What the four evaluate_*_on_device share.  None: the device route does not apply -- too many cut-offs, one outside
-        [1, min(max_cutoff, n_items)], and with `candidates_csr` also score_contract != "mf" or a requested user with more than
-        _lib.CANDIDATES_MAX_PER_ROW candidates.  Else (ids, cutoffs) as the engine takes them, and the engine holds the test
-        matrix (with `ratings` where given), the `item_weights` and the candidate matrix the call needs.
-        `evaluator_key`: a token the evaluator draws once from a process-wide counter (never id(): ids of freed objects are
-        reused), under which its test and candidate matrices are uploaded once; the engine is compared by identity through a
-        strong reference, so a rebuilt engine uploads again.  The item weights are uploaded again whenever their values change."""
+    def _device_ranking_args(self, user_id_array, cutoffs, max_cutoff, candidates_csr=None):
+        """(ids, cutoffs) as the engine's ranking entries take them, or None where the device route does not apply: too many
+        cut-offs, one outside [1, min(max_cutoff, n_items)], and with `candidates_csr` also score_contract != "mf" or a requested
+        user with more than _lib.CANDIDATES_MAX_PER_ROW candidates"""
         self._require_engine()
         cand = candidates_csr is not None
         if cand and self.score_contract != "mf":
@@ -349,6 +368,22 @@ class GANMF(BaseRecommender):
         ids = np.asarray(user_id_array).reshape(-1)
         if cand and len(ids) and np.ediff1d(candidates_csr.indptr)[ids].max() > L.CANDIDATES_MAX_PER_ROW:
             return None
+        return ids, cutoffs
+
+    def _prepare_device_evaluation(self, evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, max_cutoff, ratings=None,
+                                   item_weights=None, candidates_csr=None):
+        """What the four evaluate_*_on_device share.  None: the device route does not apply -- too many cut-offs, one outside
+        [1, min(max_cutoff, n_items)], and with `candidates_csr` also score_contract != "mf" or a requested user with more than
+        _lib.CANDIDATES_MAX_PER_ROW candidates.  Else (ids, cutoffs) as the engine takes them, and the engine holds the test
+        matrix (with `ratings` where given), the `item_weights` and the candidate matrix the call needs.
+        `evaluator_key`: a token the evaluator draws once from a process-wide counter (never id(): ids of freed objects are
+        reused), under which its test and candidate matrices are uploaded once; the engine is compared by identity through a
+        strong reference, so a rebuilt engine uploads again.  The item weights are uploaded again whenever their values change."""
+        ready = self._device_ranking_args(user_id_array, cutoffs, max_cutoff, candidates_csr)
+        if ready is None:
+            return None
+        ids, cutoffs = ready
+        cand = candidates_csr is not None
         held = getattr(self, "_test_on_device", None)
         if (held is None or held.key != evaluator_key or held.engine is not self.engine
                 or (ratings is not None and not held.has_ratings)):
@@ -366,18 +401,21 @@ class GANMF(BaseRecommender):
         return ids, cutoffs
 
     def evaluate_on_device(self, evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, disc, ideal_cum,
-                           remove_seen_flag=True):
+                           remove_seen_flag=True, remove_CustomItems_flag=False):
         """Hold-out metric sums for EvaluatorHoldoutFast without leaving the device (ganmf_evaluate): [len(cutoffs), 9]
         float64 in the order of ganmf_amd._lib.EVAL_METRICS, or None when the device route does not apply (cut-off beyond
-        the device selection, too many cut-offs).  The test matrix is uploaded once per evaluator (`evaluator_key`)."""
+        the device selection, too many cut-offs).  The test matrix is uploaded once per evaluator (`evaluator_key`).
+        `remove_CustomItems_flag` (here and on the sibling hooks): the items of set_items_to_ignore() are never ranked, as in
+        recommend()."""
         ready = self._prepare_device_evaluation(evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, self._DEVICE_TOPK_MAX)
         if ready is None:
             return None
-        return self.engine.evaluate(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
-                                    remove_seen=remove_seen_flag)
+        with self._ignored_items(remove_CustomItems_flag):
+            return self.engine.evaluate(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
+                                        remove_seen=remove_seen_flag)
 
     def evaluate_full_on_device(self, evaluator_key, urm_test_sorted, gains, ratings, item_weights, user_id_array, cutoffs,
-                                disc, ideal_cum, remove_seen_flag=True, counts=None):
+                                disc, ideal_cum, remove_seen_flag=True, counts=None, remove_CustomItems_flag=False):
         """The reference's full metric row for EvaluatorHoldoutFast(full_metrics=True) (ganmf_evaluate_full): returns the
         [len(cutoffs), 13] float64 sums of ganmf_amd._lib.EVAL_FULL_METRICS and adds the per-item counts of the lists into
         `counts` ([len(cutoffs), n_items] int64), or None when the device route does not apply (as evaluate_on_device).
@@ -387,8 +425,9 @@ class GANMF(BaseRecommender):
                                                 ratings=ratings, item_weights=item_weights)
         if ready is None:
             return None
-        return self.engine.evaluate_full(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
-                                         remove_seen=remove_seen_flag, counts=counts)[0]
+        with self._ignored_items(remove_CustomItems_flag):
+            return self.engine.evaluate_full(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
+                                             remove_seen=remove_seen_flag, counts=counts)[0]
 
     # ---- per-user candidate lists (Base/Evaluation/Evaluator.py:419-590, EvaluatorNegativeItemSample) ----------------
     @property
@@ -407,7 +446,8 @@ class GANMF(BaseRecommender):
             self.engine.set_candidates(m)
             self._cand_on_device = (key, self.engine)
 
-    def recommend_candidates(self, user_id_array, candidates_csr, cutoff, remove_seen_flag=True, candidates_key=None):
+    def recommend_candidates(self, user_id_array, candidates_csr, cutoff, remove_seen_flag=True, candidates_key=None,
+                             remove_CustomItems_flag=False):
         """Top-`cutoff` item ids of every user AMONG THAT USER'S OWN CANDIDATES, the stored entries of row `user` of
         `candidates_csr` (users x items, e.g. EvaluatorNegativeItemSample.URM_items_to_rank): an [n, cutoff] int32 array, -1 padded
         where a user has fewer unmasked candidates; ties go to the smaller item id.  Candidate scoring, seen-item mask and
@@ -422,11 +462,13 @@ class GANMF(BaseRecommender):
         if not 1 <= cutoff <= self.n_items:
             raise ValueError("recommend_candidates: cutoff %r outside [1, %d]" % (cutoff, self.n_items))
         self._candidates_on_device(candidates_csr, key=candidates_key)
-        items, _ = self.engine.recommend_candidates(ids, cutoff, transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
+        with self._ignored_items(remove_CustomItems_flag):
+            items, _ = self.engine.recommend_candidates(ids, cutoff, transposed=(self.mode == 'item'), remove_seen=remove_seen_flag)
         return items
 
     def evaluate_candidates_on_device(self, evaluator_key, urm_test_sorted, gains, candidates_csr, user_id_array, cutoffs, disc,
-                                      ideal_cum, remove_seen_flag=True, ratings=None, item_weights=None, counts=None):
+                                      ideal_cum, remove_seen_flag=True, ratings=None, item_weights=None, counts=None,
+                                      remove_CustomItems_flag=False):
         """Metric sums for EvaluatorNegativeItemSampleFast without leaving the device (ganmf_evaluate_candidates): every user
         ranked among the stored entries of its row of `candidates_csr`.  `ratings` None: [len(cutoffs), 9] float64 in the order
         of ganmf_amd._lib.EVAL_METRICS; `ratings` and `item_weights` given (full row): the [len(cutoffs), 13] sums of
@@ -441,12 +483,13 @@ class GANMF(BaseRecommender):
                                                 candidates_csr=candidates_csr)
         if ready is None:
             return None
-        got = self.engine.evaluate_candidates(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
-                                              remove_seen=remove_seen_flag, counts=counts, full=full)
+        with self._ignored_items(remove_CustomItems_flag):
+            got = self.engine.evaluate_candidates(ready[0], ready[1], disc, ideal_cum, transposed=(self.mode == 'item'),
+                                                  remove_seen=remove_seen_flag, counts=counts, full=full)
         return got[0] if full else got
 
     def evaluate_groups_on_device(self, evaluator_key, urm_test_sorted, gains, user_id_array, cutoffs, disc, ideal_cum, group_of,
-                                  n_groups, remove_seen_flag=True, candidates_csr=None, per_user=False):
+                                  n_groups, remove_seen_flag=True, candidates_csr=None, per_user=False, remove_CustomItems_flag=False):
         """Hold-out metrics per group of users without leaving the device (ganmf_evaluate_groups): (sums [n_groups, len(cutoffs), 9]
         float64 in the order of ganmf_amd._lib.EVAL_METRICS, sizes [n_groups], the [n, len(cutoffs), 9] per-user values or None).
         `group_of[i]` in [-1, n_groups) names the group of user_id_array[i] (-1: none).  `candidates_csr` None: the ranking of
@@ -464,8 +507,34 @@ class GANMF(BaseRecommender):
                                                 candidates_csr=candidates_csr)
         if ready is None:
             return None
-        return self.engine.evaluate_groups(ready[0], ready[1], disc, ideal_cum, group_of, n_groups, transposed=(self.mode == 'item'),
-                                           remove_seen=remove_seen_flag, candidates=cand, per_user=per_user)
+        with self._ignored_items(remove_CustomItems_flag):
+            return self.engine.evaluate_groups(ready[0], ready[1], disc, ideal_cum, group_of, n_groups, transposed=(self.mode == 'item'),
+                                               remove_seen=remove_seen_flag, candidates=cand, per_user=per_user)
+
+    def evaluate_diversity_on_device(self, evaluator_key, matrix, user_id_array, cutoffs, remove_seen_flag=True, candidates_csr=None,
+                                     remove_CustomItems_flag=False):
+        """Sums over the users of the intra-list diversity of their ranked lists (DIVERSITY_SIMILARITY, metrics.py:405-452) without
+        leaving the device (ganmf_evaluate_diversity): [len(cutoffs)] float64.  `matrix`: the [n_items, n_items] float32 item
+        diversity matrix, uploaded once per `evaluator_key` and engine.  The ranking is evaluate_on_device's, or with
+        `candidates_csr` evaluate_candidates_on_device's (every user among its own candidates); returns None where those return
+        None.  A list with fewer than two items at a cut-off contributes 0 (the reference would divide by zero)."""
+        cand = candidates_csr is not None
+        ready = self._device_ranking_args(user_id_array, cutoffs, L.RECOMMEND_MAX_CUTOFF if cand else self._DEVICE_TOPK_MAX,
+                                          candidates_csr)
+        if ready is None:
+            return None
+        held = getattr(self, "_diversity_on_device", None)
+        if held is None or held[0] != evaluator_key or held[1] is not self.engine:
+            if np.shape(matrix) != (self.n_items, self.n_items):
+                raise ValueError("the item diversity matrix must be %d x %d, given %r" % (self.n_items, self.n_items, np.shape(matrix)))
+            self._diversity_on_device = None
+            self.engine.set_item_diversity(matrix)
+            self._diversity_on_device = (evaluator_key, self.engine)
+        if cand:
+            self._candidates_on_device(candidates_csr, key=evaluator_key)
+        with self._ignored_items(remove_CustomItems_flag):
+            return self.engine.evaluate_diversity(ready[0], ready[1], transposed=(self.mode == 'item'), remove_seen=remove_seen_flag,
+                                                  candidates=cand)
 
     def activity_study(self, URM_test, bounds, cutoff=20, metric="MAP"):
         """ganmf_amd.studies.activity_study(self, ...): the reference's user-activity study (MFLearned.py:80-145) on the device"""
@@ -474,8 +543,7 @@ class GANMF(BaseRecommender):
 
     def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None,
                   remove_top_pop_flag=False, remove_CustomItems_flag=False, return_scores=False):
-        device_ok = (not return_scores and not remove_top_pop_flag
-                     and not remove_CustomItems_flag and cutoff is not None and 1 <= cutoff <= self._DEVICE_TOPK_MAX
+        device_ok = (not return_scores and cutoff is not None and 1 <= cutoff <= self._DEVICE_TOPK_MAX
                      and cutoff <= self.n_items)
         if not device_ok:   # full score matrix needed on the host: the reference's own route
             saved = self.URM_train
@@ -489,7 +557,8 @@ class GANMF(BaseRecommender):
             finally:
                 self.URM_train = saved
         single = np.isscalar(user_id_array)
-        items = self.recommend_topk(user_id_array, cutoff, remove_seen_flag, items_to_compute=items_to_compute)
+        items = self.recommend_topk(user_id_array, cutoff, remove_seen_flag, items_to_compute=items_to_compute,
+                                    remove_CustomItems_flag=remove_CustomItems_flag, remove_top_pop_flag=remove_top_pop_flag)
         lists = [row[row >= 0].tolist() for row in items]
         return lists[0] if single else lists
 

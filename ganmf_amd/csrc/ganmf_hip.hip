@@ -40,6 +40,7 @@
 #include "gemm_bf16p.hpp"
 #include "kernels.hpp"
 #include "cand_topk.hpp"
+#include "list_diversity.hpp"
 #include "gram_stats.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD

@@ -101,6 +101,28 @@ static int apply_score_filter(ganmf_handle* h, const char* who, float* scores, i
   return 0;
 }
 
+// The keep-mask of everything that ranks while an ignore list is set: a column stays iff the score filter (if any) lists it and the
+// ignore list does not.  Formed on the host from the two setters' bytes whenever either changes, so that the selection kernels keep
+// their one mask pointer and ganmf_scores keeps the plain filter.  The stream is idle when the setters call this.
+static int refresh_rank_mask(ganmf_handle* h) {
+  if (h->ignore_w == 0) return 0;
+  const size_t wmax = (size_t)std::max(h->U, h->N);
+  std::vector<unsigned char> keep(wmax, 1);
+  if (h->item_mask_w > 0) keep = h->filter_host;
+  for (size_t i = 0; i < wmax; ++i)
+    if (h->ignore_host[i]) keep[i] = 0;
+  TRY(grow_device(h, (void**)&h->rank_mask, &h->rank_mask_cap, wmax, 1));
+  HIP_TRY(hipMemcpy(h->rank_mask, keep.data(), wmax, hipMemcpyHostToDevice));
+  return 0;
+}
+// the mask argument of the selection kernels: score_filter_args' mask, or with an ignore list the keep-mask above
+static int rank_mask_arg(ganmf_handle* h, const char* who, int W, const unsigned char** mask) {
+  if (h->ignore_w == 0) return 0;
+  if (h->ignore_w > W) return fail(-1, "%s: the ignore list lists item %lld but the score rows have %d columns", who, (long long)h->ignore_w - 1, W);
+  *mask = h->rank_mask;
+  return 0;
+}
+
 int ganmf_set_score_filter(ganmf_handle* h, const int32_t* items, int64_t n_items, int mask_cold_rows) {
   if (!h) return fail(-1, "null handle");
   if (n_items < 0 || (n_items > 0 && !items)) return fail(-1, "ganmf_set_score_filter: bad item list");
@@ -117,10 +139,33 @@ int ganmf_set_score_filter(ganmf_handle* h, const int32_t* items, int64_t n_item
     std::vector<unsigned char> m((size_t)wmax, 0);
     for (int64_t i = 0; i < n_items; ++i) m[(size_t)items[i]] = 1;
     HIP_TRY(hipMemcpy(h->item_mask, m.data(), m.size(), hipMemcpyHostToDevice));
+    h->filter_host.swap(m);
+  } else {
+    h->filter_host.clear();
   }
   h->item_mask_w = n_items > 0 ? top : 0;
   h->mask_cold = mask_cold_rows != 0;
-  return 0;
+  return refresh_rank_mask(h);
+}
+
+int ganmf_set_items_to_ignore(ganmf_handle* h, const int32_t* items, int64_t n_items) {
+  if (!h) return fail(-1, "null handle");
+  if (n_items < 0 || (n_items > 0 && !items)) return fail(-1, "ganmf_set_items_to_ignore: bad item list");
+  if (!items) n_items = 0;
+  const int64_t wmax = std::max(h->U, h->N);
+  int64_t top = 0;
+  for (int64_t i = 0; i < n_items; ++i) {
+    if (items[i] < 0 || items[i] >= wmax) return fail(-1, "ganmf_set_items_to_ignore: item %d out of range [0,%lld)", items[i], (long long)wmax);
+    top = std::max<int64_t>(top, (int64_t)items[i] + 1);
+  }
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  h->ignore_host.assign(n_items > 0 ? (size_t)wmax : 0, 0);
+  for (int64_t i = 0; i < n_items; ++i) h->ignore_host[(size_t)items[i]] = 1;
+  h->ignore_w = top;
+  const int rc = refresh_rank_mask(h);
+  if (rc) { h->ignore_host.clear(); h->ignore_w = 0; }     // a failed upload leaves "no ignore list"
+  return rc;
 }
 
 int ganmf_scores(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, float* out) {
@@ -215,6 +260,7 @@ static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_
     return fail(-1, "%s: remove_seen needs ganmf_set_seen_csr with a %d x %d matrix", who, limit, W);
   const unsigned char* fmask; const long long* fcold;
   TRY(score_filter_args(h, who, W, limit, &fmask, &fcold));
+  TRY(rank_mask_arg(h, who, W, &fmask));
   const int cand_cap = round_up((int)std::max<long long>(longest, 1), 64);
   const size_t cand_shmem = ((size_t)2 * cand_cap + (h->ldk > CAND_REG_LD ? (size_t)h->ldk : 0)) * sizeof(float);
   if (cand && cand_shmem > 144 * 1024)
@@ -531,6 +577,64 @@ int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int tr
   if (e == hipSuccess) e = hipStreamSynchronize(h->st);
   if (e != hipSuccess) { hipStreamSynchronize(h->st); return fail(-2, "%s: %s", who, hipGetErrorString(e)); }   // (members / begin are locals)
   for (int g = 0; g < G; ++g) group_size[g] = (int64_t)(begin[(size_t)g + 1] - begin[(size_t)g]);
+  return 0;
+}
+
+// ---- ganmf_set_item_diversity / ganmf_evaluate_diversity (list_diversity.hpp) ----------------------------------------------------
+int ganmf_set_item_diversity(ganmf_handle* h, const float* matrix, int64_t width) {
+  const char* who = "ganmf_set_item_diversity";
+  if (!h) return fail(-1, "null handle");
+  if (matrix && (width < 1 || width > std::max(h->U, h->N))) return fail(-1, "%s: width %lld out of range", who, (long long)width);
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(h->div_mat); h->div_mat = nullptr; h->div_w = 0;
+  if (!matrix) return 0;
+  const size_t bytes = (size_t)width * (size_t)width * sizeof(float);
+  size_t free_b = 0, total_b = 0;     // never more than a quarter of the free device memory (the rule of ganmf_score_similarity)
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4)
+    return fail(-1, "%s: out of memory budget: a %lld x %lld matrix needs %.1f MB, over a quarter of the %.1f MB free", who,
+                (long long)width, (long long)width, bytes / 1048576.0, free_b / 1048576.0);
+  HIP_TRY(hipMalloc((void**)&h->div_mat, bytes));
+  HIP_TRY(hipMemcpy(h->div_mat, matrix, bytes, hipMemcpyHostToDevice));
+  h->div_w = width;                   // set last: a failed upload leaves "no matrix"
+  return 0;
+}
+
+int ganmf_evaluate_diversity(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, int candidates,
+                             const int32_t* cutoffs, int32_t n_cutoffs, double* sums, double* per_user) {
+  const char* who = "ganmf_evaluate_diversity";
+  if (!h || !ids || !cutoffs || !sums) return fail(-1, "%s: null argument", who);
+  if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
+  const int W = transposed ? h->U : h->N;
+  if (!h->div_mat) return fail(-1, "%s: no diversity matrix (ganmf_set_item_diversity)", who);
+  if (h->div_w != W) return fail(-1, "%s: the diversity matrix has width %lld, the score rows have %d columns", who, (long long)h->div_w, W);
+  ListDivP p{};
+  int K = 0;
+  for (int i = 0; i < n_cutoffs; ++i) {
+    if (cutoffs[i] < 1) return fail(-1, "%s: cut-off %d", who, cutoffs[i]);
+    K = std::max(K, (int)cutoffs[i]);
+    p.cutoffs[i] = cutoffs[i]; p.order[i] = i;
+  }
+  static_assert(LIST_DIV_MAX_K == GANMF_RECOMMEND_MAX_CUTOFF, "the kernel's LDS list holds the longest list rank_device takes");
+  std::stable_sort(p.order, p.order + n_cutoffs, [&](int a, int b) { return cutoffs[a] < cutoffs[b]; });
+  TRY(rank_device(h, who, candidates != 0, ids, n, transposed, K, remove_seen, nullptr, nullptr));     // (refuses K over the limit)
+  const int grid = (int)((n + 255) / 256);
+  const size_t n_user = (size_t)n * n_cutoffs, n_part = (size_t)grid * n_cutoffs;
+  TRY(grow_device(h, (void**)&h->eval_buf, &h->eval_cap, n_user + n_part, sizeof(double)));
+  double* d_user = h->eval_buf;
+  double* d_part = d_user + n_user;
+  p.items = h->topk_items; p.K = K; p.D = h->div_mat; p.W = W; p.ncut = n_cutoffs; p.out = d_user;
+  // (no profile class, like the selection kernels: the tag table is at GANMF_PROF_MAX)
+  GANMF_LAUNCH(list_diversity_kernel, dim3((unsigned)n), dim3(256), 0, h->st, p);
+  HIP_TRY(hipGetLastError());
+  GANMF_LAUNCH(column_block_sum_kernel, dim3((unsigned)grid, (unsigned)n_cutoffs), dim3(256), 0, h->st, d_user, (int)n, (int)n_cutoffs, d_part);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> part(n_part);
+  hipError_t e = hipMemcpyAsync(part.data(), d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess && per_user) e = hipMemcpyAsync(per_user, d_user, n_user * sizeof(double), hipMemcpyDeviceToHost, h->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+  if (e != hipSuccess) { hipStreamSynchronize(h->st); return fail(-2, "%s: %s", who, hipGetErrorString(e)); }
+  sum_block_partials(part, grid, n_cutoffs, sums);
   return 0;
 }
 

@@ -150,9 +150,19 @@ struct ganmf_handle {
   size_t item_mask_cap = 0;
   int64_t item_mask_w = 0;             // 0: no item filter; else one past the largest listed item
   bool mask_cold = false;
+  // ignore list (ganmf_set_items_to_ignore): byte per score column (1 = ignored) on the host, beside the host copy of the score filter's
+  // bytes; while a list is set, rank_mask holds the keep-mask everything that RANKS uses -- (no item filter, or listed by it) and not
+  // ignored -- formed by whichever of the two setters ran last.  ganmf_scores keeps reading item_mask.
+  std::vector<unsigned char> filter_host, ignore_host;
+  int64_t ignore_w = 0;                // 0: no ignore list; else one past the largest ignored item
+  unsigned char* rank_mask = nullptr;
+  size_t rank_mask_cap = 0;
   int* topk_items = nullptr;
   float* topk_vals = nullptr;
   size_t topk_cap = 0;
+  // ganmf_set_item_diversity: the [div_w, div_w] item diversity matrix of ganmf_evaluate_diversity, resident until replaced
+  float* div_mat = nullptr;
+  int64_t div_w = 0;
   // ganmf_evaluate(): URM_test in evaluation orientation (sorted rows) with the DCG gains, work buffers
   long long* test_indptr = nullptr;
   int* test_indices = nullptr;

@@ -419,6 +419,9 @@ class ShardedEngine(object):
     def set_score_filter(self, items_to_compute=None, mask_cold=False):
         self.master.set_score_filter(items_to_compute, mask_cold)
 
+    def set_items_to_ignore(self, items=None):
+        self.master.set_items_to_ignore(items)
+
     def recommend(self, ids, cutoff, transposed=False, remove_seen=True):
         self._sync_master()
         return self.master.recommend(ids, cutoff, transposed, remove_seen)
@@ -456,6 +459,13 @@ class ShardedEngine(object):
         self._sync_master()
         return self.master.evaluate_groups(ids, cutoffs, disc, ideal_cum, group_of, n_groups, transposed, remove_seen, candidates,
                                            per_user)
+
+    def set_item_diversity(self, matrix=None):
+        self.master.set_item_diversity(matrix)
+
+    def evaluate_diversity(self, ids, cutoffs, transposed=False, remove_seen=True, candidates=False, per_user=False):
+        self._sync_master()
+        return self.master.evaluate_diversity(ids, cutoffs, transposed, remove_seen, candidates, per_user)
 
     def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
         self._sync_master()

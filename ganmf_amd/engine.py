@@ -147,6 +147,15 @@ class Engine:
         items = np.ascontiguousarray(np.asarray(items_to_compute).reshape(-1), dtype=np.int32)
         L.check(self.lib.ganmf_set_score_filter(self.h, _i32p(items), len(items), int(bool(mask_cold))), "ganmf_set_score_filter")
 
+    def set_items_to_ignore(self, items=None):
+        """Columns that score -inf in everything that ranks -- recommend*, evaluate* -- until the list is cleared (None or empty),
+        on top of set_score_filter (ganmf_set_items_to_ignore; BaseRecommender.py:84-86, 207-211).  scores() is not affected."""
+        if items is None or len(items) == 0:
+            L.check(self.lib.ganmf_set_items_to_ignore(self.h, None, 0), "ganmf_set_items_to_ignore")
+            return
+        items = np.ascontiguousarray(np.asarray(items).reshape(-1), dtype=np.int32)
+        L.check(self.lib.ganmf_set_items_to_ignore(self.h, _i32p(items), len(items)), "ganmf_set_items_to_ignore")
+
     def recommend(self, ids, cutoff, transposed=False, remove_seen=True):
         """device top-k: returns (items [n, cutoff] int32 with -1 padding, scores [n, cutoff])"""
         ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
@@ -282,6 +291,30 @@ class Engine:
                                                    sizes.ctypes.data_as(C.POINTER(C.c_int64)) if G > 0 else None,
                                                    _f64p(users) if users is not None else None), "ganmf_evaluate_groups")
         return sums, sizes, users
+
+    def set_item_diversity(self, matrix=None):
+        """The [width, width] float32 item diversity matrix of evaluate_diversity, resident until replaced; None drops it
+        (ganmf_set_item_diversity).  MemoryError when it would take over a quarter of the free device memory."""
+        if matrix is None:
+            L.check(self.lib.ganmf_set_item_diversity(self.h, None, 0), "ganmf_set_item_diversity")
+            return
+        m = np.ascontiguousarray(matrix, dtype=np.float32)
+        assert m.ndim == 2 and m.shape[0] == m.shape[1]
+        L.check(self.lib.ganmf_set_item_diversity(self.h, _f32p(m), m.shape[0]), "ganmf_set_item_diversity")
+
+    def evaluate_diversity(self, ids, cutoffs, transposed=False, remove_seen=True, candidates=False, per_user=False):
+        """Sums over the users `ids` of the intra-list diversity of their ranked lists per cut-off (ganmf_evaluate_diversity; the
+        ranking of evaluate(), or with candidates=True of evaluate_candidates()): a [len(cutoffs)] float64 array, with
+        per_user=True (that, the [len(ids), len(cutoffs)] per-user values).  A list shorter than two items at a cut-off has value 0."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        cut = np.ascontiguousarray(cutoffs, dtype=np.int32).ravel()
+        sums = np.zeros(cut.size, dtype=np.float64)
+        users = np.zeros((ids.size, cut.size), dtype=np.float64) if per_user else None
+        if ids.size:
+            L.check(self.lib.ganmf_evaluate_diversity(self.h, _i32p(ids), ids.size, int(transposed), int(remove_seen), int(candidates),
+                                                      _i32p(cut), cut.size, _f64p(sums),
+                                                      _f64p(users) if users is not None else None), "ganmf_evaluate_diversity")
+        return (sums, users) if per_user else sums
 
     def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
         """Cosine similarity of the (unfiltered) score rows `ids` among themselves, formed on the device (ganmf_score_similarity;

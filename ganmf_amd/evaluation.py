@@ -4,8 +4,25 @@ metrics of Base/Evaluation/metrics.py).  The GANMF callers read `results_dic[cut
 cut-off 5, Utils_.py:64).
 
 By default both evaluators return the eleven accuracy values of METRICS.  With `full_metrics=True` they return the
-reference's whole row, FULL_METRICS in the reference's key order (Evaluator.py:20-40; DIVERSITY_SIMILARITY, which the
-reference adds only for a `diversity_object`, and ignore_items / ignore_users are not supported).
+reference's whole row, FULL_METRICS in the reference's key order (Evaluator.py:20-40).  The reference's three further
+constructor arguments (Evaluator.py:119-122) are keywords after `full_metrics`:
+  diversity_object  an object with an `item_diversity_matrix` attribute (metrics.py:405-452 Diversity_similarity) or a plain
+                    [n_items, n_items] array D with values in [0, 1] (asserted, as there).  The key DIVERSITY_SIMILARITY is in the
+                    rows iff one was given: after AVERAGE_POPULARITY in a full row (the reference's place), else appended to the
+                    eleven.  D is rounded to float32 ONCE and every route -- per user, blocks, device -- uses the rounded matrix.
+                    Per list l of length L at a cut-off: sum over i = 0 .. L-2 (the last item's row is never visited; D need not
+                    be symmetric) and j != i of D[l_i, l_j], divided by L (L - 1); the mean over the evaluated users.  A list with
+                    L < 2 has value 0 and still counts in the mean (the reference raises ZeroDivisionError there).
+  ignore_items      set_items_to_ignore(ignore_items) on the recommender around the whole evaluation (reset in a finally), every
+                    `recommend` / device call with remove_CustomItems_flag (Evaluator.py:369-370, 410-411, 275): the items are never
+                    recommended and, scoring -inf, do not count in RMSE; the relevant items are not filtered.  COVERAGE_ITEM divides
+                    by n_items - len(ignore_items) (`len`: a repeated id counts twice, metrics.py:36-46); Gini, Herfindahl and
+                    Shannon clear the ignored bins (:151-165, 201-215, 251-269).
+  ignore_users      usersToEvaluate minus the list, ascending (Evaluator.py:171-176); COVERAGE_USER divides by
+                    n_users - len(ignore_users) (metrics.py:64-73).
+Deviation: the reference's EvaluatorNegativeItemSample resets the recommender's ignore list INSIDE its user loop
+(Evaluator.py:530), so only the first evaluated user is filtered there; the negative-sample evaluators here apply ignore_items
+to every user.
 
 Metric definitions (one user, a ranked list `L` cut at c, test items `T` with ratings `w`, hit flags `h_i = [L_i in T]`):
   PRECISION = sum(h)/|L|      PRECISION_RECALL_MIN_DEN = sum(h)/min(|T|,|L|)      RECALL = sum(h)/|T|
@@ -36,6 +53,7 @@ BEYOND_ACCURACY = ("NOVELTY", "AVERAGE_POPULARITY", "DIVERSITY_MEAN_INTER_LIST",
                    "COVERAGE_USER", "DIVERSITY_GINI", "SHANNON_ENTROPY")
 FULL_METRICS = METRICS + BEYOND_ACCURACY
 _SUMMED = tuple(m for m in METRICS if m != "F1")
+DIVERSITY = "DIVERSITY_SIMILARITY"       # present in a row iff the evaluator was given a diversity_object
 
 
 def get_result_string(results_run, n_decimals=7):
@@ -72,11 +90,20 @@ def popularity_weights(pop):
     return novelty, pop / pop.max()
 
 
-def beyond_accuracy_metrics(counts, novelty_sum, popularity_sum, n_nonempty, n_eval, cutoff, n_items, n_users):
+def beyond_accuracy_metrics(counts, novelty_sum, popularity_sum, n_nonempty, n_eval, cutoff, n_items, n_users, ignore_items=None,
+                            ignore_users=None):
     """The eight beyond-accuracy values of one cut-off in float64, from the per-item recommendation counts `counts`
     ([n_items], summed over all evaluated users) and the sums over the users of the novelty terms, of the mean normalised
-    popularity of each list and of the non-empty lists.  Verbatim metrics.py get_metric_value."""
+    popularity of each list and of the non-empty lists.  Verbatim metrics.py get_metric_value.  `ignore_items` / `ignore_users`
+    (the evaluator's lists): the coverage denominators shrink by their LENGTHS, and Herfindahl, Gini and Shannon clear the
+    ignored items' bins first; Novelty, AveragePopularity and MeanInterList do not know about the lists."""
     counts = np.asarray(counts, dtype=np.float64)
+    n_ignored_items = 0 if ignore_items is None else len(ignore_items)
+    n_ignored_users = 0 if ignore_users is None else len(ignore_users)
+    seen_counts = counts
+    if n_ignored_items:
+        counts = counts.copy()
+        counts[np.asarray(ignore_items, dtype=np.int64)] = 0.0
     out = {}
     out["NOVELTY"] = novelty_sum / n_eval if n_eval else 0.0
     out["AVERAGE_POPULARITY"] = popularity_sum / n_eval if n_eval else 0.0
@@ -84,7 +111,7 @@ def beyond_accuracy_metrics(counts, novelty_sum, popularity_sum, n_nonempty, n_e
     if n_eval == 0:
         out["DIVERSITY_MEAN_INTER_LIST"] = 1.0
     else:
-        cooccurrences_cumulative = np.sum(counts ** 2) - n_eval * cutoff
+        cooccurrences_cumulative = np.sum(seen_counts ** 2) - n_eval * cutoff
         all_user_couples_count = n_eval ** 2 - n_eval
         diversity_cumulative = all_user_couples_count - cooccurrences_cumulative / cutoff
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -94,8 +121,8 @@ def beyond_accuracy_metrics(counts, novelty_sum, popularity_sum, n_nonempty, n_e
         out["DIVERSITY_HERFINDAHL"] = 1 - np.sum((counts / counts.sum()) ** 2)
     else:
         out["DIVERSITY_HERFINDAHL"] = np.nan
-    out["COVERAGE_ITEM"] = (counts > 0).sum() / n_items                       # Coverage_Item (:45-46)
-    out["COVERAGE_USER"] = n_nonempty / n_users                               # Coverage_User (:72-73)
+    out["COVERAGE_ITEM"] = (seen_counts > 0).sum() / (n_items - n_ignored_items)   # Coverage_Item (:45-46)
+    out["COVERAGE_USER"] = n_nonempty / (n_users - n_ignored_users)                # Coverage_User (:72-73)
     nonzero = counts[counts != 0]
     # Gini_Diversity (:160-178)
     n = len(nonzero)
@@ -117,14 +144,64 @@ class _FullSums(object):
         self.popularity = dict.fromkeys(cutoffs, 0.0)
         self.nonempty = dict.fromkeys(cutoffs, 0)
 
-    def rows(self, results, n_eval, cutoffs, n_items, n_users):
-        """results[c] in the reference's key order: the accuracy values as given, then the beyond-accuracy ones"""
+    def rows(self, results, n_eval, cutoffs, n_items, n_users, ignore_items=None, ignore_users=None):
+        """results[c] in the reference's key order: the accuracy values as given, then the beyond-accuracy ones, DIVERSITY_SIMILARITY
+        (when results[c] has it) after AVERAGE_POPULARITY"""
         for c in cutoffs:
             row = {m: results[c][m] for m in METRICS}
-            row.update(beyond_accuracy_metrics(self.counts[c], self.novelty[c], self.popularity[c], self.nonempty[c], n_eval, c,
-                                               n_items, n_users))
+            for name, value in beyond_accuracy_metrics(self.counts[c], self.novelty[c], self.popularity[c], self.nonempty[c], n_eval, c,
+                                                       n_items, n_users, ignore_items, ignore_users).items():
+                row[name] = value
+                if name == "AVERAGE_POPULARITY" and DIVERSITY in results[c]:
+                    row[DIVERSITY] = results[c][DIVERSITY]
             results[c] = row
         return results
+
+
+def list_diversity(D, items, cutoffs):
+    """Intra-list diversity (metrics.py:405-452) of the ranked lists `items` ([n, K] ids, -1 padded at the end) at every cut-off:
+    [n, len(cutoffs)] float64.  With L = min(c, valid ids of the row): the sum of D[l_i, l_j] over i = 0 .. L-2 and j != i, j < L,
+    divided by L (L - 1); 0 when L < 2."""
+    items = np.asarray(items)
+    n, K = items.shape
+    length = (items >= 0).sum(axis=1)
+    out = np.zeros((n, len(cutoffs)), dtype=np.float64)
+    for ci, c in enumerate(cutoffs):
+        c = min(int(c), K)
+        if c < 2 or n == 0:
+            continue
+        pos = np.arange(c)
+        off_diagonal = pos[:, None] != pos[None, :]
+        step = max(1, int(4e6) // (c * c))
+        for lo in range(0, n, step):
+            ids = items[lo:lo + step, :c]
+            ids = np.where(ids >= 0, ids, 0)
+            L = np.minimum(length[lo:lo + step], c)
+            keep = ((pos[None, :, None] + 2 <= L[:, None, None]) & (pos[None, None, :] + 1 <= L[:, None, None]) & off_diagonal[None])
+            total = (D[ids[:, :, None], ids[:, None, :]].astype(np.float64) * keep).sum(axis=(1, 2))
+            out[lo:lo + step, ci] = np.where(L >= 2, total / np.maximum(L * (L - 1), 1), 0.0)
+    return out
+
+
+class DiversitySimilarity(object):
+    """The reference's Diversity_similarity metric object (metrics.py:405-452) with the L < 2 rule of this package: a list of fewer
+    than two items adds 0 (the reference divides by zero) and counts as an evaluated user."""
+
+    def __init__(self, item_diversity_matrix):
+        D = np.asarray(item_diversity_matrix)
+        assert np.all(D >= 0.0) and np.all(D <= 1.0), "item_diversity_matrix contains value greater than 1.0 or lower than 0.0"
+        self.item_diversity_matrix = D
+        self.n_evaluated_users = 0
+        self.diversity = 0.0
+
+    def add_recommendations(self, recommended_items_ids):
+        ids = np.asarray(recommended_items_ids, dtype=np.int64).reshape(1, -1)
+        if ids.shape[1] >= 2:
+            self.diversity += float(list_diversity(self.item_diversity_matrix, ids, [ids.shape[1]])[0, 0])
+        self.n_evaluated_users += 1
+
+    def get_metric_value(self):
+        return self.diversity / self.n_evaluated_users if self.n_evaluated_users else 0.0
 
 
 class RankedListMetrics(object):
@@ -256,7 +333,8 @@ def _add_parts(a, b):
 class EvaluatorHoldout(object):
     EVALUATOR_NAME = "EvaluatorHoldout"
 
-    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
+    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False, diversity_object=None,
+                 ignore_items=None, ignore_users=None):
         if isinstance(URM_test_list, list):
             raise ValueError("List of URM_test not supported")
         self.cutoff_list = list(cutoff_list)
@@ -267,7 +345,27 @@ class EvaluatorHoldout(object):
         self.URM_test = sps.csr_matrix(URM_test_list)
         self.n_users, self.n_items = self.URM_test.shape
         n_ratings = np.ediff1d(self.URM_test.indptr)
-        self.usersToEvaluate = list(np.arange(self.n_users)[n_ratings >= minRatingsPerUser])
+        users = np.arange(self.n_users)[n_ratings >= minRatingsPerUser]
+        self.ignore_items_flag = ignore_items is not None
+        self.ignore_items_ID = np.array([] if ignore_items is None else ignore_items, dtype=np.int64).reshape(-1)
+        self.ignore_users_ID = np.array([] if ignore_users is None else ignore_users, dtype=np.int64).reshape(-1)
+        if ignore_users is not None:
+            users = users[~np.isin(users, self.ignore_users_ID)]       # ascending (the reference's set difference has no order)
+        self.usersToEvaluate = list(users)
+        # what the hooks of a device route and `recommend_topk` / `recommend_candidates` get on top of their old arguments
+        self._ignore_kw = {"remove_CustomItems_flag": True} if self.ignore_items_flag else {}
+        self.diversity_object = diversity_object
+        self._diversity = None          # the item diversity matrix every route uses: float32, rounded once
+        if diversity_object is not None:
+            D = np.asarray(getattr(diversity_object, "item_diversity_matrix", diversity_object))
+            if D.shape != (self.n_items, self.n_items):
+                raise ValueError("diversity_object: a %d x %d item diversity matrix, given %r" % (self.n_items, self.n_items, D.shape))
+            assert np.all(D >= 0.0) and np.all(D <= 1.0), "item_diversity_matrix contains value greater than 1.0 or lower than 0.0"
+            self._diversity = np.ascontiguousarray(D, dtype=np.float32)
+
+    def _new_sums(self):
+        names = _SUMMED + ((DIVERSITY,) if self._diversity is not None else ())
+        return {c: dict.fromkeys(names, 0.0) for c in self.cutoff_list}
 
     def get_user_relevant_items(self, user_id):
         return self.URM_test.indices[self.URM_test.indptr[user_id]:self.URM_test.indptr[user_id + 1]]
@@ -279,13 +377,29 @@ class EvaluatorHoldout(object):
         """the one `recommend` call of every host route (the keyword set of Evaluator.py:264-270)"""
         restrict = {} if items_to_compute is None else {"items_to_compute": items_to_compute}
         return rec.recommend(users, remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff, remove_top_pop_flag=False,
-                             remove_CustomItems_flag=False, return_scores=return_scores, **restrict)
+                             remove_CustomItems_flag=self.ignore_items_flag, return_scores=return_scores, **restrict)
+
+    def _ignoring_items(self, call, recommender_object):
+        """`call(recommender_object)` between set_items_to_ignore(ignore_items) and reset_items_to_ignore() (Evaluator.py:369-370,
+        410-411); the reset runs even when the recommender raises"""
+        if not self.ignore_items_flag:
+            return call(recommender_object)
+        recommender_object.set_items_to_ignore(self.ignore_items_ID)
+        try:
+            return call(recommender_object)
+        finally:
+            recommender_object.reset_items_to_ignore()
 
     def evaluateRecommender(self, recommender_object):
-        """(results[cutoff][metric], text).  Users are scored in blocks of min(1000, 1e8/n_items) through
-        `recommender.recommend(..., return_scores=True)` (Evaluator.py:237-277)."""
+        """(results[cutoff][metric], text) of the class's protocol (`_evaluate`), the recommender ignoring `ignore_items` for the
+        duration."""
+        return self._ignoring_items(self._evaluate, recommender_object)
+
+    def _evaluate(self, recommender_object):
+        """Users are scored in blocks of min(1000, 1e8/n_items) through `recommender.recommend(..., return_scores=True)`
+        (Evaluator.py:237-277)."""
         block_size = min(1000, int(1e8 / self.n_items))
-        sums = {c: dict.fromkeys(_SUMMED, 0.0) for c in self.cutoff_list}
+        sums = self._new_sums()
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         w_novelty = w_popularity = None
         if full is not None:
@@ -311,7 +425,11 @@ class EvaluatorHoldout(object):
         beyond-accuracy metrics are NOT part of the grouped row (`full_metrics` is ignored): RMSE needs every score, the
         others are properties of a whole set of lists.  Per-user values are float64 (RankedListMetrics(dtype=np.float64)) on
         every class and route.  `return_per_user=True`: (that dict, the [n_evaluated, n_cutoffs, 9] per-user values, the
-        evaluated user ids in the same order)."""
+        evaluated user ids in the same order).  `ignore_items` / `ignore_users` apply as in evaluateRecommender; the diversity is not
+        part of the grouped row."""
+        return self._ignoring_items(lambda rec: self._evaluate_by_group(rec, user_groups, return_per_user), recommender_object)
+
+    def _evaluate_by_group(self, recommender_object, user_groups, return_per_user):
         labels, group_idx = self._group_index(user_groups)
         return self._finish_groups(labels, group_idx, self._per_user_host(recommender_object), return_per_user)
 
@@ -386,6 +504,8 @@ class EvaluatorHoldout(object):
             for name, value in scorer(hit, gain, c).items():
                 acc[name] += value
             acc["RMSE"] += user_rmse
+            if self._diversity is not None:
+                acc[DIVERSITY] += list_diversity(self._diversity, np.asarray(recommended[:c], dtype=np.int64).reshape(1, -1), [c])[0, 0]
             if full is not None:
                 listed = np.asarray(recommended[:c], dtype=np.int64)
                 if len(listed) > 0:
@@ -397,9 +517,10 @@ class EvaluatorHoldout(object):
     def _finish_results(self, sums, full, n_eval, rmse=True, as_float=False):
         """(results, text) from the running sums.  rmse=False: the route did not compute it, NaN.  as_float: Python floats (the
         reference-order classes return the float32 / float64 scalars their sums are made of)."""
+        diversity = self._diversity is not None
         if n_eval == 0:
             print("WARNING: No users had a sufficient number of relevant items")
-            results = {c: dict.fromkeys(METRICS, 0.0) for c in self.cutoff_list}
+            results = {c: dict.fromkeys(METRICS + ((DIVERSITY,) if diversity else ()), 0.0) for c in self.cutoff_list}
         else:
             results = _finish(sums, n_eval, self.cutoff_list)
             for c in self.cutoff_list:
@@ -407,8 +528,10 @@ class EvaluatorHoldout(object):
                     results[c] = {m: float(v) for m, v in results[c].items()}
                 if not rmse:
                     results[c]["RMSE"] = float("nan")
+                if diversity:
+                    results[c][DIVERSITY] = float(sums[c][DIVERSITY]) / n_eval
         if full is not None:
-            results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users)
+            results = full.rows(results, n_eval, self.cutoff_list, self.n_items, self.n_users, self.ignore_items_ID, self.ignore_users_ID)
         return results, get_result_string(results)
 
 
@@ -425,9 +548,11 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
     kernel (ganmf_evaluate_full) and the host route takes ids and scores from `recommend(..., return_scores=True)`."""
     EVALUATOR_NAME = "EvaluatorHoldoutFast"
 
-    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
+    def __init__(self, URM_test_list, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False, diversity_object=None,
+                 ignore_items=None, ignore_users=None):
         super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen,
-                         full_metrics=full_metrics)
+                         full_metrics=full_metrics, diversity_object=diversity_object, ignore_items=ignore_items,
+                         ignore_users=ignore_users)
         K = self.max_cutoff
         self._users = np.asarray(self.usersToEvaluate, dtype=np.int64)
         self._n_test = np.ediff1d(self.URM_test.indptr)[self._users].astype(np.int64)
@@ -466,7 +591,7 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
 
     def _topk(self, rec, batch):
         if hasattr(rec, "recommend_topk"):
-            return np.asarray(rec.recommend_topk(batch, self.max_cutoff, remove_seen_flag=self.exclude_seen))
+            return np.asarray(rec.recommend_topk(batch, self.max_cutoff, remove_seen_flag=self.exclude_seen, **self._ignore_kw))
         return _pad_lists(self._recommend(rec, batch, False), self.max_cutoff)
 
     def _topk_and_rmse(self, rec, batch):
@@ -496,19 +621,32 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
             return None
         return total
 
-    def _device_sums(self, rec, call, block):
+    def _device_sums(self, rec, call, block, candidates=None):
         """A device route over all user blocks, finished: (results, text), or None when the host route is to be taken.
         `call(slice, ratings, item_weights, counts)` returns one block's sums from the recommender's hook: nine per cut-off
-        (the three arguments None), or with full_metrics 13 per cut-off, the block's per-item counts added into `counts`."""
+        (the three arguments None), or with full_metrics 13 per cut-off, the block's per-item counts added into `counts`.
+        With a diversity_object one more call per block, `rec.evaluate_diversity_on_device` (the same ranking; `candidates`: every
+        user among its own), whose sums become one more column; a recommender without that hook takes the host route."""
+        diversity = self._diversity is not None
+        if diversity and not hasattr(rec, "evaluate_diversity_on_device"):
+            return None
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         ratings = weights = counts = None
         if full is not None:
             ratings, weights = self._test_rating, popularity_weights(item_popularity(_train_matrix(rec)))
             counts = np.zeros((len(self.cutoff_list), self.n_items), dtype=np.int64)
-        dev = self._device_blocks(lambda sl: call(sl, ratings, weights, counts), len(self._users), block)
+
+        def block_sums(sl):
+            part = call(sl, ratings, weights, counts)
+            if part is None or not diversity:
+                return part
+            div = rec.evaluate_diversity_on_device(self._device_token, self._diversity, self._users[sl], self.cutoff_list,
+                                                   remove_seen_flag=self.exclude_seen, candidates_csr=candidates, **self._ignore_kw)
+            return None if div is None else np.concatenate([part, np.asarray(div, dtype=np.float64).reshape(-1, 1)], axis=1)
+        dev = self._device_blocks(block_sums, len(self._users), block)
         return None if dev is None else self._from_device(dev, full, counts)
 
-    def evaluateRecommender(self, recommender_object):
+    def _evaluate(self, recommender_object):
         rec = recommender_object
         if self._device_route(rec, "evaluate_full_on_device" if self.full_metrics else "evaluate_on_device"):
             # everything on the device: scores, seen mask, top-k AND the metric sums (only the sums, and the counts of a full row,
@@ -517,14 +655,15 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
                 if self.full_metrics:
                     return rec.evaluate_full_on_device(self._device_token, self._test_sorted, self._test_gain, ratings, weights,
                                                        self._users[sl], self.cutoff_list, self._disc, self._ideal_cum[sl],
-                                                       remove_seen_flag=self.exclude_seen, counts=counts)
+                                                       remove_seen_flag=self.exclude_seen, counts=counts, **self._ignore_kw)
                 return rec.evaluate_on_device(self._device_token, self._test_sorted, self._test_gain, self._users[sl],
-                                              self.cutoff_list, self._disc, self._ideal_cum[sl], remove_seen_flag=self.exclude_seen)
+                                              self.cutoff_list, self._disc, self._ideal_cum[sl], remove_seen_flag=self.exclude_seen,
+                                              **self._ignore_kw)
             got = self._device_sums(rec, call, self._device_block())
             if got is not None:
                 return got
         n_eval = len(self._users)
-        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
+        sums = self._new_sums()
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         w_novelty = w_popularity = None
         if full is not None:
@@ -553,10 +692,11 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
         return self._device_blocks(
             lambda sl: rec.evaluate_groups_on_device(self._device_token, self._test_sorted, self._test_gain, self._users[sl],
                                                      self.cutoff_list, self._disc, self._ideal_cum[sl], group_idx[sl], len(labels),
-                                                     remove_seen_flag=self.exclude_seen, candidates_csr=candidates, per_user=per_user),
+                                                     remove_seen_flag=self.exclude_seen, candidates_csr=candidates, per_user=per_user,
+                                                     **self._ignore_kw),
             len(self._users), block)
 
-    def evaluateRecommenderByGroup(self, recommender_object, user_groups, return_per_user=False):
+    def _evaluate_by_group(self, recommender_object, user_groups, return_per_user):
         """EvaluatorHoldout.evaluateRecommenderByGroup; with a recommender that has `evaluate_groups_on_device`
         (ganmf_evaluate_groups) ranking, per-user values and group sums stay on the device, and the host route is taken exactly
         where evaluateRecommender takes it."""
@@ -572,8 +712,10 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
         not computed there), or with `full` [n_cutoffs, 13] in the order of EVAL_FULL_METRICS beside the [n_cutoffs, n_items] counts"""
         from ._lib import EVAL_FULL_METRICS, EVAL_METRICS
         col = {name: i for i, name in enumerate(EVAL_METRICS if full is None else EVAL_FULL_METRICS)}
-        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
+        sums = self._new_sums()
         for ci, c in enumerate(self.cutoff_list):
+            if self._diversity is not None:             # the column _device_sums appended
+                sums[c][DIVERSITY] = float(dev[ci, len(col)])
             for name in _SUMMED:
                 if name in col:
                     sums[c][name] = float(dev[ci, col[name]])
@@ -599,8 +741,11 @@ class EvaluatorHoldoutFast(EvaluatorHoldout):
         gain = np.asarray(gain_block[rows, safe.ravel()]).reshape(len(batch), K) * is_rel
         n_test = self._n_test[sl].astype(np.float64)
         length = valid.sum(axis=1)
-        for c in self.cutoff_list:
+        diversity = None if self._diversity is None else list_diversity(self._diversity, items, self.cutoff_list)
+        for ci, c in enumerate(self.cutoff_list):
             r = sums[c]
+            if diversity is not None:
+                r[DIVERSITY] += diversity[:, ci].sum()
             rel = is_rel[:, :c].astype(np.float64)
             neg = (valid[:, :c] & ~is_rel[:, :c]).astype(np.float64)
             len_c = np.minimum(length, c).astype(np.float64)
@@ -649,9 +794,11 @@ def items_to_rank(URM_test, URM_test_negative):
 class _NegativeSample(object):
     """What the two negative-sample evaluators add to their hold-out base: every user's candidates, `URM_items_to_rank`"""
 
-    def __init__(self, URM_test_list, URM_test_negative, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False):
+    def __init__(self, URM_test_list, URM_test_negative, cutoff_list, minRatingsPerUser=1, exclude_seen=True, full_metrics=False,
+                 diversity_object=None, ignore_items=None, ignore_users=None):
         super().__init__(URM_test_list, cutoff_list, minRatingsPerUser=minRatingsPerUser, exclude_seen=exclude_seen,
-                         full_metrics=full_metrics)
+                         full_metrics=full_metrics, diversity_object=diversity_object, ignore_items=ignore_items,
+                         ignore_users=ignore_users)
         self.URM_items_to_rank = items_to_rank(self.URM_test, URM_test_negative)
         if self.URM_items_to_rank.shape != self.URM_test.shape:
             raise ValueError("URM_test_negative must have the shape of URM_test")
@@ -674,11 +821,14 @@ class EvaluatorNegativeItemSample(_NegativeSample, EvaluatorHoldout):
     What "only against the candidates" means is the recommender's business, as in the reference: a recommender that honours
     `items_to_compute` (the MF contract, Base/BaseMatrixFactorizationRecommender.py:113-119; GANMF(score_contract="mf")) scores
     every other item -inf; the reference's own GANMF ignores `items_to_compute` (GANMF.py:285-292; the default
-    score_contract="ganmf" here), and this evaluator around it ranks the whole catalogue, exactly as the reference's does."""
+    score_contract="ganmf" here), and this evaluator around it ranks the whole catalogue, exactly as the reference's does.
+
+    `ignore_items` applies to EVERY user.  The reference calls reset_items_to_ignore() inside its user loop (Evaluator.py:530), so
+    there only the first evaluated user is filtered -- a quirk this class (and the Fast one) deliberately does not copy."""
     EVALUATOR_NAME = "EvaluatorNegativeItemSample"
 
-    def evaluateRecommender(self, recommender_object):
-        sums = {c: dict.fromkeys(_SUMMED, 0.0) for c in self.cutoff_list}
+    def _evaluate(self, recommender_object):
+        sums = self._new_sums()
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         w_novelty = w_popularity = None
         if full is not None:
@@ -748,7 +898,7 @@ class EvaluatorNegativeItemSampleFast(_NegativeSample, EvaluatorHoldoutFast):
                 try:
                     items = np.asarray(rec.recommend_candidates(self._users[sl], self.URM_items_to_rank, self.max_cutoff,
                                                                 remove_seen_flag=self.exclude_seen,
-                                                                candidates_key=self._device_token), dtype=np.int64)
+                                                                candidates_key=self._device_token, **self._ignore_kw), dtype=np.int64)
                 except (ValueError, RuntimeError):
                     by_block = False
             if items is None:
@@ -766,7 +916,7 @@ class EvaluatorNegativeItemSampleFast(_NegativeSample, EvaluatorHoldoutFast):
             for row in items:
                 yield row[row >= 0]
 
-    def evaluateRecommenderByGroup(self, recommender_object, user_groups, return_per_user=False):
+    def _evaluate_by_group(self, recommender_object, user_groups, return_per_user):
         """EvaluatorHoldout.evaluateRecommenderByGroup with every user ranked among its own candidates; the routes of
         evaluateRecommender in its order (device candidates, full width for a recommender that ignores items_to_compute, blocks,
         users)."""
@@ -778,24 +928,24 @@ class EvaluatorNegativeItemSampleFast(_NegativeSample, EvaluatorHoldoutFast):
             if got is not None:
                 return self._finish_groups(labels, group_idx, got[2], return_per_user, sums=got[0], sizes=got[1])
         if not getattr(rec, "honours_items_to_compute", True):
-            return super().evaluateRecommenderByGroup(rec, user_groups, return_per_user=return_per_user)
+            return super()._evaluate_by_group(rec, user_groups, return_per_user)
         return self._finish_groups(labels, group_idx, self._per_user_host(rec), return_per_user)
 
-    def evaluateRecommender(self, recommender_object):
+    def _evaluate(self, recommender_object):
         rec = recommender_object
         if self._device_route(rec, "evaluate_candidates_on_device"):
             got = self._device_sums(
                 rec, lambda sl, ratings, weights, counts: rec.evaluate_candidates_on_device(
                     self._device_token, self._test_sorted, self._test_gain, self.URM_items_to_rank, self._users[sl], self.cutoff_list,
                     self._disc, self._ideal_cum[sl], remove_seen_flag=self.exclude_seen, ratings=ratings, item_weights=weights,
-                    counts=counts),
-                self._candidate_device_block())
+                    counts=counts, **self._ignore_kw),
+                self._candidate_device_block(), candidates=self.URM_items_to_rank)
             if got is not None:
                 return got
         if not getattr(rec, "honours_items_to_compute", True):
             # the reference's evaluator around this recommender ranks the whole catalogue: the full-width routes
-            return super().evaluateRecommender(rec)
-        sums = {c: {m: 0.0 for m in _SUMMED} for c in self.cutoff_list}
+            return super()._evaluate(rec)
+        sums = self._new_sums()
         full = _FullSums(self.cutoff_list, self.n_items) if self.full_metrics else None
         w_novelty = w_popularity = None
         if full is not None:

@@ -246,7 +246,8 @@ int ganmf_evaluate(ganmf_handle* h, const int32_t* ids, int64_t n, int transpose
                    int32_t n_cutoffs, const double* disc, const double* ideal_cum, double* sums);
 
 /* The reference's full metric row on the device (Base/Evaluation/Evaluator.py:262-335 with every metric object that
- * create_empty_metrics_dict builds, Evaluator.py:43-84, except DIVERSITY_SIMILARITY; no ignore_items / ignore_users).
+ * create_empty_metrics_dict builds, Evaluator.py:43-84; DIVERSITY_SIMILARITY, which the reference adds only for a diversity_object,
+ * comes from ganmf_evaluate_diversity below, ignore_items from ganmf_set_items_to_ignore; ignore_users is the caller's id list).
  * ganmf_set_test_ratings: the rating (float32) of every stored entry of the matrix ganmf_set_test_csr holds, in its order;
  *   each ganmf_set_test_csr drops them.  Needed by RMSE (metrics.py:634 rmse).
  * ganmf_set_eval_item_weights: two per-item vectors of the evaluation width, formed by the caller in float64 from the
@@ -318,6 +319,40 @@ int ganmf_evaluate_candidates(ganmf_handle* h, const int32_t* ids, int64_t n, in
 int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, int candidates,
                           const int32_t* cutoffs, int32_t n_cutoffs, const double* disc, const double* ideal_cum,
                           const int32_t* group_of, int32_t n_groups, double* group_sums, int64_t* group_size, double* per_user);
+
+/* The evaluators' ignore_items and the recommender's remove_CustomItems_flag / remove_top_pop_flag on the device
+ * (Base/BaseRecommender.py:72-90, 207-211: scores_batch[:, items] = -inf after the seen mask, before the top-k; Evaluator.py:369-370,
+ * 410-411: set around a whole evaluation).
+ * ganmf_set_items_to_ignore: handle state like the score filter, a byte mask (a repeated id is harmless); items == NULL or
+ *   n_items == 0 clears it.  While set, the listed columns score -inf in everything that RANKS, under both score contracts and in
+ *   addition to the filter of ganmf_set_score_filter: ganmf_recommend, ganmf_recommend_candidates, ganmf_evaluate, ganmf_evaluate_full,
+ *   ganmf_evaluate_candidates, ganmf_evaluate_groups and ganmf_evaluate_diversity.  It is applied where the score filter is: before the
+ *   RMSE read of the 13-sum evaluations (an ignored test item does not count in RMSE, as in the reference, whose masked score matrix
+ *   is what return_scores hands to rmse) and before the first selection round.  It does NOT apply to ganmf_scores,
+ *   ganmf_score_similarity or training (_compute_item_score is not affected in the reference either).  Range checks as
+ *   ganmf_set_score_filter: against max(num_users, num_items) here, against the score width in use when a ranking entry runs (-1).
+ *
+ * Intra-list diversity of the ranked lists (Base/Evaluation/metrics.py:405-452 Diversity_similarity; the reference's
+ * DIVERSITY_SIMILARITY, present only when the evaluator was given a diversity_object, Evaluator.py:83-85).
+ * ganmf_set_item_diversity: `matrix` is [width, width] row-major float32 (the caller rounds a float64 matrix once and uses the
+ *   rounded values on every route), resident until replaced; NULL drops it.  A matrix over a quarter of the free device memory is
+ *   refused (-1; the rule of ganmf_score_similarity).
+ * ganmf_evaluate_diversity ranks the rows `ids` exactly as ganmf_evaluate (candidates = 0) or ganmf_evaluate_candidates
+ *   (candidates = 1) does at the largest cut-off -- limits, tie rule, score filter, seen mask and ignore list are those calls' -- and
+ *   forms, for every row and cut-off c, with len = the valid ids of the row's list and L_c = min(c, len):
+ *     value = sum of D[l_i, l_j] over the ordered pairs i != j with max(i + 2, j + 1) <= L_c, divided by L_c (L_c - 1)
+ *   -- the reference's sum: rows i = 0 .. L_c - 2 only (the LAST item's row is never visited; D need not be symmetric), all other
+ *   columns.  The value is 0 when L_c < 2 (the reference raises ZeroDivisionError there); the row still counts in the caller's mean.
+ *   sums[n_cutoffs] (overwritten): the sums of the values over the n rows; per_user: NULL or [n, n_cutoffs] in position order.
+ *   float64 throughout, fixed summation order, no floating-point atomics: the same bytes on every call and handle
+ *   (ganmf_amd/csrc/list_diversity.hpp; O(n K^2) gathers for largest cut-off K).
+ *   Errors (-1, message in ganmf_last_error, nothing enqueued, the handle usable as before): no matrix held, a held width other than
+ *   the score width of `transposed`, NULL ids / cutoffs / sums, n_cutoffs outside [1, GANMF_EVAL_MAX_CUTOFFS], and the argument
+ *   errors of ganmf_recommend / ganmf_recommend_candidates. */
+int ganmf_set_items_to_ignore(ganmf_handle* h, const int32_t* items, int64_t n_items);
+int ganmf_set_item_diversity(ganmf_handle* h, const float* matrix, int64_t width);
+int ganmf_evaluate_diversity(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int remove_seen, int candidates,
+                             const int32_t* cutoffs, int32_t n_cutoffs, double* sums, double* per_user);
 
 /* Cosine similarity of the predictions on the device: the computation under the reference's collapse study
  * (AblationStudy.py:88-92,113-117: cosine_similarity of all predictions, np.mean and np.std of the [users, users] matrix, and the

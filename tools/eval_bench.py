@@ -15,7 +15,16 @@ times ganmf_evaluate_groups with that many groups (users dealt to them at random
 back, beside ganmf_evaluate on the same handle and users, at the ML-1M shape (6040 x 3706, k = 250, cut-offs 5 / 10 / 20, one user
 block): the three alternate in one process after a warm-up of each, host wall time around calls that end in a stream synchronise,
 medians of `reps` calls in one JSON line; a second line gives the device time per kernel class of one profiled grouped call (a pass of
-its own, after the timed ones)."""
+its own, after the timed ones).
+
+    python tools/eval_bench.py --diversity
+
+times EvaluatorHoldoutFast(test, [5, 10, 20], full_metrics=True, diversity_object=D).evaluateRecommender at the ML-1M shape (6040 x
+3706, k = 250, random factors, D a random [3706, 3706] float32 matrix) through its device route (ganmf_evaluate_full +
+ganmf_evaluate_diversity per user block) and through its host route (score matrix to the host, metrics and the list pairs in numpy),
+alternating in one process after a warm-up of each, host wall time around calls that end in a stream synchronise, medians in one
+JSON line; beside them the same evaluator without a diversity_object on the device route and the library call
+ganmf_evaluate_diversity alone, for the cost of the extra call."""
 import argparse
 import json
 import os
@@ -118,10 +127,55 @@ def groups_bench(n_groups, cutoffs=(5, 10, 20), reps=15):
     eng.close()
 
 
+def diversity_bench(cutoffs=(5, 10, 20), reps=9):
+    nu, ni, k = 6040, 3706, 250
+    rng = np.random.RandomState(0)
+    train = sps.random(nu, ni, density=0.04, format="csr", dtype=np.float32, random_state=1)
+    test = sps.random(nu, ni, density=0.005, format="csr", dtype=np.float32, random_state=2)
+    test.data[:] = rng.randint(1, 6, size=test.nnz)
+    model = GANMF(train, mode="user", is_experiment=True)
+    model._build(k, 16, 32)
+    model.engine.set_tensor(100, rng.standard_normal((nu, k)).astype(np.float32))
+    model.engine.set_tensor(101, rng.standard_normal((ni, k)).astype(np.float32))
+    model.URM_train = model._URM_eval
+    D = rng.rand(ni, ni).astype(np.float32)
+    dev_ev = EvaluatorHoldoutFast(test, list(cutoffs), full_metrics=True, diversity_object=D)
+    host_ev = EvaluatorHoldoutFast(test, list(cutoffs), full_metrics=True, diversity_object=D)
+    host_ev.use_device_metrics = False
+    plain_ev = EvaluatorHoldoutFast(test, list(cutoffs), full_metrics=True)
+    calls = {"device": lambda: dev_ev.evaluateRecommender(model)[0], "host": lambda: host_ev.evaluateRecommender(model)[0],
+             "device_without_diversity": lambda: plain_ev.evaluateRecommender(model)[0]}
+    rows = {name: fn() for name, fn in list(calls.items())}          # warm-up: code objects, buffers, uploads, the split of V
+    for c in cutoffs:                                                # faster and different is not faster
+        a, b = rows["device"][c]["DIVERSITY_SIMILARITY"], rows["host"][c]["DIVERSITY_SIMILARITY"]
+        assert abs(a - b) <= 1e-12 * abs(b), (c, a, b)
+        assert rows["device"][c]["MAP"] == rows["device_without_diversity"][c]["MAP"]
+    # the library call alone, on the matrix the evaluator uploaded: ranking + list pairs + user sum, ending in a stream synchronise
+    calls["evaluate_diversity_call"] = lambda: model.engine.evaluate_diversity(dev_ev._users, cutoffs)
+    times = {name: [] for name in calls}
+    for rep in range(reps):
+        # the two device routes follow each other twice per repeat, taking turns to come first behind the (long) host route
+        pair = ["device", "device_without_diversity"][::1 if rep % 2 == 0 else -1]
+        for name in ["host"] + pair + pair + ["evaluate_diversity_call"] * 2:
+            t0 = time.perf_counter(); calls[name](); times[name].append(time.perf_counter() - t0)
+    med = {name: float(np.median(t)) * 1e3 for name, t in times.items()}
+    print(json.dumps({"shape": "ml1m", "users": int(len(dev_ev._users)), "items": ni, "k": k, "cutoffs": list(cutoffs), "reps": reps,
+                      "device_ms": round(med["device"], 3), "host_ms": round(med["host"], 3),
+                      "device_without_diversity_ms": round(med["device_without_diversity"], 3),
+                      "evaluate_diversity_call_ms": round(med["evaluate_diversity_call"], 3),
+                      "host_over_device": round(med["host"] / med["device"], 2),
+                      "min_max_ms": {name: [round(min(t) * 1e3, 3), round(max(t) * 1e3, 3)] for name, t in times.items()}}), flush=True)
+    model.engine.close()
+
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--candidates", type=int, default=0, help="N candidates per user (test items included): time the candidate route")
 ap.add_argument("--groups", type=int, default=0, help="G groups: time ganmf_evaluate_groups beside ganmf_evaluate (ML-1M shape)")
+ap.add_argument("--diversity", action="store_true", help="time the full row with a diversity_object: device route beside host route")
 args = ap.parse_args()
+if args.diversity:
+    diversity_bench()
+    sys.exit(0)
 if args.groups:
     groups_bench(args.groups)
     sys.exit(0)
