@@ -80,8 +80,21 @@ class DisGANMF(GANMF):
         return self._epoch_loop(epochs, d_steps, g_steps, allow_worse, freq, after, metrics, sample_every,
                                 validation_evaluator, validation_set)
 
-    def autoencoder_codes(self):
+    def autoencoder_codes(self, row_ids=None, generated=False):
         raise AttributeError("DisGANMF has no autoencoder")
+
+    def discriminator_energy(self, row_ids=None, generated=False):
+        raise AttributeError("DisGANMF has no autoencoder: see discriminator_logits")
+
+    def discriminator_logits(self, row_ids=None, generated=False, return_features=False):
+        """The logit D([uid | x]) of DisGANMF.py:57-65 for the stored profiles of the generator rows `row_ids` (training
+        orientation; None: every row) or, with generated=True, for their generated profiles U[row_ids] . V^T: float64 [n],
+        formed on the device (ganmf_discriminate).  return_features=True: (logits, the last hidden layer's output
+        [n, d_nodes] float32 -- what feature matching compares, DisGANMF.py:132-136)."""
+        self._require_engine()
+        feat, logit = self.engine.discriminate(self._discriminator_rows(row_ids), generated=generated,
+                                               features=bool(return_features), value=True)
+        return (logit, feat) if return_features else logit
 
     def saveModel(self, folder_path, file_name):
         """DisGANMF.py:264-266: the Saver bundle only (the reference writes no build_params here and has no

@@ -584,11 +584,34 @@ class GANMF(BaseRecommender):
     def ITEM_factors(self):
         return self.user_factors() if self.mode == 'item' else self.item_factors()
 
-    def autoencoder_codes(self):
-        """GANMF.py:304-307: encoding of every training row, URM_train . We + be (off the hot path:
-        one sparse product on the host from the fetched encoder)."""
+    # ---- the discriminator's view of a profile (ganmf_discriminate) --------------------------------
+    def _discriminator_rows(self, row_ids):
+        """generator rows in training orientation (item mode: catalogue items); None = all of them"""
+        if row_ids is None:
+            return np.arange(self.num_users, dtype=np.int32)
+        return np.atleast_1d(np.asarray(row_ids)).reshape(-1).astype(np.int32)
+
+    def autoencoder_codes(self, row_ids=None, generated=False):
+        """GANMF.py:304-307: the encoding E = x . We + be of every training row -- [num_users, emb_dim] float32, training
+        orientation -- or of the rows `row_ids`; with generated=True of their generated profiles U[row_ids] . V^T instead of
+        the stored ones.  Formed on the device (ganmf_discriminate: a CSR row-sum over the stored entries; the matrix is
+        never densified).  This method used to fetch the encoder and run a scipy product on the host: the route changed,
+        the signature of the no-argument call, its shape and its dtype did not."""
         self._require_engine()
-        return np.asarray(self._URM_fit.dot(self._get(0)) + self._get(1), dtype=np.float32)
+        return self.engine.discriminate(self._discriminator_rows(row_ids), generated=generated, features=True, value=False)[0]
+
+    def discriminator_energy(self, row_ids=None, generated=False):
+        """The EBGAN energy the discriminator assigns to each row, D(x) = mean_j (dec(enc(x)) - x)_j^2 -- the
+        tf.losses.mean_squared_error of GANMF.py:68 taken per row instead of per batch -- for the stored profiles of
+        `row_ids` (None: every training row) or, with generated=True, for their generated profiles.  float64 [n], formed on
+        the device; the reconstruction never leaves it."""
+        self._require_engine()
+        return self.engine.discriminate(self._discriminator_rows(row_ids), generated=generated, features=False, value=True)[1]
+
+    def discriminator_study(self, row_ids=None):
+        """ganmf_amd.studies.discriminator_study(self, ...): real against generated rows as the discriminator sees them"""
+        from .studies import discriminator_study
+        return discriminator_study(self, row_ids=row_ids)
 
     # ---- persistence (GANMF.py:309-342) -----------------------------------------------------------
     # Same files as the reference: build_params.pkl + the tf.train.Saver bundle <name>.index /

@@ -42,6 +42,7 @@
 #include "cand_topk.hpp"
 #include "list_diversity.hpp"
 #include "gram_stats.hpp"
+#include "disc_rows.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -69,5 +70,6 @@ extern "C" {
 #include "lib/abi_core.inc"
 #include "lib/abi_train.inc"
 #include "lib/abi_score.inc"
+#include "lib/abi_disc.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

@@ -174,7 +174,8 @@ struct Bf16sLds {      // floats of LDS one workgroup needs: the piece planes, o
 // (body = device function of (block index, blocks of this GEMM): one launch can carry more than one piece of work,
 // gemm_multi.hpp; `smem` is the launch's only LDS object, Bf16sLds<...>::DW floats)
 // GRAM: the symmetric product of gram_stats.hpp, as in gemm_f32_body
-template <int BM, int BN, int BK, bool AKM, bool BKM, int NPIECE, bool F16 = false, bool GRAM = false>
+// ROWSQ: the decode product of disc_rows.hpp -- the same K loop behind rowsq_epilogue (per-row sums of squared residuals, nothing stored)
+template <int BM, int BN, int BK, bool AKM, bool BKM, int NPIECE, bool F16 = false, bool GRAM = false, bool ROWSQ = false>
 __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, const int nblk, float* __restrict__ smem) {
   static_assert(!F16 || NPIECE == 1, "fp16 pieces only in the single-piece (mixed precision) mode");
   const float sa = (F16 && p.a_scale != 0.f) ? p.a_scale : 1.f, sb = (F16 && p.b_scale != 0.f) ? p.b_scale : 1.f;
@@ -337,6 +338,9 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
   if constexpr (GRAM) {
     static_assert(NPIECE == 3 && !F16 && !AKM && !BKM, "the symmetric product is an NT product in the exact three-way split");
     gram_epilogue<BM, BN, TM, TN>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
+  } else if constexpr (ROWSQ) {
+    static_assert(NPIECE == 3 && !F16, "the per-row residual sums are formed in the exact three-way split");
+    rowsq_epilogue<BM, BN, TM, TN>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
   } else
   gemm_epilogue<BM, BN, TM, TN, 1, AKM && BKM>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
 #ifdef GANMF_PERSIST_DIAG_BUILD

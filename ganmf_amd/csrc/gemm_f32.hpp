@@ -236,6 +236,7 @@ struct EpiD {
   unsigned short* planes;
   long long plane_stride;
   double* gram_partials;   // EPI_GRAM_STATS: [tiles of the upper triangle][2] = (sum d, sum d^2) of each tile's in-range elements
+                           // rowsq_epilogue (disc_rows.hpp): [M][tiles_n] = each row's sum of d^2 over a column tile's in-range elements
 };
 
 // X[batch row m, column col .. col + 3] of the CSR rows of the batch (EpiD::csr_*): lower bound on the sorted column indices
@@ -532,6 +533,9 @@ struct TileCoord { int tm, tn, sp, bz, m0, n0; };
 __device__ inline void gram_tile_coords(const GemmP& p, int bid, int nblk, int& tm, int& tn);
 template <int BM, int BN, int TM, int TN>
 __device__ inline void gram_epilogue(const GemmP& p, const f32x16 (&acc)[TM][TN], float* smem, const TileCoord& tc_);
+// per-row sums of squared residuals of the decode product (disc_rows.hpp; gemm_bf16s_body's ROWSQ instantiation)
+template <int BM, int BN, int TM, int TN>
+__device__ inline void rowsq_epilogue(const GemmP& p, const f32x16 (&acc)[TM][TN], float* smem, const TileCoord& tc_);
 
 // KG > 1: the workgroup has KG groups of four waves that each hold a partial sum of the SAME tile (they split the
 // chunks of every K-tile between them, gemm_f32_mfma); group g stages its accumulators at smem + g * BM * BN and the row

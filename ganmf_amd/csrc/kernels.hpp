@@ -121,6 +121,49 @@ __device__ __forceinline__ void densify_row_body(const DensP& d, const int bid) 
 
 __global__ __launch_bounds__(256) void densify_rows_kernel(const DensP d) { densify_row_body(d, (int)blockIdx.x); }
 
+// The CSR row-sum of one row, by one 256-thread workgroup:  Erow[0 .. e) = be + sum_{j in [s, en)} data[j] * We[indices[j], :]  with
+// be = row ncols of We_ext.  256 threads = G groups x `width` float4 columns; group g takes the stored entries j = s + g, s + g + G, ...
+// in CSR order and the G partial sums meet in LDS (`part`, 256 float4) in group order on top of the bias: deterministic, and an
+// empty row gives exactly be.  Never writes the ones column Erow[e].  Shared by the generator step's sparse front and by
+// csr_encode_rows_kernel (disc_rows.hpp).
+__device__ __forceinline__ void csr_rowsum_body(const int* __restrict__ indices, const float* __restrict__ data, const long long s,
+                                                const long long en, const float* __restrict__ We, const int lde, const int ncols,
+                                                const int e, float* __restrict__ Erow, float4* __restrict__ part) {
+  const int tid = threadIdx.x;
+  const int c4n = (e + 3) / 4;                       // float4 columns that hold encodings (We rows are zero-padded to lde)
+  const float* bias = We + (size_t)ncols * lde;      // encoder bias = row N of We_ext
+  for (int c0 = 0; c0 < c4n; c0 += 256) {
+    const int width = min(256, c4n - c0);
+    const int G = 256 / width, g = tid / width, c = c0 + tid % width;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g < G) {
+#pragma unroll 8
+      for (long long j = s + g; j < en; j += G) {      // (index, value and row fetches of eight entries in flight)
+        const float w = data[j];
+        const float4 a = *reinterpret_cast<const float4*>(We + (size_t)indices[j] * lde + 4 * c);
+        acc.x += w * a.x; acc.y += w * a.y; acc.z += w * a.z; acc.w += w * a.w;
+      }
+    }
+    part[tid] = acc;
+    __syncthreads();
+    if (tid < width) {
+      float4 t = *reinterpret_cast<const float4*>(bias + 4 * c);
+      for (int q = 0; q < G; ++q) {
+        const float4 a = part[q * width + tid];
+        t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
+      }
+      float* dst = Erow + 4 * c;     // never the ones column E[:, e]
+      if (4 * c + 3 < e) *reinterpret_cast<float4*>(dst) = t;
+      else {
+        dst[0] = t.x;
+        if (4 * c + 1 < e) dst[1] = t.y;
+        if (4 * c + 2 < e) dst[2] = t.z;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // SURVEY 8(f)-3, sparse-aware real path of the GENERATOR step.  In a G update the real rows X are needed for ONE thing:
 // their encodings Er = X.We + be in the feature-matching term (GANMF.py:134); nothing else reads X.  For a sparse
 // binary-ish URM that is a CSR row-sum, so the [B, N] densify of X and the real half of the encode GEMM both go away.
@@ -153,39 +196,7 @@ __global__ __launch_bounds__(256) void sparse_front_kernel(const long long* __re
     for (int c = tid; c < ldk / 4; c += 256) ud[c] = us[c];
   }
   if (tid == 0) XF[(size_t)(nb + b) * ldx + ncols] = 1.0f;
-  const long long s = indptr[r], en = indptr[r + 1];
-  const int c4n = (e + 3) / 4;                       // float4 columns that hold encodings (We rows are zero-padded to lde)
-  const float* bias = We + (size_t)ncols * lde;      // encoder bias = row N of We_ext
-  for (int c0 = 0; c0 < c4n; c0 += 256) {
-    const int width = min(256, c4n - c0);
-    const int G = 256 / width, g = tid / width, c = c0 + tid % width;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (g < G) {
-#pragma unroll 8
-      for (long long j = s + g; j < en; j += G) {      // (index, value and row fetches of eight entries in flight)
-        const float w = data[j];
-        const float4 a = *reinterpret_cast<const float4*>(We + (size_t)indices[j] * lde + 4 * c);
-        acc.x += w * a.x; acc.y += w * a.y; acc.z += w * a.z; acc.w += w * a.w;
-      }
-    }
-    part[tid] = acc;
-    __syncthreads();
-    if (tid < width) {
-      float4 t = *reinterpret_cast<const float4*>(bias + 4 * c);
-      for (int q = 0; q < G; ++q) {
-        const float4 a = part[q * width + tid];
-        t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-      }
-      float* dst = E + (size_t)b * lde + 4 * c;     // never the ones column E[:, e]
-      if (4 * c + 3 < e) *reinterpret_cast<float4*>(dst) = t;
-      else {
-        dst[0] = t.x;
-        if (4 * c + 1 < e) dst[1] = t.y;
-        if (4 * c + 2 < e) dst[2] = t.z;
-      }
-    }
-    __syncthreads();
-  }
+  csr_rowsum_body(indices, data, indptr[r], indptr[r + 1], We, lde, ncols, e, E + (size_t)b * lde, part);
 }
 
 // SURVEY 8(f)-3, sparse-aware real path of the DISCRIMINATOR step: the real rows' share of the encoder gradient,

@@ -272,6 +272,7 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->colbuf); hipFree(h->parts_all); hipFree(h->sc_rows); hipFree(h->sc_out); hipFree(h->sc_pa); hipFree(h->sc_pb);
   hipFree(h->sim_mat); hipFree(h->sim_pool); hipFree(h->sim_part); hipFree(h->sim_zero);
   hipFree(h->rank_mask); hipFree(h->div_mat);
+  hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   if (h->st2) hipStreamSynchronize(h->st2);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);

@@ -206,6 +206,14 @@ struct ganmf_handle {
   double* sim_part = nullptr;
   int* sim_zero = nullptr;
   size_t sim_mat_cap = 0, sim_pool_cap = 0, sim_part_cap = 0, sim_zero_cap = 0;
+  // ganmf_discriminate (disc_rows.hpp): block buffers of its own, grown on demand -- the ids, the input block [blk, ldN] (generated rows,
+  // or DisGANMF's expanded rows), the gathered embeddings [blk, ldk], the codes / layer outputs [blk, lde] (two: the layers alternate), the
+  // per-(row, column tile) partials and the values.  The step's buffers, the staged-pass state and the beta powers are never touched.
+  int* dr_ids = nullptr;
+  float *dr_X = nullptr, *dr_Ub = nullptr, *dr_E = nullptr, *dr_A = nullptr;
+  double *dr_part = nullptr, *dr_val = nullptr;
+  size_t dr_ids_cap = 0, dr_X_cap = 0, dr_Ub_cap = 0, dr_E_cap = 0, dr_A_cap = 0, dr_part_cap = 0, dr_val_cap = 0;
+  int64_t disc_block = 0;                           // ganmf_set_discriminate_block: rows per block of the call's loop (0: a quarter of the free memory)
   int gram_arith = 1;                               // GANMF_TUNE gram: 1 (default, the faster one measured) the exact three-way bf16 split, 0 the plain fp32 MFMA body
   bool score_presplit = true;                       // GANMF_SCORE_PRESPLIT: many-tile scoring products on the pre-split persistent kernel
   // RCCL

@@ -345,7 +345,8 @@ class ShardedEngine(object):
         urm = urm_csr.tocsr()
         if urm.shape != (self.num_users, self.num_items):
             raise ValueError("ShardedEngine.set_urm: shape %r" % (urm.shape,))
-        # (the master never trains: it gets no copy of the matrix)
+        # (the master never trains: it gets its copy of the matrix only when discriminate() first needs the stored rows)
+        self._urm, self._master_has_urm = urm, False
         self._each("set_urm", [(urm[lo:hi],) for lo, hi in self.bounds])
 
     def shape(self, tid):
@@ -470,6 +471,14 @@ class ShardedEngine(object):
     def score_similarity(self, ids, transposed=False, pool=None, return_matrix=False):
         self._sync_master()
         return self.master.score_similarity(ids, transposed, pool, return_matrix)
+
+    def discriminate(self, rows, generated=False, features=True, value=True, block=None):
+        """Engine.discriminate on the master (global row ids); the training matrix goes to the master on first use"""
+        self._sync_master()
+        if not generated and not getattr(self, "_master_has_urm", False) and getattr(self, "_urm", None) is not None:
+            self.master.set_urm(self._urm)
+            self._master_has_urm = True
+        return self.master.discriminate(rows, generated, features, value, block)
 
     def snapshot_best(self):
         self._sync_master()

@@ -344,6 +344,27 @@ class Engine:
             out["matrix"] = matrix
         return out
 
+    def discriminate(self, rows, generated=False, features=True, value=True, block=None):
+        """The discriminator's view of the generator rows `rows` (training orientation), formed on the device (ganmf_discriminate):
+        of their stored profiles, or with generated=True of the unfiltered generated ones U[rows] . V^T.  Returns (features, value),
+        None for the one not asked for.  GANMF: the codes E [n, emb_dim] float32 and the per-row energies mean_j (dec(E) - x)_j^2 [n]
+        float64; DisGANMF: the last hidden layer's output [n, d_nodes] and the logits [n].  block: rows per block of the call's loop
+        (None: what a quarter of the free device memory holds)."""
+        ids = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+        if not (features or value):
+            raise ValueError("discriminate: neither features nor value asked for")
+        feat = np.empty((ids.size, int(self.cfg.emb_dim)), dtype=np.float32) if features else None
+        val = np.empty(ids.size, dtype=np.float64) if value else None
+        L.check(self.lib.ganmf_set_discriminate_block(self.h, 0 if block is None else int(block)), "ganmf_set_discriminate_block")
+        try:
+            L.check(self.lib.ganmf_discriminate(self.h, _i32p(ids), ids.size, int(bool(generated)),
+                                                _f32p(feat) if feat is not None else None,
+                                                _f64p(val) if val is not None else None), "ganmf_discriminate")
+        finally:
+            if block is not None:
+                self.lib.ganmf_set_discriminate_block(self.h, 0)
+        return feat, val
+
     def snapshot_best(self):
         L.check(self.lib.ganmf_snapshot_best(self.h), "ganmf_snapshot_best")
 

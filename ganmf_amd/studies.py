@@ -75,3 +75,38 @@ def activity_study(model, URM_test, bounds, cutoff=20, metric="MAP"):
         means = np.where(sizes > 0, sums / np.maximum(sizes, 1), np.nan)
     return dict(keys=keys, plotted=plotted, means=means, n_users=sizes, bucket=bucket, per_user=per_user,
                 skipped=int(test.shape[0] - len(ev._users)), cutoff=cutoff, metric=metric)
+
+
+def discriminator_summary(real, generated, m=None, logits=False):
+    """The host arithmetic of discriminator_study on two per-row vectors (float64).
+    logits=False (GANMF, energies): energy_real / energy_generated, their means, and with the hinge multiplier `m` the term the
+    discriminator loss adds to the real rows' error, hinge = m * mean_real - mean_generated (GANMF.py:69-70, F12 of SURVEY.md), and
+    hinge_active = hinge > 0; both None when `m` is None.
+    logits=True (DisGANMF): p_real / p_generated = sigmoid(logit), their means, and accuracy = (share of real logits > 0 + share
+    of generated logits < 0) / 2."""
+    real = np.asarray(real, dtype=np.float64).reshape(-1)
+    generated = np.asarray(generated, dtype=np.float64).reshape(-1)
+    mean = lambda v: float(v.mean()) if v.size else float("nan")
+    if logits:
+        p_real, p_gen = 1.0 / (1.0 + np.exp(-real)), 1.0 / (1.0 + np.exp(-generated))
+        acc = 0.5 * (mean((real > 0).astype(np.float64)) + mean((generated < 0).astype(np.float64)))
+        return dict(p_real=p_real, p_generated=p_gen, mean_p_real=mean(p_real), mean_p_generated=mean(p_gen), accuracy=acc)
+    out = dict(energy_real=real, energy_generated=generated, mean_real=mean(real), mean_generated=mean(generated),
+               hinge=None, hinge_active=None)
+    if m is not None:
+        out["hinge"] = float(m) * out["mean_real"] - out["mean_generated"]
+        out["hinge_active"] = bool(out["hinge"] > 0)
+    return out
+
+
+def discriminator_study(model, row_ids=None):
+    """Real against generated rows as the fitted discriminator sees them, for the generator rows `row_ids` (training orientation;
+    None: all).  The per-row vectors come from the device (ganmf_discriminate); this function only averages them, see
+    discriminator_summary.  GANMF: the EBGAN energies and the hinge m * mean_real - mean_generated, with m from model.config (a
+    model restored by loadModel has no config: hinge and hinge_active are None).  DisGANMF: sigmoid(logit) and the accuracy."""
+    model._require_engine()
+    if hasattr(model, "discriminator_logits"):
+        return discriminator_summary(model.discriminator_logits(row_ids), model.discriminator_logits(row_ids, generated=True),
+                                     logits=True)
+    m = model.config.get("m") if isinstance(getattr(model, "config", None), dict) else None
+    return discriminator_summary(model.discriminator_energy(row_ids), model.discriminator_energy(row_ids, generated=True), m=m)

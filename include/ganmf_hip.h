@@ -376,6 +376,27 @@ int ganmf_evaluate_diversity(ganmf_handle* h, const int32_t* ids, int64_t n, int
 int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, int32_t pool, double sums[4], float* pooled,
                            float* matrix);
 
+/* Discriminator inference on the device: the discriminator's view of a profile, for stored rows and for generated ones.  Replaces the
+ * reference's autoencoder_codes() (GANMF.py:304-307: encoding of the whole densified training matrix) and exposes, per row, the two
+ * terms its discriminator losses average over a batch (GANMF.py:62-70; DisGANMF.py:57-65).
+ * `rows` are generator rows in training orientation (in item mode: catalogue items): they index the matrix of ganmf_set_urm_csr and
+ * the rows of user_embeddings.  generated = 0: the input x is the stored CSR row (never densified on the host; GANMF reads it as CSR
+ * on the device as well).  generated = 1: x = U[rows] . V^T, unfiltered -- neither the score filter nor the ignore list applies.
+ *   GANMF:     features [n, emb_dim] = E = x . We + be;   value [n] = the EBGAN energy D(x) = sum_j (dec(E)_j - x_j)^2 / num_items
+ *              (tf.losses.mean_squared_error of GANMF.py:68 taken per row).  The reconstruction is never stored.
+ *   DisGANMF:  features [n, d_nodes] = the output of the last hidden layer (what feature matching compares, DisGANMF.py:132-136);
+ *              value [n] = the logit.  The float(uid) input is row_offset + rows[i].
+ * Either output may be NULL (not computed where that saves work), not both.  n = 0 returns 0 and writes nothing.
+ * Every product runs in the fp32-accurate arithmetic (exact three-way bf16 split or fp32 MFMA), also on a handle created with
+ * GANMF_FLAG_MFMA_BF16 / _F16: a diagnostic does not carry the training mode's rounding.  Sums run in a fixed order without
+ * floating-point atomics: the same bytes on every call and handle.  The rows are processed in blocks whose buffers -- the call's own --
+ * stay under a quarter of the free device memory; ganmf_set_discriminate_block caps the rows per block (0: that rule alone).
+ * Parameters, Adam moments, the beta powers and every per-pass state of training are not modified.
+ * Errors (-1, message in ganmf_last_error, nothing enqueued, the handle usable as before): a row outside [0, num_users), stored rows
+ * asked for before ganmf_set_urm_csr, both outputs NULL, n < 0. */
+int ganmf_set_discriminate_block(ganmf_handle* h, int64_t rows);
+int ganmf_discriminate(ganmf_handle* h, const int32_t* rows, int64_t n, int generated, float* features, double* value);
+
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch);
