@@ -40,6 +40,8 @@
 #include <cmath>
 #include <type_traits>
 
+#include "adam_touch.hpp"
+
 namespace ganmf {
 
 // Every kernel of the library is launched through GANMF_LAUNCH.  While a profiling scope is armed (ganmf_profile_enable:
@@ -366,9 +368,45 @@ struct GemmP {
   int n_fastest;                // list order with the tile COLUMN fastest (default: tile row fastest).  For the fused-Adam weight-gradient
                                 // products: workgroups that run at the same time then update neighbouring 256-byte segments of the same
                                 // parameter rows, i.e. whole DRAM pages of theta / m / v instead of one segment per 4-15 KiB row
+  int adam_touch;               // EPI_ADAM, unsplit, fp32 ring kernel: the workgroup loads one dword of every 128-byte line of its tile's theta / m / v in
+                                // front of the K loop (adam_touch_issue below; set by adam_touch_for, lib/gemm_run.inc)
 };
 
 #define GANMF_WAIT_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
+
+// Early touch of the Adam streams (gemm_f32_body; GemmP::adam_touch).  Behind its K loop a fused-Adam product waits for theta / m / v of
+// its tile, which nothing has asked for until then.  With the touch every thread requests, in FRONT of its operand loads, one dword of one
+// of the tile's 128-byte lines of the three arrays (adam_touch.hpp: each line once, only where the row pass reads), so the lines travel
+// to the XCD's L2 under the K loop and the row pass finds them there.  The values are never used: they stay in NR registers that
+// adam_touch_keep names once behind the K loop (an empty statement that takes them as operands, so the compiler keeps the loads;
+// vector-memory loads return in order and the loop has drained its own by then).  No arithmetic changes: results are bit-identical with
+// and without.  It pays only while the touched lines survive in the 8 x 4 MiB of L2 until the row pass: gV + Adam(V) of the generator
+// step (11 MB of state at ML-1M) gets 0.5 us shorter; on gWd_ext + gWe_ext (88 MB of state, 74 MB touched by the resident workgroups) every
+// touched line was fetched a second time and the launch got 10 us longer (profiles/r09_wgrad_touch.md) -- the host sets the flag by size.
+template <int BM, int BN, int NTHR>
+struct AdamTouchRegs {
+  static constexpr int NR = (adam_touch_slots(BM, BN) + NTHR - 1) / NTHR;
+  float v[NR];
+};
+
+template <int BM, int BN, int NTHR>
+__device__ __forceinline__ void adam_touch_issue(const GemmP& p, int m0, int n0, int tid, AdamTouchRegs<BM, BN, NTHR>& k) {
+#pragma unroll
+  for (int j = 0; j < AdamTouchRegs<BM, BN, NTHR>::NR; ++j) {
+    k.v[j] = 0.f;
+    const AdamTouch t = adam_touch_slot(BM, BN, j * NTHR + tid, m0, n0, p.M, p.N, p.ldc);
+    if (t.arr >= 0) {
+      const float* __restrict__ b = t.arr == 0 ? p.epi.adam_theta : t.arr == 1 ? p.epi.adam_m : p.epi.adam_v;
+      k.v[j] = b[t.off];
+    }
+  }
+}
+
+template <int BM, int BN, int NTHR>
+__device__ __forceinline__ void adam_touch_keep(const AdamTouchRegs<BM, BN, NTHR>& k) {
+#pragma unroll
+  for (int j = 0; j < AdamTouchRegs<BM, BN, NTHR>::NR; ++j) asm volatile("" ::"v"(k.v[j]));
+}
 
 // One operand's share of a K-tile: R rows (M or N side) x BK k's, staged by NTHR threads.
 template <int R, int BK, bool KM, int NTHR = 256>
@@ -478,47 +516,10 @@ struct Stage {
   }
 };
 
-__device__ inline int xcd_remap(int bid, int nwg) {
-  // blocks b and b+8 share an XCD (observed round-robin dispatch; speed only, never correctness)
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-__host__ __device__ inline int part_begin(int n, int parts, int i) { return (int)(((long long)n * i) / parts); }
-
-// block id -> (tile row, tile column, K split, batch).  Default: list order, tm fastest, each XCD a contiguous range of the
-// list.  GemmP::xb_m > 0: the list is re-ordered rectangle by rectangle (rectangle r = (r % xb_m, r / xb_m) of the tile grid),
-// inside a rectangle band by band, inside a band M-innermost; XCD x still takes a contiguous range of the list, i.e. its own
-// rectangle up to a few tiles of drift where the rectangles' sizes differ.  Bijective for every shape.
+// block id -> (tile row, tile column, K split, batch): adam_touch.hpp, tile_order (xcd_remap and part_begin live there too -- plain C++
+// that a host program shares).  GemmP::xb_m > 0: the XCD-blocked order; GemmP::n_fastest: list order with the tile column fastest.
 __device__ inline void tile_coords(const GemmP& p, int bid, int nblk, int& tm, int& tn, int& sp, int& bz) {
-  int t = xcd_remap(bid, nblk);
-  if (p.xb_m > 0) {
-    sp = 0; bz = 0;
-    int mb0 = 0, nb0 = 0, bm = 1, bn = 1;
-    for (int r = 0; r < 8; ++r) {
-      const int i = r % p.xb_m, j = r / p.xb_m;
-      mb0 = part_begin(p.tiles_m, p.xb_m, i); bm = part_begin(p.tiles_m, p.xb_m, i + 1) - mb0;
-      nb0 = part_begin(p.tiles_n, p.xb_n, j); bn = part_begin(p.tiles_n, p.xb_n, j + 1) - nb0;
-      if (t < bm * bn) break;
-      t -= bm * bn;
-    }
-    const int bh = min(max(p.xb_band, 1), bm);     // band height in tiles
-    const int band = t / (bh * bn);
-    const int r = t - band * bh * bn;
-    const int h = min(bh, bm - band * bh);          // the last band of a rectangle may be shorter
-    tm = mb0 + band * bh + r % h;
-    tn = nb0 + r / h;
-    return;
-  }
-  if (p.n_fastest) {
-    tn = t % p.tiles_n; t /= p.tiles_n;
-    tm = t % p.tiles_m; t /= p.tiles_m;
-  } else {
-    tm = t % p.tiles_m; t /= p.tiles_m;
-    tn = t % p.tiles_n; t /= p.tiles_n;
-  }
-  sp = t % p.nsplit;
-  bz = t / p.nsplit;
+  tile_order(TileGrid{p.tiles_m, p.tiles_n, p.nsplit, p.xb_m, p.xb_n, p.xb_band, p.n_fastest}, bid, nblk, tm, tn, sp, bz);
 }
 
 #ifndef GANMF_ADAM_HOIST
@@ -894,6 +895,14 @@ __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, con
   // makes every lane of every workgroup read the same zero-page line: an L2 hot spot that cost
   // 20-40 us on the short-K GEMMs); the tail therefore waits with vmcnt(0) instead of the counted wait.
   int kleft = kend - kbeg;   // k's remaining from the next tile to issue
+  // the touch of the Adam streams (TN products: the instantiations with the fused row pass) goes in FRONT of the operand loads: the counted
+  // vmcnt waits below assume that every load YOUNGER than a K-tile's pieces is a piece of a later K-tile
+  constexpr bool TOUCH_OK = AKM && BKM && !GRAM;
+  AdamTouchRegs<BM, BN, NTHR> touched{};
+  const bool touch = TOUCH_OK && p.adam_touch && p.nsplit == 1 && p.epi.kind == EPI_ADAM;
+  if constexpr (TOUCH_OK) {
+    if (touch) adam_touch_issue<BM, BN, NTHR>(p, m0, n0, tid, touched);
+  }
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     if (kleft > 0) {
@@ -969,6 +978,9 @@ __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, con
   GANMF_WAIT_VMCNT(0);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
+  if constexpr (TOUCH_OK) {
+    if (touch) adam_touch_keep<BM, BN, NTHR>(touched);
+  }
 
   GANMF_GEMM_STAMP(2);
   static_assert(KG * BM * BN <= NS * BUF, "the ring must hold the KG staged partial tiles");

@@ -105,6 +105,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   h->g_rows_staged = std::max(0, std::min(2, tune_env_int("g_rows_staged", 1)));
   h->pair_kg = tune_env_int("pair_kg", 4) == 1 ? 1 : 4;
   h->wgrad_seam = tune_env_int("wgrad_seam", 0);
+  h->adam_touch = tune_env_int("adam_touch", 1) != 0 ? 1 : 0;
   h->gram_arith = tune_env_int("gram", 1) == 0 ? 0 : 1;
   HIP_TRY(hipMalloc((void**)&h->seam_cnt, 2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(h->seam_cnt, 0, 2 * sizeof(unsigned long long)));

@@ -171,6 +171,11 @@ int run_gemm(ganmf_handle* h, int tag_gemm, int tag_red, GemmP g, bool akm, bool
   return 0;
 }
 
+// Early touch of the Adam streams of a fused-Adam product with an [M, ld] parameter (GemmP::adam_touch): only while the three arrays fit half of the
+// chip's 8 x 4 MiB of L2 -- the touched lines must still be there when the row pass asks for them, and the operands stream through the same caches.
+// Measured: 11 MB (V at ML-1M) pays, 88 MB (Wd + We) costs 10 us of a 44 us launch (profiles/r09_wgrad_touch.md); nothing in between has been run.
+inline int adam_touch_for(const ganmf_handle* h, long long M, long long ld) { return h->adam_touch && 12 * M * ld <= (16ll << 20) ? 1 : 0; }
+
 // the combined launches (front_kernel, de_dcoef_kernel) carry the 16-wave split-bf16 loop where the stand-alone product would run it:
 // GANMF_X3KG bit 0, and only when the handle leaves the arithmetic to the planner (a forced fp32-MFMA handle keeps the fp32 MFMA)
 inline bool combined_x3(const ganmf_handle* h) { return (h->x3kg & 1) != 0 && h->tune.mode == MFMA_AUTO; }

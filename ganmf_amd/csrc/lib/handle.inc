@@ -241,6 +241,7 @@ struct ganmf_handle {
   int adam_nfast = 3;                  // GANMF_ADAM_NFAST: tile order of the fused-Adam weight-gradient launch (GemmP::n_fastest)
   int wgrad_xb = 16;                   // GANMF_TUNE wgrad_xb: gWd of the paired launch in XCD-blocked tile order, bands of this many tile rows (0: list order)
   int wgrad_seam = 0;                  // GANMF_TUNE wgrad_seam: the slab sum of dE as the first block range of the fused weight-gradient launch (wgrad_seam_kernel)
+  int adam_touch = 1;                  // GANMF_TUNE adam_touch: gV + Adam(V) touches its tile's theta / m / v lines in front of the K loop (GemmP::adam_touch, adam_touch_for)
   unsigned long long* seam_cnt = nullptr;      // [2] device words: arrivals of the reduce blocks (monotonic over the handle's life), timeout flag
   unsigned long long seam_target = 0;          // arrivals every launch so far has added up to
   int pair_kg = 4;                     // GANMF_TUNE pair_kg: K groups of the gUb + gV pair launch (4: the 16-wave form, two per CU now that its SGPRs are capped at 80; 1: 4-wave workgroups)

@@ -848,6 +848,7 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
       g.epi.kind = EPI_ADAM; g.epi.adam_theta = h->V.p; g.epi.adam_m = h->V.m; g.epi.adam_v = h->V.v;
       g.epi.adam_alpha = h->scal + h->g_alpha; g.epi.adam_reg = h->cfg.g_reg;
       g.epi.sq_partials = reg ? reg_v : nullptr;
+      g.adam_touch = adam_touch_for(h, g.M, g.ldc);
     }
     GemmTune ft;
     ft.tile = 64; ft.ring = 2; ft.nsplit = 1;
@@ -909,6 +910,7 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
       fill_plan(g0, p0);
       fill_plan(g1, p1);
       if (fused && (h->adam_nfast & 2)) g1.n_fastest = 1;
+      if (fused) g1.adam_touch = adam_touch_for(h, g1.M, g1.ldc);
       if (fused) *regn_v = p1.sq_count;
       const int n0 = p0.tiles_m * p0.tiles_n * p0.nsplit, n1 = p1.tiles_m * p1.tiles_n;
       {
