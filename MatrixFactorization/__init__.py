@@ -1,0 +1,9 @@
+"""Drop-in package name for the matrix-factorisation recommender this repository implements.
+
+The reference's drivers import `MatrixFactorization.IALSRecommender.IALSRecommender` next to other modules of the same package
+(`MatrixFactorization.PureSVDRecommender`, the Cython models; RecSysExp.py, RunBestParameters.py), which live only in the reference
+tree.  As `GANRec/` does, this package therefore extends its search path with every other `MatrixFactorization/` directory on
+`sys.path`: `MatrixFactorization.IALSRecommender` resolves here (first entry), every other submodule in the reference's directory."""
+import pkgutil
+
+__path__ = pkgutil.extend_path(__path__, __name__)

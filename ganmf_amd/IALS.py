@@ -1,0 +1,199 @@
+"""IALSRecommender -- implicit-feedback ALS (WRMF), host mirror of the reference class
+(MatrixFactorization/IALSRecommender.py:15-210; "ALS" / "WRMF" in the learned-MF studies of MFLearned.py).
+
+Same constructor, fit() keyword arguments, early-stopping attributes and saved-model layout as the reference, so it can stand in for
+`MatrixFactorization.IALSRecommender.IALSRecommender` under RecSysExp.py / RunBestParameters.py.  Every factor is computed by
+libganmf_hip.so: one epoch is two calls of ganmf_als_half_sweep (a Gram product and one Cholesky solve per warm row, HIP kernels on
+gfx950) on a GANMF_MODEL_MF handle; scoring, recommendation and evaluation are the device routes of DeviceScoringMixin under the MF
+contract (Base/BaseMatrixFactorizationRecommender.py:94-143).  This file holds the confidence scaling, the initial factors, the epoch
+loop with its early stopping, and persistence."""
+import io
+import json
+import os
+import zipfile
+
+import numpy as np
+import scipy.sparse as sps
+
+from . import _lib as L
+from .base import BaseRecommender
+from .device_scoring import DeviceScoringMixin
+from .engine import Engine
+
+
+class IALSRecommender(DeviceScoringMixin, BaseRecommender):
+    RECOMMENDER_NAME = "IALSRecommender"
+
+    AVAILABLE_CONFIDENCE_SCALING = ["linear", "log"]
+    MAX_FACTORS = L.ALS_MAX_FACTORS
+
+    # what the device-scoring surface reads: users are rows, and the MF contract always holds (IALSRecommender derives from
+    # BaseMatrixFactorizationRecommender in the reference)
+    mode = "user"
+    score_contract = "mf"
+
+    def __init__(self, URM_train, device=0, verbose=False):
+        super(IALSRecommender, self).__init__(URM_train)
+        self._URM_eval = self.URM_train
+        self.device = device
+        self.verbose = verbose
+        self.use_bias = False
+        self.engine = None
+        self.num_factors = None
+        self.epochs_best = 0
+        self.best_validation_metric = None
+
+    # ---- engine plumbing -----------------------------------------------------------------------
+    def _make_engine(self, num_factors):
+        """a factors-only handle (GANMF_MODEL_MF); emb_dim and batch_size mean nothing to it"""
+        return Engine(self.n_users, self.n_items, num_factors, 1, 1, model=L.MODEL_MF, device=self.device)
+
+    def _build(self, num_factors):
+        if not 1 <= int(num_factors) <= self.MAX_FACTORS:
+            raise ValueError("{}: num_factors must be in [1, {}] (a row's system has to fit the LDS of a compute unit), provided was "
+                             "{}".format(self.RECOMMENDER_NAME, self.MAX_FACTORS, num_factors))
+        self.num_factors = int(num_factors)
+        if self.engine is not None:
+            self.engine.close()
+        self.engine = self._make_engine(self.num_factors)
+        self.engine.set_seen(self._URM_eval)
+        self._reset_score_filter()
+
+    def _require_engine(self):
+        if self.engine is None:
+            raise RuntimeError("{}: model has no device state; call fit() or loadModel() first".format(self.RECOMMENDER_NAME))
+
+    # ---- fit (IALSRecommender.py:40-126) -----------------------------------------------------------
+    def _confidence(self, confidence_scaling, alpha, epsilon):
+        """C in float32 on the host: 1 + alpha r, or 1 + alpha log(1 + r / epsilon), at the stored entries of URM_train"""
+        C = sps.csr_matrix(self.URM_train, dtype=np.float32, copy=True)
+        if confidence_scaling == "linear":
+            C.data = (1.0 + alpha * C.data).astype(np.float32)
+        else:
+            C.data = (1.0 + alpha * np.log(1.0 + C.data / epsilon)).astype(np.float32)
+        return C
+
+    def fit(self, epochs=300, num_factors=20, confidence_scaling="linear", alpha=1.0, epsilon=1.0, reg=1e-3, init_mean=0.0,
+            init_std=0.1, **earlystopping_kwargs):
+        """The reference's fit().  init_mean / init_std are accepted and, as in the reference, not used: ITEM factors start as
+        num_factors**-0.5 * random_sample on numpy's global stream, USER factors as zeros (the reference leaves them
+        uninitialised; users without an interaction are never solved for and stay zero here)."""
+        if confidence_scaling not in self.AVAILABLE_CONFIDENCE_SCALING:
+            raise ValueError("Value for 'confidence_scaling' not recognized. Acceptable values are {}, provided was '{}'".format(
+                self.AVAILABLE_CONFIDENCE_SCALING, confidence_scaling))
+        self._build(num_factors)
+        self.alpha, self.epsilon, self.reg = alpha, epsilon, reg
+        C = self._confidence(confidence_scaling, alpha, epsilon)
+        C_csc = C.tocsc()
+        self.engine.set_confidence(0, C)
+        self.engine.set_confidence(1, sps.csr_matrix((C_csc.data, C_csc.indices, C_csc.indptr), shape=(self.n_items, self.n_users)))
+        self.engine.set_tensor(L.T_USER_EMB, np.zeros((self.n_users, self.num_factors), dtype=np.float32))
+        self.engine.set_tensor(L.T_ITEM_EMB, self.num_factors ** -0.5 * np.random.random_sample((self.n_items, self.num_factors)))
+        self._update_best_model()
+        self._train_with_early_stopping(epochs, **earlystopping_kwargs)
+        self.engine.restore_best()      # USER_factors = USER_factors_best, ITEM_factors = ITEM_factors_best
+
+    def _run_epoch(self, num_epoch):
+        self.engine.als_half_sweep(0, self.reg)      # users from items
+        self.engine.als_half_sweep(1, self.reg)      # items from the new users
+
+    def _update_best_model(self):
+        """the best factors stay on the device, in the handle's `best` slots"""
+        self.engine.snapshot_best()
+
+    def _train_with_early_stopping(self, epochs_max, epochs_min=0, validation_every_n=None, stop_on_validation=False,
+                                   validation_metric=None, lower_validations_allowed=None, evaluator_object=None):
+        """The training loop of Base/Incremental_Training_Early_Stopping.py:93-259.  Three uses: no evaluator (all epochs, the
+        last model is the best one); an evaluator with validation_every_n and validation_metric (all epochs, the model of the best
+        validation is kept); and with stop_on_validation and lower_validations_allowed as well (stops once that many validations
+        in a row did not improve, not before epoch index epochs_min).  Maintains epochs_best and best_validation_metric."""
+        if not epochs_max > 0:
+            raise ValueError("{}: Number of epochs_max must be > 0, passed was {}".format(self.RECOMMENDER_NAME, epochs_max))
+        if not 0 <= epochs_min <= epochs_max:
+            raise ValueError("{}: epochs_min must be in [0, epochs_max], passed are epochs_min {}, epochs_max {}".format(
+                self.RECOMMENDER_NAME, epochs_min, epochs_max))
+        validating = evaluator_object is not None
+        if validating and (validation_every_n is None or validation_metric is None
+                           or (stop_on_validation and lower_validations_allowed is None)):
+            raise ValueError("{}: Inconsistent parameters passed, please check the supported uses".format(self.RECOMMENDER_NAME))
+        self.best_validation_metric = None
+        self.epochs_best = 0
+        worse_in_a_row = 0
+        for epoch in range(epochs_max):
+            self._run_epoch(epoch)
+            if not validating:
+                self.epochs_best = epoch      # (the reference's count without validation: the index of the last epoch)
+                continue
+            if (epoch + 1) % validation_every_n != 0:
+                continue
+            results, _ = evaluator_object.evaluateRecommender(self)
+            value = results[list(results.keys())[0]][validation_metric]      # several cut-offs: the first one
+            if self.best_validation_metric is None or self.best_validation_metric < value:
+                self.best_validation_metric = value
+                self._update_best_model()
+                self.epochs_best = epoch + 1
+                worse_in_a_row = 0
+            else:
+                worse_in_a_row += 1
+            if stop_on_validation and worse_in_a_row >= lower_validations_allowed and epoch >= epochs_min:
+                if self.verbose:
+                    print("{}: Convergence reached! Terminating at epoch {}. Best value for '{}' at epoch {} is {:.4f}".format(
+                        self.RECOMMENDER_NAME, epoch + 1, validation_metric, self.epochs_best, self.best_validation_metric))
+                break
+        if not validating:
+            self._update_best_model()
+
+    def get_early_stopping_final_epochs_dict(self):
+        return {"epochs": self.epochs_best}
+
+    # ---- factors (Base/BaseMatrixFactorizationRecommender.py:94-143) -----------------------------
+    @property
+    def USER_factors(self):
+        self._require_engine()
+        return self.engine.get_tensor(L.T_USER_EMB)
+
+    @property
+    def ITEM_factors(self):
+        self._require_engine()
+        return self.engine.get_tensor(L.T_ITEM_EMB)
+
+    # ---- persistence: the layout the reference's DataIO writes (Base/DataIO.py:103-183) ----------
+    def _zip_path(self, folder_path, file_name):
+        return os.path.join(folder_path, (self.RECOMMENDER_NAME if file_name is None else file_name) + ".zip")
+
+    def saveModel(self, folder_path, file_name=None):
+        self._require_engine()
+        os.makedirs(folder_path, exist_ok=True)
+        arrays = {"USER_factors": self.USER_factors, "ITEM_factors": self.ITEM_factors,
+                  "_cold_user_mask": np.ediff1d(self._URM_eval.indptr) == 0}
+        jsons = {"use_bias": self.use_bias}
+        kinds = dict([(n, "np.ndarray") for n in arrays] + [(n, "json") for n in jsons])
+        files = dict([(n, n + ".npy") for n in arrays] + [(n, n + ".json") for n in jsons])
+        jsons["__DataIO_attribute_to_type_dict"] = kinds
+        jsons["__DataIO_attribute_to_file_name"] = files
+        with zipfile.ZipFile(self._zip_path(folder_path, file_name), "w", compression=zipfile.ZIP_DEFLATED) as z:
+            for name, a in arrays.items():
+                buf = io.BytesIO()
+                np.save(buf, a, allow_pickle=False)
+                z.writestr(name + ".npy", buf.getvalue())
+            for name, obj in jsons.items():
+                z.writestr(name + ".json", json.dumps(obj))
+
+    def loadModel(self, folder_path, file_name=None):
+        with zipfile.ZipFile(self._zip_path(folder_path, file_name)) as z:
+            kinds = json.loads(z.read("__DataIO_attribute_to_type_dict.json").decode())
+            files = json.loads(z.read("__DataIO_attribute_to_file_name.json").decode())
+            data = {}
+            for name, member in files.items():
+                raw = z.read(member)
+                data[name] = np.load(io.BytesIO(raw), allow_pickle=False) if kinds[name] == "np.ndarray" else json.loads(raw.decode())
+        if data.get("use_bias"):
+            raise ValueError("{}: a saved model with biases is not supported".format(self.RECOMMENDER_NAME))
+        U, V = np.asarray(data["USER_factors"]), np.asarray(data["ITEM_factors"])
+        if U.shape[0] != self.n_users or V.shape[0] != self.n_items or U.shape[1] != V.shape[1]:
+            raise ValueError("{}: saved factors are {} and {}, URM_train is {} x {}".format(
+                self.RECOMMENDER_NAME, U.shape, V.shape, self.n_users, self.n_items))
+        self._build(U.shape[1])
+        self.engine.set_tensor(L.T_USER_EMB, U)
+        self.engine.set_tensor(L.T_ITEM_EMB, V)
+        self._update_best_model()

@@ -6,7 +6,7 @@ fallback: without the HIP library and a GPU the classes raise.
 """
 from ._lib import build_library, library_path, load_library  # noqa: F401
 
-__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF"]
+__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "IALSRecommender"]
 
 
 def __getattr__(name):
@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "DisGANMF":
         from .DisGANMF import DisGANMF
         return DisGANMF
+    if name == "IALSRecommender":
+        from .IALS import IALSRecommender
+        return IALSRecommender
     raise AttributeError(name)

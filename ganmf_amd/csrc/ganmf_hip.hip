@@ -43,6 +43,7 @@
 #include "list_diversity.hpp"
 #include "gram_stats.hpp"
 #include "disc_rows.hpp"
+#include "als_rows.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -71,5 +72,6 @@ extern "C" {
 #include "lib/abi_train.inc"
 #include "lib/abi_score.inc"
 #include "lib/abi_disc.inc"
+#include "lib/abi_als.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

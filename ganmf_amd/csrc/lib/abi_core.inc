@@ -44,7 +44,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h);
 int ganmf_create(const ganmf_cfg* cfg, ganmf_handle** out) {
   if (!cfg || !out) return fail(-1, "ganmf_create: null argument");
   if (cfg->abi_version != GANMF_ABI_VERSION) return fail(-1, "ganmf_create: ABI version %d != %d", cfg->abi_version, GANMF_ABI_VERSION);
-  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
+  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF && cfg->model != GANMF_MODEL_MF) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
   if (cfg->model == GANMF_MODEL_DISGANMF && (cfg->d_layers < 1 || cfg->d_layers > 16 || cfg->d_act < 0 || cfg->d_act > 3))
     return fail(-1, "ganmf_create: DisGANMF needs 1 <= d_layers <= 16 and a known activation");
   if (cfg->num_users < 1 || cfg->num_items < 1 || cfg->num_factors < 1 || cfg->emb_dim < 1 || cfg->batch_size < 1)
@@ -153,12 +153,14 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   TRY(dalloc((float**)&h->counters2, COUNTER_CAP));
   const int U = h->U, N = h->N, k = h->k, e = h->e, B = h->B;
   const bool dis = cfg->model == GANMF_MODEL_DISGANMF;
+  const bool mf = cfg->model == GANMF_MODEL_MF;      // factors only: no discriminator, no minibatch buffers
   // parameters; D gradients contiguous for a single all-reduce
   const int world = std::max(1, (int)cfg->world_size);
   TRY(alloc_tensor(h->Ue, U, k, false, 1));      // rows of U belong to their rank: never communicated
   TRY(alloc_tensor(h->V, N, k, true, world));
   TRY(dalloc(&h->V_alt, h->V.cap));
-  if (!dis) {
+  if (mf) {
+  } else if (!dis) {
     TRY(alloc_tensor(h->We, N + 1, e, false, world));   // We_ext: row N = encoder bias
     TRY(alloc_tensor(h->Wd, e + 1, N, false, world, h->ldN));   // Wd_ext: row e = decoder bias; shares the leading dimension of the [.., N] work buffers
     h->gD_elems = h->We.cap + h->Wd.cap;
@@ -186,42 +188,44 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   TRY(dalloc((float**)&h->perm, (size_t)3 * U));
   h->pos = h->perm + U;
   h->pos_step = h->perm + 2 * (size_t)U;
-  TRY(dalloc(&h->XF, (size_t)2 * B * h->ldN));
-  h->XF_own = h->XF;
-  TRY(dalloc(&h->Ub, (size_t)B * h->ldk));
-  h->Ub_own = h->Ub;
-  TRY(dalloc(&h->dF, (size_t)B * h->ldN));
-  TRY(dalloc(&h->gUb, (size_t)B * h->ldk));
-  h->gUb_own = h->gUb;
-  // bias-folding ones columns: XF[:, N] = 1 (and E[:, e] = 1 / a_l[:, e] = 1) for every row; epilogues never store there
-  std::vector<float> ones((size_t)2 * B, 1.0f);
-  HIP_TRY(hipMemcpy2D(h->XF + N, (size_t)h->ldN * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
-  if (!dis) {
-    TRY(dalloc(&h->E, (size_t)2 * B * h->lde));
-    TRY(dalloc(&h->Es, (size_t)2 * B * h->lde));
-    TRY(dalloc(&h->Dl, (size_t)2 * B * h->ldN));
-    TRY(dalloc(&h->dE, (size_t)2 * B * h->lde));
-    HIP_TRY(hipMemcpy2D(h->E + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
+  if (!mf) {      // minibatch work buffers of the adversarial step
+    TRY(dalloc(&h->XF, (size_t)2 * B * h->ldN));
+    h->XF_own = h->XF;
+    TRY(dalloc(&h->Ub, (size_t)B * h->ldk));
+    h->Ub_own = h->Ub;
+    TRY(dalloc(&h->dF, (size_t)B * h->ldN));
+    TRY(dalloc(&h->gUb, (size_t)B * h->ldk));
+    h->gUb_own = h->gUb;
+    // bias-folding ones columns: XF[:, N] = 1 (and E[:, e] = 1 / a_l[:, e] = 1) for every row; epilogues never store there
+    std::vector<float> ones((size_t)2 * B, 1.0f);
+    HIP_TRY(hipMemcpy2D(h->XF + N, (size_t)h->ldN * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
+    if (!dis) {
+      TRY(dalloc(&h->E, (size_t)2 * B * h->lde));
+      TRY(dalloc(&h->Es, (size_t)2 * B * h->lde));
+      TRY(dalloc(&h->Dl, (size_t)2 * B * h->ldN));
+      TRY(dalloc(&h->dE, (size_t)2 * B * h->lde));
+      HIP_TRY(hipMemcpy2D(h->E + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
 #ifdef GANMF_PERSIST_DIAG_BUILD
-    h->wgrad_stream = env_int("GANMF_WGRAD_STREAM", 0) != 0;
+      h->wgrad_stream = env_int("GANMF_WGRAD_STREAM", 0) != 0;
 #endif
-    if (h->wgrad_stream) {      // three bf16 pieces per activation element (dalloc counts floats: two bf16 each)
-      h->ps_N = (long long)2 * B * h->ldN; h->ps_e = (long long)2 * B * h->lde;
-      TRY(dalloc((float**)&h->pl_XF, (size_t)(3 * h->ps_N + 1) / 2));
-      TRY(dalloc((float**)&h->pl_Dl, (size_t)(3 * h->ps_N + 1) / 2));
-      TRY(dalloc((float**)&h->pl_Es, (size_t)(3 * h->ps_e + 1) / 2));
-      TRY(dalloc((float**)&h->pl_dE, (size_t)(3 * h->ps_e + 1) / 2));
-      TRY(dalloc(&h->wgs_dump, 2048 + 64));
+      if (h->wgrad_stream) {      // three bf16 pieces per activation element (dalloc counts floats: two bf16 each)
+        h->ps_N = (long long)2 * B * h->ldN; h->ps_e = (long long)2 * B * h->lde;
+        TRY(dalloc((float**)&h->pl_XF, (size_t)(3 * h->ps_N + 1) / 2));
+        TRY(dalloc((float**)&h->pl_Dl, (size_t)(3 * h->ps_N + 1) / 2));
+        TRY(dalloc((float**)&h->pl_Es, (size_t)(3 * h->ps_e + 1) / 2));
+        TRY(dalloc((float**)&h->pl_dE, (size_t)(3 * h->ps_e + 1) / 2));
+        TRY(dalloc(&h->wgs_dump, 2048 + 64));
+      }
+    } else {
+      h->Al.resize(h->L, nullptr);
+      for (int l = 0; l < h->L; ++l) {
+        TRY(dalloc(&h->Al[l], (size_t)2 * B * h->lde));
+        HIP_TRY(hipMemcpy2D(h->Al[l] + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
+      }
+      TRY(dalloc(&h->dz0, (size_t)2 * B * h->lde));
+      TRY(dalloc(&h->dz1, (size_t)2 * B * h->lde));
+      TRY(dalloc(&h->dlogit, (size_t)2 * B));
     }
-  } else {
-    h->Al.resize(h->L, nullptr);
-    for (int l = 0; l < h->L; ++l) {
-      TRY(dalloc(&h->Al[l], (size_t)2 * B * h->lde));
-      HIP_TRY(hipMemcpy2D(h->Al[l] + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
-    }
-    TRY(dalloc(&h->dz0, (size_t)2 * B * h->lde));
-    TRY(dalloc(&h->dz1, (size_t)2 * B * h->lde));
-    TRY(dalloc(&h->dlogit, (size_t)2 * B));
   }
   TRY(dalloc(&h->rs, (size_t)2 * B));
   h->tab_cap = (int)(U / std::max(B, 1)) + 2;
@@ -273,6 +277,8 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->colbuf); hipFree(h->parts_all); hipFree(h->sc_rows); hipFree(h->sc_out); hipFree(h->sc_pa); hipFree(h->sc_pb);
   hipFree(h->sim_mat); hipFree(h->sim_pool); hipFree(h->sim_part); hipFree(h->sim_zero);
   hipFree(h->rank_mask); hipFree(h->div_mat);
+  for (AlsSide& s : h->als) { hipFree(s.indptr); hipFree(s.indices); hipFree(s.conf); }
+  hipFree(h->als_G); hipFree(h->als_bad);
   hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   if (h->st2) hipStreamSynchronize(h->st2);

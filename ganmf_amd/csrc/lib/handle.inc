@@ -31,6 +31,14 @@ struct LocalGroup {
   LocalPtrs bufs{};
 };
 
+// one side of the ALS confidence matrix (ganmf_als_set_confidence): CSR over the rows that side solves
+struct AlsSide {
+  long long* indptr = nullptr;
+  int* indices = nullptr;
+  float* conf = nullptr;
+  int64_t rows = 0, nnz = 0;
+};
+
 struct ganmf_handle {
   ganmf_cfg cfg;
   int dev = 0;
@@ -214,6 +222,11 @@ struct ganmf_handle {
   double *dr_part = nullptr, *dr_val = nullptr;
   size_t dr_ids_cap = 0, dr_X_cap = 0, dr_Ub_cap = 0, dr_E_cap = 0, dr_A_cap = 0, dr_part_cap = 0, dr_val_cap = 0;
   int64_t disc_block = 0;                           // ganmf_set_discriminate_block: rows per block of the call's loop (0: a quarter of the free memory)
+  // ganmf_als_half_sweep (als_rows.hpp): the confidence matrix in both orientations, G = Y^T Y [k, ldk], and the failure words
+  // [1 + max(U, N)] (word 0: any row of the call, word 1 + u: row u)
+  AlsSide als[2];
+  float* als_G = nullptr;
+  int* als_bad = nullptr;
   int gram_arith = 1;                               // GANMF_TUNE gram: 1 (default, the faster one measured) the exact three-way bf16 split, 0 the plain fp32 MFMA body
   bool score_presplit = true;                       // GANMF_SCORE_PRESPLIT: many-tile scoring products on the pre-split persistent kernel
   // RCCL

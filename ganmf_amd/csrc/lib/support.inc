@@ -62,6 +62,7 @@ bool find_view(ganmf_handle* h, int id, View* v) {
   };
   if (id == GANMF_T_USER_EMB) return one(&h->Ue, 0, 0, h->U, h->k);
   if (id == GANMF_T_ITEM_EMB) return one(&h->V, 0, 0, h->N, h->k);
+  if (h->cfg.model == GANMF_MODEL_MF) return false;      // the two factor tensors are all such a handle holds
   if (h->cfg.model == GANMF_MODEL_GANMF) {
     switch (id) {
       case 0: return one(&h->We, 0, 0, h->N, h->e);      // autoencoder/encoding/kernel
@@ -89,7 +90,7 @@ bool find_view(ganmf_handle* h, int id, View* v) {
 std::vector<Tensor*> all_tensors(ganmf_handle* h) {
   std::vector<Tensor*> v = {&h->Ue, &h->V};
   if (h->cfg.model == GANMF_MODEL_GANMF) { v.push_back(&h->We); v.push_back(&h->Wd); }
-  else { for (auto& t : h->Wl) v.push_back(&t); v.push_back(&h->Wo); }
+  else if (h->cfg.model == GANMF_MODEL_DISGANMF) { for (auto& t : h->Wl) v.push_back(&t); v.push_back(&h->Wo); }
   return v;
 }
 

@@ -365,6 +365,22 @@ class Engine:
                 self.lib.ganmf_set_discriminate_block(self.h, 0)
         return feat, val
 
+    # -- implicit ALS (ganmf_als_*) -------------------------------------------------------------
+    def set_confidence(self, side, csr):
+        """The confidences of one side (ganmf_als_set_confidence): side 0 a users x items CSR, side 1 its transpose, items x users;
+        the stored values are the confidences c themselves (float32)."""
+        m = csr.tocsr()
+        indptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(m.indices, dtype=np.int32)
+        conf = np.ascontiguousarray(m.data, dtype=np.float32)
+        L.check(self.lib.ganmf_als_set_confidence(self.h, int(side), indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices),
+                                                  _f32p(conf), m.shape[0], m.shape[1]), "ganmf_als_set_confidence")
+
+    def als_half_sweep(self, side, reg):
+        """One ALS half sweep on the device (ganmf_als_half_sweep): side 0 rewrites the user factors of every user with a stored
+        entry from the item factors, side 1 the item factors from the user factors."""
+        L.check(self.lib.ganmf_als_half_sweep(self.h, int(side), float(reg)), "ganmf_als_half_sweep")
+
     def snapshot_best(self):
         L.check(self.lib.ganmf_snapshot_best(self.h), "ganmf_snapshot_best")
 

@@ -64,6 +64,11 @@ def search_space(model_name, n_users, n_items):
                 Dim("d_hidden_act", "categorical", choices=["linear", "tanh", "relu", "sigmoid"]),
                 Dim("d_layers", "integer", 1, 5), Dim("num_factors", "integer", 5, min(250, n_users, n_items))] + \
             common + [Dim("d_nodes", "integer", 4, width)]
+    elif model_name == "IALSRecommender":      # RecSysExp.py's IALS ranges (the search ends at 250 factors; the kernel's limit is 256)
+        dims = [Dim("num_factors", "integer", 1, min(250, n_users, n_items)),
+                Dim("confidence_scaling", "categorical", choices=["linear", "log"]),
+                Dim("alpha", "real", 1e-3, 50.0, "log-uniform"), Dim("reg", "real", 1e-5, 1e-2, "log-uniform"),
+                Dim("epsilon", "real", 1e-3, 10.0, "log-uniform")]
     else:
         raise ValueError("search_space: unknown model %r" % model_name)
     return dims

@@ -31,7 +31,12 @@ extern "C" {
 
 typedef struct ganmf_handle ganmf_handle;
 
-enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1 };
+/* GANMF_MODEL_MF: a plain matrix-factorisation model (Base/BaseMatrixFactorizationRecommender.py:94-143: USER_factors, ITEM_factors).  The
+ * handle holds only GANMF_T_USER_EMB / GANMF_T_ITEM_EMB (GANMF_SLOT_PARAM and GANMF_SLOT_BEST) and what scoring, recommendation and
+ * evaluation need; emb_dim, batch_size and the learning rates are ignored (emb_dim and batch_size must still be >= 1).  The training
+ * entries and ganmf_discriminate return -1 on it; every scoring, recommend, evaluate, snapshot and tensor entry works unchanged.  Its
+ * factors come from ganmf_als_half_sweep or ganmf_set_tensor. */
+enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2 };
 enum { GANMF_ACT_LINEAR = 0, GANMF_ACT_TANH = 1, GANMF_ACT_RELU = 2, GANMF_ACT_SIGMOID = 3 };
 
 /* Tensor ids.  Discriminator tensors are numbered in the order of the reference's
@@ -396,6 +401,28 @@ int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int t
  * asked for before ganmf_set_urm_csr, both outputs NULL, n < 0. */
 int ganmf_set_discriminate_block(ganmf_handle* h, int64_t rows);
 int ganmf_discriminate(ganmf_handle* h, const int32_t* rows, int64_t n, int generated, float* features, double* value);
+
+/* Implicit-feedback ALS (WRMF) on the device: replaces the per-row Python loop of the reference's IALS
+ * (MatrixFactorization/IALSRecommender.py:137-201, _run_epoch / _update_row: one np.linalg.inv per user and per item per epoch).  The
+ * entries act on the tensors GANMF_T_USER_EMB / GANMF_T_ITEM_EMB of ANY single-GPU handle; a GANMF_MODEL_MF handle has nothing else.
+ * ganmf_als_set_confidence: replaces the confidence matrix C and its transpose (IALSRecommender.py:100-126, _build_confidence_matrix,
+ *   C_csc).  side 0: users x items, [num_users, num_items]; side 1: its transpose, [num_items, num_users], which the caller forms.
+ *   `conf` holds the confidence c (1 + alpha r, or 1 + alpha log(1 + r / epsilon)) of every stored entry; entries that are not stored
+ *   have c = 1 and preference 0.  Any CSR whose columns are in range; a row's entries are summed in stored order.  Resident until
+ *   replaced.
+ * ganmf_als_half_sweep: one side of _run_epoch.  side 0 rewrites the user factors X from the item factors Y (IALSRecommender.py:141-145),
+ *   side 1 the item factors from the user factors (:147-151).  For every row u with at least one stored entry, with P(u) its columns,
+ *     B = Y^T Y + sum_{j in P(u)} (c_j - 1) y_j y_j^T + reg I,   b = sum_{j in P(u)} c_j y_j,   X[u, :] = B^-1 b        (:167-201)
+ *   Rows without a stored entry are not touched (the reference loops over warm rows only, :139-140).  Y^T Y is one fp32-MFMA product
+ *   per call; the rows are solved by als_rows_kernel (ganmf_amd/csrc/als_rows.hpp): fp32 throughout, Cholesky instead of the reference's
+ *   inverse, no atomics, fixed summation order -- the same bytes on every call and handle.  Blocking.
+ *   Errors: -1 with nothing enqueued for num_factors > GANMF_ALS_MAX_FACTORS (a row's packed triangle has to fit the 160 KiB of LDS of a
+ *   CU), a side without confidences, a data-parallel handle; -4 when a row's system is not positive definite in fp32 (reg <= 0 with
+ *   rank-deficient factors, or a reg below the rounding of Y^T Y, about 1e-7 of its largest entry, with such factors): the message names the first such row, those rows keep their factors, all others are updated. */
+#define GANMF_ALS_MAX_FACTORS 256
+int ganmf_als_set_confidence(ganmf_handle* h, int side, const int64_t* indptr, const int32_t* indices, const float* conf, int64_t n_rows,
+                             int64_t n_cols);
+int ganmf_als_half_sweep(ganmf_handle* h, int side, float reg);
 
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
