@@ -1,9 +1,10 @@
-"""Drop-in package name for the matrix-factorisation recommender this repository implements.
+"""Drop-in package name for the matrix-factorisation recommenders this repository implements.
 
-The reference's drivers import `MatrixFactorization.IALSRecommender.IALSRecommender` next to other modules of the same package
-(`MatrixFactorization.PureSVDRecommender`, the Cython models; RecSysExp.py, RunBestParameters.py), which live only in the reference
-tree.  As `GANRec/` does, this package therefore extends its search path with every other `MatrixFactorization/` directory on
-`sys.path`: `MatrixFactorization.IALSRecommender` resolves here (first entry), every other submodule in the reference's directory."""
+The reference's drivers import `MatrixFactorization.IALSRecommender.IALSRecommender` and
+`MatrixFactorization.PureSVDRecommender.PureSVDRecommender` next to other modules of the same package (the Cython models;
+RecSysExp.py, RunBestParameters.py), which live only in the reference tree.  As `GANRec/` does, this package therefore extends its
+search path with every other `MatrixFactorization/` directory on `sys.path`: `MatrixFactorization.IALSRecommender` and
+`MatrixFactorization.PureSVDRecommender` resolve here (first entry), every other submodule in the reference's directory."""
 import pkgutil
 
 __path__ = pkgutil.extend_path(__path__, __name__)

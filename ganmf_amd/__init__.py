@@ -6,7 +6,7 @@ fallback: without the HIP library and a GPU the classes raise.
 """
 from ._lib import build_library, library_path, load_library  # noqa: F401
 
-__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "IALSRecommender"]
+__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "IALSRecommender", "PureSVDRecommender"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "IALSRecommender":
         from .IALS import IALSRecommender
         return IALSRecommender
+    if name == "PureSVDRecommender":
+        from .PureSVD import PureSVDRecommender
+        return PureSVDRecommender
     raise AttributeError(name)

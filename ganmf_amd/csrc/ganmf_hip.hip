@@ -44,6 +44,7 @@
 #include "gram_stats.hpp"
 #include "disc_rows.hpp"
 #include "als_rows.hpp"
+#include "svd_rows.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -73,5 +74,6 @@ extern "C" {
 #include "lib/abi_score.inc"
 #include "lib/abi_disc.inc"
 #include "lib/abi_als.inc"
+#include "lib/abi_svd.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

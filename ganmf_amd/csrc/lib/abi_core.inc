@@ -279,6 +279,8 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->rank_mask); hipFree(h->div_mat);
   for (AlsSide& s : h->als) { hipFree(s.indptr); hipFree(s.indices); hipFree(s.conf); }
   hipFree(h->als_G); hipFree(h->als_bad);
+  hipFree(h->svd_P[0]); hipFree(h->svd_P[1]); hipFree(h->svd_G); hipFree(h->svd_X); hipFree(h->svd_Wl);
+  hipFree(h->svd_lam); hipFree(h->svd_flag);
   hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   if (h->st2) hipStreamSynchronize(h->st2);

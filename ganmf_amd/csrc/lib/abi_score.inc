@@ -624,7 +624,7 @@ int ganmf_evaluate_diversity(ganmf_handle* h, const int32_t* ids, int64_t n, int
   double* d_user = h->eval_buf;
   double* d_part = d_user + n_user;
   p.items = h->topk_items; p.K = K; p.D = h->div_mat; p.W = W; p.ncut = n_cutoffs; p.out = d_user;
-  // (no profile class, like the selection kernels: the tag table is at GANMF_PROF_MAX)
+  // (no profile class, like the selection kernels: it is not timed per class)
   GANMF_LAUNCH(list_diversity_kernel, dim3((unsigned)n), dim3(256), 0, h->st, p);
   HIP_TRY(hipGetLastError());
   GANMF_LAUNCH(column_block_sum_kernel, dim3((unsigned)grid, (unsigned)n_cutoffs), dim3(256), 0, h->st, d_user, (int)n, (int)n_cutoffs, d_part);

@@ -94,7 +94,8 @@ enum Tag : int {
   T_GEMM_GWD, T_RED_GWD, T_GEMM_GWE, T_RED_GWE, T_ADAM_D, T_GEMM_DF, T_RED_DF, T_GEMM_GUB, T_RED_GUB, T_GEMM_GV,
   T_RED_GV, T_ADAM_V, T_ADAM_U, T_MULTIRED, T_ALLREDUCE, T_SCORE_GEMM, T_RED_SCORE, T_DIS_FWD, T_RED_DIS_FWD, T_DIS_HEAD,
   T_DIS_GW, T_RED_DIS_GW, T_DIS_BWD, T_RED_DIS_BWD, T_FRONT, T_GWD_RED, T_PAIR, T_DE_DCOEF, T_WPAIR,
-  T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_SIM_GRAM, T_SIM_AUX, T_EVAL_GROUPS, T_COUNT
+  T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_SIM_GRAM, T_SIM_AUX, T_EVAL_GROUPS,
+  T_SVD_SPMM, T_SVD_GRAM, T_SVD_GRAM_RED, T_SVD_APPLY, T_SVD_APPLY_RED, T_SVD_CHOL, T_SVD_EIG, T_SVD_GLUE, T_COUNT
 };
 const char* const kTagName[T_COUNT] = {
   "densify_rows+gather", "gemm_generator[B,k]x[N,k]^T", "reduce_generator", "gemm_encode[2B,N]x[N,e]",
@@ -113,7 +114,10 @@ const char* const kTagName[T_COUNT] = {
   // ganmf_score_similarity: the symmetric Gram product with its statistics, and the row normalisation / block means around it
   "gram_similarity[n,W]x[n,W]^T + stats", "similarity_normalize / pool",
   // ganmf_evaluate_groups: the per-user metric values and their sums per group of users
-  "eval_groups: per-user metrics / group sums"};
+  "eval_groups: per-user metrics / group sums",
+  // ganmf_pure_svd: sparse x dense panel, Gram and apply products with their split-K sums, Cholesky + inverse, Jacobi, select / finish
+  "svd_spmm[rows,nnz]x[cols,l]", "svd_gram[n,l]^Tx[n,l]", "reduce_svd_gram", "svd_apply[n,l]x[l,.]", "reduce_svd_apply",
+  "svd_cholesky_inverse[l,l]", "svd_jacobi[l,l]", "svd_select / finish"};
 static_assert(T_COUNT <= GANMF_PROF_MAX, "ganmf_profile_read's callers size their buffer by GANMF_PROF_MAX");
 
 struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };

@@ -31,7 +31,8 @@ struct LocalGroup {
   LocalPtrs bufs{};
 };
 
-// one side of the ALS confidence matrix (ganmf_als_set_confidence): CSR over the rows that side solves
+// one side of the handle's weighted sparse matrix (ganmf_als_set_confidence): CSR over that side's rows -- the ALS confidences, or
+// the URM itself for ganmf_pure_svd
 struct AlsSide {
   long long* indptr = nullptr;
   int* indices = nullptr;
@@ -227,6 +228,13 @@ struct ganmf_handle {
   AlsSide als[2];
   float* als_G = nullptr;
   int* als_bad = nullptr;
+  // ganmf_pure_svd (svd_rows.hpp): the two panels [max(U, N), svd_ldl] the iteration alternates between, the Gram matrix and the
+  // inverse Cholesky factor [svd_ldl, svd_ldl], the [svd_ldl, ldk] matrix W of the final products, lambda [svd_ldl] | sigma [ldk],
+  // and the failure words (SvdCholP::flag).  Allocated by the first call, regrown by a call with a wider n_random.
+  float* svd_P[2] = {nullptr, nullptr};
+  float *svd_G = nullptr, *svd_X = nullptr, *svd_Wl = nullptr, *svd_lam = nullptr;
+  int* svd_flag = nullptr;
+  int svd_ldl = 0;
   int gram_arith = 1;                               // GANMF_TUNE gram: 1 (default, the faster one measured) the exact three-way bf16 split, 0 the plain fp32 MFMA body
   bool score_presplit = true;                       // GANMF_SCORE_PRESPLIT: many-tile scoring products on the pre-split persistent kernel
   // RCCL

@@ -367,8 +367,8 @@ class Engine:
 
     # -- implicit ALS (ganmf_als_*) -------------------------------------------------------------
     def set_confidence(self, side, csr):
-        """The confidences of one side (ganmf_als_set_confidence): side 0 a users x items CSR, side 1 its transpose, items x users;
-        the stored values are the confidences c themselves (float32)."""
+        """One side of the handle's weighted sparse matrix (ganmf_als_set_confidence): side 0 a users x items CSR, side 1 its
+        transpose, items x users; the stored values are the confidences c themselves for ALS, the URM's data for pure_svd (float32)."""
         m = csr.tocsr()
         indptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(m.indices, dtype=np.int32)
@@ -380,6 +380,16 @@ class Engine:
         """One ALS half sweep on the device (ganmf_als_half_sweep): side 0 rewrites the user factors of every user with a stored
         entry from the item factors, side 1 the item factors from the user factors."""
         L.check(self.lib.ganmf_als_half_sweep(self.h, int(side), float(reg)), "ganmf_als_half_sweep")
+
+    def pure_svd(self, omega, n_iter):
+        """Randomized truncated SVD of the matrix uploaded by set_confidence (side 0 the URM, side 1 its transpose) into the two
+        factor tensors (ganmf_pure_svd): omega is the [min(num_users, num_items), n_random] test matrix, n_iter the number of
+        power iterations.  Returns the num_factors singular values (float32)."""
+        om = np.ascontiguousarray(omega, dtype=np.float32)
+        assert om.ndim == 2
+        sigma = np.empty(int(self.cfg.num_factors), dtype=np.float32)
+        L.check(self.lib.ganmf_pure_svd(self.h, _f32p(om), int(om.shape[1]), int(n_iter), _f32p(sigma)), "ganmf_pure_svd")
+        return sigma
 
     def snapshot_best(self):
         L.check(self.lib.ganmf_snapshot_best(self.h), "ganmf_snapshot_best")

@@ -35,7 +35,7 @@ typedef struct ganmf_handle ganmf_handle;
  * handle holds only GANMF_T_USER_EMB / GANMF_T_ITEM_EMB (GANMF_SLOT_PARAM and GANMF_SLOT_BEST) and what scoring, recommendation and
  * evaluation need; emb_dim, batch_size and the learning rates are ignored (emb_dim and batch_size must still be >= 1).  The training
  * entries and ganmf_discriminate return -1 on it; every scoring, recommend, evaluate, snapshot and tensor entry works unchanged.  Its
- * factors come from ganmf_als_half_sweep or ganmf_set_tensor. */
+ * factors come from ganmf_als_half_sweep, ganmf_pure_svd or ganmf_set_tensor. */
 enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2 };
 enum { GANMF_ACT_LINEAR = 0, GANMF_ACT_TANH = 1, GANMF_ACT_RELU = 2, GANMF_ACT_SIGMOID = 3 };
 
@@ -218,7 +218,11 @@ int ganmf_restore_best(ganmf_handle* h);
 /* Measurement hooks (bench.py).  ganmf_profile_enable(1) makes every kernel launch of the
  * training step be bracketed by hipEvents on the handle's stream; ganmf_profile_read returns per
  * kernel class the number of launches, total milliseconds and total algorithmic FLOPs / bytes. */
-#define GANMF_PROF_MAX 48
+/* GANMF_PROF_MAX: an upper bound of the number of kernel classes, for sizing the caller's array.  It was 48 until the library had 48
+ * classes and is 64 since ganmf_pure_svd added eight; ganmf_profile_read returns only the classes that were launched and never
+ * writes more than `cap` entries, so a caller compiled against the earlier value cannot be overrun; it loses entries only if more
+ * than 48 classes ran in one profile.  No structure or signature changed: GANMF_ABI_VERSION stays. */
+#define GANMF_PROF_MAX 64
 typedef struct ganmf_prof_entry {
   char name[48];
   int64_t launches;
@@ -405,7 +409,8 @@ int ganmf_discriminate(ganmf_handle* h, const int32_t* rows, int64_t n, int gene
 /* Implicit-feedback ALS (WRMF) on the device: replaces the per-row Python loop of the reference's IALS
  * (MatrixFactorization/IALSRecommender.py:137-201, _run_epoch / _update_row: one np.linalg.inv per user and per item per epoch).  The
  * entries act on the tensors GANMF_T_USER_EMB / GANMF_T_ITEM_EMB of ANY single-GPU handle; a GANMF_MODEL_MF handle has nothing else.
- * ganmf_als_set_confidence: replaces the confidence matrix C and its transpose (IALSRecommender.py:100-126, _build_confidence_matrix,
+ * ganmf_als_set_confidence: uploads the handle's weighted sparse matrix, both orientations (ganmf_pure_svd reads the same two uploads,
+ *   with the URM's data as the values); for ALS it replaces the confidence matrix C and its transpose (IALSRecommender.py:100-126, _build_confidence_matrix,
  *   C_csc).  side 0: users x items, [num_users, num_items]; side 1: its transpose, [num_items, num_users], which the caller forms.
  *   `conf` holds the confidence c (1 + alpha r, or 1 + alpha log(1 + r / epsilon)) of every stored entry; entries that are not stored
  *   have c = 1 and preference 0.  Any CSR whose columns are in range; a row's entries are summed in stored order.  Resident until
@@ -423,6 +428,31 @@ int ganmf_discriminate(ganmf_handle* h, const int32_t* rows, int64_t n, int gene
 int ganmf_als_set_confidence(ganmf_handle* h, int side, const int64_t* indptr, const int32_t* indices, const float* conf, int64_t n_rows,
                              int64_t n_cols);
 int ganmf_als_half_sweep(ganmf_handle* h, int side, float reg);
+
+/* PureSVD on the device: replaces sklearn.utils.extmath.randomized_svd as the reference's PureSVDRecommender calls it
+ * (MatrixFactorization/PureSVDRecommender.py:29-37: n_components = num_factors, defaults otherwise).  Acts on GANMF_T_USER_EMB /
+ * GANMF_T_ITEM_EMB of ANY single-GPU handle, a GANMF_MODEL_MF one included.  The two uploads of ganmf_als_set_confidence are "the
+ * handle's weighted sparse matrix, both orientations": for the ALS entries the values are confidences, for this entry they are the
+ * URM's data (side 0 the URM, side 1 its transpose).
+ *   omega: host array [min(num_users, num_items), n_random], row-major: the random test matrix (the caller draws it, so a seeded run
+ *   equals the reference's); n_random = num_factors + oversampling (sklearn: + 10); n_iter power iterations (sklearn: 7 if
+ *   num_factors < 0.1 min(shape), else 4).  With M = URM if num_users >= num_items, else URM^T:
+ *     Q = omega;  n_iter times: Q = orth(M Q), Q = orth(M^T Q);  Q = orth(M Q);  Z = M^T Q;  Z^T Z = W diag(lambda) W^T (descending)
+ *     left = Q W[:, :k],  sigma . right = Z W[:, :k],  sigma = the column norms of Z W[:, :k]
+ *   USER = left, ITEM = Z W (M = URM), or USER = Z W / sigma, ITEM = (Q W) sigma (M = URM^T); every column of USER has its entry of
+ *   largest magnitude positive, ITEM's column carries the same sign (sklearn's svd_flip).  orth is Cholesky-QR applied twice
+ *   (sklearn normalises by LU between power iterations: with the same omega the result is the same subspace); the eigenpairs come
+ *   from a one-sided Jacobi iteration (ganmf_amd/csrc/svd_rows.hpp).  fp32 throughout, no atomics, fixed summation order: the same
+ *   bytes on every call.  sigma (may be NULL) receives the num_factors singular values.  Blocking.  Pad columns stay zero.
+ *   Errors: -1 with nothing enqueued for n_random < num_factors, n_random > min(num_users, num_items), n_random >
+ *   GANMF_SVD_MAX_RANDOM (the Cholesky factor's packed triangle has to fit the 160 KiB of LDS of a CU), n_iter < 0, a value of omega
+ *   that is not finite, a side that has not been uploaded, a data-parallel handle.  -4 when a Cholesky factorisation meets a pivot
+ *   that is not positive (the matrix has a rank below n_random, or Cholesky-QR lost it in fp32), when the eigensolver has not
+ *   converged after 30 sweeps, or when one of the num_factors eigenvalues kept is not positive: the message names the stage (which
+ *   half step, which pass).  The factor tensors are written only after all of this has been checked: any failure leaves them as
+ *   they were. */
+#define GANMF_SVD_MAX_RANDOM 280
+int ganmf_pure_svd(ganmf_handle* h, const float* omega, int n_random, int n_iter, float* sigma);
 
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
