@@ -47,6 +47,55 @@ def test_restatement_equals_dense_weighted_least_squares():
     assert np.abs(Yi[0] - want).max() <= 1e-10 * max(1.0, np.abs(want).max())
 
 
+@pytest.mark.parametrize("n_rows", [34, 36])
+def test_edge_matrix_has_the_stated_rows(n_rows):
+    M = H.edge_matrix(n_rows, 260, 3)
+    assert M.shape == (n_rows, 260) and M.dtype == np.float32
+    want = [0, 1, 2, 31, 32, 33, 63, 64, 65, 96, 97, 0, 0, 0, 0, 0, 200, 0, 0, 1, 1, 0, 0, 200, 5, 5, 5, 5, 5, 64, 0, 33, 200, 5]
+    want += [7, 7] * (n_rows == 36)
+    assert np.diff(M.indptr).tolist() == want == H.edge_lengths(n_rows)
+    assert H.EDGE_TWIN_ROWS == (24, 25, 26, 27, 28, 33)
+    assert set(np.unique(M.data)) <= {1.0, 2.0, 3.0, 4.0, 5.0}
+    rows = [(M.indices[M.indptr[u]:M.indptr[u + 1]], M.data[M.indptr[u]:M.indptr[u + 1]]) for u in range(n_rows)]
+    for u, (cols, _) in enumerate(rows):
+        assert len(set(cols.tolist())) == len(cols), u          # no repeated column
+        assert cols.size == 0 or (0 <= cols.min() and cols.max() < 260)
+    for u in H.EDGE_TWIN_ROWS:
+        assert np.array_equal(rows[u][0], rows[24][0]) and np.array_equal(rows[u][1], rows[24][1])
+    # only the twins are copies: two other rows of one length are drawn one by one
+    assert not np.array_equal(rows[16][0], rows[23][0])
+    # the same seed gives the same matrix, another seed another one
+    again, other = H.edge_matrix(n_rows, 260, 3), H.edge_matrix(n_rows, 260, 4)
+    assert np.array_equal(again.indices, M.indices) and np.array_equal(again.data, M.data)
+    assert not np.array_equal(other.indices, M.indices)
+    with pytest.raises(ValueError):
+        H.edge_matrix(35)
+
+
+@pytest.mark.parametrize("k,reg,scaling", [(8, 1e-5, "linear"), (40, 1e-2, "log"), (97, 1e-2, "linear")])
+def test_cholesky_restatement_equals_the_inverse_restatement(k, reg, scaling):
+    """float64, 36 x 260: two algorithms behind the same B and b"""
+    alpha, eps = (2.0, 1.0) if scaling == "linear" else (10.0, 0.5)
+    C = H.confidence(H.edge_matrix(36, 260, 5), scaling, alpha, eps)
+    rng = np.random.RandomState(k)
+    X0 = rng.rand(36, k)
+    Y = k ** -0.5 * rng.rand(260, k)
+    a, b = H.half_sweep(X0, Y, C, reg, np.float64), H.half_sweep_cholesky(X0, Y, C, reg, np.float64)
+    assert b.dtype == np.float64
+    assert H.row_error(b, a) <= 1e-10
+    assert np.array_equal(H.row_errors(b, a).max(), H.row_error(b, a))
+    empty = np.flatnonzero(np.diff(C.indptr) == 0)
+    assert empty.size == 11 and np.array_equal(b[empty], X0[empty])
+    # in float32 it computes in float32: close to float64, not equal to it
+    c = H.half_sweep_cholesky(X0, Y, C, reg, np.float32)
+    assert c.dtype == np.float32 and 0 < H.row_error(c, a) < 1e-2
+    # system_matrix is the B and b both solve
+    B, rhs = H.system_matrix(Y, C, 16, reg)
+    assert np.abs(B.dot(a[16]) - rhs).max() <= 1e-10 * np.abs(rhs).max()
+    with pytest.raises(np.linalg.LinAlgError):
+        H.half_sweep_cholesky(X0, Y, C, -1e3, np.float64)
+
+
 class _ScriptedEvaluator(object):
     """returns the next value of `values` as MAP at cut-off 5 and records the item factors it was shown"""
 
