@@ -8,7 +8,10 @@ _LIB_PATH = os.environ.get("GANMF_LIB_PATH") or os.path.join(_HERE, "libganmf_hi
 _lib = None
 
 ABI_VERSION = 2
-MODEL_GANMF, MODEL_DISGANMF, MODEL_MF = 0, 1, 2
+MODEL_GANMF, MODEL_DISGANMF, MODEL_MF, MODEL_ITEMSIM = 0, 1, 2, 3
+ITEMKNN_MAX_TOPK = 1024            # include/ganmf_hip.h GANMF_ITEMKNN_MAX_TOPK
+# include/ganmf_hip.h GANMF_ITEMKNN_*: the denominator ganmf_itemknn_fit applies to the dot products
+ITEMKNN_PRODUCT, ITEMKNN_TANIMOTO, ITEMKNN_DICE, ITEMKNN_TVERSKY, ITEMKNN_SHRINK_ONLY, ITEMKNN_RAW = 0, 1, 2, 3, 4, 5
 ALS_MAX_FACTORS = 256              # include/ganmf_hip.h GANMF_ALS_MAX_FACTORS
 SVD_MAX_RANDOM = 280               # include/ganmf_hip.h GANMF_SVD_MAX_RANDOM
 FLAG_MFMA_F32, FLAG_MFMA_BF16, FLAG_MFMA_F16 = 1, 2, 4     # include/ganmf_hip.h GANMF_FLAG_*
@@ -30,7 +33,7 @@ SYMBOLS = [
     "ganmf_create", "ganmf_destroy", "ganmf_comm_unique_id", "ganmf_comm_init", "ganmf_comm_init_local", "ganmf_comm_abort", "ganmf_comm_info", "ganmf_set_urm_csr",
     "ganmf_set_tensor", "ganmf_get_tensor", "ganmf_tensor_shape", "ganmf_get_adam_powers",
     "ganmf_set_adam_powers", "ganmf_train_epoch", "ganmf_train_epoch_ragged", "ganmf_train_step", "ganmf_scores",
-    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
+    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
     "ganmf_bench_scores", "ganmf_gemm_f32", "ganmf_crc32c", "ganmf_device_count", "ganmf_abi_version", "ganmf_last_error",
 ]
 
@@ -124,6 +127,9 @@ def load_library():
         "ganmf_als_set_confidence": (C.c_int, [vp, C.c_int, P(C.c_int64), P(C.c_int32), f32p, i64, i64]),
         "ganmf_als_half_sweep": (C.c_int, [vp, C.c_int, C.c_float]),
         "ganmf_pure_svd": (C.c_int, [vp, f32p, C.c_int, C.c_int, f32p]),
+        "ganmf_itemknn_fit": (C.c_int, [vp, C.c_int, i32, C.c_float, C.c_float, C.c_float, f32p, f32p, P(C.c_int64)]),
+        "ganmf_itemknn_get": (C.c_int, [vp, P(C.c_int64), P(C.c_int32), f32p]),
+        "ganmf_set_item_similarity": (C.c_int, [vp, P(C.c_int64), P(C.c_int32), f32p, i64]),
         "ganmf_crc32c": (C.c_uint32, [C.c_uint32, vp, C.c_uint64]),
         "ganmf_snapshot_best": (C.c_int, [vp]),
         "ganmf_restore_best": (C.c_int, [vp]),

@@ -45,6 +45,7 @@
 #include "disc_rows.hpp"
 #include "als_rows.hpp"
 #include "svd_rows.hpp"
+#include "itemknn_rows.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -75,5 +76,6 @@ extern "C" {
 #include "lib/abi_disc.inc"
 #include "lib/abi_als.inc"
 #include "lib/abi_svd.inc"
+#include "lib/abi_itemknn.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

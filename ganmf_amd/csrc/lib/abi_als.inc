@@ -28,12 +28,17 @@ int ganmf_als_set_confidence(ganmf_handle* h, int side, const int64_t* indptr, c
     HIP_TRY(hipMemcpy(s.conf, conf, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
   }
   s.rows = n_rows; s.nnz = nnz;
+  s.canonical = true;
+  for (int64_t r = 0; r < n_rows && s.canonical; ++r)
+    for (int64_t j = indptr[r] + 1; j < indptr[r + 1]; ++j)
+      if (indices[j] <= indices[j - 1]) { s.canonical = false; break; }
   return 0;
 }
 
 int ganmf_als_half_sweep(ganmf_handle* h, int side, float reg) {
   const char* who = "ganmf_als_half_sweep";
   if (!h) return fail(-1, "null handle");
+  TRY(needs_tensors(h, who));
   if (side != 0 && side != 1) return fail(-1, "%s: side must be 0 (user factors from item factors) or 1 (the reverse)", who);
   const int k = h->k;
   if (k > ALS_MAX_K) return fail(-1, "%s: num_factors %d is above the limit of %d (a row's packed triangle has to fit the LDS of a CU)", who, k, ALS_MAX_K);

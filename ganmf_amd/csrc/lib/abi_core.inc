@@ -44,7 +44,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h);
 int ganmf_create(const ganmf_cfg* cfg, ganmf_handle** out) {
   if (!cfg || !out) return fail(-1, "ganmf_create: null argument");
   if (cfg->abi_version != GANMF_ABI_VERSION) return fail(-1, "ganmf_create: ABI version %d != %d", cfg->abi_version, GANMF_ABI_VERSION);
-  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF && cfg->model != GANMF_MODEL_MF) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
+  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF && cfg->model != GANMF_MODEL_MF && cfg->model != GANMF_MODEL_ITEMSIM) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
   if (cfg->model == GANMF_MODEL_DISGANMF && (cfg->d_layers < 1 || cfg->d_layers > 16 || cfg->d_act < 0 || cfg->d_act > 3))
     return fail(-1, "ganmf_create: DisGANMF needs 1 <= d_layers <= 16 and a known activation");
   if (cfg->num_users < 1 || cfg->num_items < 1 || cfg->num_factors < 1 || cfg->emb_dim < 1 || cfg->batch_size < 1)
@@ -153,12 +153,15 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   TRY(dalloc((float**)&h->counters2, COUNTER_CAP));
   const int U = h->U, N = h->N, k = h->k, e = h->e, B = h->B;
   const bool dis = cfg->model == GANMF_MODEL_DISGANMF;
-  const bool mf = cfg->model == GANMF_MODEL_MF;      // factors only: no discriminator, no minibatch buffers
+  const bool sim = cfg->model == GANMF_MODEL_ITEMSIM;      // a weighted URM and an item similarity matrix: no tensor at all
+  const bool mf = cfg->model == GANMF_MODEL_MF || sim;      // factors only (or not even those): no discriminator, no minibatch buffers
   // parameters; D gradients contiguous for a single all-reduce
   const int world = std::max(1, (int)cfg->world_size);
-  TRY(alloc_tensor(h->Ue, U, k, false, 1));      // rows of U belong to their rank: never communicated
-  TRY(alloc_tensor(h->V, N, k, true, world));
-  TRY(dalloc(&h->V_alt, h->V.cap));
+  if (!sim) {
+    TRY(alloc_tensor(h->Ue, U, k, false, 1));      // rows of U belong to their rank: never communicated
+    TRY(alloc_tensor(h->V, N, k, true, world));
+    TRY(dalloc(&h->V_alt, h->V.cap));
+  }
   if (mf) {
   } else if (!dis) {
     TRY(alloc_tensor(h->We, N + 1, e, false, world));   // We_ext: row N = encoder bias
@@ -279,6 +282,7 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->rank_mask); hipFree(h->div_mat);
   for (AlsSide& s : h->als) { hipFree(s.indptr); hipFree(s.indices); hipFree(s.conf); }
   hipFree(h->als_G); hipFree(h->als_bad);
+  hipFree(h->knn_indptr); hipFree(h->knn_nbr); hipFree(h->knn_val); hipFree(h->knn_dense);
   hipFree(h->svd_P[0]); hipFree(h->svd_P[1]); hipFree(h->svd_G); hipFree(h->svd_X); hipFree(h->svd_Wl);
   hipFree(h->svd_lam); hipFree(h->svd_flag);
   hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
@@ -466,6 +470,7 @@ int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* ind
 
 int ganmf_tensor_shape(ganmf_handle* h, int tensor_id, int64_t* rows, int64_t* cols) {
   View v;
+  if (h) TRY(needs_tensors(h, "ganmf_tensor_shape"));
   if (!h || !find_view(h, tensor_id, &v)) return fail(-1, "unknown tensor id %d", tensor_id);
   if (rows) *rows = v.rows;
   if (cols) *cols = v.cols;
@@ -474,6 +479,7 @@ int ganmf_tensor_shape(ganmf_handle* h, int tensor_id, int64_t* rows, int64_t* c
 
 static int copy_view(ganmf_handle* h, int tensor_id, int slot, float* host, int64_t n, bool to_device, const char* who) {
   View v;
+  if (h) TRY(needs_tensors(h, who));
   if (!h || !host || !find_view(h, tensor_id, &v)) return fail(-1, "%s: unknown tensor id %d", who, tensor_id);
   if (n != (int64_t)v.rows * v.cols) return fail(-1, "%s: tensor %d has %lld elements, got %lld", who, tensor_id, (long long)v.rows * v.cols, (long long)n);
   // data-parallel runs keep the Adam moments of a REPLICATED tensor sharded: rank r updates slice r only (dp_update), the other

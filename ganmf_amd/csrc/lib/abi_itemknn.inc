@@ -1,0 +1,208 @@
+// abi_itemknn.inc -- C ABI: item-based nearest neighbours on a GANMF_MODEL_ITEMSIM handle: ganmf_itemknn_fit / ganmf_itemknn_get /
+// ganmf_set_item_similarity, and the second score source behind scores_device (itemknn_rows.hpp)
+// (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
+
+static int itemsim_handle(ganmf_handle* h, const char* who) {
+  if (h->cfg.model != GANMF_MODEL_ITEMSIM) return fail(-1, "%s: needs a GANMF_MODEL_ITEMSIM handle", who);
+  if (h->has_comm && h->cfg.world_size > 1) return fail(-1, "%s: single-GPU entry", who);
+  return 0;
+}
+static int itemsim_side(ganmf_handle* h, const char* who, int side) {
+  const AlsSide& s = h->als[side];
+  if (!s.indptr) return fail(-1, "%s: ganmf_als_set_confidence has not been called for side %d (the weighted URM%s)", who, side, side ? ", by item" : "");
+  if (!s.canonical)
+    return fail(-1, "%s: side %d has a row whose columns do not ascend or repeat; this model needs the canonical form (sorted indices, duplicates summed)", who, side);
+  return 0;
+}
+
+static int itemsim_ready(ganmf_handle* h, const char* who, int transposed) {
+  if (h->cfg.model != GANMF_MODEL_ITEMSIM) return 0;
+  if (transposed) return fail(-1, "%s: transposed = 1 is not defined on a GANMF_MODEL_ITEMSIM handle (its scores are URM[users] . W)", who);
+  TRY(itemsim_side(h, who, 0));
+  if (h->knn_nnz < 0) return fail(-1, "%s: the handle holds no item similarity matrix (ganmf_itemknn_fit or ganmf_set_item_similarity)", who);
+  return 0;
+}
+
+static int itemsim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W, int ldw) {
+  KnnScoreP p{};
+  const AlsSide& s = h->als[0];
+  p.r_indptr = s.indptr; p.r_items = s.indices; p.r_val = s.conf;
+  p.w_indptr = h->knn_indptr; p.w_nbr = h->knn_nbr; p.w_val = h->knn_val;
+  p.ids = ids_dev; p.n = (int)n; p.n_items = W; p.out = h->sc_out; p.ldo = ldw;
+  const bool lds = W <= KNN_SCORE_LDS;
+  const int G = !lds ? 4 : 8 * W <= KNN_SCORE_GROUP ? 8 : 4 * W <= KNN_SCORE_GROUP ? 4 : 2 * W <= KNN_SCORE_GROUP ? 2 : 1;
+  if (!lds) {      // dense profiles in global memory, whole groups of rows
+    const size_t rows = (size_t)round_up((int)n, 8);
+    TRY(grow_device(h, (void**)&h->knn_dense, &h->knn_dense_cap, rows * ldw, sizeof(float)));
+    HIP_TRY(hipMemsetAsync(h->knn_dense, 0, rows * ldw * sizeof(float), h->st));
+    p.dense = h->knn_dense; p.ldd = ldw;
+    GANMF_LAUNCH(itemknn_densify_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, p);
+    HIP_TRY(hipGetLastError());
+  }
+  const unsigned groups = (unsigned)((n + G - 1) / G);
+  const unsigned chunks_max = (unsigned)((W + KNN_THREADS - 1) / KNN_THREADS);
+  const unsigned chunks = std::max(1u, std::min(chunks_max, (1024u + groups - 1) / groups));      // about a thousand workgroups
+  const size_t shmem = lds ? (size_t)G * W * sizeof(float) : 0;
+  const double nnz_w = (double)std::max<int64_t>(h->knn_nnz, 0);
+  Scope sc(h, T_KNN_SCORE, 2.0 * n * nnz_w, 8.0 * nnz_w * groups + 4.0 * n * W);
+  switch (lds ? G : 0) {
+    case 8:
+      TRY(allow_lds((const void*)itemknn_score_kernel<8, true>, shmem));
+      GANMF_LAUNCH((itemknn_score_kernel<8, true>), dim3(groups, chunks), dim3(KNN_THREADS), shmem, h->st, p);
+      break;
+    case 4:
+      TRY(allow_lds((const void*)itemknn_score_kernel<4, true>, shmem));
+      GANMF_LAUNCH((itemknn_score_kernel<4, true>), dim3(groups, chunks), dim3(KNN_THREADS), shmem, h->st, p);
+      break;
+    case 2:
+      TRY(allow_lds((const void*)itemknn_score_kernel<2, true>, shmem));
+      GANMF_LAUNCH((itemknn_score_kernel<2, true>), dim3(groups, chunks), dim3(KNN_THREADS), shmem, h->st, p);
+      break;
+    case 1:
+      TRY(allow_lds((const void*)itemknn_score_kernel<1, true>, shmem));
+      GANMF_LAUNCH((itemknn_score_kernel<1, true>), dim3(groups, chunks), dim3(KNN_THREADS), shmem, h->st, p);
+      break;
+    default:
+      GANMF_LAUNCH((itemknn_score_kernel<4, false>), dim3(groups, chunks), dim3(KNN_THREADS), 0, h->st, p);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// the held matrix is dropped (a failed fit or upload leaves "no matrix")
+static void itemsim_drop(ganmf_handle* h) {
+  hipFree(h->knn_indptr); hipFree(h->knn_nbr); hipFree(h->knn_val);
+  h->knn_indptr = nullptr; h->knn_nbr = nullptr; h->knn_val = nullptr; h->knn_nnz = -1;
+}
+
+int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_items) {
+  const char* who = "ganmf_set_item_similarity";
+  if (!h || !indptr) return fail(-1, "%s: null argument", who);
+  TRY(itemsim_handle(h, who));
+  if (n_items != h->N) return fail(-1, "%s: the handle has %d items, given %lld", who, h->N, (long long)n_items);
+  TRY(check_csr(who, indptr, indices, n_items, n_items, false, false));
+  const int64_t nnz = indptr[n_items];
+  if (nnz > 0 && !data) return fail(-1, "%s: null argument", who);
+  for (int64_t j = 0; j < nnz; ++j)
+    if (!std::isfinite(data[j])) return fail(-1, "%s: weight %lld is not finite", who, (long long)j);
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  itemsim_drop(h);
+  HIP_TRY(hipMalloc((void**)&h->knn_indptr, (size_t)(n_items + 1) * sizeof(long long)));
+  HIP_TRY(hipMalloc((void**)&h->knn_nbr, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int)));
+  HIP_TRY(hipMalloc((void**)&h->knn_val, (size_t)std::max<int64_t>(nnz, 1) * sizeof(float)));
+  HIP_TRY(hipMemcpy(h->knn_indptr, indptr, (size_t)(n_items + 1) * sizeof(long long), hipMemcpyHostToDevice));
+  if (nnz) {
+    HIP_TRY(hipMemcpy(h->knn_nbr, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->knn_val, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
+  }
+  h->knn_nnz = nnz;      // set last
+  return 0;
+}
+
+int ganmf_itemknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float* data) {
+  const char* who = "ganmf_itemknn_get";
+  if (!h || !indptr) return fail(-1, "%s: null argument", who);
+  TRY(itemsim_handle(h, who));
+  if (h->knn_nnz < 0) return fail(-1, "%s: the handle holds no item similarity matrix", who);
+  if (h->knn_nnz > 0 && (!indices || !data)) return fail(-1, "%s: null argument", who);
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  HIP_TRY(hipMemcpy(indptr, h->knn_indptr, (size_t)(h->N + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  if (h->knn_nnz > 0) {
+    HIP_TRY(hipMemcpy(indices, h->knn_nbr, (size_t)h->knn_nnz * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(data, h->knn_val, (size_t)h->knn_nnz * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+static_assert(KNN_MAX_TOPK == GANMF_ITEMKNN_MAX_TOPK, "top-k limit of the kernels and of the header");
+static_assert(KNN_PRODUCT == GANMF_ITEMKNN_PRODUCT && KNN_RAW == GANMF_ITEMKNN_RAW, "similarity kinds of the kernels and of the header");
+
+// temporaries of one fit, released on every way out
+struct KnnFitTmp {
+  float *den_a = nullptr, *den_b = nullptr, *row = nullptr, *val = nullptr;
+  int *idx = nullptr, *cnt = nullptr;
+  ~KnnFitTmp() { hipFree(den_a); hipFree(den_b); hipFree(row); hipFree(val); hipFree(idx); hipFree(cnt); }
+};
+
+int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, float p0, float p1, const float* den_a, const float* den_b,
+                      int64_t* nnz_out) {
+  const char* who = "ganmf_itemknn_fit";
+  if (!h || !nnz_out) return fail(-1, "%s: null argument", who);
+  TRY(itemsim_handle(h, who));
+  if (kind < 0 || kind >= KNN_KINDS) return fail(-1, "%s: unknown similarity kind %d", who, kind);
+  if (topk < 1 || topk > GANMF_ITEMKNN_MAX_TOPK) return fail(-1, "%s: topk %d out of range [1,%d] (GANMF_ITEMKNN_MAX_TOPK)", who, topk, GANMF_ITEMKNN_MAX_TOPK);
+  if (!(shrink >= 0.f) || !std::isfinite(shrink)) return fail(-1, "%s: shrink must be finite and >= 0", who);
+  if (kind == KNN_SHRINK_ONLY && shrink == 0.f) return fail(-1, "%s: GANMF_ITEMKNN_SHRINK_ONLY divides by shrink, which is 0", who);
+  if (kind == KNN_TVERSKY && (!std::isfinite(p0) || !std::isfinite(p1))) return fail(-1, "%s: the Tversky coefficients are not finite", who);
+  if (kind <= KNN_TVERSKY && !den_a) return fail(-1, "%s: kind %d needs den_a", who, kind);
+  if (kind == KNN_PRODUCT && !den_b) return fail(-1, "%s: kind %d needs den_b", who, kind);
+  TRY(itemsim_side(h, who, 0));
+  TRY(itemsim_side(h, who, 1));
+  const int n = h->N, k = std::min<int>(topk, n);
+  for (int j = 0; j < n && kind <= KNN_TVERSKY; ++j)
+    if (!std::isfinite(den_a[j]) || (kind == KNN_PRODUCT && !std::isfinite(den_b[j]))) return fail(-1, "%s: denominator term %d is not finite", who, j);
+  HIP_TRY(hipSetDevice(h->dev));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  itemsim_drop(h);
+  KnnFitTmp t;
+  const AlsSide& s = h->als[1];
+  KnnFitP p{};
+  p.c_indptr = s.indptr; p.c_users = s.indices; p.c_val = s.conf;
+  p.n_items = n; p.n_users = h->U; p.kind = kind; p.topk = k;
+  p.s = (float)((double)shrink + 1e-6); p.shrink = shrink; p.p0 = p0; p.p1 = p1;
+  if (kind <= KNN_TVERSKY) {
+    HIP_TRY(hipMalloc((void**)&t.den_a, (size_t)n * sizeof(float)));
+    HIP_TRY(hipMemcpy(t.den_a, den_a, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    p.den_a = t.den_a;
+  }
+  if (kind == KNN_PRODUCT) {
+    HIP_TRY(hipMalloc((void**)&t.den_b, (size_t)n * sizeof(float)));
+    HIP_TRY(hipMemcpy(t.den_b, den_b, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    p.den_b = t.den_b;
+  }
+  p.slab = std::min(KNN_SLAB, round_up(h->U, 64));
+  p.row_lds = n <= KNN_ROW_LDS ? 1 : 0;
+  unsigned grid = (unsigned)std::min(n, 8192);
+  if (!p.row_lds) {      // a private row per workgroup in global memory: at most 512 of them
+    grid = (unsigned)std::min(n, 512);
+    p.ld_row = round_up(n, LD_ALIGN);
+    HIP_TRY(hipMalloc((void**)&t.row, (size_t)grid * p.ld_row * sizeof(float)));
+    p.row_glob = t.row;
+  }
+  HIP_TRY(hipMalloc((void**)&t.idx, (size_t)n * k * sizeof(int)));
+  HIP_TRY(hipMalloc((void**)&t.val, (size_t)n * k * sizeof(float)));
+  HIP_TRY(hipMalloc((void**)&t.cnt, (size_t)n * sizeof(int)));
+  p.out_idx = t.idx; p.out_val = t.val; p.out_cnt = t.cnt;
+  const size_t shmem = ((size_t)p.slab + (p.row_lds ? (size_t)n : 0)) * sizeof(float);
+  TRY(allow_lds((const void*)itemknn_fit_kernel, shmem));
+  {      // every workgroup walks the whole matrix once per slab of its item
+    Scope sc(h, T_KNN_FIT, 2.0 * n * (double)s.nnz, 8.0 * n * (double)s.nnz);
+    GANMF_LAUNCH(itemknn_fit_kernel, dim3(grid), dim3(KNN_THREADS), shmem, h->st, p);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<int> cnt((size_t)n);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), t.cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  std::vector<long long> ip((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (cnt[(size_t)i] < 0 || cnt[(size_t)i] > k) return fail(-2, "%s: item %d reports %d neighbours of at most %d", who, i, cnt[(size_t)i], k);
+    ip[(size_t)i + 1] = ip[(size_t)i] + cnt[(size_t)i];
+  }
+  const long long nnz = ip[(size_t)n];
+  HIP_TRY(hipMalloc((void**)&h->knn_indptr, ip.size() * sizeof(long long)));
+  HIP_TRY(hipMalloc((void**)&h->knn_nbr, (size_t)std::max<long long>(nnz, 1) * sizeof(int)));
+  HIP_TRY(hipMalloc((void**)&h->knn_val, (size_t)std::max<long long>(nnz, 1) * sizeof(float)));
+  HIP_TRY(hipMemcpy(h->knn_indptr, ip.data(), ip.size() * sizeof(long long), hipMemcpyHostToDevice));
+  {
+    Scope sc(h, T_KNN_PACK, 0.0, 16.0 * (double)nnz);
+    GANMF_LAUNCH(itemknn_pack_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, (const int*)t.idx, (const float*)t.val,
+                 (const int*)t.cnt, k, (const long long*)h->knn_indptr, h->knn_nbr, h->knn_val);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(h->st));
+  h->knn_nnz = nnz;      // set last: any failure above leaves "no matrix"
+  *nnz_out = nnz;
+  return 0;
+}

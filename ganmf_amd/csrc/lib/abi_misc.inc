@@ -2,6 +2,7 @@
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 int ganmf_snapshot_best(ganmf_handle* h) {
   if (!h) return fail(-1, "null handle");
+  TRY(needs_tensors(h, "ganmf_snapshot_best"));
   HIP_TRY(hipSetDevice(h->dev));
   for (Tensor* t : all_tensors(h))
     HIP_TRY(hipMemcpyAsync(t->best, t->p, t->padded() * sizeof(float), hipMemcpyDeviceToDevice, h->st));
@@ -11,6 +12,7 @@ int ganmf_snapshot_best(ganmf_handle* h) {
 
 int ganmf_restore_best(ganmf_handle* h) {
   if (!h) return fail(-1, "null handle");
+  TRY(needs_tensors(h, "ganmf_restore_best"));
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
   for (Tensor* t : all_tensors(h))

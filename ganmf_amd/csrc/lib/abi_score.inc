@@ -58,8 +58,22 @@ static int score_product(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
   return run_gemm(h, T_SCORE_GEMM, T_RED_SCORE, g, false, false);
 }
 
+// The second score source (abi_itemknn.inc): a GANMF_MODEL_ITEMSIM handle scores through its item similarity matrix,
+// out[r, i] = sum over the stored neighbours j of item i of x[u_r, j] . W[j, i].  itemsim_ready: what such a handle needs before any
+// scoring entry enqueues something (0 on every other model).
+static int itemsim_ready(ganmf_handle* h, const char* who, int transposed);
+static int itemsim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W, int ldw);
+
 static int scores_device(ganmf_handle* h, const int* ids_dev, int64_t n, int transposed, float** out_dev, int* width,
                          int* ld_out) {
+  if (h->cfg.model == GANMF_MODEL_ITEMSIM) {      // same [n, ldw] buffer and padding as the GEMM path: everything downstream is unchanged
+    TRY(itemsim_ready(h, "scores", transposed));
+    const int W = h->N, ldw = round_up(W, LD_ALIGN);
+    TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
+    TRY(itemsim_product(h, ids_dev, n, W, ldw));
+    *out_dev = h->sc_out; *width = W; *ld_out = ldw;
+    return 0;
+  }
   Tensor& colsT = transposed ? h->Ue : h->V;   // the other factor
   const int W = colsT.rows, ldw = round_up(W, LD_ALIGN);
   TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
@@ -171,6 +185,7 @@ int ganmf_set_items_to_ignore(ganmf_handle* h, const int32_t* items, int64_t n_i
 int ganmf_scores(ganmf_handle* h, const int32_t* ids, int64_t n, int transposed, float* out) {
   if (!h || !ids || !out) return fail(-1, "ganmf_scores: null argument");
   if (n < 1 || n > (1 << 30)) return fail(-1, "ganmf_scores: n out of range");
+  TRY(itemsim_ready(h, "ganmf_scores", transposed));
   const int limit = transposed ? h->N : h->U;
   for (int64_t i = 0; i < n; ++i)
     if (ids[i] < 0 || ids[i] >= limit) return fail(-1, "ganmf_scores: id %d out of range [0,%d)", ids[i], limit);
@@ -240,6 +255,8 @@ static int allow_lds(const void* kernel, size_t shmem) {
 static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_t* ids, int64_t n, int transposed, int32_t cutoff,
                        int remove_seen, int** ids_dev_out, const RmseP* rmse) {
   if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
+  if (cand) TRY(needs_tensors(h, who));      // (candidate scoring gathers factor rows)
+  TRY(itemsim_ready(h, who, transposed));
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
   if (cand && !h->cand_indptr) return fail(-1, "%s: no candidate matrix (ganmf_set_candidates_csr)", who);
   if (cand && (h->cand_rows != limit || h->cand_cols != W))
@@ -640,6 +657,7 @@ int ganmf_evaluate_diversity(ganmf_handle* h, const int32_t* ids, int64_t n, int
 
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch) {
   if (!h || iters < 1) return fail(-1, "ganmf_bench_scores: bad argument");
+  TRY(needs_tensors(h, "ganmf_bench_scores"));
   const int limit = transposed ? h->N : h->U;
   if (n < 1 || n > limit) return fail(-1, "ganmf_bench_scores: n out of range");
   HIP_TRY(hipSetDevice(h->dev));
@@ -683,6 +701,7 @@ int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int t
                            float* matrix) {
   const char* who = "ganmf_score_similarity";
   if (!h || !ids || !sums) return fail(-1, "%s: null argument", who);
+  TRY(needs_tensors(h, who));
   if (n < 1 || n > SIM_MAX_ROWS) return fail(-1, "%s: n out of range [1,%lld]", who, (long long)SIM_MAX_ROWS);
   const int limit = transposed ? h->N : h->U;
   for (int64_t i = 0; i < n; ++i)

@@ -38,6 +38,7 @@ struct AlsSide {
   int* indices = nullptr;
   float* conf = nullptr;
   int64_t rows = 0, nnz = 0;
+  bool canonical = false;      // every row's columns ascend without repeats (what the GANMF_MODEL_ITEMSIM entries need)
 };
 
 struct ganmf_handle {
@@ -228,6 +229,15 @@ struct ganmf_handle {
   AlsSide als[2];
   float* als_G = nullptr;
   int* als_bad = nullptr;
+  // GANMF_MODEL_ITEMSIM (itemknn_rows.hpp): the item similarity matrix W by target item -- column i of the reference's W_sparse is
+  // knn_nbr / knn_val [knn_indptr[i], knn_indptr[i + 1]) -- from ganmf_itemknn_fit or ganmf_set_item_similarity; knn_dense: the dense
+  // profiles [rows, ld] of the scoring route for catalogues above one workgroup's LDS, grown on demand
+  long long* knn_indptr = nullptr;
+  int* knn_nbr = nullptr;
+  float* knn_val = nullptr;
+  int64_t knn_nnz = -1;      // -1: no matrix held
+  float* knn_dense = nullptr;
+  size_t knn_dense_cap = 0;
   // ganmf_pure_svd (svd_rows.hpp): the two panels [max(U, N), svd_ldl] the iteration alternates between, the Gram matrix and the
   // inverse Cholesky factor [svd_ldl, svd_ldl], the [svd_ldl, ldk] matrix W of the final products, lambda [svd_ldl] | sigma [ldk],
   // and the failure words (SvdCholP::flag).  Allocated by the first call, regrown by a call with a wider n_random.

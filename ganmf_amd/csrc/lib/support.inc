@@ -51,6 +51,14 @@ void free_tensor(Tensor& t, bool grad_separate) {
   if (grad_separate) hipFree(t.g);
 }
 
+// GANMF_MODEL_ITEMSIM holds the weighted URM and an item similarity matrix, no tensor at all: the entries that read or write factors,
+// discriminator weights or their snapshots refuse such a handle before they touch anything
+int needs_tensors(const ganmf_handle* h, const char* who) {
+  if (h->cfg.model == GANMF_MODEL_ITEMSIM)
+    return fail(-1, "%s: a GANMF_MODEL_ITEMSIM handle holds a weighted URM and an item similarity matrix and has no tensors", who);
+  return 0;
+}
+
 // A reference variable as up to two row segments of a folded tensor.
 struct Seg { Tensor* t; int row0, col0, rows, cols, host_row0; };
 struct View { int rows, cols, nseg; Seg seg[2]; };
@@ -88,7 +96,9 @@ bool find_view(ganmf_handle* h, int id, View* v) {
 }
 
 std::vector<Tensor*> all_tensors(ganmf_handle* h) {
-  std::vector<Tensor*> v = {&h->Ue, &h->V};
+  std::vector<Tensor*> v;
+  if (h->cfg.model == GANMF_MODEL_ITEMSIM) return v;
+  v = {&h->Ue, &h->V};
   if (h->cfg.model == GANMF_MODEL_GANMF) { v.push_back(&h->We); v.push_back(&h->Wd); }
   else if (h->cfg.model == GANMF_MODEL_DISGANMF) { for (auto& t : h->Wl) v.push_back(&t); v.push_back(&h->Wo); }
   return v;

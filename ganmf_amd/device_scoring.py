@@ -18,9 +18,13 @@ _TestOnDevice = collections.namedtuple("_TestOnDevice", "key engine has_ratings"
 
 class DeviceScoringMixin(object):
 
+    # under the MF contract a user without a training interaction scores -inf everywhere; a class whose reference scores such a
+    # user like any other (the similarity-matrix models: all zeros) sets this to False and keeps the contract's item filter
+    mask_cold_users = True
+
     def _reset_score_filter(self):
         """no item filter; the cold-user mask only under the MF contract (the reference's GANMF scores every user)"""
-        self.engine.set_score_filter(None, mask_cold=(self.score_contract == "mf"))
+        self.engine.set_score_filter(None, mask_cold=(self.score_contract == "mf" and self.mask_cold_users))
 
     # ---- scoring (GANMF.py:285-292) ---------------------------------------------------------------
     def _compute_item_score(self, user_id_array, items_to_compute=None):
@@ -48,10 +52,11 @@ class DeviceScoringMixin(object):
         """context (MF contract only): scores / recommend / evaluate restricted to `items_to_compute`; the cold-user mask stays on"""
         eng = self.engine
         reset = self._reset_score_filter
+        mask_cold = self.mask_cold_users
 
         class _Ctx(object):
             def __enter__(self_inner):
-                eng.set_score_filter(items_to_compute, mask_cold=True)
+                eng.set_score_filter(items_to_compute, mask_cold=mask_cold)
 
             def __exit__(self_inner, *exc):
                 reset()

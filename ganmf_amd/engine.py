@@ -391,6 +391,53 @@ class Engine:
         L.check(self.lib.ganmf_pure_svd(self.h, _f32p(om), int(om.shape[1]), int(n_iter), _f32p(sigma)), "ganmf_pure_svd")
         return sigma
 
+    # -- item-based nearest neighbours (ganmf_itemknn_*, a MODEL_ITEMSIM engine) ------------------
+    def itemknn_fit(self, kind, topk, shrink=0.0, p0=1.0, p1=1.0, den_a=None, den_b=None):
+        """The item similarity matrix from the matrix uploaded by set_confidence (side 0 the weighted URM, side 1 its transpose),
+        left on the device (ganmf_itemknn_fit): kind is one of L.ITEMKNN_*, den_a / den_b the per-item float32 terms of its
+        denominator (None where the kind reads none).  Returns the number of stored similarities."""
+        a = None if den_a is None else np.ascontiguousarray(den_a, dtype=np.float32).ravel()
+        b = None if den_b is None else np.ascontiguousarray(den_b, dtype=np.float32).ravel()
+        assert all(v is None or v.size == self.num_items for v in (a, b))
+        nnz = C.c_int64(0)
+        L.check(self.lib.ganmf_itemknn_fit(self.h, int(kind), int(topk), float(shrink), float(p0), float(p1),
+                                           _f32p(a) if a is not None else None, _f32p(b) if b is not None else None,
+                                           C.byref(nnz)), "ganmf_itemknn_fit")
+        self._knn_nnz = int(nnz.value)
+        return self._knn_nnz
+
+    def item_similarity(self):
+        """The held item similarity matrix as the reference lays W_sparse out (ganmf_itemknn_get): scipy CSR float32
+        [num_items, num_items], rows = neighbour, columns = item."""
+        import scipy.sparse as sps
+        n = self.num_items
+        nnz = getattr(self, "_knn_nnz", None)
+        if nnz is None:
+            raise L.GanmfError("item_similarity: the engine holds no item similarity matrix")
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        indices = np.zeros(max(nnz, 1), dtype=np.int32)
+        data = np.zeros(max(nnz, 1), dtype=np.float32)
+        L.check(self.lib.ganmf_itemknn_get(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices), _f32p(data)),
+                "ganmf_itemknn_get")
+        by_item = sps.csc_matrix((data[:nnz], indices[:nnz], indptr), shape=(n, n))      # column i = the neighbours of item i
+        return by_item.tocsr()
+
+    def set_item_similarity(self, W_sparse):
+        """Uploads an item similarity matrix in the reference's layout (rows = neighbour, columns = item), any scipy format
+        (ganmf_set_item_similarity)."""
+        import scipy.sparse as sps
+        W = sps.csc_matrix(W_sparse, dtype=np.float32)
+        if W.shape != (self.num_items, self.num_items):
+            raise ValueError("set_item_similarity: W_sparse must be %d x %d, given %r" % (self.num_items, self.num_items, W.shape))
+        W.sum_duplicates()
+        W.sort_indices()
+        indptr = np.ascontiguousarray(W.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(W.indices, dtype=np.int32)
+        data = np.ascontiguousarray(W.data, dtype=np.float32)
+        L.check(self.lib.ganmf_set_item_similarity(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices), _f32p(data),
+                                                   self.num_items), "ganmf_set_item_similarity")
+        self._knn_nnz = int(indptr[-1])
+
     def snapshot_best(self):
         L.check(self.lib.ganmf_snapshot_best(self.h), "ganmf_snapshot_best")
 

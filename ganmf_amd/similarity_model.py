@@ -1,0 +1,79 @@
+"""What the similarity-matrix models computed by libganmf_hip.so share on the host -- the counterpart of FactorModelMixin for the
+reference's BaseSimilarityMatrixRecommender family (Base/BaseSimilarityMatrixRecommender.py:16-92: scores = URM_train[users] . W_sparse):
+the handle that holds a weighted URM and an item similarity matrix instead of tensors (GANMF_MODEL_ITEMSIM), W_sparse read from the
+device, and persistence in the layout the reference's DataIO writes for {"W_sparse": ...} (Base/DataIO.py:103-183).  A class that uses
+it provides RECOMMENDER_NAME, URM_train, n_users / n_items, device, _URM_eval and _reset_score_filter()."""
+import io
+import json
+import os
+import zipfile
+
+import numpy as np
+import scipy.sparse as sps
+
+from . import _lib as L
+from .engine import Engine
+
+
+class SimilarityModelMixin(object):
+    # ---- engine plumbing -----------------------------------------------------------------------
+    def _make_engine(self):
+        """a similarity-matrix handle (GANMF_MODEL_ITEMSIM); num_factors, emb_dim and batch_size mean nothing to it"""
+        return Engine(self.n_users, self.n_items, 1, 1, 1, model=L.MODEL_ITEMSIM, device=self.device)
+
+    def _build(self):
+        """A fresh engine that holds URM_train -- the matrix the scores are formed from, weighted if fit() weighted it -- in both
+        orientations, in canonical form, and the seen mask."""
+        if self.engine is not None:
+            self.engine.close()
+        urm = sps.csr_matrix(self.URM_train, dtype=np.float32, copy=True)
+        urm.sum_duplicates()
+        urm.sort_indices()
+        by_item = urm.tocsc()
+        by_item.sort_indices()
+        self.engine = self._make_engine()
+        self.engine.set_confidence(0, urm)
+        self.engine.set_confidence(1, sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr), shape=(self.n_items, self.n_users)))
+        self.engine.set_seen(self._URM_eval)
+        self._reset_score_filter()
+
+    def _require_engine(self):
+        if self.engine is None:
+            raise RuntimeError("{}: model has no device state; call fit() or loadModel() first".format(self.RECOMMENDER_NAME))
+
+    # ---- the similarity matrix (Base/BaseSimilarityMatrixRecommender.py:16-30) --------------------
+    @property
+    def W_sparse(self):
+        """scipy CSR float32 [n_items, n_items], rows = neighbour, columns = item: the reference's layout"""
+        self._require_engine()
+        return self.engine.item_similarity()
+
+    # ---- persistence: the layout the reference's DataIO writes (Base/DataIO.py:103-183) ----------
+    def _zip_path(self, folder_path, file_name):
+        return os.path.join(folder_path, (self.RECOMMENDER_NAME if file_name is None else file_name) + ".zip")
+
+    def saveModel(self, folder_path, file_name=None):
+        self._require_engine()
+        os.makedirs(folder_path, exist_ok=True)
+        jsons = {"__DataIO_attribute_to_type_dict": {"W_sparse": "sps.spmatrix"},
+                 "__DataIO_attribute_to_file_name": {"W_sparse": "W_sparse.npz"}}
+        buf = io.BytesIO()
+        sps.save_npz(buf, self.W_sparse)
+        with zipfile.ZipFile(self._zip_path(folder_path, file_name), "w", compression=zipfile.ZIP_DEFLATED) as z:
+            z.writestr("W_sparse.npz", buf.getvalue())
+            for name, obj in jsons.items():
+                z.writestr(name + ".json", json.dumps(obj))
+
+    def loadModel(self, folder_path, file_name=None):
+        """The saved W_sparse goes to the device; the scores are formed from this object's URM_train (as in the reference, whose
+        saved model holds W_sparse only)."""
+        with zipfile.ZipFile(self._zip_path(folder_path, file_name)) as z:
+            kinds = json.loads(z.read("__DataIO_attribute_to_type_dict.json").decode())
+            files = json.loads(z.read("__DataIO_attribute_to_file_name.json").decode())
+            if kinds.get("W_sparse") != "sps.spmatrix":
+                raise ValueError("{}: the saved model holds no sparse W_sparse".format(self.RECOMMENDER_NAME))
+            W = sps.load_npz(io.BytesIO(z.read(files["W_sparse"])))
+        if W.shape != (self.n_items, self.n_items):
+            raise ValueError("{}: the saved W_sparse is {}, URM_train has {} items".format(self.RECOMMENDER_NAME, W.shape, self.n_items))
+        self._build()
+        self.engine.set_item_similarity(W)

@@ -36,7 +36,14 @@ typedef struct ganmf_handle ganmf_handle;
  * evaluation need; emb_dim, batch_size and the learning rates are ignored (emb_dim and batch_size must still be >= 1).  The training
  * entries and ganmf_discriminate return -1 on it; every scoring, recommend, evaluate, snapshot and tensor entry works unchanged.  Its
  * factors come from ganmf_als_half_sweep, ganmf_pure_svd or ganmf_set_tensor. */
-enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2 };
+/* GANMF_MODEL_ITEMSIM: a similarity-matrix model (Base/BaseSimilarityMatrixRecommender.py:73-92: scores = URM_train[users] . W_sparse).
+ * The handle holds no tensor at all: it holds the weighted URM in both orientations (ganmf_als_set_confidence) and the item similarity
+ * matrix W (ganmf_itemknn_fit or ganmf_set_item_similarity).  num_factors, emb_dim and batch_size are ignored (each must still be >= 1).
+ * ganmf_scores, ganmf_recommend, ganmf_evaluate, ganmf_evaluate_full, ganmf_evaluate_groups and ganmf_evaluate_diversity (candidates = 0),
+ * the score filter, the ignore list and the seen / test uploads work unchanged: only the source of the score rows differs.  The
+ * training, discriminator, tensor, snapshot, ALS, SVD, candidate and score-similarity entries return -1 on it with a message that
+ * names the model, and enqueue nothing.  The enum gained a value; no structure or signature changed: GANMF_ABI_VERSION stays. */
+enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2, GANMF_MODEL_ITEMSIM = 3 };
 enum { GANMF_ACT_LINEAR = 0, GANMF_ACT_TANH = 1, GANMF_ACT_RELU = 2, GANMF_ACT_SIGMOID = 3 };
 
 /* Tensor ids.  Discriminator tensors are numbered in the order of the reference's
@@ -453,6 +460,48 @@ int ganmf_als_half_sweep(ganmf_handle* h, int side, float reg);
  *   they were. */
 #define GANMF_SVD_MAX_RANDOM 280
 int ganmf_pure_svd(ganmf_handle* h, const float* omega, int n_random, int n_iter, float* sigma);
+
+/* Item-based nearest neighbours on the device (KNN/ItemKNNCFRecommender.py; Base/Similarity/Compute_Similarity_Python.py:209-384,
+ * which the reference runs in pure Python when its Cython extension is absent).  All three entries need a GANMF_MODEL_ITEMSIM handle.
+ * The weighted URM goes up through ganmf_als_set_confidence -- side 0: users x items, side 1: its transpose (the URM by item column)
+ * -- in canonical form: inside a row the indices ascend without repeats.
+ * ganmf_itemknn_fit: for every item i
+ *     w_j = sum_u x_ui x_uj for every item j;  w_i = 0;  the kind's value v_j (below);  the min(topk, num_items) largest v_j are
+ *     selected and those that are not zero are kept (Compute_Similarity_Python.py:297-356),
+ *   with s = shrink + 1e-6 and the per-item float32 vectors den_a / den_b the caller forms in float64 (the column norms, sums of
+ *   squares or their powers, Compute_Similarity_Python.py:242-250):
+ *     GANMF_ITEMKNN_PRODUCT      w / (den_a[i] den_b[j] + s)                                    cosine, asymmetric cosine
+ *     GANMF_ITEMKNN_TANIMOTO     w / (den_a[i] + den_a[j] - w + s)                              jaccard / tanimoto
+ *     GANMF_ITEMKNN_DICE         w / (den_a[i] + den_a[j] + s)
+ *     GANMF_ITEMKNN_TVERSKY      w / (w + (den_a[i] - w) p0 + (den_a[j] - w) p1 + s)
+ *     GANMF_ITEMKNN_SHRINK_ONLY  w / shrink                                                     not normalised, shrink != 0
+ *     GANMF_ITEMKNN_RAW          w
+ *   (den_a / den_b may be NULL for the kinds that do not read them; p0 / p1 are read by TVERSKY only).  Every w_j is one fp32 FMA chain
+ *   over ascending users, there is no floating-point atomic anywhere: two fits from the same uploads return the same bytes.  Among
+ *   exactly equal values the smaller item id is selected (the rule of ganmf_recommend).  The [num_items, num_items] matrix of the w_j
+ *   never exists: one row per workgroup, in LDS or (wide catalogues) in a private global row.  Any num_items and num_users.  The
+ *   handle then holds W BY TARGET ITEM: column i of the reference's W_sparse = the kept neighbours j of item i with their values,
+ *   neighbours ascending.  *nnz receives the number of stored entries.  Blocking.
+ *   Errors (-1, nothing enqueued, the held W dropped only once every check has passed): an unknown kind, topk < 1 or above
+ *   GANMF_ITEMKNN_MAX_TOPK (the selection runs topk arg-max rounds per item; the reference's search space ends at 1000), shrink < 0
+ *   or not finite, SHRINK_ONLY with shrink = 0, a missing den vector or a term that is not finite, a side that has not been uploaded
+ *   or is not canonical, a data-parallel handle, a handle of another model.
+ * ganmf_itemknn_get: the held W to the caller: indptr [num_items + 1], indices / data [nnz] (neighbour ids and weights of every
+ *   target item in turn).
+ * ganmf_set_item_similarity: uploads a W by target item (a saved model; any other W_sparse model, such as P3alpha or SLIM): row i
+ *   of the CSR arrays = column i of W_sparse.  Columns may have any length and order; checks as the other CSR uploads (monotone
+ *   indptr from 0, indices in [0, n_items)), n_items must be the handle's num_items, weights finite.
+ * Scores on such a handle: out[r, i] = sum over the stored neighbours j of item i of x[ids[r], j] W[j, i], an fp32 FMA chain in stored
+ *   order, 0 where nothing is stored (a user without interactions scores 0 everywhere, as in the reference); x is side 0.  The
+ *   product is sparse: a workgroup keeps the dense profiles of a group of users in LDS and reads every stored weight once per group.
+ *   transposed = 1 is an error (-1). */
+#define GANMF_ITEMKNN_MAX_TOPK 1024
+enum { GANMF_ITEMKNN_PRODUCT = 0, GANMF_ITEMKNN_TANIMOTO = 1, GANMF_ITEMKNN_DICE = 2, GANMF_ITEMKNN_TVERSKY = 3,
+       GANMF_ITEMKNN_SHRINK_ONLY = 4, GANMF_ITEMKNN_RAW = 5 };
+int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, float p0, float p1, const float* den_a, const float* den_b,
+                      int64_t* nnz);
+int ganmf_itemknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float* data);
+int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_items);
 
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
