@@ -148,20 +148,3 @@ class ItemKNNCFRecommender(SimilarityModelMixin, DeviceScoringMixin, BaseRecomme
             by_item.sort_indices()
             self.engine.set_confidence(1, sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr),
                                                          shape=(self.n_items, self.n_users)))
-
-    # ---- what a similarity-matrix model does not have ---------------------------------------------
-    honours_items_to_compute = True
-
-    def prediction_similarity(self, *args, **kwargs):
-        raise NotImplementedError("{}: the prediction-similarity study is defined on factor models".format(self.RECOMMENDER_NAME))
-
-    def recommend_candidates(self, *args, **kwargs):
-        raise NotImplementedError("{}: candidate scoring gathers factor rows; rank with recommend(items_to_compute=...)".format(
-            self.RECOMMENDER_NAME))
-
-    def _device_ranking_args(self, user_id_array, cutoffs, max_cutoff, candidates_csr=None):
-        """no candidate route on the device (it gathers factor rows): the candidate hooks return None and
-        EvaluatorNegativeItemSampleFast takes its other route, recommend(items_to_compute=...)"""
-        if candidates_csr is not None:
-            return None
-        return super(ItemKNNCFRecommender, self)._device_ranking_args(user_id_array, cutoffs, max_cutoff)

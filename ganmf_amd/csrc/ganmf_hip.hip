@@ -46,6 +46,7 @@
 #include "als_rows.hpp"
 #include "svd_rows.hpp"
 #include "itemknn_rows.hpp"
+#include "p3_rows.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -77,5 +78,6 @@ extern "C" {
 #include "lib/abi_als.inc"
 #include "lib/abi_svd.inc"
 #include "lib/abi_itemknn.inc"
+#include "lib/abi_p3.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

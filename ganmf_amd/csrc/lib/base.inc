@@ -96,7 +96,7 @@ enum Tag : int {
   T_DIS_GW, T_RED_DIS_GW, T_DIS_BWD, T_RED_DIS_BWD, T_FRONT, T_GWD_RED, T_PAIR, T_DE_DCOEF, T_WPAIR,
   T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_SIM_GRAM, T_SIM_AUX, T_EVAL_GROUPS,
   T_SVD_SPMM, T_SVD_GRAM, T_SVD_GRAM_RED, T_SVD_APPLY, T_SVD_APPLY_RED, T_SVD_CHOL, T_SVD_EIG, T_SVD_GLUE,
-  T_KNN_FIT, T_KNN_PACK, T_KNN_SCORE, T_COUNT
+  T_KNN_FIT, T_KNN_PACK, T_KNN_SCORE, T_P3_ROWS, T_P3_NORMALIZE, T_P3_COLUMNS, T_COUNT
 };
 const char* const kTagName[T_COUNT] = {
   "densify_rows+gather", "gemm_generator[B,k]x[N,k]^T", "reduce_generator", "gemm_encode[2B,N]x[N,e]",
@@ -120,7 +120,9 @@ const char* const kTagName[T_COUNT] = {
   "svd_spmm[rows,nnz]x[cols,l]", "svd_gram[n,l]^Tx[n,l]", "reduce_svd_gram", "svd_apply[n,l]x[l,.]", "reduce_svd_apply",
   "svd_cholesky_inverse[l,l]", "svd_jacobi[l,l]", "svd_select / finish",
   // ganmf_itemknn_fit: one similarity row and its top-k per item, the columns packed by neighbour id; the sparse scoring product
-  "itemknn_fit: similarity row + top-k", "itemknn_pack", "itemknn_scores[n,items]x W"};
+  "itemknn_fit: similarity row + top-k", "itemknn_pack", "itemknn_scores[n,items]x W",
+  // ganmf_p3_fit: one row of the random walk and its top-k per source item, the row normalisation, the top-k per target item
+  "p3_rows: walk row + top-k", "p3_normalize", "p3_columns: column top-k / transpose"};
 static_assert(T_COUNT <= GANMF_PROF_MAX, "ganmf_profile_read's callers size their buffer by GANMF_PROF_MAX");
 
 struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };

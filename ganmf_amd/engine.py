@@ -406,6 +406,20 @@ class Engine:
         self._knn_nnz = int(nnz.value)
         return self._knn_nnz
 
+    def p3_fit(self, topk, row_scale, col_scale=None, normalize=False, col_topk=None):
+        """The P3alpha / RP3beta matrix from the uploads of set_confidence -- side 0 the URM the scores are formed from, side 1 the
+        transition weights Pui^alpha by item -- left on the device (ganmf_p3_fit): row_scale [num_items] = (1 / deg_i)^alpha,
+        col_scale [num_items] = deg_j^-beta or None, normalize: the rows divided by their L1 norm between the two selections,
+        col_topk: the second, column-wise selection (None: topk; 0: none).  Returns the number of stored weights."""
+        a = np.ascontiguousarray(row_scale, dtype=np.float32).ravel()
+        b = None if col_scale is None else np.ascontiguousarray(col_scale, dtype=np.float32).ravel()
+        assert all(v is None or v.size == self.num_items for v in (a, b))
+        nnz = C.c_int64(0)
+        L.check(self.lib.ganmf_p3_fit(self.h, int(topk), int(topk if col_topk is None else col_topk), int(bool(normalize)),
+                                      _f32p(a), _f32p(b) if b is not None else None, C.byref(nnz)), "ganmf_p3_fit")
+        self._knn_nnz = int(nnz.value)
+        return self._knn_nnz
+
     def item_similarity(self):
         """The held item similarity matrix as the reference lays W_sparse out (ganmf_itemknn_get): scipy CSR float32
         [num_items, num_items], rows = neighbour, columns = item."""

@@ -48,6 +48,23 @@ class SimilarityModelMixin(object):
         self._require_engine()
         return self.engine.item_similarity()
 
+    # ---- what a similarity-matrix model does not have ---------------------------------------------
+    honours_items_to_compute = True
+
+    def prediction_similarity(self, *args, **kwargs):
+        raise NotImplementedError("{}: the prediction-similarity study is defined on factor models".format(self.RECOMMENDER_NAME))
+
+    def recommend_candidates(self, *args, **kwargs):
+        raise NotImplementedError("{}: candidate scoring gathers factor rows; rank with recommend(items_to_compute=...)".format(
+            self.RECOMMENDER_NAME))
+
+    def _device_ranking_args(self, user_id_array, cutoffs, max_cutoff, candidates_csr=None):
+        """no candidate route on the device (it gathers factor rows): the candidate hooks return None and
+        EvaluatorNegativeItemSampleFast takes its other route, recommend(items_to_compute=...)"""
+        if candidates_csr is not None:
+            return None
+        return super(SimilarityModelMixin, self)._device_ranking_args(user_id_array, cutoffs, max_cutoff)
+
     # ---- persistence: the layout the reference's DataIO writes (Base/DataIO.py:103-183) ----------
     def _zip_path(self, folder_path, file_name):
         return os.path.join(folder_path, (self.RECOMMENDER_NAME if file_name is None else file_name) + ".zip")

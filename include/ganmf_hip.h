@@ -503,6 +503,36 @@ int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
 int ganmf_itemknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float* data);
 int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_items);
 
+/* The graph-based item models P3alpha and RP3beta on the device (GraphBased/P3alphaRecommender.py:52-141, RP3betaRecommender.py:
+ * 49-151): a three-step random walk item -> user -> item, W = Piu^alpha . Pui^alpha with Pui the URM with every user row divided by
+ * its L1 norm and Piu ones at the stored entries of the URM's transpose, every item row divided by its stored count deg_i.  Needs a
+ * GANMF_MODEL_ITEMSIM handle with both sides uploaded through ganmf_als_set_confidence in canonical form: side 0 is the matrix the
+ * scores are formed from; side 1 holds, for this call, Pui^alpha BY ITEM (items x users, the URM's pattern with the transition weights
+ * as values, formed by the caller in float64 and rounded once).  Piu^alpha has one value per item, row_scale[i] = (1 / deg_i)^alpha at
+ * every user stored in row i of side 1 (a stored explicit zero counts in deg_i and contributes 0 to the product).
+ * ganmf_p3_fit:
+ *   row pass, for every source item i:
+ *     w_j = sum_u row_scale[i] * Pui^alpha[u, j] over the users u stored in row i of side 1, for every item j;
+ *     w_j *= col_scale[j] when col_scale is given (RP3beta: deg_j^-beta, 0 where deg_j = 0; NULL for P3alpha);  w_i = 0;
+ *     the min(topk, num_items) largest w_j are selected and those that are not zero are kept: row i of R.
+ *   normalize != 0: every row of R is divided by the sum of the absolute values of its entries (summed in stored order, ascending
+ *     target id, in fp64; one rounding per value).  Empty rows stay empty.
+ *   column pass, for every target item j: the min(col_topk, num_items) largest non-zero entries of column j of R are kept (the
+ *     reference's similarityMatrixTopK works column-wise).  This pass does no arithmetic: its values are bit copies of R's.
+ *     col_topk = 0 skips the selection: R itself, transposed to the handle's layout, is held.
+ *   Every w_j is one fp32 FMA chain fmaf(row_scale[i], Pui^alpha[u, j], acc) over ascending users, there is no floating-point atomic
+ *   anywhere: two fits from the same uploads return the same bytes.  Among exactly equal values the smaller item id is selected in
+ *   both selections (the rule of ganmf_itemknn_fit and ganmf_recommend).  One row (column) of the walk per workgroup, in LDS or (wide
+ *   catalogues) in a private global row; any num_items and num_users.  The handle then holds W BY TARGET ITEM as after
+ *   ganmf_itemknn_fit -- scores[u, j] = sum_i x[u, i] W[i, j], the target is column j, its neighbours are the source rows i, ascending
+ *   -- and ganmf_itemknn_get, ganmf_set_item_similarity, the scores and every ranking and evaluation entry work on it unchanged.
+ *   *nnz receives the number of stored entries.  Blocking.
+ *   Errors (-1, nothing enqueued, the held W dropped only once every check has passed): topk outside [1, GANMF_ITEMKNN_MAX_TOPK],
+ *   col_topk outside [0, GANMF_ITEMKNN_MAX_TOPK], a scale that is negative or not finite, row_scale NULL, a side that has not been
+ *   uploaded or is not canonical, a data-parallel handle, a handle of another model. */
+int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize, const float* row_scale, const float* col_scale,
+                 int64_t* nnz);
+
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch);
