@@ -6,17 +6,19 @@ Same constructor, fit() keyword arguments, early-stopping attributes and saved-m
 libganmf_hip.so: one epoch is two calls of ganmf_als_half_sweep (a Gram product and one Cholesky solve per warm row, HIP kernels on
 gfx950) on a GANMF_MODEL_MF handle; scoring, recommendation and evaluation are the device routes of DeviceScoringMixin under the MF
 contract (Base/BaseMatrixFactorizationRecommender.py:94-143).  This file holds the confidence scaling, the initial factors and the epoch
-loop with its early stopping; the engine plumbing, the factor properties and persistence are FactorModelMixin's (factor_model.py)."""
+loop, whose early stopping is EarlyStoppingMixin's (incremental_training.py); the engine plumbing, the factor properties and persistence are
+FactorModelMixin's (factor_model.py)."""
 import numpy as np
 import scipy.sparse as sps
 
 from . import _lib as L
 from .base import BaseRecommender
 from .device_scoring import DeviceScoringMixin
+from .incremental_training import EarlyStoppingMixin
 from .factor_model import FactorModelMixin
 
 
-class IALSRecommender(FactorModelMixin, DeviceScoringMixin, BaseRecommender):
+class IALSRecommender(EarlyStoppingMixin, FactorModelMixin, DeviceScoringMixin, BaseRecommender):
     RECOMMENDER_NAME = "IALSRecommender"
 
     AVAILABLE_CONFIDENCE_SCALING = ["linear", "log"]
@@ -76,48 +78,3 @@ class IALSRecommender(FactorModelMixin, DeviceScoringMixin, BaseRecommender):
     def _update_best_model(self):
         """the best factors stay on the device, in the handle's `best` slots"""
         self.engine.snapshot_best()
-
-    def _train_with_early_stopping(self, epochs_max, epochs_min=0, validation_every_n=None, stop_on_validation=False,
-                                   validation_metric=None, lower_validations_allowed=None, evaluator_object=None):
-        """The training loop of Base/Incremental_Training_Early_Stopping.py:93-259.  Three uses: no evaluator (all epochs, the
-        last model is the best one); an evaluator with validation_every_n and validation_metric (all epochs, the model of the best
-        validation is kept); and with stop_on_validation and lower_validations_allowed as well (stops once that many validations
-        in a row did not improve, not before epoch index epochs_min).  Maintains epochs_best and best_validation_metric."""
-        if not epochs_max > 0:
-            raise ValueError("{}: Number of epochs_max must be > 0, passed was {}".format(self.RECOMMENDER_NAME, epochs_max))
-        if not 0 <= epochs_min <= epochs_max:
-            raise ValueError("{}: epochs_min must be in [0, epochs_max], passed are epochs_min {}, epochs_max {}".format(
-                self.RECOMMENDER_NAME, epochs_min, epochs_max))
-        validating = evaluator_object is not None
-        if validating and (validation_every_n is None or validation_metric is None
-                           or (stop_on_validation and lower_validations_allowed is None)):
-            raise ValueError("{}: Inconsistent parameters passed, please check the supported uses".format(self.RECOMMENDER_NAME))
-        self.best_validation_metric = None
-        self.epochs_best = 0
-        worse_in_a_row = 0
-        for epoch in range(epochs_max):
-            self._run_epoch(epoch)
-            if not validating:
-                self.epochs_best = epoch      # (the reference's count without validation: the index of the last epoch)
-                continue
-            if (epoch + 1) % validation_every_n != 0:
-                continue
-            results, _ = evaluator_object.evaluateRecommender(self)
-            value = results[list(results.keys())[0]][validation_metric]      # several cut-offs: the first one
-            if self.best_validation_metric is None or self.best_validation_metric < value:
-                self.best_validation_metric = value
-                self._update_best_model()
-                self.epochs_best = epoch + 1
-                worse_in_a_row = 0
-            else:
-                worse_in_a_row += 1
-            if stop_on_validation and worse_in_a_row >= lower_validations_allowed and epoch >= epochs_min:
-                if self.verbose:
-                    print("{}: Convergence reached! Terminating at epoch {}. Best value for '{}' at epoch {} is {:.4f}".format(
-                        self.RECOMMENDER_NAME, epoch + 1, validation_metric, self.epochs_best, self.best_validation_metric))
-                break
-        if not validating:
-            self._update_best_model()
-
-    def get_early_stopping_final_epochs_dict(self):
-        return {"epochs": self.epochs_best}

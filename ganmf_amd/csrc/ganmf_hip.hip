@@ -47,6 +47,8 @@
 #include "svd_rows.hpp"
 #include "itemknn_rows.hpp"
 #include "p3_rows.hpp"
+#include "slim_bpr.hpp"
+#include "slim_sched.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -79,5 +81,6 @@ extern "C" {
 #include "lib/abi_svd.inc"
 #include "lib/abi_itemknn.inc"
 #include "lib/abi_p3.inc"
+#include "lib/abi_slim.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

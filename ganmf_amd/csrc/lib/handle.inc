@@ -41,6 +41,23 @@ struct AlsSide {
   bool canonical = false;      // every row's columns ascend without repeats (what the GANMF_MODEL_ITEMSIM entries need)
 };
 
+// SLIM-BPR training state of a GANMF_MODEL_ITEMSIM handle (ganmf_slim_bpr_init; slim_bpr.hpp): S and the optimiser state in float64,
+// the profiles the samples are drawn from and summed over (a copy of side 0's pattern, or the caller's), the eligible users, and what
+// the host carries from call to call: the epoch counter of the sampler and Adam's beta powers
+struct SlimState {
+  bool ready = false;
+  int symmetric = 0, sgd = 0;
+  double lr = 0, li = 0, lj = 0, gamma = 0, b1 = 0, b2 = 0, b1_pow = 0, b2_pow = 0;
+  uint64_t seed = 0;
+  int64_t epoch = 0;
+  size_t cells = 0;
+  double *S = nullptr, *st0 = nullptr, *st1 = nullptr;
+  long long* indptr = nullptr;
+  int* items = nullptr;
+  int* eligible = nullptr;
+  int n_eligible = 0;
+};
+
 struct ganmf_handle {
   ganmf_cfg cfg;
   int dev = 0;
@@ -238,6 +255,7 @@ struct ganmf_handle {
   int64_t knn_nnz = -1;      // -1: no matrix held
   float* knn_dense = nullptr;
   size_t knn_dense_cap = 0;
+  SlimState slim;                                   // ganmf_slim_bpr_* (slim_bpr.hpp)
   // ganmf_pure_svd (svd_rows.hpp): the two panels [max(U, N), svd_ldl] the iteration alternates between, the Gram matrix and the
   // inverse Cholesky factor [svd_ldl, svd_ldl], the [svd_ldl, ldk] matrix W of the final products, lambda [svd_ldl] | sigma [ldk],
   // and the failure words (SvdCholP::flag).  Allocated by the first call, regrown by a call with a wider n_random.

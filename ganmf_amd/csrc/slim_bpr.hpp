@@ -1,0 +1,295 @@
+// slim_bpr.hpp -- SLIM-BPR trained on the device: the epoch of the reference's SLIM_BPR/Cython/SLIM_BPR_Cython_Epoch.pyx:198-347 (dense
+// and symmetric storage), its sampler (:427-471) and get_S (:373-421), restated as HIP kernels.  float64 throughout, as the reference.
+//
+// Storage.  S is [n, n] row-major, or -- symmetric -- one cell per unordered pair: cell(a, b) = S[r (r + 1) / 2 + c] with
+// r = max(a, b), c = min(a, b) (the reference's Triangular_Matrix).  The optimiser state is two [n] vectors: st0 the AdaGrad / RMSprop
+// cache or Adam's first moment, st1 Adam's second moment.
+//
+// One sample (u, i, j), one workgroup of SLIM_THREADS threads (slim_sample):
+//   x = sum over the profile of u of cell(i, s) - cell(j, s): thread t adds the entries t, t + 256, ... of the profile in ascending
+//       order, then the 256 partial sums are added by a fixed binary tree in LDS.  The same bytes on every run.
+//   g = 1 / (1 + exp(x)); thread 0 updates the state of i and j and forms the step `upd` (sgd: g; adagrad / rmsprop: g / (sqrt(c_i) +
+//       1e-8); adam: the bias-corrected moments of i ONLY, with the beta powers of this sample, pows[2 t], pows[2 t + 1], formed on
+//       the host by repeated multiplication).
+//   every s of the profile, one thread each: s != i: cell(i, s) += lr (upd - li cell(i, s));  s != j: cell(j, s) -= lr (upd - lj cell(j, s)).
+//   No two of these touch one cell, with one exception: symmetric storage and a list that names a j INSIDE the profile (the sampler
+//   never does; an injected list may): cell(i, j) is then written at s = j and at s = i.  Thread 0 applies that pair alone, in the
+//   order of s, as the reference's loop over the ascending profile does.
+//   Floating-point contraction is off: every product and sum rounds once, as on the reference's x86-64 build.
+//
+// Routes (slim_update_kernel).  walk = 1: ONE workgroup applies list[first, first + count) in order, a barrier between samples.
+// walk = 0: workgroup b applies list[order[first + b]]; the caller launches one grid per level of slim_sched.hpp, whose samples
+// share no item.  Both routes run slim_sample, so they write the same bytes.  No workgroup waits for another inside a kernel.
+//
+// Sampler (slim_draw_kernel), one thread per sample, counter-based.  With mix() the output function of splitmix64,
+//     mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+//     key = mix(mix(mix(seed) ^ epoch) ^ index);   word(stream, attempt) = mix(key ^ (stream << 32 | attempt));
+//     below(w, m) = ((w >> 32) * m) >> 32          (a value in [0, m), m < 2^32)
+//   user:     u = below(word(0, a), n_users) for a = 0, 1, ... until 0 < |profile(u)| < n_items; after SLIM_ATTEMPTS refusals
+//             u = eligible[below(word(0, SLIM_ATTEMPTS), n_eligible)] (the eligible users ascending): uniform over them either way;
+//   positive: i = profile(u)[below(word(1, 0), |profile(u)|)];
+//   negative: j = below(word(2, a), n_items) for a = 0, 1, ... until j is not in the profile (binary search); after SLIM_ATTEMPTS
+//             refusals the k-th item outside the profile, k = below(word(2, SLIM_ATTEMPTS), n_items - |profile(u)|).
+//
+// get_S (slim_rows_kernel): one workgroup per row; the row is copied (from the triangle when symmetric) into a private float64 row,
+// its diagonal entry zero, and the topk largest are selected in float64 by arg-max rounds with ties to the smaller id; the non-zero
+// picks are rounded to float32 and stored in the layout itemknn_pack_kernel reads.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "itemknn_rows.hpp"
+
+namespace ganmf {
+
+constexpr int SLIM_THREADS = 256;
+constexpr int SLIM_ATTEMPTS = 64;
+enum SlimSgd : int { SLIM_SGD = 0, SLIM_ADAGRAD = 1, SLIM_RMSPROP = 2, SLIM_ADAM = 3, SLIM_SGD_MODES = 4 };
+
+struct SlimP {
+  const long long* indptr;     // the profiles: users x items, items ascending without repeats inside a user
+  const int* items;
+  double* S;
+  double* st0;
+  double* st1;
+  int n_items, symmetric, sgd;
+  double lr, li, lj, gamma, b1, b2;
+  const int* users;            // the sample list
+  const int* pos;
+  const int* neg;
+  const double* pows;          // adam: [2 n] beta_1^t', beta_2^t' of every sample; else null
+  const long long* order;      // walk = 0: the samples sorted by level
+};
+
+__host__ __device__ __forceinline__ size_t slim_cell(int symmetric, int n, int a, int b) {
+  if (symmetric) {
+    const size_t r = (size_t)(a > b ? a : b), c = (size_t)(a > b ? b : a);
+    return r * (r + 1) / 2 + c;
+  }
+  return (size_t)a * (size_t)n + (size_t)b;
+}
+
+__device__ __forceinline__ bool slim_in_profile(const int* __restrict__ items, long long a, long long b, int item) {
+  const long long q = knn_lower_bound(items, a, b, item);
+  return q < b && items[q] == item;
+}
+
+__device__ __forceinline__ void slim_sample(const SlimP& p, long long t, double* red, double* sh_upd) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  const int u = p.users[t], i = p.pos[t], j = p.neg[t];
+  const long long a = p.indptr[u], b = p.indptr[u + 1];
+  const int n = p.n_items, sym = p.symmetric;
+  double acc = 0.0;
+  for (long long q = a + tid; q < b; q += SLIM_THREADS) {
+    const int s = p.items[q];
+    acc += p.S[slim_cell(sym, n, i, s)] - p.S[slim_cell(sym, n, j, s)];
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int o = SLIM_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double x = red[0];
+    const double g = 1.0 / (1.0 + exp(x));
+    double upd = g;
+    if (p.sgd == SLIM_ADAGRAD) {
+      const double ci = p.st0[i] + g * g;
+      p.st0[i] = ci;
+      p.st0[j] = p.st0[j] + g * g;
+      upd = g / (sqrt(ci) + 1e-8);
+    } else if (p.sgd == SLIM_RMSPROP) {
+      const double ci = p.st0[i] * p.gamma + (1.0 - p.gamma) * (g * g);
+      p.st0[i] = ci;
+      p.st0[j] = p.st0[j] * p.gamma + (1.0 - p.gamma) * (g * g);
+      upd = g / (sqrt(ci) + 1e-8);
+    } else if (p.sgd == SLIM_ADAM) {
+      const double m1 = p.st0[i] * p.b1 + (1.0 - p.b1) * g;
+      const double m2 = p.st1[i] * p.b2 + (1.0 - p.b2) * (g * g);
+      p.st0[i] = m1;
+      p.st1[i] = m2;
+      const double h1 = m1 / (1.0 - p.pows[2 * t]);
+      const double h2 = m2 / (1.0 - p.pows[2 * t + 1]);
+      upd = h1 / (sqrt(h2) + 1e-8);
+      p.st0[j] = p.st0[j] * p.b1 + (1.0 - p.b1) * g;
+      p.st1[j] = p.st1[j] * p.b2 + (1.0 - p.b2) * (g * g);
+    }
+    *sh_upd = upd;
+  }
+  __syncthreads();
+  const double upd = *sh_upd;
+  // symmetric storage and both i and j inside the profile: cell(i, j) is written twice, by thread 0 below
+  const bool pair = sym && slim_in_profile(p.items, a, b, j) && slim_in_profile(p.items, a, b, i);
+  for (long long q = a + tid; q < b; q += SLIM_THREADS) {
+    const int s = p.items[q];
+    if (s != i && !(pair && s == j)) {
+      double* c = p.S + slim_cell(sym, n, i, s);
+      const double v = *c;
+      *c = v + p.lr * (upd - p.li * v);
+    }
+    if (s != j && !(pair && s == i)) {
+      double* c = p.S + slim_cell(sym, n, j, s);
+      const double v = *c;
+      *c = v - p.lr * (upd - p.lj * v);
+    }
+  }
+  if (pair && tid == 0) {
+    double* c = p.S + slim_cell(sym, n, i, j);
+    double v = *c;
+    if (j < i) {      // s = j comes first: the i update, then (s = i) the j update
+      v = v + p.lr * (upd - p.li * v);
+      v = v - p.lr * (upd - p.lj * v);
+    } else {
+      v = v - p.lr * (upd - p.lj * v);
+      v = v + p.lr * (upd - p.li * v);
+    }
+    *c = v;
+  }
+}
+
+__global__ __launch_bounds__(SLIM_THREADS) void slim_update_kernel(const SlimP p, long long first, long long count, int walk) {
+  __shared__ double red[SLIM_THREADS];
+  __shared__ double sh_upd;
+  if (walk) {
+    if (blockIdx.x != 0) return;
+    for (long long t = first; t < first + count; ++t) {
+      slim_sample(p, t, red, &sh_upd);
+      __syncthreads();      // this sample's cells and state are written before the next one reads them
+    }
+  } else {
+    if ((long long)blockIdx.x >= count) return;
+    slim_sample(p, p.order[first + blockIdx.x], red, &sh_upd);
+  }
+}
+
+// ---- the sampler ------------------------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ unsigned long long slim_mix(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ __forceinline__ unsigned long long slim_word(unsigned long long key, unsigned stream, unsigned attempt) {
+  return slim_mix(key ^ (((unsigned long long)stream << 32) | attempt));
+}
+__host__ __device__ __forceinline__ unsigned slim_below(unsigned long long w, unsigned m) {
+  return (unsigned)(((w >> 32) * (unsigned long long)m) >> 32);
+}
+
+struct SlimDrawP {
+  const long long* indptr;
+  const int* items;
+  const int* eligible;         // [n_eligible] the users with 0 < |profile| < n_items, ascending
+  int n_users, n_items, n_eligible;
+  unsigned long long seed;
+  long long epoch0, per_epoch, n;      // sample g of the call: epoch epoch0 + g / per_epoch, index g % per_epoch
+  int* users;
+  int* pos;
+  int* neg;
+};
+
+__global__ __launch_bounds__(SLIM_THREADS) void slim_draw_kernel(const SlimDrawP p) {
+  const long long g = (long long)blockIdx.x * SLIM_THREADS + threadIdx.x;
+  if (g >= p.n) return;
+  const unsigned long long epoch = (unsigned long long)(p.epoch0 + g / p.per_epoch), index = (unsigned long long)(g % p.per_epoch);
+  const unsigned long long key = slim_mix(slim_mix(slim_mix(p.seed) ^ epoch) ^ index);
+  int u = -1;
+  long long a = 0, b = 0;
+  for (unsigned at = 0; at < (unsigned)SLIM_ATTEMPTS; ++at) {
+    const int c = (int)slim_below(slim_word(key, 0, at), (unsigned)p.n_users);
+    a = p.indptr[c];
+    b = p.indptr[c + 1];
+    if (b > a && b - a < p.n_items) { u = c; break; }
+  }
+  if (u < 0) {
+    u = p.eligible[slim_below(slim_word(key, 0, SLIM_ATTEMPTS), (unsigned)p.n_eligible)];
+    a = p.indptr[u];
+    b = p.indptr[u + 1];
+  }
+  const int len = (int)(b - a);
+  const int i = p.items[a + slim_below(slim_word(key, 1, 0), (unsigned)len)];
+  int j = -1;
+  for (unsigned at = 0; at < (unsigned)SLIM_ATTEMPTS; ++at) {
+    const int c = (int)slim_below(slim_word(key, 2, at), (unsigned)p.n_items);
+    if (!slim_in_profile(p.items, a, b, c)) { j = c; break; }
+  }
+  if (j < 0) {      // the k-th item outside the (ascending) profile
+    j = (int)slim_below(slim_word(key, 2, SLIM_ATTEMPTS), (unsigned)(p.n_items - len));
+    for (long long q = a; q < b && p.items[q] <= j; ++q) ++j;
+  }
+  p.users[g] = u;
+  p.pos[g] = i;
+  p.neg[g] = j;
+}
+
+// ---- get_S: the diagonal, and the top-k of every row in float64 ---------------------------------------------------------------------
+__global__ __launch_bounds__(SLIM_THREADS) void slim_zero_diag_kernel(double* S, int n, int symmetric) {
+  const int i = blockIdx.x * SLIM_THREADS + threadIdx.x;
+  if (i < n) S[slim_cell(symmetric, n, i, i)] = 0.0;
+}
+
+struct SlimRowP {
+  const double* S;
+  int n_items, symmetric, topk;      // topk <= min(KNN_MAX_TOPK, n_items)
+  double* rows;                      // [gridDim.x, n_items] a private row per workgroup
+  int* out_idx;                      // [n_items, topk] picks in descending order of value
+  float* out_val;
+  int* out_cnt;                      // [n_items] stored picks (the non-zero ones)
+};
+
+__global__ __launch_bounds__(SLIM_THREADS) void slim_rows_kernel(const SlimRowP p) {
+  __shared__ double wv[SLIM_THREADS / 64];
+  __shared__ int wi[SLIM_THREADS / 64];
+  __shared__ int s_stop;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = p.n_items;
+  double* w = p.rows + (size_t)blockIdx.x * n;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    int neg = 0;
+    for (int j = tid; j < n; j += SLIM_THREADS) {
+      const double v = j == i ? 0.0 : p.S[slim_cell(p.symmetric, n, i, j)];
+      neg |= v < 0.0;
+      w[j] = v;
+    }
+    const int any_neg = __syncthreads_or(neg);
+    int* out_idx = p.out_idx + (size_t)i * p.topk;
+    float* out_val = p.out_val + (size_t)i * p.topk;
+    int cnt = 0;
+    for (int t = 0; t < p.topk; ++t) {
+      double bv = -INFINITY;
+      int bi = 0x7fffffff;
+      for (int j = tid; j < n; j += SLIM_THREADS) {
+        const double v = w[j];
+        if (v > bv) { bv = v; bi = j; }      // ids ascend along the scan: the first maximum wins
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(bv, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+      }
+      if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+      __syncthreads();
+      if (tid == 0) {
+        double v = wv[0];
+        int best = wi[0];
+        for (int q = 1; q < SLIM_THREADS / 64; ++q)
+          if (wv[q] > v || (wv[q] == v && wi[q] < best)) { v = wv[q]; best = wi[q]; }
+        const bool ok = v > -INFINITY && best != 0x7fffffff;
+        if (ok && v != 0.0) {
+          out_idx[cnt] = best;
+          out_val[cnt] = (float)v;
+          ++cnt;
+        }
+        if (ok) w[best] = -INFINITY;
+        // nothing left, or only zeros left in a row without negative values: no later round stores anything
+        s_stop = (!ok || (v == 0.0 && !any_neg)) ? 1 : 0;
+      }
+      __syncthreads();
+      if (s_stop) break;
+    }
+    if (tid == 0) p.out_cnt[i] = cnt;
+    __syncthreads();      // (s_stop, wv / wi and the row are reused by the next item)
+  }
+}
+
+}  // namespace ganmf

@@ -420,6 +420,66 @@ class Engine:
         self._knn_nnz = int(nnz.value)
         return self._knn_nnz
 
+    # -- SLIM-BPR (ganmf_slim_bpr_*, a MODEL_ITEMSIM engine) ----------------------------------------
+    def slim_bpr_init(self, symmetric=True, sgd_mode="adagrad", learning_rate=1e-4, lambda_i=0.0, lambda_j=0.0, gamma=0.995,
+                      beta_1=0.9, beta_2=0.999, seed=0, profiles=None):
+        """Zeroed float64 S (one cell per unordered pair when symmetric) and optimiser state on the device (ganmf_slim_bpr_init).
+        profiles: the users x items CSR the samples are drawn from and summed over (canonical form); None: the pattern of side 0."""
+        if sgd_mode not in L.SLIM_SGD_MODES:
+            raise ValueError("SGD_mode not valid. Acceptable values are: 'sgd', 'adagrad', 'rmsprop', 'adam'. Provided value was '{}'".format(
+                sgd_mode))
+        indptr = indices = None
+        if profiles is not None:
+            m = profiles.tocsr()
+            if m.shape != (self.num_users, self.num_items):
+                raise ValueError("slim_bpr_init: profiles must be %d x %d, given %r" % (self.num_users, self.num_items, m.shape))
+            indptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+            indices = np.ascontiguousarray(m.indices, dtype=np.int32)
+        L.check(self.lib.ganmf_slim_bpr_init(self.h, int(bool(symmetric)), L.SLIM_SGD_MODES[sgd_mode], float(learning_rate), float(lambda_i),
+                                             float(lambda_j), float(gamma), float(beta_1), float(beta_2), int(seed) & (2 ** 64 - 1),
+                                             indptr.ctypes.data_as(C.POINTER(C.c_int64)) if indptr is not None else None,
+                                             _i32p(indices) if indices is not None else None), "ganmf_slim_bpr_init")
+
+    def slim_bpr_draw(self, epoch, n_epochs=1):
+        """(users, pos, neg), int32 [n_epochs * (num_users + 1)]: the samples of the epochs [epoch, epoch + n_epochs)"""
+        n = int(n_epochs) * (self.num_users + 1)
+        out = [np.zeros(n, dtype=np.int32) for _ in range(3)]
+        L.check(self.lib.ganmf_slim_bpr_draw(self.h, int(epoch), int(n_epochs), _i32p(out[0]), _i32p(out[1]), _i32p(out[2])),
+                "ganmf_slim_bpr_draw")
+        return tuple(out)
+
+    def slim_bpr_run(self, users, pos, neg, mode=L.SLIM_AUTO):
+        """Applies the samples in list order (ganmf_slim_bpr_run); returns the number of levels (0 on the sequential route)."""
+        u, i, j = (np.ascontiguousarray(v, dtype=np.int32).ravel() for v in (users, pos, neg))
+        assert u.size == i.size == j.size
+        levels = C.c_int64(0)
+        L.check(self.lib.ganmf_slim_bpr_run(self.h, _i32p(u), _i32p(i), _i32p(j), u.size, int(mode), C.byref(levels)), "ganmf_slim_bpr_run")
+        return int(levels.value)
+
+    def slim_bpr_epochs(self, n_epochs=1, mode=L.SLIM_AUTO):
+        """Draws and applies the next n_epochs epochs (ganmf_slim_bpr_epochs); returns the number of levels."""
+        levels = C.c_int64(0)
+        L.check(self.lib.ganmf_slim_bpr_epochs(self.h, int(n_epochs), int(mode), C.byref(levels)), "ganmf_slim_bpr_epochs")
+        return int(levels.value)
+
+    def slim_bpr_finish(self, topk):
+        """get_S and the column top-K: the held W from the current S (ganmf_slim_bpr_finish); returns the stored weights."""
+        nnz = C.c_int64(0)
+        L.check(self.lib.ganmf_slim_bpr_finish(self.h, int(topk), C.byref(nnz)), "ganmf_slim_bpr_finish")
+        self._knn_nnz = int(nnz.value)
+        return self._knn_nnz
+
+    def slim_bpr_state(self):
+        """dict: S [num_items, num_items] float64 (dense, both halves when symmetric), state0 / state1 [num_items], beta_powers [2],
+        epoch (ganmf_slim_bpr_get_state)"""
+        n = self.num_items
+        S = np.zeros((n, n), dtype=np.float64)
+        s0, s1, pw = np.zeros(n), np.zeros(n), np.zeros(2)
+        epoch = C.c_int64(0)
+        L.check(self.lib.ganmf_slim_bpr_get_state(self.h, _f64p(S), _f64p(s0), _f64p(s1), _f64p(pw), C.byref(epoch)),
+                "ganmf_slim_bpr_get_state")
+        return {"S": S, "state0": s0, "state1": s1, "beta_powers": pw, "epoch": int(epoch.value)}
+
     def item_similarity(self):
         """The held item similarity matrix as the reference lays W_sparse out (ganmf_itemknn_get): scipy CSR float32
         [num_items, num_items], rows = neighbour, columns = item."""

@@ -533,6 +533,54 @@ int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int3
 int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize, const float* row_scale, const float* col_scale,
                  int64_t* nnz);
 
+/* SLIM-BPR trained on the device (SLIM_BPR/Cython/SLIM_BPR_Cython_Epoch.pyx: the epoch :198-347, the sampler :427-471, get_S
+ * :373-421; dense and symmetric storage, not the tree-CSR mode).  All entries need a GANMF_MODEL_ITEMSIM handle; everything is
+ * float64, as in the reference.  ganmf_amd/csrc/slim_bpr.hpp states the kernels, the storage and the generator in full.
+ * ganmf_slim_bpr_init: allocates S -- [num_items, num_items], or with symmetric != 0 one cell per unordered pair of items, S[a, b]
+ *   and S[b, a] being one value -- and the per-item optimiser state (state0: the AdaGrad / RMSprop cache or Adam's first moment;
+ *   state1: Adam's second moment), all zero, and resets the epoch counter and Adam's beta powers (beta_1, beta_2).  The profiles the
+ *   samples are drawn from and summed over are indptr / indices (users x items, canonical form: ascending without repeats), or with
+ *   indptr = NULL the pattern of side 0 of ganmf_als_set_confidence; the library keeps its own copy.  An earlier training state is
+ *   dropped; the held W is not touched.  Errors: -1 for an unknown sgd mode, parameters that are not finite (beta outside [0, 1) for
+ *   Adam), profiles that are not canonical, and when no user has a profile that is neither empty nor full (the reference's sampler
+ *   would not return); -2 "out of memory", naming the bytes asked for, when an allocation fails: the handle holds no training state
+ *   then and stays usable.
+ * ganmf_slim_bpr_draw: the samples of the epochs [epoch, epoch + n_epochs), num_users + 1 per epoch (the reference's count with its
+ *   batch size of 1), to users / pos / neg [n_epochs * (num_users + 1)].  One launch, one thread per sample; a sample is a pure function
+ *   of (seed, epoch, index in the epoch) and the profiles: a uniform user whose profile is neither empty nor full, a uniform item of
+ *   the profile, a uniform item outside it.  Training state is not read or changed.
+ * ganmf_slim_bpr_run: applies the n samples (users[t], pos[t], neg[t]) with the reference's sequential semantics: for t = 0, 1, ...
+ *     x = sum over s in profile(u) of S[i, s] - S[j, s];  g = 1 / (1 + exp(x));  the state of i and j and the step `upd` (the moments
+ *     of i only for Adam, whose beta powers advance once per sample);  S[i, s] += lr (upd - lambda_i S[i, s]) for s != i;
+ *     S[j, s] -= lr (upd - lambda_j S[j, s]) for s != j.
+ *   One workgroup per sample; the sum is a fixed tree: the same bytes on every run.  mode GANMF_SLIM_SEQUENTIAL: one workgroup walks
+ *   the list in order.  GANMF_SLIM_LEVELLED (symmetric = 0 only): a sample touches rows i and j of S and the state of i and j only, so
+ *   the host sorts the list into levels (ganmf_amd/csrc/slim_sched.hpp: level = 1 + the larger level of the last earlier samples that
+ *   named i or j) and launches one grid per level; the bytes are those of the sequential route.  GANMF_SLIM_AUTO: levelled when
+ *   symmetric = 0.  *n_levels (may be NULL) receives the number of levels, 0 on the sequential route.  n = 0 is allowed.  Errors (-1,
+ *   nothing enqueued): ids out of range, pos[t] == neg[t], an unknown mode, LEVELLED with symmetric storage, no training state.
+ * ganmf_slim_bpr_epochs: ganmf_slim_bpr_draw of the next n_epochs epochs followed by ganmf_slim_bpr_run of them, the samples staying
+ *   on the device (their items are copied back once, for the schedule); advances the epoch counter.
+ * ganmf_slim_bpr_finish: get_S and the class's similarityMatrixTopK: the diagonal of S is set to zero; of every row of S the
+ *   min(topk, num_items) largest values are selected in float64, ties to the smaller id, and the non-zero ones kept and rounded to
+ *   float32 (row i of R); of every column of R the min(topk, num_items) largest non-zeros are kept (the kernels of ganmf_p3_fit's column
+ *   pass, bit copies).  The handle then holds that matrix as W BY TARGET ITEM, W[i, j] = S[i, j] where kept -- the reference's
+ *   orientation: the scores sum S[s, j] over the profile, the training sums S[j, s] -- as after ganmf_itemknn_fit.  S and the state
+ *   stay: training continues.  *nnz receives the stored entries.  Errors (-1): topk < 1, min(topk, num_items) above
+ *   GANMF_ITEMKNN_MAX_TOPK, no training state.
+ * ganmf_slim_bpr_get_state: S as a dense [num_items, num_items] matrix (both halves when symmetric), state0 / state1 [num_items], the
+ *   two beta powers the next sample would divide by, the epoch counter.  Every pointer may be NULL. */
+enum { GANMF_SLIM_SGD = 0, GANMF_SLIM_ADAGRAD = 1, GANMF_SLIM_RMSPROP = 2, GANMF_SLIM_ADAM = 3 };
+enum { GANMF_SLIM_AUTO = 0, GANMF_SLIM_SEQUENTIAL = 1, GANMF_SLIM_LEVELLED = 2 };
+int ganmf_slim_bpr_init(ganmf_handle* h, int symmetric, int sgd_mode, double learning_rate, double lambda_i, double lambda_j, double gamma,
+                        double beta_1, double beta_2, uint64_t seed, const int64_t* indptr, const int32_t* indices);
+int ganmf_slim_bpr_draw(ganmf_handle* h, int64_t epoch, int64_t n_epochs, int32_t* users, int32_t* pos, int32_t* neg);
+int ganmf_slim_bpr_run(ganmf_handle* h, const int32_t* users, const int32_t* pos, const int32_t* neg, int64_t n, int mode,
+                       int64_t* n_levels);
+int ganmf_slim_bpr_epochs(ganmf_handle* h, int64_t n_epochs, int mode, int64_t* n_levels);
+int ganmf_slim_bpr_finish(ganmf_handle* h, int32_t topk, int64_t* nnz);
+int ganmf_slim_bpr_get_state(ganmf_handle* h, double* S, double* state0, double* state1, double* beta_powers, int64_t* epoch);
+
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch);
