@@ -6,7 +6,7 @@ fallback: without the HIP library and a GPU the classes raise.
 """
 from ._lib import build_library, library_path, load_library  # noqa: F401
 
-__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "IALSRecommender", "PureSVDRecommender"]
+__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "CFGAN", "IALSRecommender", "PureSVDRecommender"]
 
 
 def __getattr__(name):
@@ -16,6 +16,9 @@ def __getattr__(name):
     if name == "DisGANMF":
         from .DisGANMF import DisGANMF
         return DisGANMF
+    if name == "CFGAN":
+        from .CFGAN import CFGAN
+        return CFGAN
     if name == "IALSRecommender":
         from .IALS import IALSRecommender
         return IALSRecommender

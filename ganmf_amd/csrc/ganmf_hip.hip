@@ -49,6 +49,8 @@
 #include "p3_rows.hpp"
 #include "slim_bpr.hpp"
 #include "slim_sched.hpp"
+#include "cfgan_masks.hpp"
+#include "cfgan_rows.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -68,6 +70,7 @@ namespace {
 #include "lib/gemm_run.inc"
 #include "lib/step_ganmf.inc"
 #include "lib/step_disganmf.inc"
+#include "lib/step_cfgan.inc"
 #include "lib/epoch.inc"
 }  // namespace
 
@@ -82,5 +85,6 @@ extern "C" {
 #include "lib/abi_itemknn.inc"
 #include "lib/abi_p3.inc"
 #include "lib/abi_slim.inc"
+#include "lib/abi_cfgan.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

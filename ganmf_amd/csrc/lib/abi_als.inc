@@ -39,6 +39,7 @@ int ganmf_als_half_sweep(ganmf_handle* h, int side, float reg) {
   const char* who = "ganmf_als_half_sweep";
   if (!h) return fail(-1, "null handle");
   TRY(needs_tensors(h, who));
+  TRY(not_cfgan(h, who));
   if (side != 0 && side != 1) return fail(-1, "%s: side must be 0 (user factors from item factors) or 1 (the reverse)", who);
   const int k = h->k;
   if (k > ALS_MAX_K) return fail(-1, "%s: num_factors %d is above the limit of %d (a row's packed triangle has to fit the LDS of a CU)", who, k, ALS_MAX_K);

@@ -44,9 +44,17 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h);
 int ganmf_create(const ganmf_cfg* cfg, ganmf_handle** out) {
   if (!cfg || !out) return fail(-1, "ganmf_create: null argument");
   if (cfg->abi_version != GANMF_ABI_VERSION) return fail(-1, "ganmf_create: ABI version %d != %d", cfg->abi_version, GANMF_ABI_VERSION);
-  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF && cfg->model != GANMF_MODEL_MF && cfg->model != GANMF_MODEL_ITEMSIM) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
+  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF && cfg->model != GANMF_MODEL_MF && cfg->model != GANMF_MODEL_ITEMSIM && cfg->model != GANMF_MODEL_CFGAN) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
   if (cfg->model == GANMF_MODEL_DISGANMF && (cfg->d_layers < 1 || cfg->d_layers > 16 || cfg->d_act < 0 || cfg->d_act > 3))
     return fail(-1, "ganmf_create: DisGANMF needs 1 <= d_layers <= 16 and a known activation");
+  if (cfg->model == GANMF_MODEL_CFGAN) {
+    if (cfg->d_layers < 1 || cfg->d_layers > 16 || cfg->d_act < 0 || cfg->d_act > 3)
+      return fail(-1, "ganmf_create: CFGAN needs 1 <= d_layers <= 16 and a known activation");
+    if (cfg->world_size > 1) return fail(-1, "ganmf_create: GANMF_MODEL_CFGAN is single-GPU (world_size %d)", cfg->world_size);
+    if (cfg->flags & (GANMF_FLAG_MFMA_BF16 | GANMF_FLAG_MFMA_F16))
+      return fail(-1, "ganmf_create: GANMF_MODEL_CFGAN runs the fp32-accurate products only (the bf16 / fp16 MFMA flags are refused)");
+    if (cfg->num_items > (1LL << 29)) return fail(-1, "ganmf_create: CFGAN's discriminator input is 2 x num_items wide: dimension too large");
+  }
   if (cfg->num_users < 1 || cfg->num_items < 1 || cfg->num_factors < 1 || cfg->emb_dim < 1 || cfg->batch_size < 1)
     return fail(-1, "ganmf_create: non-positive dimension");
   if (cfg->num_users > (1LL << 30) || cfg->num_items > (1LL << 30)) return fail(-1, "ganmf_create: dimension too large");
@@ -154,15 +162,18 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   const int U = h->U, N = h->N, k = h->k, e = h->e, B = h->B;
   const bool dis = cfg->model == GANMF_MODEL_DISGANMF;
   const bool sim = cfg->model == GANMF_MODEL_ITEMSIM;      // a weighted URM and an item similarity matrix: no tensor at all
+  const bool cfgan = cfg->model == GANMF_MODEL_CFGAN;      // two MLPs: the discriminator here, the generator and the work buffers by ganmf_cfgan_init
   const bool mf = cfg->model == GANMF_MODEL_MF || sim;      // factors only (or not even those): no discriminator, no minibatch buffers
   // parameters; D gradients contiguous for a single all-reduce
   const int world = std::max(1, (int)cfg->world_size);
-  if (!sim) {
+  if (!sim && !cfgan) {
     TRY(alloc_tensor(h->Ue, U, k, false, 1));      // rows of U belong to their rank: never communicated
     TRY(alloc_tensor(h->V, N, k, true, world));
     TRY(dalloc(&h->V_alt, h->V.cap));
   }
   if (mf) {
+  } else if (cfgan) {
+    TRY(cfgan_create(h));
   } else if (!dis) {
     TRY(alloc_tensor(h->We, N + 1, e, false, world));   // We_ext: row N = encoder bias
     TRY(alloc_tensor(h->Wd, e + 1, N, false, world, h->ldN));   // Wd_ext: row e = decoder bias; shares the leading dimension of the [.., N] work buffers
@@ -191,7 +202,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   TRY(dalloc((float**)&h->perm, (size_t)3 * U));
   h->pos = h->perm + U;
   h->pos_step = h->perm + 2 * (size_t)U;
-  if (!mf) {      // minibatch work buffers of the adversarial step
+  if (!mf && !cfgan) {      // minibatch work buffers of the adversarial step
     TRY(dalloc(&h->XF, (size_t)2 * B * h->ldN));
     h->XF_own = h->XF;
     TRY(dalloc(&h->Ub, (size_t)B * h->ldk));
@@ -287,6 +298,7 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->svd_P[0]); hipFree(h->svd_P[1]); hipFree(h->svd_G); hipFree(h->svd_X); hipFree(h->svd_Wl);
   hipFree(h->svd_lam); hipFree(h->svd_flag);
   hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
+  cfgan_free(h);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   if (h->st2) hipStreamSynchronize(h->st2);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -314,6 +326,7 @@ int ganmf_comm_unique_id(uint8_t out128[128]) {
 
 int ganmf_comm_init_local(ganmf_handle* h, int32_t group_id) {
   if (!h) return fail(-1, "null handle");
+  TRY(not_cfgan(h, "ganmf_comm_init_local"));
   if (h->has_comm) return fail(-1, "ganmf_comm_init_local: handle already has a communicator");
   const int world = h->cfg.world_size, rank = h->cfg.rank;
   if (world < 1 || world > LOCAL_MAX_WORLD || rank < 0 || rank >= world)
@@ -334,6 +347,7 @@ int ganmf_comm_init_local(ganmf_handle* h, int32_t group_id) {
 
 int ganmf_comm_init(ganmf_handle* h, const uint8_t id128[128]) {
   if (!h) return fail(-1, "null handle");
+  TRY(not_cfgan(h, "ganmf_comm_init"));
   HIP_TRY(hipSetDevice(h->dev));
   ncclUniqueId id;
   memcpy(&id, id128, 128);

@@ -113,6 +113,7 @@ int ganmf_discriminate(ganmf_handle* h, const int32_t* rows, int64_t n, int gene
   const char* who = "ganmf_discriminate";
   if (!h) return fail(-1, "null handle");
   TRY(needs_tensors(h, who));
+  TRY(not_cfgan(h, who));
   if (h->cfg.model == GANMF_MODEL_MF) return fail(-1, "%s: a GANMF_MODEL_MF handle has no discriminator", who);
   if (!features && !value) return fail(-1, "%s: neither features nor value asked for", who);
   if (n < 0 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);

@@ -3,6 +3,7 @@
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
 static int itemsim_handle(ganmf_handle* h, const char* who) {
+  TRY(not_cfgan(h, who));
   if (h->cfg.model != GANMF_MODEL_ITEMSIM) return fail(-1, "%s: needs a GANMF_MODEL_ITEMSIM handle", who);
   if (h->has_comm && h->cfg.world_size > 1) return fail(-1, "%s: single-GPU entry", who);
   return 0;

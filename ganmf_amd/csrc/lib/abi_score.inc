@@ -74,6 +74,13 @@ static int scores_device(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
     *out_dev = h->sc_out; *width = W; *ld_out = ldw;
     return 0;
   }
+  if (h->cfg.model == GANMF_MODEL_CFGAN) {      // the third source (step_cfgan.inc): the generator's output for the rows, or rows of its transpose
+    const int W = transposed ? h->U : h->N, ldw = round_up(W, LD_ALIGN);
+    TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
+    TRY(cfgan_scores(h, ids_dev, n, transposed, h->sc_out, ldw));
+    *out_dev = h->sc_out; *width = W; *ld_out = ldw;
+    return 0;
+  }
   Tensor& colsT = transposed ? h->Ue : h->V;   // the other factor
   const int W = colsT.rows, ldw = round_up(W, LD_ALIGN);
   TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
@@ -256,6 +263,7 @@ static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_
                        int remove_seen, int** ids_dev_out, const RmseP* rmse) {
   if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
   if (cand) TRY(needs_tensors(h, who));      // (candidate scoring gathers factor rows)
+  if (cand) TRY(not_cfgan(h, who));
   TRY(itemsim_ready(h, who, transposed));
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
   if (cand && !h->cand_indptr) return fail(-1, "%s: no candidate matrix (ganmf_set_candidates_csr)", who);
@@ -658,6 +666,7 @@ int ganmf_evaluate_diversity(ganmf_handle* h, const int32_t* ids, int64_t n, int
 int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters, float* ms_per_launch) {
   if (!h || iters < 1) return fail(-1, "ganmf_bench_scores: bad argument");
   TRY(needs_tensors(h, "ganmf_bench_scores"));
+  TRY(not_cfgan(h, "ganmf_bench_scores"));
   const int limit = transposed ? h->N : h->U;
   if (n < 1 || n > limit) return fail(-1, "ganmf_bench_scores: n out of range");
   HIP_TRY(hipSetDevice(h->dev));

@@ -88,6 +88,7 @@ int ganmf_pure_svd(ganmf_handle* h, const float* omega, int n_random, int n_iter
   const char* who = "ganmf_pure_svd";
   if (!h || !omega) return fail(-1, "%s: null argument", who);
   TRY(needs_tensors(h, who));
+  TRY(not_cfgan(h, who));
   const int k = h->k, l = n_random, mn = std::min(h->U, h->N);
   if (l < k) return fail(-1, "%s: n_random %d is below num_factors %d", who, l, k);
   if (l > mn) return fail(-1, "%s: n_random %d is above min(num_users, num_items) = %d", who, l, mn);

@@ -11,6 +11,7 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
                              const int32_t* local_batch_rows, float* d_losses, float* g_losses) {
   if (!h || (!perm && n > 0)) return fail(-1, "ganmf_train_epoch: null argument");
   TRY(needs_tensors(h, "ganmf_train_epoch"));
+  TRY(not_cfgan(h, "ganmf_train_epoch"));
   if (h->cfg.model == GANMF_MODEL_MF) return fail(-1, "ganmf_train_epoch: a GANMF_MODEL_MF handle holds factors only and has no adversarial training; its factors come from ganmf_als_half_sweep or ganmf_set_tensor");
   if (!h->has_urm) return fail(-1, "ganmf_train_epoch: ganmf_set_urm_csr has not been called");
   if (n < 0 || n > h->U) return fail(-1, "ganmf_train_epoch: n=%lld out of range", (long long)n);
@@ -195,6 +196,7 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
 int ganmf_train_step(ganmf_handle* h, int kind, const int32_t* uids, int32_t n, float* loss) {
   if (!h || !uids) return fail(-1, "ganmf_train_step: null argument");
   TRY(needs_tensors(h, "ganmf_train_step"));
+  TRY(not_cfgan(h, "ganmf_train_step"));
   if (h->cfg.model == GANMF_MODEL_MF) return fail(-1, "ganmf_train_step: a GANMF_MODEL_MF handle holds factors only and has no adversarial training; its factors come from ganmf_als_half_sweep or ganmf_set_tensor");
   if (!h->has_urm) return fail(-1, "ganmf_train_step: ganmf_set_urm_csr has not been called");
   if (n < 1 || n > h->B) return fail(-1, "ganmf_train_step: batch of %d rows (handle batch_size %d)", n, h->B);

@@ -58,6 +58,29 @@ struct SlimState {
   int n_eligible = 0;
 };
 
+// CFGAN state of a GANMF_MODEL_CFGAN handle (ganmf_cfgan_init; step_cfgan.inc).  The discriminator lives in the handle's DisGANMF
+// members (Wl, Wo, Al, dz0, dz1, dlogit; Wl[0] is [2N + 1, e]: condition rows, input rows, bias row); the generator, the masks and the
+// step's work buffers live here.  Bm = max(d_batch, g_batch) rows.
+struct CfganState {
+  bool ready = false;
+  int g = 0, Lg = 0, act = 0, ldg = 0;      // generator width, depth, activation
+  int d_batch = 0, g_batch = 0, scheme = 0, Bm = 0, ldx = 0, words = 0;
+  float zr_coef = 0.f;
+  uint64_t seed = 0;
+  std::vector<Tensor> Gl;        // l = 0: [N + 1, g] (row N the bias); l > 0: [g + 1, g]
+  Tensor Go;                     // [g + 1, N] (row g the bias), leading dimension ldN
+  std::vector<float*> Hl;        // hidden outputs [Bm, ldg] with the ones column at g
+  float *C = nullptr, *fake = nullptr, *dfake = nullptr, *DX = nullptr, *dh0 = nullptr, *dh1 = nullptr;
+  float *zr_part = nullptr, *loss_rows = nullptr, *sq = nullptr, *loss_dev = nullptr;
+  size_t loss_cap = 0;
+  unsigned* planes = nullptr;    // [2][U][words]: CFGAN_PLANE_ZR, CFGAN_PLANE_PM
+  int* k_rows = nullptr;         // [U]
+  // scoring: scratch of a block of scored rows, and (item mode) the transposed G(all rows) [N, ld(U)] as of cache_version
+  float *sc_C = nullptr, *sc_H0 = nullptr, *sc_H1 = nullptr, *sc_F = nullptr, *cache = nullptr;
+  size_t sc_rows = 0;
+  long long cache_version = -1;
+};
+
 struct ganmf_handle {
   ganmf_cfg cfg;
   int dev = 0;
@@ -256,6 +279,7 @@ struct ganmf_handle {
   float* knn_dense = nullptr;
   size_t knn_dense_cap = 0;
   SlimState slim;                                   // ganmf_slim_bpr_* (slim_bpr.hpp)
+  CfganState cf;                                    // ganmf_cfgan_* (cfgan_masks.hpp, cfgan_rows.hpp)
   // ganmf_pure_svd (svd_rows.hpp): the two panels [max(U, N), svd_ldl] the iteration alternates between, the Gram matrix and the
   // inverse Cholesky factor [svd_ldl, svd_ldl], the [svd_ldl, ldk] matrix W of the final products, lambda [svd_ldl] | sigma [ldk],
   // and the failure words (SvdCholP::flag).  Allocated by the first call, regrown by a call with a wider n_random.

@@ -59,6 +59,14 @@ int needs_tensors(const ganmf_handle* h, const char* who) {
   return 0;
 }
 
+// GANMF_MODEL_CFGAN holds two MLPs and no factor tensors, trains through ganmf_cfgan_* and scores through its generator: the entries
+// built on factors or on the other models' steps refuse it before they touch anything
+int not_cfgan(const ganmf_handle* h, const char* who) {
+  if (h->cfg.model == GANMF_MODEL_CFGAN)
+    return fail(-1, "%s: not defined on a GANMF_MODEL_CFGAN handle (two MLPs, no factor tensors; it trains through ganmf_cfgan_* and scores through its generator)", who);
+  return 0;
+}
+
 // A reference variable as up to two row segments of a folded tensor.
 struct Seg { Tensor* t; int row0, col0, rows, cols, host_row0; };
 struct View { int rows, cols, nseg; Seg seg[2]; };
@@ -68,6 +76,25 @@ bool find_view(ganmf_handle* h, int id, View* v) {
     v->rows = rows; v->cols = cols; v->nseg = 1; v->seg[0] = {t, row0, col0, rows, cols, 0};
     return true;
   };
+  if (h->cfg.model == GANMF_MODEL_CFGAN) {
+    // discriminator ids as DisGANMF's (layer 0 is [2N, e]: condition rows then input rows, the bias is row 2N of the folded tensor);
+    // generator ids from GANMF_T_CFGAN_G0, laid out the same way (G_output/kernel [g, N], G_output/bias [N])
+    const int N = h->N, e = h->e, g = h->cf.g, L = h->L, Lg = h->cf.Lg;
+    if (id >= 0 && id <= 2 * L + 1) {
+      if (id == 2 * L) { v->rows = e; v->cols = 1; v->nseg = 1; v->seg[0] = {&h->Wo, 0, 0, 1, e, 0}; return true; }
+      if (id == 2 * L + 1) return one(&h->Wo, 0, e, 1, 1);
+      const int l = id / 2;
+      if (id & 1) return one(&h->Wl[l], l == 0 ? 2 * N : e, 0, 1, e);
+      return one(&h->Wl[l], 0, 0, l == 0 ? 2 * N : e, e);
+    }
+    const int gid = id - GANMF_T_CFGAN_G0;
+    if (!h->cf.ready || gid < 0 || gid > 2 * Lg + 1) return false;
+    if (gid == 2 * Lg) return one(&h->cf.Go, 0, 0, g, N);
+    if (gid == 2 * Lg + 1) return one(&h->cf.Go, g, 0, 1, N);
+    const int l = gid / 2;
+    if (gid & 1) return one(&h->cf.Gl[l], l == 0 ? N : g, 0, 1, g);
+    return one(&h->cf.Gl[l], 0, 0, l == 0 ? N : g, g);
+  }
   if (id == GANMF_T_USER_EMB) return one(&h->Ue, 0, 0, h->U, h->k);
   if (id == GANMF_T_ITEM_EMB) return one(&h->V, 0, 0, h->N, h->k);
   if (h->cfg.model == GANMF_MODEL_MF) return false;      // the two factor tensors are all such a handle holds
@@ -98,6 +125,13 @@ bool find_view(ganmf_handle* h, int id, View* v) {
 std::vector<Tensor*> all_tensors(ganmf_handle* h) {
   std::vector<Tensor*> v;
   if (h->cfg.model == GANMF_MODEL_ITEMSIM) return v;
+  if (h->cfg.model == GANMF_MODEL_CFGAN) {      // no factor tensors: the discriminator's layers, then the generator's
+    for (auto& t : h->Wl) v.push_back(&t);
+    v.push_back(&h->Wo);
+    for (auto& t : h->cf.Gl) v.push_back(&t);
+    if (h->cf.ready) v.push_back(&h->cf.Go);
+    return v;
+  }
   v = {&h->Ue, &h->V};
   if (h->cfg.model == GANMF_MODEL_GANMF) { v.push_back(&h->We); v.push_back(&h->Wd); }
   else if (h->cfg.model == GANMF_MODEL_DISGANMF) { for (auto& t : h->Wl) v.push_back(&t); v.push_back(&h->Wo); }

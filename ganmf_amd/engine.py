@@ -480,6 +480,61 @@ class Engine:
                 "ganmf_slim_bpr_get_state")
         return {"S": S, "state0": s0, "state1": s1, "beta_powers": pw, "epoch": int(epoch.value)}
 
+    # -- CFGAN (ganmf_cfgan_*, a MODEL_CFGAN engine) ------------------------------------------------
+    def cfgan_init(self, g_nodes, g_layers, g_act, d_batch, g_batch, scheme, zr_coefficient, seed, k_rows):
+        """The generator, the two batch sizes, the scheme ("ZR" | "PM" | "ZP"), the zero-reconstruction coefficient, the mask
+        sampler's seed and the subset size of every row (ganmf_cfgan_init); once per engine."""
+        k = np.ascontiguousarray(k_rows, dtype=np.int32).ravel()
+        assert k.size == self.num_users
+        self._cfgan_batches = (min(int(d_batch), self.num_users), min(int(g_batch), self.num_users))
+        L.check(self.lib.ganmf_cfgan_init(self.h, int(g_nodes), int(g_layers), L.ACT[g_act], int(d_batch), int(g_batch),
+                                          L.CFGAN_SCHEMES[scheme], float(zr_coefficient), int(seed) & (2 ** 64 - 1), _i32p(k)),
+                "ganmf_cfgan_init")
+
+    @property
+    def cfgan_words(self):
+        """32-bit words per row of a mask plane"""
+        return (self.num_items + 31) // 32
+
+    def cfgan_draw_masks(self, epoch):
+        """the device sampler's masks of `epoch` (ganmf_cfgan_draw_masks)"""
+        L.check(self.lib.ganmf_cfgan_draw_masks(self.h, int(epoch)), "ganmf_cfgan_draw_masks")
+
+    def cfgan_set_masks(self, zr=None, pm=None):
+        """Uploads the two bit planes, uint32 [num_users, cfgan_words] each (pack_mask_rows' layout); None clears a plane."""
+        planes = []
+        for a in (zr, pm):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+                assert a.shape == (self.num_users, self.cfgan_words)
+            planes.append(a)
+        u32p = C.POINTER(C.c_uint32)
+        L.check(self.lib.ganmf_cfgan_set_masks(self.h, *[a.ctypes.data_as(u32p) if a is not None else None for a in planes]),
+                "ganmf_cfgan_set_masks")
+
+    def cfgan_masks(self):
+        """(zr, pm): the two bit planes held, uint32 [num_users, cfgan_words] each (ganmf_cfgan_get_masks)"""
+        out = [np.zeros((self.num_users, self.cfgan_words), dtype=np.uint32) for _ in range(2)]
+        u32p = C.POINTER(C.c_uint32)
+        L.check(self.lib.ganmf_cfgan_get_masks(self.h, out[0].ctypes.data_as(u32p), out[1].ctypes.data_as(u32p)), "ganmf_cfgan_get_masks")
+        return out[0], out[1]
+
+    def cfgan_step(self, kind, row0, nrows):
+        """one optimiser step (0: D, 1: G) on the rows [row0, row0 + nrows); returns its loss (ganmf_cfgan_step)"""
+        loss = C.c_float()
+        L.check(self.lib.ganmf_cfgan_step(self.h, int(kind), int(row0), int(nrows), C.byref(loss)), "ganmf_cfgan_step")
+        return np.float32(loss.value)
+
+    def cfgan_epoch(self, epoch, d_steps=1, g_steps=1, draw=True):
+        """One epoch in one call (ganmf_cfgan_epoch): the masks of `epoch` when draw, d_steps passes of D steps, g_steps passes of
+        G steps.  Returns (d_losses, g_losses), one float32 per step."""
+        db, gb = self._cfgan_batches
+        nd, ng = int(d_steps) * (-(-self.num_users // db)), int(g_steps) * (-(-self.num_users // gb))
+        dl, gl = np.zeros(max(nd, 1), dtype=np.float32), np.zeros(max(ng, 1), dtype=np.float32)
+        L.check(self.lib.ganmf_cfgan_epoch(self.h, int(epoch), int(d_steps), int(g_steps), int(bool(draw)), _f32p(dl), _f32p(gl)),
+                "ganmf_cfgan_epoch")
+        return dl[:nd], gl[:ng]
+
     def item_similarity(self):
         """The held item similarity matrix as the reference lays W_sparse out (ganmf_itemknn_get): scipy CSR float32
         [num_items, num_items], rows = neighbour, columns = item."""

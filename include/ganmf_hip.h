@@ -43,7 +43,17 @@ typedef struct ganmf_handle ganmf_handle;
  * the score filter, the ignore list and the seen / test uploads work unchanged: only the source of the score rows differs.  The
  * training, discriminator, tensor, snapshot, ALS, SVD, candidate and score-similarity entries return -1 on it with a message that
  * names the model, and enqueue nothing.  The enum gained a value; no structure or signature changed: GANMF_ABI_VERSION stays. */
-enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2, GANMF_MODEL_ITEMSIM = 3 };
+/* GANMF_MODEL_CFGAN: CFGAN (GANRec/CFGAN.py): an MLP generator over the row's own profile and an MLP discriminator over [profile |
+ * profile-shaped input], trained with per-epoch zero-reconstruction / partial-masking masks.  emb_dim, d_layers, d_act, d_lr, g_lr, d_reg
+ * and g_reg of ganmf_cfg describe the discriminator and the two optimisers; batch_size is the larger of the two batch sizes;
+ * num_factors, m and recon_coefficient are ignored (num_factors must still be >= 1); world_size must be 1 and the bf16 / fp16 MFMA flags
+ * are refused.  ganmf_cfgan_init supplies the rest (below).  The handle holds no factor tensors.  The tensor, snapshot, seen / test
+ * upload, ganmf_scores, ganmf_recommend, ganmf_evaluate* (candidates = 0), score filter, ignore list and score-similarity entries work
+ * unchanged: only the source of the score rows differs (transposed = 0: G(profile of row id); transposed = 1: rows of the transposed
+ * G(all rows), cached on the device until a parameter changes).  ganmf_train_epoch / _epoch_ragged / _step, ganmf_discriminate,
+ * ganmf_als_half_sweep, ganmf_pure_svd, the item-similarity, P3 and SLIM entries, the candidate entries, ganmf_bench_scores and the two
+ * communicator entries return -1 on it with a message that names the model.  The enum gained a value; no structure or signature changed: GANMF_ABI_VERSION stays. */
+enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2, GANMF_MODEL_ITEMSIM = 3, GANMF_MODEL_CFGAN = 4 };
 enum { GANMF_ACT_LINEAR = 0, GANMF_ACT_TANH = 1, GANMF_ACT_RELU = 2, GANMF_ACT_SIGMOID = 3 };
 
 /* Tensor ids.  Discriminator tensors are numbered in the order of the reference's
@@ -53,6 +63,10 @@ enum { GANMF_ACT_LINEAR = 0, GANMF_ACT_TANH = 1, GANMF_ACT_RELU = 2, GANMF_ACT_S
  * Generator tensors (GANMF.py:122): */
 #define GANMF_T_USER_EMB 100 /* generator/user_embeddings [U,k] */
 #define GANMF_T_ITEM_EMB 101 /* generator/item_embeddings [N,k] */
+/* CFGAN: the discriminator's ids are DisGANMF's (2l D_hidden_l/kernel -- layer 0 is [2N, e], condition rows first -- 2l+1 its bias,
+ * 2L D_output/kernel [e,1], 2L+1 D_output/bias [1]); the generator's start here and are laid out the same way:
+ * G0 + 2l G_hidden_l/kernel ([N, g] for l = 0, else [g, g]), G0 + 2l+1 its bias, G0 + 2Lg G_output/kernel [g, N], G0 + 2Lg+1 G_output/bias [N] */
+#define GANMF_T_CFGAN_G0 200
 
 /* which copy of a tensor */
 enum { GANMF_SLOT_PARAM = 0, GANMF_SLOT_ADAM_M = 1, GANMF_SLOT_ADAM_V = 2, GANMF_SLOT_BEST = 3 };
@@ -580,6 +594,33 @@ int ganmf_slim_bpr_run(ganmf_handle* h, const int32_t* users, const int32_t* pos
 int ganmf_slim_bpr_epochs(ganmf_handle* h, int64_t n_epochs, int mode, int64_t* n_levels);
 int ganmf_slim_bpr_finish(ganmf_handle* h, int32_t topk, int64_t* nnz);
 int ganmf_slim_bpr_get_state(ganmf_handle* h, double* S, double* state0, double* state1, double* beta_powers, int64_t* epoch);
+
+/* ---- CFGAN (GANRec/CFGAN.py) on a GANMF_MODEL_CFGAN handle -------------------------------------------------------------------
+ * ganmf_cfgan_init: the generator (g_layers >= 1 hidden layers of g_nodes with activation g_act, then a linear layer of width
+ *   num_items), the two batch sizes (each clipped to num_users; the larger must not exceed the handle's batch_size), the scheme, the
+ *   zero-reconstruction coefficient, the mask sampler's seed and the subset size k_rows[r] of every row (formed by the caller: the
+ *   reference sizes BOTH masks by int(n * float(zr_ratio))).  Once per handle.  All parameters start at zero: ganmf_set_tensor.
+ * ganmf_cfgan_draw_masks: the device sampler for `epoch`.  For every row and every plane the scheme uses (ZR: the zero-reconstruction
+ *   plane; PM: the partial-masking plane; ZP: both, independent) the k_rows[r] non-interactions with the smallest 32-bit keys, ties to
+ *   the smaller column; key = high half of the splitmix64 output function over a counter packed from (seed, epoch, plane, row, column).
+ *   A pure function of those five: the same bytes on every call and every device.  Needs ganmf_set_urm_csr.
+ * ganmf_cfgan_set_masks / ganmf_cfgan_get_masks: the two bit planes [num_users, ceil(num_items / 32)] of 32-bit words, bit (j & 31)
+ *   of word (j >> 5) = column j (np.packbits(..., bitorder='little') viewed as little-endian uint32).  set: a NULL plane is cleared;
+ *   get: a NULL pointer is skipped.  A set bit on a profile column is the caller's business (the reference's masks never have one).
+ * ganmf_cfgan_step: one optimiser step (kind 0: discriminator, 1: generator) on the training rows [row0, row0 + nrows) with the masks
+ *   held; *loss (may be NULL) receives the step's loss at the pre-update parameters.
+ * ganmf_cfgan_epoch: one epoch in one call, nothing crossing the bus inside it: with draw != 0 the masks of `epoch`, then d_steps
+ *   passes of discriminator steps over rows 0.. in slices of d_batch, then g_steps passes of generator steps in slices of g_batch
+ *   (last slice ragged, no shuffle); d_losses [d_steps * ceil(U / d_batch)] and g_losses likewise receive every step's loss.  The
+ *   same kernels in the same order as the same slices through ganmf_cfgan_step: the same bytes. */
+enum { GANMF_CFGAN_ZR = 0, GANMF_CFGAN_PM = 1, GANMF_CFGAN_ZP = 2 };
+int ganmf_cfgan_init(ganmf_handle* h, int32_t g_nodes, int32_t g_layers, int g_act, int32_t d_batch, int32_t g_batch, int scheme,
+                     float zr_coefficient, uint64_t seed, const int32_t* k_rows);
+int ganmf_cfgan_draw_masks(ganmf_handle* h, int64_t epoch);
+int ganmf_cfgan_set_masks(ganmf_handle* h, const uint32_t* zr, const uint32_t* pm);
+int ganmf_cfgan_get_masks(ganmf_handle* h, uint32_t* zr, uint32_t* pm);
+int ganmf_cfgan_step(ganmf_handle* h, int kind, int64_t row0, int32_t nrows, float* loss);
+int ganmf_cfgan_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g_steps, int draw, float* d_losses, float* g_losses);
 
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
