@@ -123,14 +123,10 @@ class ItemKNNCFRecommender(SimilarityModelMixin, DeviceScoringMixin, BaseRecomme
         den_a = den_b = None
         if binarise:
             # the similarity sees ones at the stored entries; the scores keep URM_train's values
-            ones = sps.csr_matrix(self.URM_train, dtype=np.float32, copy=True)
-            ones.sum_duplicates()
-            ones.sort_indices()
+            ones = self._canonical(self.URM_train)
             ones.data[:] = 1.0
-            by_item = ones.tocsc()
-            by_item.sort_indices()
-            self.engine.set_confidence(1, sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr),
-                                                         shape=(self.n_items, self.n_users)))
+            by_item = self._urm_by_item(ones)
+            self.engine.set_confidence(1, by_item)
             den_a = np.diff(by_item.indptr).astype(np.float64)      # sums of squares of a column of ones
         elif kind == L.ITEMKNN_PRODUCT:
             data32 = sps.csc_matrix(self.URM_train, dtype=np.float32)      # what the device multiplies
@@ -142,9 +138,5 @@ class ItemKNNCFRecommender(SimilarityModelMixin, DeviceScoringMixin, BaseRecomme
             else:
                 den_a = den_b = norm
         self.engine.itemknn_fit(kind, topk, shrink=float(shrink), p0=p0, p1=p1, den_a=den_a, den_b=den_b)
-        if binarise:      # side 1 back to URM_train's own values (nothing reads it after the fit; kept consistent with side 0)
-            by_item = sps.csc_matrix(self.URM_train, dtype=np.float32)
-            by_item.sum_duplicates()
-            by_item.sort_indices()
-            self.engine.set_confidence(1, sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr),
-                                                         shape=(self.n_items, self.n_users)))
+        if binarise:
+            self._restore_side1()

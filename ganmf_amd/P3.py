@@ -24,9 +24,7 @@ def transition_terms(URM_train, alpha, beta=None):
     pui_by_item: items x users CSR in canonical form, the pattern of URM_train by item with the values (x_ui / sum_j |x_uj|)^alpha;
     col_scale[j] = deg_j^-beta (0 where deg_j = 0), None when beta is None.
     deg counts STORED entries: an explicit zero counts (the reference sets ones at every stored entry of the transpose)."""
-    urm = sps.csr_matrix(URM_train, dtype=np.float32, copy=True)
-    urm.sum_duplicates()
-    urm.sort_indices()
+    urm = SimilarityModelMixin._canonical(URM_train)
     n_users, n_items = urm.shape
     lengths = np.diff(urm.indptr)
     x = urm.data.astype(np.float64)
@@ -45,9 +43,7 @@ def transition_terms(URM_train, alpha, beta=None):
         col_scale = np.zeros(n_items, dtype=np.float64)
         col_scale[some] = np.power(deg[some], -float(beta))
         col_scale = col_scale.astype(np.float32)
-    by_item = sps.csr_matrix((p.astype(np.float32), urm.indices, urm.indptr), shape=urm.shape).tocsc()
-    by_item.sort_indices()
-    pui_by_item = sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr), shape=(n_items, n_users))
+    pui_by_item = SimilarityModelMixin._urm_by_item(sps.csr_matrix((p.astype(np.float32), urm.indices, urm.indptr), shape=urm.shape))
     return row_scale.astype(np.float32), pui_by_item, col_scale
 
 
@@ -102,12 +98,7 @@ class _GraphWalkRecommender(SimilarityModelMixin, DeviceScoringMixin, BaseRecomm
         row_scale, pui_by_item, col_scale = transition_terms(self.URM_train, alpha, beta)
         self.engine.set_confidence(1, pui_by_item)      # the walk reads the transition weights where the URM by item was
         self.engine.p3_fit(topk, row_scale, col_scale=col_scale, normalize=bool(normalize_similarity), col_topk=topk)
-        # side 1 back to URM_train's own values (nothing reads it after the fit; kept consistent with side 0)
-        by_item = sps.csc_matrix(self.URM_train, dtype=np.float32)
-        by_item.sum_duplicates()
-        by_item.sort_indices()
-        self.engine.set_confidence(1, sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr),
-                                                     shape=(self.n_items, self.n_users)))
+        self._restore_side1()
 
 
 class P3alphaRecommender(_GraphWalkRecommender):

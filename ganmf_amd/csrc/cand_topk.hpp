@@ -17,7 +17,7 @@
 //   RMSE        (kRmse, ganmf_evaluate_candidates with counts) as mask_topk_rmse_kernel forms it, thread for thread: squared fp32
 //               errors over r's test items, finite ones only -- a test item that is no candidate scores -inf under the MF contract's
 //               items_to_compute rule and drops out -- NaN without any.
-//   selection   `cutoff` rounds of a block-wide arg-max with removal over the candidate POSITIONS; ties go to the smaller position =
+//   selection   `cutoff` rounds of block_argmax (topk_rounds.hpp) with removal over the candidate POSITIONS; ties go to the smaller position =
 //               the smaller item id.  Outputs are global item ids and scores, [n, cutoff], padded with -1 / -inf: the layout
 //               eval_topk_kernel / eval_topk_full_kernel read.  An exhausted row pads the rest at once and stops.
 #pragma once
@@ -191,26 +191,10 @@ __device__ __forceinline__ void cand_topk_body(const CandP& p, const RmseP& rp) 
   int* oi = p.out_items + (size_t)b * p.cutoff;
   float* ov = p.out_vals + (size_t)b * p.cutoff;
   for (int t = 0; t < p.cutoff; ++t) {
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int j = tid; j < nc; j += 256) {
-      const float v = s[j];
-      if (v > bv) { bv = v; bi = j; }       // strided scan visits positions in increasing order: first max wins
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float xv = __shfl_xor(bv, o);
-      const int xi = __shfl_xor(bi, o);
-      if (xv > bv || (xv == bv && xi < bi)) { bv = xv; bi = xi; }
-    }
-    if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
-    __syncthreads();
-    float v = wv[0];
-    int i = wi[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (wv[w] > v || (wv[w] == v && wi[w] < i)) { v = wv[w]; i = wi[w]; }
-    const bool ok = v > -INFINITY && i != 0x7fffffff;      // the same for every thread
+    block_argmax(s, nc, wv, wi);
+    float v;
+    int i;
+    const bool ok = argmax_of_waves(wv, wi, &v, &i);      // every thread folds the slots: the same for every thread
     if (!ok) {
       for (int t2 = t + tid; t2 < p.cutoff; t2 += 256) { oi[t2] = -1; ov[t2] = -INFINITY; }
       break;

@@ -38,6 +38,7 @@
 #include "gemm_bf16k.hpp"
 #include "gemm_persist.hpp"
 #include "gemm_bf16p.hpp"
+#include "topk_rounds.hpp"
 #include "kernels.hpp"
 #include "cand_topk.hpp"
 #include "list_diversity.hpp"

@@ -4,8 +4,9 @@
 //
 // Fit: one workgroup per target item i.  The [n_items, n_items] matrix of dot products never exists: a workgroup holds ONE row of it
 // -- w_j = sum_u x_ui x_uj for every j -- in LDS (KNN_ROW_LDS floats; wider catalogues: a private row in global memory, one per
-// workgroup of the grid), applies the similarity's denominator, and selects the top-k of the row with the arg-max rounds of
-// mask_topk_kernel (kernels.hpp): ties go to the smaller item id.
+// workgroup of the grid), applies the similarity's denominator, and selects the top-k of the row with select_topk_nonzero
+// (topk_rounds.hpp, the arg-max rounds of mask_topk_kernel): ties go to the smaller item id, zeros are dropped.  The row builder,
+// SimRowP and sim_row_accumulate, is shared with p3_rows_kernel (p3_rows.hpp); only what fills the slab differs.
 //   w_j: column i of the URM (row i of side 1 of ganmf_als_set_confidence, users ascending) is expanded into a dense vector over one
 //   slab of KNN_SLAB users in LDS; thread t owns the items j = t, t + 256, ... and walks column j's entries inside the slab in stored
 //   order.  Slabs are taken in ascending order and slabs without an entry of column i are skipped, so every w_j is one fp32 FMA chain
@@ -17,10 +18,12 @@
 // nothing is stored.  Catalogues above KNN_SCORE_LDS floats read the dense profiles from global memory instead.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "topk_rounds.hpp"
 
 namespace ganmf {
 
 constexpr int KNN_THREADS = 256;
+static_assert(KNN_THREADS == TOPK_THREADS, "the fits select with the rounds of topk_rounds.hpp");
 constexpr int KNN_MAX_TOPK = 1024;      // GANMF_ITEMKNN_MAX_TOPK: the selection's bound (GANMF_RECOMMEND_MAX_CUTOFF)
 constexpr int KNN_SLAB = 8192;          // users per LDS slab of the fit (32 KiB)
 constexpr int KNN_ROW_LDS = 28672;      // floats of the similarity row kept in LDS (112 KiB; with the slab 144 KiB of the CU's 160)
@@ -28,15 +31,13 @@ constexpr int KNN_SCORE_LDS = 32768;    // floats of dense profiles a scoring wo
 constexpr int KNN_SCORE_GROUP = 16384;  // ... and what G > 1 users may take together (64 KiB: two workgroups per CU)
 enum KnnKind : int { KNN_PRODUCT = 0, KNN_TANIMOTO = 1, KNN_DICE = 2, KNN_TVERSKY = 3, KNN_SHRINK_ONLY = 4, KNN_RAW = 5, KNN_KINDS = 6 };
 
-struct KnnFitP {
+// What the row builders of the item-similarity fits share (itemknn_fit_kernel here, p3_rows_kernel in p3_rows.hpp)
+struct SimRowP {
   const long long* c_indptr;   // side 1: items x users, users ascending inside an item
   const int* c_users;
   const float* c_val;
   int n_items, n_users;
-  int kind, topk;              // topk <= min(KNN_MAX_TOPK, n_items)
-  float s, shrink, p0, p1;     // s = shrink + 1e-6 (formed in float64 by the host)
-  const float* den_a;          // [n_items], per kind (KnnKind); den_b: PRODUCT only
-  const float* den_b;
+  int topk;                    // <= min(KNN_MAX_TOPK, n_items)
   int slab;                    // users per slab (<= KNN_SLAB): the first `slab` floats of the dynamic LDS
   int row_lds;                 // 1: the row follows the slab in LDS; 0: row_glob + blockIdx.x * ld_row
   float* row_glob;
@@ -46,6 +47,13 @@ struct KnnFitP {
   int* out_cnt;                // [n_items] stored picks (the non-zero ones)
 };
 
+struct KnnFitP : SimRowP {
+  int kind;                    // KnnKind
+  float s, shrink, p0, p1;     // s = shrink + 1e-6 (formed in float64 by the host)
+  const float* den_a;          // [n_items], per kind (KnnKind); den_b: PRODUCT only
+  const float* den_b;
+};
+
 // first position in [a, b) whose user is >= u
 __device__ __forceinline__ long long knn_lower_bound(const int* __restrict__ users, long long a, long long b, int u) {
   while (a < b) {
@@ -53,6 +61,41 @@ __device__ __forceinline__ long long knn_lower_bound(const int* __restrict__ use
     if (users[m] < u) a = m + 1; else b = m;
   }
   return a;
+}
+
+// The slab walk: w_j = sum_u fill(q_u) c_val[u, j] for every j, where column i of side 1 -- expanded into the slab xs with fill(q) at
+// the user of its stored entry q, 0 elsewhere -- is one factor and column j the other.  One slab of users at a time, ascending, slabs
+// without an entry of column i skipped; thread t owns the items j = t, t + 256, ... so every w_j is one fp32 FMA chain over ascending
+// users.  Called by the whole workgroup; ends behind a barrier.
+template <typename FillFn>
+__device__ __forceinline__ void sim_row_accumulate(const SimRowP& p, float* xs, float* w, int i, FillFn fill) {
+  const int tid = threadIdx.x, n = p.n_items;
+  const long long cs = p.c_indptr[i], ce = p.c_indptr[i + 1];
+  for (int j = tid; j < n; j += KNN_THREADS) w[j] = 0.f;
+  long long at = cs;      // first entry of column i not yet expanded (the same value in every thread)
+  while (at < ce) {
+    const int base = (p.c_users[at] / p.slab) * p.slab;      // the next slab that holds an entry of column i
+    const long long top = (long long)base + p.slab;
+    const long long end = top > p.n_users ? ce : knn_lower_bound(p.c_users, at, ce, (int)top);
+    __syncthreads();      // the readers of the slab before this one (and the zero fill of w) are done
+    for (int t = tid; t < p.slab; t += KNN_THREADS) xs[t] = 0.f;
+    __syncthreads();
+    for (long long q = at + tid; q < end; q += KNN_THREADS) xs[p.c_users[q] - base] = fill(q);
+    __syncthreads();
+    for (int j = tid; j < n; j += KNN_THREADS) {
+      const long long a = p.c_indptr[j], b = p.c_indptr[j + 1];
+      long long q = base == 0 ? a : knn_lower_bound(p.c_users, a, b, base);
+      float acc = w[j];
+      for (; q < b; ++q) {
+        const int u = p.c_users[q];
+        if (u >= top) break;
+        acc = fmaf(xs[u - base], p.c_val[q], acc);
+      }
+      w[j] = acc;
+    }
+    at = end;
+  }
+  __syncthreads();
 }
 
 __device__ __forceinline__ float knn_value(const KnnFitP& p, float w, float dai, int j) {
@@ -71,38 +114,13 @@ __global__ __launch_bounds__(KNN_THREADS) void itemknn_fit_kernel(const KnnFitP 
   __shared__ float wv[4];
   __shared__ int wi[4];
   __shared__ int s_stop;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   float* xs = knn_lds;
   float* w = p.row_lds ? knn_lds + p.slab : p.row_glob + (size_t)blockIdx.x * p.ld_row;
   const int n = p.n_items;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
-    const long long cs = p.c_indptr[i], ce = p.c_indptr[i + 1];
-    for (int j = tid; j < n; j += KNN_THREADS) w[j] = 0.f;
-    // ---- w_j = sum_u x_ui x_uj, one slab of users at a time, ascending ----
-    long long at = cs;      // first entry of column i not yet expanded (the same value in every thread)
-    while (at < ce) {
-      const int base = (p.c_users[at] / p.slab) * p.slab;      // the next slab that holds an entry of column i
-      const long long top = (long long)base + p.slab;
-      const long long end = top > p.n_users ? ce : knn_lower_bound(p.c_users, at, ce, (int)top);
-      __syncthreads();      // the readers of the slab before this one (and the zero fill of w) are done
-      for (int t = tid; t < p.slab; t += KNN_THREADS) xs[t] = 0.f;
-      __syncthreads();
-      for (long long q = at + tid; q < end; q += KNN_THREADS) xs[p.c_users[q] - base] = p.c_val[q];
-      __syncthreads();
-      for (int j = tid; j < n; j += KNN_THREADS) {
-        const long long a = p.c_indptr[j], b = p.c_indptr[j + 1];
-        long long q = base == 0 ? a : knn_lower_bound(p.c_users, a, b, base);
-        float acc = w[j];
-        for (; q < b; ++q) {
-          const int u = p.c_users[q];
-          if (u >= top) break;
-          acc = fmaf(xs[u - base], p.c_val[q], acc);
-        }
-        w[j] = acc;
-      }
-      at = end;
-    }
-    __syncthreads();
+    // ---- w_j = sum_u x_ui x_uj: the slab holds the stored values of column i ----
+    sim_row_accumulate(p, xs, w, i, [&p](long long q) { return p.c_val[q]; });
     // ---- w_i = 0, the similarity's denominator (thread t owns the same j as above) ----
     const float dai = p.den_a ? p.den_a[i] : 0.f;
     int neg = 0;
@@ -114,42 +132,9 @@ __global__ __launch_bounds__(KNN_THREADS) void itemknn_fit_kernel(const KnnFitP 
       w[j] = v;
     }
     const int any_neg = __syncthreads_or(neg);
-    // ---- the topk largest of the row, the non-zero ones stored (Compute_Similarity_Python.py:346-356): arg-max rounds with removal ----
-    int cnt = 0;
-    for (int t = 0; t < p.topk; ++t) {
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int j = tid; j < n; j += KNN_THREADS) {
-        const float v = w[j];
-        if (v > bv) { bv = v; bi = j; }      // strided scan visits ids in increasing order: first max wins
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-      }
-      if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
-      __syncthreads();
-      if (tid == 0) {
-        float v = wv[0];
-        int b = wi[0];
-        for (int q = 1; q < 4; ++q)
-          if (wv[q] > v || (wv[q] == v && wi[q] < b)) { v = wv[q]; b = wi[q]; }
-        const bool ok = v > -INFINITY && b != 0x7fffffff;
-        if (ok && v != 0.f) {
-          p.out_idx[(size_t)i * p.topk + cnt] = b;
-          p.out_val[(size_t)i * p.topk + cnt] = v;
-          ++cnt;
-        }
-        if (ok) w[b] = -INFINITY;
-        // nothing left, or only zeros left in a row without negative values: no later round stores anything
-        s_stop = (!ok || (v == 0.f && !any_neg)) ? 1 : 0;
-      }
-      __syncthreads();
-      if (s_stop) break;
-    }
-    if (tid == 0) p.out_cnt[i] = cnt;
+    // ---- the topk largest of the row, the non-zero ones stored (Compute_Similarity_Python.py:346-356) ----
+    select_topk_nonzero(w, n, p.topk, any_neg, p.out_idx + (size_t)i * p.topk, p.out_val + (size_t)i * p.topk, p.out_cnt + i, wv, wi,
+                        &s_stop);
     __syncthreads();      // (s_stop, wv / wi and the row are reused by the next item)
   }
 }

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gemm_f32.hpp"
+#include "topk_rounds.hpp"
 
 namespace ganmf {
 
@@ -1025,7 +1026,7 @@ __global__ __launch_bounds__(64 * UIDG_GROUPS) void dis_uid_grad_kernel(const fl
 // ---- recommend(): seen items -> -inf, then top-k by score (Base/BaseRecommender.py:189-234) ---------
 // One workgroup per score row.  The row is staged in LDS when it fits (lds_cap floats), otherwise the
 // selection works in place on the (private) score buffer.  k rounds of a block-wide arg-max with
-// removal; ties go to the smaller item id; exhausted rows (everything -inf) yield -1.
+// removal (block_argmax, topk_rounds.hpp); ties go to the smaller item id; exhausted rows (everything -inf) yield -1.
 // kRmse (ganmf_evaluate_full): between the masking and the first selection round -- the in-place path overwrites every picked
 // item with -inf -- the row's RMSE over the user's test items (Base/Evaluation/metrics.py:634 rmse on the score row that
 // recommend(..., return_scores=True) returns): squared fp32 errors of the finite ones, summed in a fixed order, NaN without any.
@@ -1089,25 +1090,11 @@ __device__ __forceinline__ void mask_topk_body(float* __restrict__ scores, int l
     }
   }
   for (int t = 0; t < k; ++t) {
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < W; i += 256) {
-      const float v = row[i];
-      if (v > bv) { bv = v; bi = i; }       // strided scan visits ids in increasing order: first max wins
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
-    __syncthreads();
+    block_argmax(row, W, wv, wi);
     if (tid == 0) {
-      float v = wv[0]; int i = wi[0];
-      for (int w = 1; w < 4; ++w)
-        if (wv[w] > v || (wv[w] == v && wi[w] < i)) { v = wv[w]; i = wi[w]; }
-      const bool ok = v > -INFINITY && i != 0x7fffffff;
+      float v;
+      int i;
+      const bool ok = argmax_of_waves(wv, wi, &v, &i);
       out_items[(size_t)r * k + t] = ok ? i : -1;
       out_vals[(size_t)r * k + t] = ok ? v : -INFINITY;
       if (ok) row[i] = -INFINITY;

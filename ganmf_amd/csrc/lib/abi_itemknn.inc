@@ -70,10 +70,130 @@ static int itemsim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W
   return 0;
 }
 
-// the held matrix is dropped (a failed fit or upload leaves "no matrix")
+// The held matrix is dropped.  Every fit and upload drops first and sets h->knn_nnz LAST, behind its final synchronise: any failure
+// in between leaves "no matrix" (knn_nnz < 0), whatever has been allocated by then (the next drop or the handle's end frees it).
 static void itemsim_drop(ganmf_handle* h) {
   hipFree(h->knn_indptr); hipFree(h->knn_nbr); hipFree(h->knn_val);
   h->knn_indptr = nullptr; h->knn_nbr = nullptr; h->knn_val = nullptr; h->knn_nnz = -1;
+}
+
+// ---- what the fits share (ganmf_itemknn_fit, ganmf_p3_fit, ganmf_slim_bpr_finish) --------------------------------------------------
+// The picks of one selection pass -- [n, k] ids and values in descending order of value, [n] counts -- and the private rows of the
+// global route, released on every way out.
+struct SimPicks {
+  int *idx = nullptr, *cnt = nullptr;
+  float *val = nullptr, *row = nullptr;
+  int alloc(int n, int k, size_t row_floats) {
+    if (row_floats) HIP_TRY(hipMalloc((void**)&row, row_floats * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&idx, (size_t)n * k * sizeof(int)));
+    HIP_TRY(hipMalloc((void**)&val, (size_t)n * k * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&cnt, (size_t)n * sizeof(int)));
+    return 0;
+  }
+  ~SimPicks() { hipFree(idx); hipFree(cnt); hipFree(val); hipFree(row); }
+};
+// a compact matrix between two passes (R of ganmf_p3_fit and of ganmf_slim_bpr_finish)
+struct SimCsr {
+  long long* indptr = nullptr;
+  int* idx = nullptr;
+  float* val = nullptr;
+  long long nnz = 0;
+  ~SimCsr() { hipFree(indptr); hipFree(idx); hipFree(val); }
+};
+// host vectors of a fit on the device, released on every way out
+struct SimFloats {
+  float *a = nullptr, *b = nullptr;
+  ~SimFloats() { hipFree(a); hipFree(b); }
+};
+static int upload_floats(float** dst, const float* src, int n) {
+  HIP_TRY(hipMalloc((void**)dst, (size_t)n * sizeof(float)));
+  HIP_TRY(hipMemcpy(*dst, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Where a workgroup keeps its dense row of n floats: in LDS up to KNN_ROW_LDS items, one workgroup per item up to 8192 of them; above,
+// a private row in global memory ([grid, ld_row] floats), at most 512 workgroups.
+struct SimRowPlan {
+  int row_lds;
+  unsigned grid;
+  long long ld_row;
+  size_t row_floats() const { return row_lds ? 0 : (size_t)grid * ld_row; }
+};
+static SimRowPlan itemsim_row_plan(int n) {
+  SimRowPlan r{};
+  r.row_lds = n <= KNN_ROW_LDS ? 1 : 0;
+  r.grid = (unsigned)std::min(n, r.row_lds ? 8192 : 512);
+  r.ld_row = r.row_lds ? 0 : round_up(n, LD_ALIGN);
+  return r;
+}
+
+// What the two row builders read (SimRowP: side 1, the slab, the plan's row, the picks); returns the dynamic LDS of their launch:
+// the slab, and behind it the row where the plan keeps it in LDS.
+static size_t itemsim_row_args(ganmf_handle* h, int k, const SimRowPlan& plan, const SimPicks& t, SimRowP* p) {
+  const AlsSide& s = h->als[1];
+  p->c_indptr = s.indptr; p->c_users = s.indices; p->c_val = s.conf;
+  p->n_items = h->N; p->n_users = h->U; p->topk = k;
+  p->slab = std::min(KNN_SLAB, round_up(h->U, 64));
+  p->row_lds = plan.row_lds; p->row_glob = t.row; p->ld_row = plan.ld_row;
+  p->out_idx = t.idx; p->out_val = t.val; p->out_cnt = t.cnt;
+  return ((size_t)p->slab + (plan.row_lds ? (size_t)h->N : 0)) * sizeof(float);
+}
+
+// [n] counts from the device (enqueued behind the kernel that wrote them) to an indptr on the host
+static int itemsim_indptr(ganmf_handle* h, const char* who, const int* cnt_dev, int n, long long most, std::vector<int64_t>& ip) {
+  std::vector<int> cnt((size_t)n);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), cnt_dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  ip.assign((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (cnt[(size_t)i] < 0 || cnt[(size_t)i] > most) return fail(-2, "%s: item %d reports %d entries of at most %lld", who, i, cnt[(size_t)i], most);
+    ip[(size_t)i + 1] = ip[(size_t)i] + cnt[(size_t)i];
+  }
+  return 0;
+}
+
+// the three arrays of a compact [n, n] matrix (one element where it is empty), its indptr uploaded
+static int itemsim_alloc(const int64_t* ip, int n, long long** indptr, int** idx, float** val) {
+  const size_t room = (size_t)std::max<int64_t>(ip[n], 1);
+  HIP_TRY(hipMalloc((void**)indptr, (size_t)(n + 1) * sizeof(long long)));
+  HIP_TRY(hipMalloc((void**)idx, room * sizeof(int)));
+  HIP_TRY(hipMalloc((void**)val, room * sizeof(float)));
+  HIP_TRY(hipMemcpy(*indptr, ip, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// The picks of a pass (k per item in their layout, at most `most` stored) to a compact matrix, ids ascending inside an item: the
+// counts read back, the indptr formed and checked, the matrix allocated, itemknn_pack_kernel.  Into temporaries between two passes,
+// into the handle for the result.
+static int itemsim_compact(ganmf_handle* h, const char* who, const SimPicks& t, int k, long long most, long long** indptr, int** idx,
+                           float** val, long long* nnz) {
+  const int n = h->N;
+  std::vector<int64_t> ip;
+  TRY(itemsim_indptr(h, who, t.cnt, n, most, ip));
+  *nnz = ip[(size_t)n];
+  TRY(itemsim_alloc(ip.data(), n, indptr, idx, val));
+  Scope sc(h, T_KNN_PACK, 0.0, 16.0 * (double)*nnz);
+  GANMF_LAUNCH(itemknn_pack_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, (const int*)t.idx, (const float*)t.val,
+               (const int*)t.cnt, k, (const long long*)*indptr, *idx, *val);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The column pass (p3_columns_kernel): the ck largest non-zeros of every column of R, bit copies, into the picks.  The dense column
+// lives where the plan puts a row, and the grid is the plan's: min(n, 8192) workgroups with the column in LDS, at most 512 above.
+static int itemsim_columns(ganmf_handle* h, const SimCsr& R, int ck, const SimRowPlan& plan, const SimPicks& t) {
+  const int n = h->N;
+  P3ColP p{};
+  p.r_indptr = R.indptr; p.r_idx = R.idx; p.r_val = R.val;
+  p.n_items = n; p.topk = ck;
+  p.row_lds = plan.row_lds; p.row_glob = t.row; p.ld_row = plan.ld_row;
+  p.out_idx = t.idx; p.out_val = t.val; p.out_cnt = t.cnt;
+  const size_t shmem = plan.row_lds ? (size_t)n * sizeof(float) : 0;
+  TRY(allow_lds((const void*)p3_columns_kernel, shmem));
+  Scope sc(h, T_P3_COLUMNS, 0.0, 16.0 * (double)n * n);
+  GANMF_LAUNCH(p3_columns_kernel, dim3(plan.grid), dim3(KNN_THREADS), shmem, h->st, p);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_items) {
@@ -89,15 +209,12 @@ int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int3
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   itemsim_drop(h);
-  HIP_TRY(hipMalloc((void**)&h->knn_indptr, (size_t)(n_items + 1) * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&h->knn_nbr, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&h->knn_val, (size_t)std::max<int64_t>(nnz, 1) * sizeof(float)));
-  HIP_TRY(hipMemcpy(h->knn_indptr, indptr, (size_t)(n_items + 1) * sizeof(long long), hipMemcpyHostToDevice));
+  TRY(itemsim_alloc(indptr, (int)n_items, &h->knn_indptr, &h->knn_nbr, &h->knn_val));
   if (nnz) {
     HIP_TRY(hipMemcpy(h->knn_nbr, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->knn_val, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
   }
-  h->knn_nnz = nnz;      // set last
+  h->knn_nnz = nnz;
   return 0;
 }
 
@@ -120,13 +237,6 @@ int ganmf_itemknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float*
 static_assert(KNN_MAX_TOPK == GANMF_ITEMKNN_MAX_TOPK, "top-k limit of the kernels and of the header");
 static_assert(KNN_PRODUCT == GANMF_ITEMKNN_PRODUCT && KNN_RAW == GANMF_ITEMKNN_RAW, "similarity kinds of the kernels and of the header");
 
-// temporaries of one fit, released on every way out
-struct KnnFitTmp {
-  float *den_a = nullptr, *den_b = nullptr, *row = nullptr, *val = nullptr;
-  int *idx = nullptr, *cnt = nullptr;
-  ~KnnFitTmp() { hipFree(den_a); hipFree(den_b); hipFree(row); hipFree(val); hipFree(idx); hipFree(cnt); }
-};
-
 int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, float p0, float p1, const float* den_a, const float* den_b,
                       int64_t* nnz_out) {
   const char* who = "ganmf_itemknn_fit";
@@ -147,63 +257,27 @@ int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   itemsim_drop(h);
-  KnnFitTmp t;
+  SimFloats den;
+  SimPicks t;
   const AlsSide& s = h->als[1];
+  const SimRowPlan plan = itemsim_row_plan(n);
   KnnFitP p{};
-  p.c_indptr = s.indptr; p.c_users = s.indices; p.c_val = s.conf;
-  p.n_items = n; p.n_users = h->U; p.kind = kind; p.topk = k;
-  p.s = (float)((double)shrink + 1e-6); p.shrink = shrink; p.p0 = p0; p.p1 = p1;
-  if (kind <= KNN_TVERSKY) {
-    HIP_TRY(hipMalloc((void**)&t.den_a, (size_t)n * sizeof(float)));
-    HIP_TRY(hipMemcpy(t.den_a, den_a, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    p.den_a = t.den_a;
-  }
-  if (kind == KNN_PRODUCT) {
-    HIP_TRY(hipMalloc((void**)&t.den_b, (size_t)n * sizeof(float)));
-    HIP_TRY(hipMemcpy(t.den_b, den_b, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    p.den_b = t.den_b;
-  }
-  p.slab = std::min(KNN_SLAB, round_up(h->U, 64));
-  p.row_lds = n <= KNN_ROW_LDS ? 1 : 0;
-  unsigned grid = (unsigned)std::min(n, 8192);
-  if (!p.row_lds) {      // a private row per workgroup in global memory: at most 512 of them
-    grid = (unsigned)std::min(n, 512);
-    p.ld_row = round_up(n, LD_ALIGN);
-    HIP_TRY(hipMalloc((void**)&t.row, (size_t)grid * p.ld_row * sizeof(float)));
-    p.row_glob = t.row;
-  }
-  HIP_TRY(hipMalloc((void**)&t.idx, (size_t)n * k * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&t.val, (size_t)n * k * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&t.cnt, (size_t)n * sizeof(int)));
-  p.out_idx = t.idx; p.out_val = t.val; p.out_cnt = t.cnt;
-  const size_t shmem = ((size_t)p.slab + (p.row_lds ? (size_t)n : 0)) * sizeof(float);
+  p.kind = kind; p.s = (float)((double)shrink + 1e-6); p.shrink = shrink; p.p0 = p0; p.p1 = p1;
+  if (kind <= KNN_TVERSKY) TRY(upload_floats(&den.a, den_a, n));
+  if (kind == KNN_PRODUCT) TRY(upload_floats(&den.b, den_b, n));
+  p.den_a = den.a; p.den_b = den.b;
+  TRY(t.alloc(n, k, plan.row_floats()));
+  const size_t shmem = itemsim_row_args(h, k, plan, t, &p);
   TRY(allow_lds((const void*)itemknn_fit_kernel, shmem));
   {      // every workgroup walks the whole matrix once per slab of its item
     Scope sc(h, T_KNN_FIT, 2.0 * n * (double)s.nnz, 8.0 * n * (double)s.nnz);
-    GANMF_LAUNCH(itemknn_fit_kernel, dim3(grid), dim3(KNN_THREADS), shmem, h->st, p);
+    GANMF_LAUNCH(itemknn_fit_kernel, dim3(plan.grid), dim3(KNN_THREADS), shmem, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  std::vector<int> cnt((size_t)n);
-  HIP_TRY(hipMemcpyAsync(cnt.data(), t.cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->st));
+  long long nnz = 0;
+  TRY(itemsim_compact(h, who, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
   HIP_TRY(hipStreamSynchronize(h->st));
-  std::vector<long long> ip((size_t)n + 1, 0);
-  for (int i = 0; i < n; ++i) {
-    if (cnt[(size_t)i] < 0 || cnt[(size_t)i] > k) return fail(-2, "%s: item %d reports %d neighbours of at most %d", who, i, cnt[(size_t)i], k);
-    ip[(size_t)i + 1] = ip[(size_t)i] + cnt[(size_t)i];
-  }
-  const long long nnz = ip[(size_t)n];
-  HIP_TRY(hipMalloc((void**)&h->knn_indptr, ip.size() * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&h->knn_nbr, (size_t)std::max<long long>(nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&h->knn_val, (size_t)std::max<long long>(nnz, 1) * sizeof(float)));
-  HIP_TRY(hipMemcpy(h->knn_indptr, ip.data(), ip.size() * sizeof(long long), hipMemcpyHostToDevice));
-  {
-    Scope sc(h, T_KNN_PACK, 0.0, 16.0 * (double)nnz);
-    GANMF_LAUNCH(itemknn_pack_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, (const int*)t.idx, (const float*)t.val,
-                 (const int*)t.cnt, k, (const long long*)h->knn_indptr, h->knn_nbr, h->knn_val);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(h->st));
-  h->knn_nnz = nnz;      // set last: any failure above leaves "no matrix"
+  h->knn_nnz = nnz;
   *nnz_out = nnz;
   return 0;
 }

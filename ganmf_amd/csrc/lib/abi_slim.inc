@@ -268,19 +268,15 @@ int ganmf_slim_bpr_finish(ganmf_handle* h, int32_t topk, int64_t* nnz_out) {
   HIP_TRY(hipStreamSynchronize(h->st));
   itemsim_drop(h);
   const SlimState& s = h->slim;
-  P3FitTmp t;      // (the same temporaries as ganmf_p3_fit's two passes)
+  SimPicks t;
+  SimCsr R;
   SlimFinishTmp d;
-  const int row_lds = n <= KNN_ROW_LDS ? 1 : 0;
+  // slim_rows_kernel keeps its float64 row in global memory whatever n: at most 512 workgroups.  The column pass takes the plan of the
+  // other fits as it is: min(n, 8192) workgroups with the column in LDS, above KNN_ROW_LDS the same 512 with a private float row each.
+  const SimRowPlan plan = itemsim_row_plan(n);
   const unsigned grid = (unsigned)std::min(n, 512);
-  long long ld_row = 0;
   TRY(slim_alloc(who, "the private float64 rows", (void**)&d.rows, (size_t)grid * n * sizeof(double)));
-  if (!row_lds) {
-    ld_row = round_up(n, LD_ALIGN);
-    HIP_TRY(hipMalloc((void**)&t.row, (size_t)grid * ld_row * sizeof(float)));
-  }
-  HIP_TRY(hipMalloc((void**)&t.idx, (size_t)n * k * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&t.val, (size_t)n * k * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&t.cnt, (size_t)n * sizeof(int)));
+  TRY(t.alloc(n, k, plan.row_floats()));
   // ---- get_S: the diagonal, then the top-k of every float64 row, rounded to float32 ----
   GANMF_LAUNCH(slim_zero_diag_kernel, dim3((unsigned)((n + SLIM_THREADS - 1) / SLIM_THREADS)), dim3(SLIM_THREADS), 0, h->st, s.S, n, s.symmetric);
   HIP_TRY(hipGetLastError());
@@ -291,46 +287,13 @@ int ganmf_slim_bpr_finish(ganmf_handle* h, int32_t topk, int64_t* nnz_out) {
     GANMF_LAUNCH(slim_rows_kernel, dim3(grid), dim3(SLIM_THREADS), 0, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  std::vector<long long> ip;
-  TRY(p3_indptr(h, who, t.cnt, n, k, ip));
-  const long long r_nnz = ip[(size_t)n];
-  HIP_TRY(hipMalloc((void**)&t.r_indptr, ip.size() * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&t.r_idx, (size_t)std::max<long long>(r_nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&t.r_val, (size_t)std::max<long long>(r_nnz, 1) * sizeof(float)));
-  HIP_TRY(hipMemcpy(t.r_indptr, ip.data(), ip.size() * sizeof(long long), hipMemcpyHostToDevice));
-  {
-    Scope sc(h, T_KNN_PACK, 0.0, 16.0 * (double)r_nnz);
-    GANMF_LAUNCH(itemknn_pack_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, (const int*)t.idx, (const float*)t.val,
-                 (const int*)t.cnt, k, (const long long*)t.r_indptr, t.r_idx, t.r_val);
-    HIP_TRY(hipGetLastError());
-  }
+  TRY(itemsim_compact(h, who, t, k, k, &R.indptr, &R.idx, &R.val, &R.nnz));
   // ---- similarityMatrixTopK: the k largest non-zeros of every column (p3_columns_kernel, bit copies) ----
-  {
-    P3ColP p{};
-    p.r_indptr = t.r_indptr; p.r_idx = t.r_idx; p.r_val = t.r_val;
-    p.n_items = n; p.topk = k;
-    p.row_lds = row_lds; p.row_glob = t.row; p.ld_row = ld_row;
-    p.out_idx = t.idx; p.out_val = t.val; p.out_cnt = t.cnt;
-    const size_t shmem = row_lds ? (size_t)n * sizeof(float) : 0;
-    TRY(allow_lds((const void*)p3_columns_kernel, shmem));
-    Scope sc(h, T_P3_COLUMNS, 0.0, 16.0 * (double)n * n);
-    GANMF_LAUNCH(p3_columns_kernel, dim3(row_lds ? (unsigned)std::min(n, 8192) : grid), dim3(KNN_THREADS), shmem, h->st, p);
-    HIP_TRY(hipGetLastError());
-  }
-  TRY(p3_indptr(h, who, t.cnt, n, k, ip));
-  const long long nnz = ip[(size_t)n];
-  HIP_TRY(hipMalloc((void**)&h->knn_indptr, ip.size() * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&h->knn_nbr, (size_t)std::max<long long>(nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&h->knn_val, (size_t)std::max<long long>(nnz, 1) * sizeof(float)));
-  HIP_TRY(hipMemcpy(h->knn_indptr, ip.data(), ip.size() * sizeof(long long), hipMemcpyHostToDevice));
-  {
-    Scope sc(h, T_KNN_PACK, 0.0, 16.0 * (double)nnz);
-    GANMF_LAUNCH(itemknn_pack_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, (const int*)t.idx, (const float*)t.val,
-                 (const int*)t.cnt, k, (const long long*)h->knn_indptr, h->knn_nbr, h->knn_val);
-    HIP_TRY(hipGetLastError());
-  }
+  TRY(itemsim_columns(h, R, k, plan, t));
+  long long nnz = 0;
+  TRY(itemsim_compact(h, who, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
   HIP_TRY(hipStreamSynchronize(h->st));
-  h->knn_nnz = nnz;      // set last: any failure above leaves "no matrix"
+  h->knn_nnz = nnz;
   *nnz_out = nnz;
   return 0;
 }

@@ -2,16 +2,18 @@
 // GraphBased/P3alphaRecommender.py:52-141 and RP3betaRecommender.py:49-151, W = top-k per column of (row-normalised) top-k per row of
 // Piu^alpha . Pui^alpha (. diag(deg^-beta)).  The kernels of itemknn_rows.hpp are used as they are for the packing and the scores.
 //
-// Row pass: one workgroup per SOURCE item i, in the shape of itemknn_fit_kernel.  Side 1 of the handle holds Pui^alpha by item (the
+// Row pass: one workgroup per SOURCE item i, on the row builder of itemknn_fit_kernel (SimRowP, sim_row_accumulate: itemknn_rows.hpp;
+// the slab is filled with row_scale[i] instead of the stored value).  Side 1 of the handle holds Pui^alpha by item (the
 // pattern of the URM by item, the transition weights as values).  Piu^alpha has one value per item, row_scale[i] = (1 / deg_i)^alpha, at
 // the users stored in column i: that is what the LDS slab of KNN_SLAB users holds (0 elsewhere).  Thread t owns the targets
 // j = t, t + 256, ... and w_j = sum_u Piu[i, u] Pui[u, j] is one fp32 FMA chain fmaf(slab[u], val[q], acc) over ascending users; slabs
 // are taken in ascending order, those without an entry of column i skipped.  Then one multiply by col_scale[j] (RP3beta's popularity
-// penalty; absent for P3alpha), w_i = 0, and topk arg-max rounds with ties to the smaller j; the non-zero picks are stored.
+// penalty; absent for P3alpha), w_i = 0, and select_topk_nonzero (topk_rounds.hpp): topk arg-max rounds with ties to the smaller j; the
+// non-zero picks are stored.
 // itemknn_pack_kernel turns them into the compact row-major matrix R, columns ascending inside a row.
 // Row normalisation: every row of R divided by the sum of the absolute values of its entries, summed in stored order in fp64.
 // Column pass: one workgroup per TARGET item j holds column j of R as a dense vector over the source items (thread t owns the rows
-// i = t, t + 256, ... and finds j in row i by binary search over its ascending columns), then runs the same arg-max rounds: col_topk
+// i = t, t + 256, ... and finds j in row i by binary search over its ascending columns), then runs the same select_topk_nonzero: col_topk
 // largest, ties to the smaller i, zeros dropped.  It does no arithmetic: its values are bit copies.  Without a second selection
 // (col_topk = 0) R is transposed instead: a histogram of its column ids, then an ordered compaction of every column (the same search,
 // positions from a ballot over ascending i).  No floating-point atomic anywhere: two fits return the same bytes.
@@ -21,21 +23,9 @@
 
 namespace ganmf {
 
-struct P3RowP {
-  const long long* c_indptr;   // side 1: items x users, users ascending inside an item; values Pui^alpha
-  const int* c_users;
-  const float* c_val;
-  int n_items, n_users;
-  int topk;                    // <= min(KNN_MAX_TOPK, n_items)
+struct P3RowP : SimRowP {      // side 1 holds Pui^alpha
   const float* row_scale;      // [n_items] (1 / deg_i)^alpha
   const float* col_scale;      // [n_items] deg_j^-beta, or null
-  int slab;                    // users per slab (<= KNN_SLAB): the first `slab` floats of the dynamic LDS
-  int row_lds;                 // 1: the row follows the slab in LDS; 0: row_glob + blockIdx.x * ld_row
-  float* row_glob;
-  long long ld_row;
-  int* out_idx;                // [n_items, topk] picks in descending order of value
-  float* out_val;
-  int* out_cnt;                // [n_items] stored picks (the non-zero ones)
 };
 
 struct P3ColP {
@@ -52,48 +42,6 @@ struct P3ColP {
   int* out_cnt;
 };
 
-// The topk largest of w[0, n), the non-zero ones stored in descending order (arg-max rounds with removal, ties to the smaller id: the
-// selection of itemknn_fit_kernel).  Called by the whole workgroup after a barrier behind the last write of w; thread 0 stores the count.
-__device__ __forceinline__ void p3_select(float* w, int n, int topk, int any_neg, int* out_idx, float* out_val, int* out_cnt,
-                                          float* wv, int* wi, int* s_stop) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int cnt = 0;
-  for (int t = 0; t < topk; ++t) {
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int j = tid; j < n; j += KNN_THREADS) {
-      const float v = w[j];
-      if (v > bv) { bv = v; bi = j; }      // strided scan visits ids in increasing order: first max wins
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      float v = wv[0];
-      int b = wi[0];
-      for (int q = 1; q < 4; ++q)
-        if (wv[q] > v || (wv[q] == v && wi[q] < b)) { v = wv[q]; b = wi[q]; }
-      const bool ok = v > -INFINITY && b != 0x7fffffff;
-      if (ok && v != 0.f) {
-        out_idx[cnt] = b;
-        out_val[cnt] = v;
-        ++cnt;
-      }
-      if (ok) w[b] = -INFINITY;
-      // nothing left, or only zeros left in a row without negative values: no later round stores anything
-      *s_stop = (!ok || (v == 0.f && !any_neg)) ? 1 : 0;
-    }
-    __syncthreads();
-    if (*s_stop) break;
-  }
-  if (tid == 0) *out_cnt = cnt;
-}
-
 __global__ __launch_bounds__(KNN_THREADS) void p3_rows_kernel(const P3RowP p) {
   extern __shared__ __attribute__((aligned(16))) float p3_lds[];
   __shared__ float wv[4];
@@ -104,34 +52,9 @@ __global__ __launch_bounds__(KNN_THREADS) void p3_rows_kernel(const P3RowP p) {
   float* w = p.row_lds ? p3_lds + p.slab : p.row_glob + (size_t)blockIdx.x * p.ld_row;
   const int n = p.n_items;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
-    const long long cs = p.c_indptr[i], ce = p.c_indptr[i + 1];
+    // ---- w_j = sum_u Piu[i, u] Pui[u, j]: the slab holds the one value of row i of Piu ----
     const float rs = p.row_scale[i];
-    for (int j = tid; j < n; j += KNN_THREADS) w[j] = 0.f;
-    // ---- w_j = sum_u Piu[i, u] Pui[u, j], one slab of users at a time, ascending ----
-    long long at = cs;      // first entry of column i not yet expanded (the same value in every thread)
-    while (at < ce) {
-      const int base = (p.c_users[at] / p.slab) * p.slab;      // the next slab that holds an entry of column i
-      const long long top = (long long)base + p.slab;
-      const long long end = top > p.n_users ? ce : knn_lower_bound(p.c_users, at, ce, (int)top);
-      __syncthreads();      // the readers of the slab before this one (and the zero fill of w) are done
-      for (int t = tid; t < p.slab; t += KNN_THREADS) xs[t] = 0.f;
-      __syncthreads();
-      for (long long q = at + tid; q < end; q += KNN_THREADS) xs[p.c_users[q] - base] = rs;
-      __syncthreads();
-      for (int j = tid; j < n; j += KNN_THREADS) {
-        const long long a = p.c_indptr[j], b = p.c_indptr[j + 1];
-        long long q = base == 0 ? a : knn_lower_bound(p.c_users, a, b, base);
-        float acc = w[j];
-        for (; q < b; ++q) {
-          const int u = p.c_users[q];
-          if (u >= top) break;
-          acc = fmaf(xs[u - base], p.c_val[q], acc);
-        }
-        w[j] = acc;
-      }
-      at = end;
-    }
-    __syncthreads();
+    sim_row_accumulate(p, xs, w, i, [rs](long long) { return rs; });
     // ---- the popularity penalty, w_i = 0 (thread t owns the same j as above) ----
     int neg = 0;
     for (int j = tid; j < n; j += KNN_THREADS) {
@@ -142,7 +65,8 @@ __global__ __launch_bounds__(KNN_THREADS) void p3_rows_kernel(const P3RowP p) {
       w[j] = v;
     }
     const int any_neg = __syncthreads_or(neg);
-    p3_select(w, n, p.topk, any_neg, p.out_idx + (size_t)i * p.topk, p.out_val + (size_t)i * p.topk, p.out_cnt + i, wv, wi, &s_stop);
+    select_topk_nonzero(w, n, p.topk, any_neg, p.out_idx + (size_t)i * p.topk, p.out_val + (size_t)i * p.topk, p.out_cnt + i, wv, wi,
+                        &s_stop);
     __syncthreads();      // (s_stop, wv / wi and the row are reused by the next item)
   }
 }
@@ -190,7 +114,8 @@ __global__ __launch_bounds__(KNN_THREADS) void p3_columns_kernel(const P3ColP p)
       w[i] = v;
     }
     const int any_neg = __syncthreads_or(neg);
-    p3_select(w, n, p.topk, any_neg, p.out_idx + (size_t)j * p.topk, p.out_val + (size_t)j * p.topk, p.out_cnt + j, wv, wi, &s_stop);
+    select_topk_nonzero(w, n, p.topk, any_neg, p.out_idx + (size_t)j * p.topk, p.out_val + (size_t)j * p.topk, p.out_cnt + j, wv, wi,
+                        &s_stop);
     __syncthreads();
   }
 }

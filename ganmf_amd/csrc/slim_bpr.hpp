@@ -32,8 +32,8 @@
 //             refusals the k-th item outside the profile, k = below(word(2, SLIM_ATTEMPTS), n_items - |profile(u)|).
 //
 // get_S (slim_rows_kernel): one workgroup per row; the row is copied (from the triangle when symmetric) into a private float64 row,
-// its diagonal entry zero, and the topk largest are selected in float64 by arg-max rounds with ties to the smaller id; the non-zero
-// picks are rounded to float32 and stored in the layout itemknn_pack_kernel reads.
+// its diagonal entry zero, and the topk largest are selected in float64 by select_topk_nonzero<double> (topk_rounds.hpp: arg-max
+// rounds with ties to the smaller id); the non-zero picks are rounded to float32 and stored in the layout itemknn_pack_kernel reads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "itemknn_rows.hpp"
@@ -41,6 +41,7 @@
 namespace ganmf {
 
 constexpr int SLIM_THREADS = 256;
+static_assert(SLIM_THREADS == TOPK_THREADS, "slim_rows_kernel selects with the rounds of topk_rounds.hpp");
 constexpr int SLIM_ATTEMPTS = 64;
 enum SlimSgd : int { SLIM_SGD = 0, SLIM_ADAGRAD = 1, SLIM_RMSPROP = 2, SLIM_ADAM = 3, SLIM_SGD_MODES = 4 };
 
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(SLIM_THREADS) void slim_rows_kernel(const SlimRowP 
   __shared__ double wv[SLIM_THREADS / 64];
   __shared__ int wi[SLIM_THREADS / 64];
   __shared__ int s_stop;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = p.n_items;
+  const int tid = threadIdx.x, n = p.n_items;
   double* w = p.rows + (size_t)blockIdx.x * n;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     int neg = 0;
@@ -253,41 +254,7 @@ __global__ __launch_bounds__(SLIM_THREADS) void slim_rows_kernel(const SlimRowP 
     const int any_neg = __syncthreads_or(neg);
     int* out_idx = p.out_idx + (size_t)i * p.topk;
     float* out_val = p.out_val + (size_t)i * p.topk;
-    int cnt = 0;
-    for (int t = 0; t < p.topk; ++t) {
-      double bv = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int j = tid; j < n; j += SLIM_THREADS) {
-        const double v = w[j];
-        if (v > bv) { bv = v; bi = j; }      // ids ascend along the scan: the first maximum wins
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-      }
-      if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
-      __syncthreads();
-      if (tid == 0) {
-        double v = wv[0];
-        int best = wi[0];
-        for (int q = 1; q < SLIM_THREADS / 64; ++q)
-          if (wv[q] > v || (wv[q] == v && wi[q] < best)) { v = wv[q]; best = wi[q]; }
-        const bool ok = v > -INFINITY && best != 0x7fffffff;
-        if (ok && v != 0.0) {
-          out_idx[cnt] = best;
-          out_val[cnt] = (float)v;
-          ++cnt;
-        }
-        if (ok) w[best] = -INFINITY;
-        // nothing left, or only zeros left in a row without negative values: no later round stores anything
-        s_stop = (!ok || (v == 0.0 && !any_neg)) ? 1 : 0;
-      }
-      __syncthreads();
-      if (s_stop) break;
-    }
-    if (tid == 0) p.out_cnt[i] = cnt;
+    select_topk_nonzero(w, n, p.topk, any_neg, out_idx, out_val, p.out_cnt + i, wv, wi, &s_stop);
     __syncthreads();      // (s_stop, wv / wi and the row are reused by the next item)
   }
 }

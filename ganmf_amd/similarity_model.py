@@ -26,16 +26,33 @@ class SimilarityModelMixin(object):
         orientations, in canonical form, and the seen mask."""
         if self.engine is not None:
             self.engine.close()
-        urm = sps.csr_matrix(self.URM_train, dtype=np.float32, copy=True)
-        urm.sum_duplicates()
-        urm.sort_indices()
-        by_item = urm.tocsc()
-        by_item.sort_indices()
+        urm = self._canonical(self.URM_train)
         self.engine = self._make_engine()
         self.engine.set_confidence(0, urm)
-        self.engine.set_confidence(1, sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr), shape=(self.n_items, self.n_users)))
+        self.engine.set_confidence(1, self._urm_by_item(urm))
         self.engine.set_seen(self._URM_eval)
         self._reset_score_filter()
+
+    @staticmethod
+    def _canonical(urm):
+        """a float32 CSR copy with sorted indices and duplicates summed"""
+        urm = sps.csr_matrix(urm, dtype=np.float32, copy=True)
+        urm.sum_duplicates()
+        urm.sort_indices()
+        return urm
+
+    @staticmethod
+    def _urm_by_item(urm):
+        """The canonical items x users CSR (float32, users ascending inside an item, duplicates summed) of a users x items matrix:
+        what side 1 of the handle holds."""
+        by_item = SimilarityModelMixin._canonical(urm).tocsc()
+        by_item.sort_indices()
+        return sps.csr_matrix((by_item.data, by_item.indices, by_item.indptr), shape=(urm.shape[1], urm.shape[0]))
+
+    def _restore_side1(self):
+        """side 1 back to URM_train's own values after a fit that put other values there (nothing reads it after the fit; kept
+        consistent with side 0)"""
+        self.engine.set_confidence(1, self._urm_by_item(self.URM_train))
 
     def _require_engine(self):
         if self.engine is None:

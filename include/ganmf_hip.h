@@ -492,7 +492,8 @@ int ganmf_pure_svd(ganmf_handle* h, const float* omega, int n_random, int n_iter
  *     GANMF_ITEMKNN_RAW          w
  *   (den_a / den_b may be NULL for the kinds that do not read them; p0 / p1 are read by TVERSKY only).  Every w_j is one fp32 FMA chain
  *   over ascending users, there is no floating-point atomic anywhere: two fits from the same uploads return the same bytes.  Among
- *   exactly equal values the smaller item id is selected (the rule of ganmf_recommend).  The [num_items, num_items] matrix of the w_j
+ *   exactly equal values the smaller item id is selected: select_topk_nonzero (ganmf_amd/csrc/topk_rounds.hpp), the one selection of
+ *   every fit on such a handle, built on the arg-max round of ganmf_recommend.  The [num_items, num_items] matrix of the w_j
  *   never exists: one row per workgroup, in LDS or (wide catalogues) in a private global row.  Any num_items and num_users.  The
  *   handle then holds W BY TARGET ITEM: column i of the reference's W_sparse = the kept neighbours j of item i with their values,
  *   neighbours ascending.  *nnz receives the number of stored entries.  Blocking.
@@ -536,7 +537,7 @@ int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int3
  *     col_topk = 0 skips the selection: R itself, transposed to the handle's layout, is held.
  *   Every w_j is one fp32 FMA chain fmaf(row_scale[i], Pui^alpha[u, j], acc) over ascending users, there is no floating-point atomic
  *   anywhere: two fits from the same uploads return the same bytes.  Among exactly equal values the smaller item id is selected in
- *   both selections (the rule of ganmf_itemknn_fit and ganmf_recommend).  One row (column) of the walk per workgroup, in LDS or (wide
+ *   both selections (select_topk_nonzero, as in ganmf_itemknn_fit).  One row (column) of the walk per workgroup, in LDS or (wide
  *   catalogues) in a private global row; any num_items and num_users.  The handle then holds W BY TARGET ITEM as after
  *   ganmf_itemknn_fit -- scores[u, j] = sum_i x[u, i] W[i, j], the target is column j, its neighbours are the source rows i, ascending
  *   -- and ganmf_itemknn_get, ganmf_set_item_similarity, the scores and every ranking and evaluation entry work on it unchanged.
@@ -576,9 +577,9 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
  * ganmf_slim_bpr_epochs: ganmf_slim_bpr_draw of the next n_epochs epochs followed by ganmf_slim_bpr_run of them, the samples staying
  *   on the device (their items are copied back once, for the schedule); advances the epoch counter.
  * ganmf_slim_bpr_finish: get_S and the class's similarityMatrixTopK: the diagonal of S is set to zero; of every row of S the
- *   min(topk, num_items) largest values are selected in float64, ties to the smaller id, and the non-zero ones kept and rounded to
- *   float32 (row i of R); of every column of R the min(topk, num_items) largest non-zeros are kept (the kernels of ganmf_p3_fit's column
- *   pass, bit copies).  The handle then holds that matrix as W BY TARGET ITEM, W[i, j] = S[i, j] where kept -- the reference's
+ *   min(topk, num_items) largest values are selected in float64 (select_topk_nonzero), ties to the smaller id, and the non-zero
+ *   ones kept and rounded to float32 (row i of R); of every column of R the min(topk, num_items) largest non-zeros are kept (the
+ *   kernels of ganmf_p3_fit's column pass, bit copies).  The handle then holds that matrix as W BY TARGET ITEM, W[i, j] = S[i, j] where kept -- the reference's
  *   orientation: the scores sum S[s, j] over the profile, the training sums S[j, s] -- as after ganmf_itemknn_fit.  S and the state
  *   stay: training continues.  *nnz receives the stored entries.  Errors (-1): topk < 1, min(topk, num_items) above
  *   GANMF_ITEMKNN_MAX_TOPK, no training state.
