@@ -26,14 +26,16 @@ typedef float f32x4k __attribute__((ext_vector_type(4)));      // (a native vect
 // serialises the whole prefetch (first build of this kernel: 34 us for the encode GEMM, 20 us without its fetches).
 struct SplitItemK {
   const float* zp;
-  const float* ptr;
-  long long inc;      // floats per K-tile
-  int aux, dst, ld;
+  const float* ptr;      // first 16 bytes of the item in the next K-tile (a lane outside the operand: its zero-page line)
+  long long inc;      // floats per K-tile (0: zero-page lane)
+  long long second;   // floats from the item's first 16 bytes to its second: 4 (K-contiguous), ld (K-major: the next k-row) or 0 (K-major zero-page lane)
+  int aux, dst;      // K-major: first k-row of the item inside a K-tile; dword offset of the item inside a piece plane
   int dst1 = 0;      // K-major: dword offset of the item's second k-row RELATIVE to dst
   bool km;
   __device__ inline void init(bool km_, const float* __restrict__ base, int ld_, int r0, int rlimit, int kbeg, const float* zero, int w,
                               const int* __restrict__ gather = nullptr) {
-    km = km_; ld = ld_;
+    km = km_;
+    const int ld = ld_;
     zp = zero + (w & 255) * 8;
     if (!km) {
       using S = SplitStage<64, 64, false>;
@@ -42,6 +44,7 @@ struct SplitItemK {
       const int src_row = (ok && gather) ? gather[r0 + row] : r0 + row;      // (GemmP::a_gather: the embedding lookup rides in the fetch)
       ptr = ok ? base + (size_t)src_row * ld + kbeg + 8 * c8 : zp;
       inc = ok ? 64 : 0;
+      second = 4;
       aux = 0;
       dst = row * 32 + 4 * (c8 ^ S::swz(row));
       dst1 = 0;
@@ -49,21 +52,33 @@ struct SplitItemK {
       using S = SplitStage<64, 64, true>;
       const int kp = w / S::RQ, rq = w % S::RQ;
       const bool ok = (r0 + 4 * rq) < ld;
-      ptr = base + (size_t)(kbeg + 2 * kp) * ld + r0 + 4 * rq;
-      inc = (long long)64 * ld;
-      aux = ok ? 2 * kp : -1;
+      ptr = ok ? base + (size_t)(kbeg + 2 * kp) * ld + r0 + 4 * rq : zp;
+      inc = ok ? (long long)64 * ld : 0;
+      second = ok ? ld : 0;
+      aux = 2 * kp;
       dst = (2 * kp) * S::KROW + 4 * ((rq >> 1) ^ S::swzk(2 * kp)) + 2 * (rq & 1);
       dst1 = (2 * kp + 1) * S::KROW + 4 * ((rq >> 1) ^ S::swzk(2 * kp + 1)) + 2 * (rq & 1) - dst;
     }
   }
   // the two source addresses of the item in the K-tile that starts kleft k's before the end of the range (no memory access here)
+  // Two per-lane adds in every K-tile, the same for either layout.  Only the LAST K-tile of a slice can be partial, and only a K-major item
+  // then has k-rows that do not exist (a K-contiguous one reads its row's zero pad): a scalar branch -- kleft and km are wave-uniform --
+  // guards the zero-page selects, so that every other tile executes no compare and no select for its addresses; the empty asm keeps
+  // hipcc from turning the branch back into selects.  (One loop body: round 5's second body for the last tile cost 0.5 us per launch.)
   __device__ inline void addresses(int kleft, const float*& s0, const float*& s1) {
-    if (!km) { s0 = ptr; s1 = ptr + 4; }
-    else {
-      s0 = (aux >= 0 && aux < kleft) ? ptr : zp;
-      s1 = (aux >= 0 && aux + 1 < kleft) ? ptr + ld : zp;
-    }
+    // (values read in front of the branch: a select between members behind the asm becomes a select of their addresses, and hipcc then keeps
+    // the item in scratch -- whose loads and stores the counted waits do not allow for)
+    const float* const z = zp;
+    const float* a0 = ptr;
+    const float* a1 = ptr + second;
+    const int k0 = aux;
     ptr += inc;
+    if (kleft < 64 && km) {
+      asm volatile("; partial last K-tile");
+      a0 = k0 < kleft ? a0 : z;
+      a1 = k0 + 1 < kleft ? a1 : z;
+    }
+    s0 = a0; s1 = a1;
   }
   // `tok`: the token of the counted wait that covers this item's two loads (bf16k_wait_vm): the first instruction that reads a loaded
   // register carries it as an operand, so nothing of the split can be scheduled in front of the wait.  (Rounds 3-4 folded it into the
@@ -135,7 +150,7 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
   const float sa = (F16 && p.a_scale != 0.f) ? p.a_scale : 1.f, sb = (F16 && p.b_scale != 0.f) ? p.b_scale : 1.f;
   using FA = SplitStage<64, 64, AKM>;
   using FB = SplitStage<64, 64, BKM>;
-  unsigned* const buf = reinterpret_cast<unsigned*>(smem);      // [2][A planes x 3 | B planes x 3]
+  const unsigned lds0 = lds_addr(smem);      // [2][A planes x 3 | B planes x 3]; the one conversion of the LDS pointer
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -157,7 +172,17 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
                        (AKM || !p.a_gather) ? nullptr : p.a_gather + (size_t)bz * p.a_gather_batch);
   else it.init(BKM, p.B, p.ldb, n0, p.N, kbeg, p.zero_page, tid - 512);
   constexpr int OPER = bf16k_oper<NPIECE>();      // dwords of one plane buffer: [A planes x NPIECE | B planes x NPIECE]
-  unsigned* const my_planes = buf + (stage_a ? 0 : NPIECE * FA::PLANE) + it.dst;      // this thread's 16 bytes of piece 0, buffer 0
+  // LDS byte addresses, formed once: this thread's 16 bytes of piece 0, buffer 0 (K-major: the 8 bytes of its first and of its second k-row) and
+  // this lane's fragments of the A and B piece planes 0 of buffer 0.  Piece (+ 8 KiB) and buffer (+ OPER dwords) are constants of the instruction.
+  // One base per plane buffer (lds_base): what is added to it stays below the 64 KiB of the instruction's offset.
+  unsigned my_planes[2], my_planes1[2], frag_a[2], frag_b[2];
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    my_planes[b] = lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER + (stage_a ? 0 : NPIECE * FA::PLANE) + it.dst));
+    my_planes1[b] = lds_base<NPIECE == 3>(my_planes[b] + 4u * (unsigned)it.dst1);
+    frag_a[b] = lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER) + FA::frag_off(wr * 32, kg, li, lh));
+    frag_b[b] = lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER + NPIECE * FA::PLANE) + FB::frag_off(wc * 32, kg, li, lh));
+  }
   const float my_scale = stage_a ? sa : sb;
 
   f32x4k rg[PD][2];
@@ -178,8 +203,9 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
     kleft -= BK;
   };
   // `nwait` = vector-memory loads issued after the two of the K-tile in slot s (loads return in order)
-  auto store_tile = [&](auto ss, int b, int nwait) {
+  auto store_tile = [&](auto ss, auto bb, int nwait) {
     constexpr int s = decltype(ss)::value;
+    constexpr int b = decltype(bb)::value;      // plane buffer
     const f32x4k v[2] = {rg[s][0], rg[s][1]};
     const int tok = bf16k_wait_vm(nwait, v[0], v[1]);
     u32x4 pc[3];
@@ -190,27 +216,26 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
     } else
 #endif
     it.template split<NPIECE, F16>(v, pc, tok, my_scale);
-    unsigned* o = my_planes + b * OPER;
     if (it.km) {      // (wave-uniform) K-major image: the item's two k-rows are two 8-byte stores per piece
       typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
       for (int q = 0; q < NPIECE; ++q) {
-        *reinterpret_cast<u32x2*>(o + q * FA::PLANE) = u32x2{pc[q][0], pc[q][1]};
-        *reinterpret_cast<u32x2*>(o + q * FA::PLANE + it.dst1) = u32x2{pc[q][2], pc[q][3]};
+        lds_write<u32x2>(my_planes[b] + 4u * (unsigned)(q * FA::PLANE), u32x2{pc[q][0], pc[q][1]});
+        lds_write<u32x2>(my_planes1[b] + 4u * (unsigned)(q * FA::PLANE), u32x2{pc[q][2], pc[q][3]});
       }
     } else {
 #pragma unroll
-      for (int q = 0; q < NPIECE; ++q) *reinterpret_cast<u32x4*>(o + q * FA::PLANE) = pc[q];
+      for (int q = 0; q < NPIECE; ++q) lds_write<u32x4>(my_planes[b] + 4u * (unsigned)(q * FA::PLANE), pc[q]);
     }
   };
   // prologue: K-tiles 0 .. PD-1 requested, tile 0 split into buffer 0
   static_for<0, PD>([&](auto ss) { if (decltype(ss)::value < nt) load_tile(ss); });
-  store_tile(std::integral_constant<int, 0>{}, 0, 2 * (min(nt, PD) - 1));
+  store_tile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, 2 * (min(nt, PD) - 1));
   // everything requested so far lands before the loop is entered (the requests went out back to back with tile 0's, which the split
   // above has waited for): should hipcc move a prefetch register at the loop header, it moves a register that is complete
   if constexpr (PD == 4) asm volatile("s_waitcnt vmcnt(0)" :: "v"(rg[0][0]), "v"(rg[0][1]), "v"(rg[1][0]), "v"(rg[1][1]), "v"(rg[2][0]), "v"(rg[2][1]), "v"(rg[3][0]), "v"(rg[3][1]));
   else asm volatile("s_waitcnt vmcnt(0)" :: "v"(rg[0][0]), "v"(rg[0][1]), "v"(rg[1][0]), "v"(rg[1][1]));
-  static_assert(PD == 4 || PD == 2, "the wait above names every prefetch register");
+  static_assert(PD == 4 || PD == 2, "the wait above names every prefetch register");      // (PD even: K-tile t of slot s lies in buffer s & 1)
   at_entry();
   __syncthreads();
 #ifdef GANMF_PERSIST_DIAG_BUILD
@@ -219,12 +244,12 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
 
   auto step = [&](auto ss, int t) {      // K-tile t, whose registers were slot s = t % PD (consumed in iteration t - 1)
     constexpr int s = decltype(ss)::value, s1 = (s + 1) % PD;
-    const unsigned* planes = buf + (t & 1) * OPER;
+    constexpr int b = s & 1;      // plane buffer: t & 1 == s & 1
     u32x4 pa[3], pb[3];
 #pragma unroll
-    for (int q = 0; q < NPIECE; ++q) pa[q] = FA::frag(planes + q * FA::PLANE, wr * 32, kg, li, lh);
+    for (int q = 0; q < NPIECE; ++q) pa[q] = FA::frag_at(frag_a[b] + 4u * (unsigned)(q * FA::PLANE));
 #pragma unroll
-    for (int q = 0; q < NPIECE; ++q) pb[q] = FB::frag(planes + NPIECE * FA::PLANE + q * FB::PLANE, wc * 32, kg, li, lh);
+    for (int q = 0; q < NPIECE; ++q) pb[q] = FB::frag_at(frag_b[b] + 4u * (unsigned)(q * FB::PLANE));
     // the registers of tile t are free: request tile t + PD into them (before the MFMAs: the longer the fetch has)
 #ifdef GANMF_PERSIST_DIAG_BUILD
     if (p.diag & 16) { if (t + PD < nt) kleft -= BK; } else      // timing only: no operand fetches after the prologue
@@ -254,7 +279,7 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
 #endif
     // under the MFMAs: split K-tile t + 1 into the other buffer.  Issued after its two loads: those of tiles t + 2 .. min(t + PD, nt - 1),
     // and the entry hook's EXTRA loads if tile t + 1 was requested in the prologue
-    if (t + 1 < nt) store_tile(std::integral_constant<int, s1>{}, (t + 1) & 1, 2 * (min(t + PD, nt - 1) - (t + 1)) + (t + 1 < PD ? EXTRA : 0));
+    if (t + 1 < nt) store_tile(std::integral_constant<int, s1>{}, std::integral_constant<int, (s1 & 1)>{}, 2 * (min(t + PD, nt - 1) - (t + 1)) + (t + 1 < PD ? EXTRA : 0));
     __syncthreads();
   };
   for (int t = 0; t < nt; t += PD)

@@ -31,6 +31,44 @@
 
 namespace ganmf {
 
+// LDS byte addresses.  A K loop converts its shared-memory pointer ONCE (the conversion from a generic pointer carries a null check: a
+// compare and a select) and forms every plane address in front of the loop as an integer; piece, plane and buffer are compile-time
+// constants added to it, which the ds instructions take as their immediate offset.
+__device__ inline unsigned lds_addr(const void* p) {
+#if defined(__HIP_DEVICE_COMPILE__)      // (LDS pointers are 32 bits wide in the device pass only)
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
+#else
+  (void)p;
+  return 0u;
+#endif
+}
+// A base address the compiler cannot take apart again.  The workgroup's LDS starts at a known address, so hipcc re-associates base + constant
+// sums and pushes ALL constants into the instruction's offset -- and those that exceed its 16 bits (the second plane buffer of the 16-wave loops:
+// + 48 KiB and more) come back as one v_add_u32 per access.  A loop keeps one such base per plane buffer and operand; what it adds to it fits.
+// (OPAQUE = false: the plain sum -- the one-piece loops' planes all lie below 64 KiB)
+template <bool OPAQUE = true>
+__device__ inline unsigned lds_base(unsigned addr) {
+  if constexpr (OPAQUE) asm("" : "+v"(addr));
+  return addr;
+}
+template <class T>
+__device__ inline T lds_read(unsigned addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *(__attribute__((address_space(3))) const T*)addr;
+#else
+  (void)addr;
+  return T{};
+#endif
+}
+template <class T>
+__device__ inline void lds_write(unsigned addr, const T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *(__attribute__((address_space(3))) T*)addr = v;
+#else
+  (void)addr; (void)v;
+#endif
+}
+
 template <int R, int BK, bool KM>
 struct SplitStage {
   static constexpr int NW = R * BK / 8;       // work items (8 elements each) per K-tile
@@ -51,13 +89,16 @@ struct SplitStage {
   __device__ static inline int swz(int row) { return BK == 32 ? (row >> 2) & 3 : (row >> 1) & 7; }
 
   const float* zp;          // this lane's 32-byte line of the zero page
-  const float* ptr[NI];     // source of the next tile (KM: first of the two k-rows)
-  int aux[NI];              // !KM: pointer increment per tile (0: zero-page lane); KM: first k-row of the item or -1
-  int dst[NI];              // dword offset inside a plane (K-major: of the item's first k-row)
-  int dst1[NI];             // K-major: of its second k-row
+  const float* ptr[NI];     // source of the next tile (KM: first of the two k-rows; a lane whose columns lie past ld: its zero-page line)
+  int aux[NI];              // !KM: pointer increment per tile (0: zero-page lane); KM: first k-row of the item
+  long long kinc[NI];       // K-major: floats per K-tile (0: zero-page lane)
+  int krow[NI];             // K-major: floats from the item's first k-row to its second (ld; 0: zero-page lane)
+  unsigned dst[NI];         // LDS byte address in piece plane 0 (K-major: of the item's first k-row)
+  unsigned dst1[NI];        // K-major: of its second k-row
 
+  // `lds_planes`: LDS byte address of this operand's piece plane 0 (lds_addr)
   __device__ inline void init(const float* __restrict__ base, int ld, int r0, int rlimit, int kbeg,
-                              const float* zero, int tid) {
+                              const float* zero, int tid, unsigned lds_planes) {
     zp = zero + (tid & 255) * 8;
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
@@ -67,41 +108,56 @@ struct SplitStage {
         const bool ok = (r0 + row) < rlimit;
         ptr[j] = ok ? base + (size_t)(r0 + row) * ld + kbeg + 8 * c8 : zp;
         aux[j] = ok ? BK : 0;
-        dst[j] = row * (BK / 2) + 4 * (c8 ^ swz(row));
+        dst[j] = lds_planes + 4u * (unsigned)(row * (BK / 2) + 4 * (c8 ^ swz(row)));
       } else {
         const int kp = w / RQ, rq = w % RQ;
         const bool ok = (r0 + 4 * rq) < ld;
-        ptr[j] = base + (size_t)(kbeg + 2 * kp) * ld + r0 + 4 * rq;
-        aux[j] = ok ? 2 * kp : -1;
-        dst[j] = (2 * kp) * KROW + 4 * ((rq >> 1) ^ swzk(2 * kp)) + 2 * (rq & 1);
-        dst1[j] = (2 * kp + 1) * KROW + 4 * ((rq >> 1) ^ swzk(2 * kp + 1)) + 2 * (rq & 1);
+        ptr[j] = ok ? base + (size_t)(kbeg + 2 * kp) * ld + r0 + 4 * rq : zp;
+        kinc[j] = ok ? (long long)BK * ld : 0;
+        krow[j] = ok ? ld : 0;
+        aux[j] = 2 * kp;
+        dst[j] = lds_planes + 4u * (unsigned)((2 * kp) * KROW + 4 * ((rq >> 1) ^ swzk(2 * kp)) + 2 * (rq & 1));
+        dst1[j] = lds_planes + 4u * (unsigned)((2 * kp + 1) * KROW + 4 * ((rq >> 1) ^ swzk(2 * kp + 1)) + 2 * (rq & 1));
       }
     }
   }
 
   // fetch this thread's share of the tile that starts kleft k's before the end of the K range
-  __device__ inline void load(float4 (&v)[NI][2], int ld, int kleft) {
+  __device__ inline void load(float4 (&v)[NI][2], int kleft) {
+    const float* s0[NI];
+    const float* s1[NI];
+    const float* const z = zp;      // (read in front of the branch below)
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-      if constexpr (!KM) {
-        const float* s = ptr[j];
-        v[j][0] = *reinterpret_cast<const float4*>(s);
-        v[j][1] = *reinterpret_cast<const float4*>(s + 4);
-        ptr[j] += aux[j];
-      } else {
-        const float* s0 = (aux[j] >= 0 && aux[j] < kleft) ? ptr[j] : zp;
-        const float* s1 = (aux[j] >= 0 && aux[j] + 1 < kleft) ? ptr[j] + ld : zp;
-        v[j][0] = *reinterpret_cast<const float4*>(s0);
-        v[j][1] = *reinterpret_cast<const float4*>(s1);
-        ptr[j] += (size_t)BK * ld;
+      s0[j] = ptr[j];
+      if constexpr (!KM) { s1[j] = ptr[j] + 4; ptr[j] += aux[j]; }
+      else { s1[j] = ptr[j] + krow[j]; ptr[j] += kinc[j]; }
+    }
+    if constexpr (KM) {
+      // only the LAST K-tile of a slice can be partial: its missing k-rows come from the zero page.  A scalar branch (kleft is uniform),
+      // so that every other tile executes no compare and no select for its addresses; the empty asm keeps hipcc from turning the branch
+      // back into selects
+      if (kleft < BK) {
+        asm volatile("; partial last K-tile");
+#pragma unroll
+        for (int j = 0; j < NI; ++j) {
+          s0[j] = aux[j] < kleft ? s0[j] : z;
+          s1[j] = aux[j] + 1 < kleft ? s1[j] : z;
+        }
       }
+    }
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      v[j][0] = *reinterpret_cast<const float4*>(s0[j]);
+      v[j][1] = *reinterpret_cast<const float4*>(s1[j]);
     }
   }
 
-  // split / round and write the pieces to the planes at `planes` (piece q at planes + q * PLANE)
+  // split / round and write the pieces to this operand's planes of the buffer `buf_bytes` behind the one init() was given
+  // (piece q at + q * PLANE dwords: buffer and piece are constants of the instruction)
   bool diag_nosplit = false;
   template <int NPIECE, bool F16 = false>
-  __device__ inline void store(unsigned* __restrict__ planes, const float4 (&v)[NI][2], float scale = 1.f) const {
+  __device__ inline void store(const float4 (&v)[NI][2], float scale = 1.f, unsigned buf_bytes = 0u) const {
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       // the four pairs of this item: 8 consecutive k of one row, or 8 consecutive rows of one k-row
@@ -130,12 +186,40 @@ struct SplitStage {
       for (int q = 0; q < NPIECE; ++q) {
         if constexpr (KM) {
           typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-          *reinterpret_cast<u32x2*>(planes + q * PLANE + dst[j]) = u32x2{pc[q][0], pc[q][1]};
-          *reinterpret_cast<u32x2*>(planes + q * PLANE + dst1[j]) = u32x2{pc[q][2], pc[q][3]};
+          lds_write<u32x2>(dst[j] + buf_bytes + 4u * (unsigned)(q * PLANE), u32x2{pc[q][0], pc[q][1]});
+          lds_write<u32x2>(dst1[j] + buf_bytes + 4u * (unsigned)(q * PLANE), u32x2{pc[q][2], pc[q][3]});
         } else {
-          *reinterpret_cast<u32x4*>(planes + q * PLANE + dst[j]) = pc[q];
+          lds_write<u32x4>(dst[j] + buf_bytes + 4u * (unsigned)(q * PLANE), pc[q]);
         }
       }
+    }
+  }
+
+  // The fragment reads with the lane's address formed ONCE: frag_off() is the byte offset inside a piece plane of the 32-row block at
+  // tile row rb, MFMA step c, lane (i, h) -- what frag() below computes per call -- and frag_at() reads one piece at an LDS byte address
+  // (plane base + frag_off + constants).  A further MFMA step is + frag_step bytes in the K-major image (c stands outside its chunk XOR).
+  static constexpr unsigned frag_step = 16 * KROW * 4;
+  __device__ static inline unsigned frag_off(int rb, int c, int i, int h) {
+    if constexpr (!KM) {
+      return 4u * (unsigned)((rb + i) * (BK / 2) + 4 * ((2 * c + h) ^ swz(i)));
+    } else {
+      const int l16 = i & 15, gi = i >> 4, qq = l16 >> 2, pp = l16 & 3;
+      return (unsigned)((16 * c + 8 * h + qq) * (KROW * 4) + ((((rb >> 3) + 2 * gi + (pp >> 1)) ^ swzk(qq)) << 4) + ((pp & 1) << 3));
+    }
+  }
+  __device__ static inline u32x4 frag_at(unsigned addr) {
+    if constexpr (!KM) {
+      return lds_read<u32x4>(addr);
+    } else {
+#if defined(__HIP_DEVICE_COMPILE__)
+      typedef __attribute__((address_space(3))) s16x4* lds_s16x4_p;
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)addr);
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(addr + 4 * (KROW * 4)));
+      return __builtin_bit_cast(u32x4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+#else
+      (void)addr;
+      return u32x4{0u, 0u, 0u, 0u};
+#endif
     }
   }
 
@@ -189,6 +273,7 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
   static_assert(Bf16sLds<BM, BN, BK, NPIECE>::OPER == NPIECE * (SA::PLANE + SB::PLANE), "LDS budget");
   unsigned* const planes_a = reinterpret_cast<unsigned*>(smem);
   unsigned* const planes_b = planes_a + NPIECE * SA::PLANE;
+  const unsigned lds_a = lds_addr(smem), lds_b = lds_a + 4u * (unsigned)(NPIECE * SA::PLANE);      // (the one conversion of this launch's LDS pointer)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -222,31 +307,44 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
 
   SA la;
   SB lb;
-  la.init(p.A + (size_t)bz * p.a_batch_stride, p.lda, m0, p.M, kbeg, p.zero_page, tid);
-  lb.init(p.B, p.ldb, n0, p.N, kbeg, p.zero_page, tid);
+  la.init(p.A + (size_t)bz * p.a_batch_stride, p.lda, m0, p.M, kbeg, p.zero_page, tid, lds_a);
+  lb.init(p.B, p.ldb, n0, p.N, kbeg, p.zero_page, tid, lds_b);
 #ifdef GANMF_PERSIST_DIAG_BUILD
   la.diag_nosplit = lb.diag_nosplit = (p.diag & 2) != 0;
 #endif
 
   float4 ra[SA::NI][2], rb[SB::NI][2];
   int kleft = kend - kbeg;
-  la.load(ra, p.lda, kleft);
-  lb.load(rb, p.ldb, kleft);
+  la.load(ra, kleft);
+  lb.load(rb, kleft);
   kleft -= BK;
-  la.template store<NPIECE, F16>(planes_a, ra, sa);
-  lb.template store<NPIECE, F16>(planes_b, rb, sb);
+  la.template store<NPIECE, F16>(ra, sa);
+  lb.template store<NPIECE, F16>(rb, sb);
   __syncthreads();
+
+  // K-major fragments: this lane's address in piece plane 0 of every 32-row block, formed once (MFMA step and piece are constants of the read)
+  unsigned fa[TM], fb[TN];
+#pragma unroll
+  for (int a = 0; a < TM; ++a) fa[a] = lds_a + SA::frag_off(wr * WM + a * 32, 0, li, lh);
+#pragma unroll
+  for (int b = 0; b < TN; ++b) fb[b] = lds_b + SB::frag_off(wc * WN + b * 32, 0, li, lh);
 
   u32x4 pa[2][TM][NPIECE], pb[2][TN][NPIECE];
   auto load_frags = [&](int set, int c) {
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
-      for (int q = 0; q < NPIECE; ++q) pa[set][a][q] = SA::frag(planes_a + q * SA::PLANE, wr * WM + a * 32, c, li, lh);
+      for (int q = 0; q < NPIECE; ++q) {
+        if constexpr (AKM) pa[set][a][q] = SA::frag_at(fa[a] + c * SA::frag_step + 4u * (unsigned)(q * SA::PLANE));
+        else pa[set][a][q] = SA::frag(planes_a + q * SA::PLANE, wr * WM + a * 32, c, li, lh);
+      }
 #pragma unroll
     for (int b = 0; b < TN; ++b)
 #pragma unroll
-      for (int q = 0; q < NPIECE; ++q) pb[set][b][q] = SB::frag(planes_b + q * SB::PLANE, wc * WN + b * 32, c, li, lh);
+      for (int q = 0; q < NPIECE; ++q) {
+        if constexpr (BKM) pb[set][b][q] = SB::frag_at(fb[b] + c * SB::frag_step + 4u * (unsigned)(q * SB::PLANE));
+        else pb[set][b][q] = SB::frag(planes_b + q * SB::PLANE, wc * WN + b * 32, c, li, lh);
+      }
   };
   // Two accumulators per block in the split mode: the hi.hi products (weight 1) go to `acc`, the five correction
   // products (weights 2^-9 .. 2^-18) to `accl`, which stays ~2^-8 of `acc`, so the small terms are not rounded away
@@ -293,8 +391,8 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
       if (!(p.diag & 16))            // timing only: the first K-tile's registers are reused (no operand traffic after the prologue)
 #endif
       {
-      la.load(ra, p.lda, kleft);
-      lb.load(rb, p.ldb, kleft);
+      la.load(ra, kleft);
+      lb.load(rb, kleft);
       }
       kleft -= BK;
     }
@@ -312,8 +410,8 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
     __syncthreads();                 // every wave has read its fragments: the planes may be overwritten
     if (it < 12) GANMF_S_STAMP(3 + 5 * it);
     if (more) {
-      la.template store<NPIECE, F16>(planes_a, ra, sa);
-      lb.template store<NPIECE, F16>(planes_b, rb, sb);
+      la.template store<NPIECE, F16>(ra, sa);
+      lb.template store<NPIECE, F16>(rb, sb);
       if (it < 12) GANMF_S_STAMP(4 + 5 * it);
       __syncthreads();
       if (it < 12) GANMF_S_STAMP(5 + 5 * it);

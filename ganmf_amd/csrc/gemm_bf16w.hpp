@@ -58,7 +58,7 @@ __device__ __forceinline__ void bf16w_mainloop(const GemmP& p, const int tm, con
   constexpr int BM = BF16W_BM, BN = BF16W_BN, BK = BF16W_BK, PD = BF16W_PD, PA = BF16W_PA, PB = BF16W_PB, OPER = bf16w_oper<NPIECE>();
   const float sa = (F16 && p.a_scale != 0.f) ? p.a_scale : 1.f, sb = (F16 && p.b_scale != 0.f) ? p.b_scale : 1.f;
   typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  unsigned* const buf = reinterpret_cast<unsigned*>(smem);      // [2][A planes x 3 | B planes x 3]
+  const unsigned lds0 = lds_addr(smem);      // [2][A planes x 3 | B planes x 3]; the one conversion of the LDS pointer
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -101,79 +101,108 @@ __device__ __forceinline__ void bf16w_mainloop(const GemmP& p, const int tm, con
   int tload = 0;      // next K-tile to request
   auto load_tile = [&](auto ss) {
     constexpr int s = decltype(ss)::value;
-    const bool last = tload == nt - 1, past = tload >= nt;      // (past: a prologue slot behind a short K range -- requested all the same, from the zero page)
-    const float* a0 = ((last && !in_a) || past) ? zp : s0;
-    const float* a1 = a0 + 4;
-    const float* b0 = !BKM ? (((last && !in_b) || past) ? zp : s2) : ((kb < kleft) ? s2 : zp);
+    // (values read in front of the branch: a select between the captured variables THEMSELVES behind the asm becomes a select of their
+    // addresses, and hipcc then keeps them in scratch -- whose loads and stores the counted waits do not allow for)
+    const float* const zp_ = zp;
+    const float* const s0_ = s0;
+    const float* const s2_ = s2;
+    const int kleft_ = kleft;
+    const float* a0 = s0_;
+    const float* b0 = s2_;
+    // Only the last K-tile of the range (and a prologue slot behind a short range: requested all the same) can need the zero page: a scalar
+    // branch -- tload, nt and kleft are uniform -- guards the selects, so that every other tile executes no compare and no select for its
+    // addresses; the empty asm keeps hipcc from turning the branch back into selects.  The item's second 16 bytes ride in the load's offset.
+    if (tload >= nt - 1) {
+      asm volatile("; last K-tile");
+      const bool last = tload == nt - 1, past = tload >= nt;
+      a0 = ((last && !in_a) || past) ? zp_ : s0_;
+      b0 = !BKM ? (((last && !in_b) || past) ? zp_ : s2_) : ((kb < kleft_) ? s2_ : zp_);
+    }
     kleft -= BK;
     f32x4k l0, l1, l2;
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(l0) : "v"(a0) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(l1) : "v"(a1) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(l1) : "v"(a0) : "memory");
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(l2) : "v"(b0) : "memory");
     rg[s][0] = l0; rg[s][1] = l1; rg[s][2] = l2;
     s0 += i0; s2 += i2;
     ++tload;
   };
   // `nwait` = vector-memory loads issued after the three of the K-tile in slot s (loads return in order)
-  auto store_tile = [&](auto ss, int b, int nwait) {
+  // (LDS byte addresses, formed once, one base per plane buffer and operand -- lds_base: the piece added to it fits the store's offset)
+  unsigned st_a[2], st_b[2];
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    st_a[b] = lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER + dsta));
+    st_b[b] = lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER + NPIECE * PA + dstb));
+  }
+  auto store_tile = [&](auto ss, auto bb, int nwait) {
     constexpr int s = decltype(ss)::value;
+    constexpr int b = decltype(bb)::value;      // plane buffer
     const f32x4k v0 = rg[s][0], v1 = rg[s][1], v2 = rg[s][2];
     const int tok = bf16w_wait_vm(nwait, v0, v1, v2);
-    unsigned* o = buf + b * OPER + dsta;
-    unsigned* ob = buf + b * OPER + NPIECE * PA + dstb;
+    const unsigned o = st_a[b], ob = st_b[b];
     if constexpr (NPIECE == 3) {
       unsigned h0, m0_, l0, h1, m1, l1, h2, m2, l2, h3, m3, l3;
       split_bf16x3_tok(v0.x, v0.y, h0, m0_, l0, tok); split_bf16x3_tok(v0.z, v0.w, h1, m1, l1, tok);
       split_bf16x3_tok(v1.x, v1.y, h2, m2, l2, tok); split_bf16x3_tok(v1.z, v1.w, h3, m3, l3, tok);
-      *reinterpret_cast<u32x4*>(o) = u32x4{h0, h1, h2, h3};
-      *reinterpret_cast<u32x4*>(o + PA) = u32x4{m0_, m1, m2, m3};
-      *reinterpret_cast<u32x4*>(o + 2 * PA) = u32x4{l0, l1, l2, l3};
+      lds_write<u32x4>(o, u32x4{h0, h1, h2, h3});
+      lds_write<u32x4>(o + 4u * PA, u32x4{m0_, m1, m2, m3});
+      lds_write<u32x4>(o + 8u * PA, u32x4{l0, l1, l2, l3});
       split_bf16x3_tok(v2.x, v2.y, h0, m0_, l0, tok); split_bf16x3_tok(v2.z, v2.w, h1, m1, l1, tok);
-      *reinterpret_cast<u32x2*>(ob) = u32x2{h0, h1};
-      *reinterpret_cast<u32x2*>(ob + PB) = u32x2{m0_, m1};
-      *reinterpret_cast<u32x2*>(ob + 2 * PB) = u32x2{l0, l1};
+      lds_write<u32x2>(ob, u32x2{h0, h1});
+      lds_write<u32x2>(ob + 4u * PB, u32x2{m0_, m1});
+      lds_write<u32x2>(ob + 8u * PB, u32x2{l0, l1});
     } else if constexpr (F16) {      // (every element is multiplied by its operand's scale before anything else reads it: the scale carries the token)
       const float ca = __uint_as_float(__float_as_uint(sa) | (unsigned)tok), cb = __uint_as_float(__float_as_uint(sb) | (unsigned)tok);
-      *reinterpret_cast<u32x4*>(o) = u32x4{cvt_pk_f16(v0.x * ca, v0.y * ca), cvt_pk_f16(v0.z * ca, v0.w * ca),
-                                           cvt_pk_f16(v1.x * ca, v1.y * ca), cvt_pk_f16(v1.z * ca, v1.w * ca)};
-      *reinterpret_cast<u32x2*>(ob) = u32x2{cvt_pk_f16(v2.x * cb, v2.y * cb), cvt_pk_f16(v2.z * cb, v2.w * cb)};
+      lds_write<u32x4>(o, u32x4{cvt_pk_f16(v0.x * ca, v0.y * ca), cvt_pk_f16(v0.z * ca, v0.w * ca),
+                                cvt_pk_f16(v1.x * ca, v1.y * ca), cvt_pk_f16(v1.z * ca, v1.w * ca)});
+      lds_write<u32x2>(ob, u32x2{cvt_pk_f16(v2.x * cb, v2.y * cb), cvt_pk_f16(v2.z * cb, v2.w * cb)});
     } else {
-      *reinterpret_cast<u32x4*>(o) = u32x4{cvt_pk_bf16_tok(v0.x, v0.y, tok), cvt_pk_bf16_tok(v0.z, v0.w, tok),
-                                           cvt_pk_bf16_tok(v1.x, v1.y, tok), cvt_pk_bf16_tok(v1.z, v1.w, tok)};
-      *reinterpret_cast<u32x2*>(ob) = u32x2{cvt_pk_bf16_tok(v2.x, v2.y, tok), cvt_pk_bf16_tok(v2.z, v2.w, tok)};
+      lds_write<u32x4>(o, u32x4{cvt_pk_bf16_tok(v0.x, v0.y, tok), cvt_pk_bf16_tok(v0.z, v0.w, tok),
+                                cvt_pk_bf16_tok(v1.x, v1.y, tok), cvt_pk_bf16_tok(v1.z, v1.w, tok)});
+      lds_write<u32x2>(ob, u32x2{cvt_pk_bf16_tok(v2.x, v2.y, tok), cvt_pk_bf16_tok(v2.z, v2.w, tok)});
     }
   };
   // prologue: K-tiles 0 .. PD-1 requested, tile 0 split into buffer 0; everything requested lands before the loop is entered
   // (all PD slots without a branch: with the requests inside `if (slot < nt)` hipcc joins the paths with COPIES of registers whose loads
   // are in flight -- tools/check_asm_prefetch.py)
   static_for<0, PD>([&](auto ss) { load_tile(ss); });
-  store_tile(std::integral_constant<int, 0>{}, 0, 3 * (PD - 1));
+  store_tile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, 3 * (PD - 1));
   asm volatile("s_waitcnt vmcnt(0)" :: "v"(rg[0][0]), "v"(rg[0][1]), "v"(rg[0][2]), "v"(rg[1][0]), "v"(rg[1][1]), "v"(rg[1][2]));
-  static_assert(PD == 2, "the wait above names every prefetch register");
+  static_assert(PD == 2, "the wait above names every prefetch register");      // (PD even: K-tile t of slot s lies in buffer s & 1)
   __syncthreads();
 #ifdef GANMF_PERSIST_DIAG_BUILD
   if (p.stamps && tid == 0) p.stamps[(size_t)blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();      // first K-tile split into LDS
 #endif
 
-  const int fa = (wr * 32 + li) * (BK / 2) + (((2 * kg + lh) ^ (li & 15)) << 2);      // this lane's fragment of an A plane / of a B plane
-  const int fb = li * (BK / 2) + (((2 * kg + lh) ^ (li & 15)) << 2);
+  // this lane's fragment of an A plane / of a B plane: LDS byte addresses in piece plane 0 of buffer 0
+  unsigned fa[2], fb[2];
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    fa[b] = lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER + (wr * 32 + li) * (BK / 2) + (((2 * kg + lh) ^ (li & 15)) << 2)));
+    if constexpr (!BKM) fb[b] = lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER + NPIECE * PA + li * (BK / 2) + (((2 * kg + lh) ^ (li & 15)) << 2)));
+    else fb[b] = 0u;
+  }
   // K-major B: ds_read_b64_tr_b16 (SplitStage<.., true>::frag): lane 4 qq + pp of a 16-lane group gives the address of k-row qq, columns
   // 4 pp .. 4 pp + 3 of a 4 (k) x 16 (n) block and receives column (lane & 15) of the four k-rows; group li >> 4 takes columns 16 .. 31;
   // lane half lh the k-rows 16 kg + 8 lh + 0..7 in two reads (+ 0..3, + 4..7)
-  const int fbt = ((16 * kg + 8 * lh + ((li & 15) >> 2)) * (BN / 2) * 4) + 32 * (li >> 4) + 8 * (li & 3);      // bytes inside a B plane
+  unsigned fbt[2];      // (byte address in piece plane 0 of B, per plane buffer)
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+    fbt[b] = !BKM ? 0u : lds_base<NPIECE == 3>(lds0 + 4u * (unsigned)(b * OPER + NPIECE * PA) + (unsigned)(((16 * kg + 8 * lh + ((li & 15) >> 2)) * (BN / 2) * 4) + 32 * (li >> 4) + 8 * (li & 3)));
   auto step = [&](auto ss, int t) {      // K-tile t, whose registers were slot s = t % PD (consumed in iteration t - 1)
     constexpr int s = decltype(ss)::value, s1_ = (s + 1) % PD;
-    const unsigned* planes = buf + (t & 1) * OPER;
+    constexpr int b = s & 1;      // plane buffer: t & 1 == s & 1
     u32x4 pa[3], pb[3];
 #pragma unroll
-    for (int q = 0; q < NPIECE; ++q) pa[q] = *reinterpret_cast<const u32x4*>(planes + q * PA + fa);
+    for (int q = 0; q < NPIECE; ++q) pa[q] = lds_read<u32x4>(fa[b] + 4u * (unsigned)(q * PA));
     if constexpr (!BKM) {
 #pragma unroll
-      for (int q = 0; q < NPIECE; ++q) pb[q] = *reinterpret_cast<const u32x4*>(planes + NPIECE * PA + q * PB + fb);
+      for (int q = 0; q < NPIECE; ++q) pb[q] = lds_read<u32x4>(fb[b] + 4u * (unsigned)(q * PB));
     } else {
 #if defined(__HIP_DEVICE_COMPILE__)      // (LDS pointers are 32 bits wide in the device pass only)
       typedef __attribute__((address_space(3))) s16x4* lds_s16x4_p;
-      const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned*)(planes + NPIECE * PA) + (unsigned)fbt;
+      const unsigned base = fbt[b];
 #pragma unroll
       for (int q = 0; q < NPIECE; ++q) {
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(base + q * PB * 4));
@@ -202,7 +231,7 @@ __device__ __forceinline__ void bf16w_mainloop(const GemmP& p, const int tm, con
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pa[0]), __builtin_bit_cast(bf16x8, pb[0]), acc, 0, 0, 0);
     }
     // under the MFMAs: split K-tile t + 1 into the other buffer; behind its three loads went those of tiles t + 2 .. min(t + PD, nt - 1)
-    if (t + 1 < nt) store_tile(std::integral_constant<int, s1_>{}, (t + 1) & 1, 3 * (min(t + PD, nt - 1) - (t + 1)));
+    if (t + 1 < nt) store_tile(std::integral_constant<int, s1_>{}, std::integral_constant<int, (s1_ & 1)>{}, 3 * (min(t + PD, nt - 1) - (t + 1)));
     __syncthreads();
   };
   for (int t = 0; t < nt; t += PD)

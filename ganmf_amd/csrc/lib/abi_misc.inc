@@ -66,16 +66,26 @@ int ganmf_profile_read(ganmf_handle* h, ganmf_prof_entry* out, int32_t cap, int3
   return 0;
 }
 
-int ganmf_gemm_f32(int device, const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K,
-                   int a_kmajor, int b_kmajor, int tile, int nsplit, int iters, float* ms) {
+// ganmf_gemm_f32 / ganmf_gemm_f32_ex.  `a_gather` (M ids into the a_rows rows of a K-contiguous A), `bk` (GemmPlan::bk: 32 = the 4-wave staged
+// kernel's 32-deep K-tile) and `adam_m` (the fused-Adam epilogue on theta = m = v = 0, lr_t = 1e-3, no L2 term: C returns theta, adam_m the first
+// moment, which is (1 - beta1) x the product) reach what the step's launches use and the plain entry cannot ask for.
+static int gemm_f32_entry(int device, const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K,
+                          int a_kmajor, int b_kmajor, int tile, int nsplit, int iters, float* ms,
+                          const int32_t* a_gather, int64_t a_rows, int bk, float* adam_m) {
   if (!A || !B || !C || M < 1 || N < 1 || K < 1) return fail(-1, "ganmf_gemm_f32: bad argument");
+  if (a_gather && (a_kmajor || a_rows < 1)) return fail(-1, "ganmf_gemm_f32_ex: a row list needs a K-contiguous A with a_rows >= 1 rows");
+  if (bk != 0 && bk != 32) return fail(-1, "ganmf_gemm_f32_ex: bk must be 0 or 32");
+  if (adam_m && (iters > 1 || ms)) return fail(-1, "ganmf_gemm_f32_ex: the Adam epilogue updates its state: one launch, no timing (iters = 1, ms = NULL)");
+  if (a_gather)
+    for (int64_t r = 0; r < M; ++r)
+      if (a_gather[r] < 0 || a_gather[r] >= a_rows) return fail(-1, "ganmf_gemm_f32_ex: row id out of range");
   if (a_kmajor && !b_kmajor) return fail(-1, "ganmf_gemm_f32: the TT layout is not part of the GANMF path");
   if (tile != 0 && tile != 64 && tile != 128) return fail(-1, "ganmf_gemm_f32: tile must be 0, 64 or 128");
   HIP_TRY(hipSetDevice(device));
-  const int ar = a_kmajor ? K : M, ac = a_kmajor ? M : K;
+  const int ar = a_kmajor ? K : (a_gather ? (int)a_rows : M), ac = a_kmajor ? M : K;
   const int br = b_kmajor ? K : N, bc = b_kmajor ? N : K;
   const int lda = round_up(ac, LD_ALIGN), ldb = round_up(bc, LD_ALIGN), ldc = round_up((int)N, LD_ALIGN);
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr, *slab = nullptr, *zp = nullptr;
+  float *dA = nullptr, *dB = nullptr, *dC = nullptr, *slab = nullptr, *zp = nullptr, *dIds = nullptr, *dMom = nullptr, *dAlpha = nullptr;
   TRY(dalloc(&zp, 2048 + 64));
   TRY(dalloc(&dA, (size_t)ar * lda)); TRY(dalloc(&dB, (size_t)br * ldb)); TRY(dalloc(&dC, (size_t)M * ldc));
   HIP_TRY(hipMemcpy2D(dA, (size_t)lda * 4, A, (size_t)ac * 4, (size_t)ac * 4, ar, hipMemcpyHostToDevice));
@@ -83,8 +93,20 @@ int ganmf_gemm_f32(int device, const float* A, const float* B, float* C, int64_t
   GemmP g{};
   g.A = dA; g.lda = lda; g.B = dB; g.ldb = ldb; g.C = dC; g.ldc = ldc;
   g.M = (int)M; g.N = (int)N; g.K = (int)K; g.nbatch = 1; g.epi.kind = EPI_STORE; g.zero_page = zp; g.c_pad_writable = 1;
+  if (a_gather) {
+    TRY(dalloc(&dIds, (size_t)M));
+    HIP_TRY(hipMemcpy(dIds, a_gather, (size_t)M * 4, hipMemcpyHostToDevice));
+    g.a_gather = reinterpret_cast<const int*>(dIds);
+  }
+  if (adam_m) {      // theta (= C), m, v start at zero (dalloc clears)
+    const float alpha = 1e-3f;
+    TRY(dalloc(&dMom, 2 * (size_t)M * ldc)); TRY(dalloc(&dAlpha, 64));
+    HIP_TRY(hipMemcpy(dAlpha, &alpha, 4, hipMemcpyHostToDevice));
+    g.epi.kind = EPI_ADAM; g.epi.adam_theta = dC; g.epi.adam_m = dMom; g.epi.adam_v = dMom + (size_t)M * ldc;
+    g.epi.adam_alpha = dAlpha; g.epi.adam_reg = 0.f;
+  }
   GemmTune tune;
-  tune.tile = tile; tune.nsplit = nsplit;
+  tune.tile = tile; tune.nsplit = adam_m ? 1 : nsplit; tune.bk = bk;
   tune.mode = env_mfma_mode(MFMA_DEFAULT);
   tune.ring = tune_env_int("ring", 0);
   if (tune.ring != 0 && tune.ring != 2 && tune.ring != 3 && tune.ring != 4) tune.ring = 0;
@@ -93,7 +115,7 @@ int ganmf_gemm_f32(int device, const float* A, const float* B, float* C, int64_t
   tune.kg = tune_env_int("kg", 0);
   tune.tile_order = tune_env_int("tile_order", 0);
   if (tune.kg != 0 && tune.kg != 1 && tune.kg != 2 && tune.kg != 4) tune.kg = 0;
-  GemmPlan pl = gemm_plan(g.M, g.N, g.K, 1, false, tune);
+  GemmPlan pl = gemm_plan(g.M, g.N, g.K, 1, false, tune, adam_m != nullptr);
   pl.persist = gemm_persist_eligible(g, a_kmajor, b_kmajor, pl, tune.persist) ? (tune.persist >= 2 ? tune.persist : 1) : 0;
   if (tune_env_int("skinny", 1) && tile == 0 && nsplit == 0) { if (!plan_skinny(pl, g, a_kmajor != 0) && tune_env_int("skinny_n", 1)) plan_skinny_n(pl, g, a_kmajor != 0); }
   if (env_int("GANMF_X3KG", 0) && pl.mode == MFMA_F32 && pl.tile == 64 && pl.kg == 4 && pl.ring == 3 && !pl.persist) pl.mode = MFMA_BF16X3;      // (tests: the 16-wave split-bf16 kernel)
@@ -103,6 +125,9 @@ int ganmf_gemm_f32(int device, const float* A, const float* B, float* C, int64_t
             g.M, g.N, g.K, pl.tile, pl.ring, pl.kg, pl.nsplit, pl.kps,
             pl.mode == MFMA_BF16X3 ? "bf16x3" : pl.mode == MFMA_BF16 ? "bf16" : pl.mode == MFMA_F16 ? "f16" : "f32", pl.tiles_m * pl.tiles_n * pl.nsplit, pl.est_us,
             pl.skinny ? " (skinny-K stream)" : pl.skinny_n ? " (skinny-N stream)" : pl.wide32 ? " (64 x 32 tiles, 128-deep K-tiles)" : pl.persist ? " (persistent tile walk)" : "");
+  // (the row list is read by the 16-wave kernels' operand fetch only: any other plan would silently multiply the ungathered rows)
+  if (a_gather && !(pl.tile == 64 && pl.kg == 4 && !pl.persist && !pl.skinny && !pl.skinny_n && !pl.wide32))
+    return fail(-1, "ganmf_gemm_f32_ex: a row list needs a 16-wave 64 x 64 plan (tile = 64, GANMF_TUNE kg=4,ring=3)");
   // GANMF_TUNE planes=1 (tests): both operands split into bf16 x 3 planes ahead of the launch -- the 16-wave plan then runs its DMA
   // form (gemm_planes.hpp), which must reproduce the in-loop split bit for bit
   bf16raw *plA = nullptr, *plB = nullptr;
@@ -138,9 +163,21 @@ int ganmf_gemm_f32(int device, const float* A, const float* B, float* C, int64_t
     hipEventDestroy(a); hipEventDestroy(b);
   }
   HIP_TRY(hipMemcpy2D(C, (size_t)N * 4, dC, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
-  hipFree(dA); hipFree(dB); hipFree(dC); hipFree(zp); hipFree(plA); hipFree(plB);
+  if (adam_m) HIP_TRY(hipMemcpy2D(adam_m, (size_t)N * 4, dMom, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
+  hipFree(dA); hipFree(dB); hipFree(dC); hipFree(zp); hipFree(plA); hipFree(plB); hipFree(dIds); hipFree(dMom); hipFree(dAlpha);
   if (slab) hipFree(slab);
   if (counters) hipFree(counters);
   return 0;
+}
+
+int ganmf_gemm_f32(int device, const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K,
+                   int a_kmajor, int b_kmajor, int tile, int nsplit, int iters, float* ms) {
+  return gemm_f32_entry(device, A, B, C, M, N, K, a_kmajor, b_kmajor, tile, nsplit, iters, ms, nullptr, 0, 0, nullptr);
+}
+
+int ganmf_gemm_f32_ex(int device, const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K,
+                      int a_kmajor, int b_kmajor, int tile, int nsplit, int iters, float* ms,
+                      const int32_t* a_gather, int64_t a_rows, int bk, float* adam_m) {
+  return gemm_f32_entry(device, A, B, C, M, N, K, a_kmajor, b_kmajor, tile, nsplit, iters, ms, a_gather, a_rows, bk, adam_m);
 }
 

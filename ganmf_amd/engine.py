@@ -644,3 +644,26 @@ def gemm_f32(A, B, a_kmajor=False, b_kmajor=False, tile=0, nsplit=0, iters=1, de
     L.check(lib.ganmf_gemm_f32(device, _f32p(A), _f32p(B), _f32p(out), M, N, K, int(a_kmajor), int(b_kmajor),
                                tile, nsplit, iters, C.byref(ms)), "ganmf_gemm_f32")
     return out, ms.value
+
+
+def gemm_f32_ex(A, B, a_kmajor=False, b_kmajor=False, tile=0, nsplit=0, iters=1, device=0, a_gather=None, bk=0, adam=False):
+    """gemm_f32 with what only the step's launches use (ganmf_gemm_f32_ex): `a_gather` -- row r of the product's A is A[a_gather[r]];
+    `bk` = 32 -- the 4-wave staged kernel's 32-deep K-tile; `adam` -- the fused-Adam epilogue on zero state: returns (theta, m, ms)
+    with m = (1 - beta1) x the product (one launch: no timing, ms = 0)."""
+    lib = L.load_library()
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    B = np.ascontiguousarray(B, dtype=np.float32)
+    K, M = (A.shape if a_kmajor else A.shape[::-1])
+    Kb, N = (B.shape if b_kmajor else B.shape[::-1])
+    assert K == Kb, (A.shape, B.shape)
+    ids, a_rows = None, 0
+    if a_gather is not None:
+        ids = np.ascontiguousarray(a_gather, dtype=np.int32)
+        a_rows, M = A.shape[0], len(ids)
+    out = np.empty((M, N), dtype=np.float32)
+    mom = np.empty((M, N), dtype=np.float32) if adam else None
+    ms = C.c_float()
+    L.check(lib.ganmf_gemm_f32_ex(device, _f32p(A), _f32p(B), _f32p(out), M, N, K, int(a_kmajor), int(b_kmajor), tile, nsplit, iters,
+                                  None if adam else C.byref(ms), ids.ctypes.data_as(C.POINTER(C.c_int32)) if ids is not None else None, a_rows, bk,
+                                  _f32p(mom) if adam else None), "ganmf_gemm_f32_ex")
+    return (out, mom, ms.value) if adam else (out, ms.value)

@@ -635,6 +635,16 @@ int ganmf_bench_scores(ganmf_handle* h, int64_t n, int transposed, int32_t iters
 int ganmf_gemm_f32(int device, const float* A, const float* B, float* C, int64_t M, int64_t N,
                    int64_t K, int a_kmajor, int b_kmajor, int tile, int nsplit, int iters, float* ms);
 
+/* The same entry with what only the training step's launches use (tests of their K loops):
+ *   a_gather  NULL, or M row ids: row r of the product's A is row a_gather[r] of the [a_rows, K] matrix A (a_kmajor = 0; needs a
+ *             16-wave 64 x 64 plan: tile = 64 with GANMF_TUNE kg=4,ring=3)
+ *   bk        0 auto, 32: the 32-deep K-tile of the 4-wave staged split-bf16 kernel (GANMF_MFMA=bf16x3, tile = 64)
+ *   adam_m    NULL, or [M, N]: the product runs unsplit behind the fused TF-Adam epilogue on theta = m = v = 0 with lr_t = 1e-3 and
+ *             no L2 term; C returns the updated theta and adam_m the first moment, (1 - beta1) x the product */
+int ganmf_gemm_f32_ex(int device, const float* A, const float* B, float* C, int64_t M, int64_t N,
+                      int64_t K, int a_kmajor, int b_kmajor, int tile, int nsplit, int iters, float* ms,
+                      const int32_t* a_gather, int64_t a_rows, int bk, float* adam_m);
+
 /* Host-only helper of the checkpoint writer/reader (ganmf_amd/tf_bundle.py): CRC-32C (Castagnoli), the
  * checksum tf.train.Saver stores per tensor and per table block (GANMF.py:309-314,337-339).  Pass crc = 0
  * to start; feed the previous return value to continue over a second buffer. */
