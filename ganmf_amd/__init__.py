@@ -6,7 +6,7 @@ fallback: without the HIP library and a GPU the classes raise.
 """
 from ._lib import build_library, library_path, load_library  # noqa: F401
 
-__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "CFGAN", "IALSRecommender", "PureSVDRecommender"]
+__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "CFGAN", "CAAE", "IALSRecommender", "PureSVDRecommender"]
 
 
 def __getattr__(name):
@@ -19,6 +19,9 @@ def __getattr__(name):
     if name == "CFGAN":
         from .CFGAN import CFGAN
         return CFGAN
+    if name == "CAAE":
+        from .CAAE import CAAE
+        return CAAE
     if name == "IALSRecommender":
         from .IALS import IALSRecommender
         return IALSRecommender

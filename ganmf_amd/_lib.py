@@ -8,7 +8,7 @@ _LIB_PATH = os.environ.get("GANMF_LIB_PATH") or os.path.join(_HERE, "libganmf_hi
 _lib = None
 
 ABI_VERSION = 2
-MODEL_GANMF, MODEL_DISGANMF, MODEL_MF, MODEL_ITEMSIM, MODEL_CFGAN = 0, 1, 2, 3, 4
+MODEL_GANMF, MODEL_DISGANMF, MODEL_MF, MODEL_ITEMSIM, MODEL_CFGAN, MODEL_CAAE = 0, 1, 2, 3, 4, 5
 ITEMKNN_MAX_TOPK = 1024            # include/ganmf_hip.h GANMF_ITEMKNN_MAX_TOPK
 # include/ganmf_hip.h GANMF_ITEMKNN_*: the denominator ganmf_itemknn_fit applies to the dot products
 ITEMKNN_PRODUCT, ITEMKNN_TANIMOTO, ITEMKNN_DICE, ITEMKNN_TVERSKY, ITEMKNN_SHRINK_ONLY, ITEMKNN_RAW = 0, 1, 2, 3, 4, 5
@@ -23,6 +23,11 @@ ACT = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
 T_USER_EMB, T_ITEM_EMB = 100, 101
 T_CFGAN_G0 = 200                  # include/ganmf_hip.h GANMF_T_CFGAN_G0: first generator tensor of a MODEL_CFGAN handle
 CFGAN_SCHEMES = {"ZR": 0, "PM": 1, "ZP": 2}      # include/ganmf_hip.h GANMF_CFGAN_*
+# include/ganmf_hip.h GANMF_T_CAAE_*: the item bias and the first tensor of G / G' of a MODEL_CAAE handle; GANMF_CAAE_*
+T_CAAE_ITEM_BIAS, T_CAAE_G0, T_CAAE_GPR0 = 102, 300, 400
+CAAE_MAX_FACTORS, CAAE_MAX_D_BSIZE = 256, 16384
+CAAE_DRAWS = {"perm": 0, "neg_g": 1, "neg_gpr": 2, "users_g": 3, "users_gpr": 4, "nu": 5, "items_g": 6, "items_gpr": 7, "cdf_g": 8,
+              "cdf_gpr": 9}
 SLOT_PARAM, SLOT_ADAM_M, SLOT_ADAM_V, SLOT_BEST = 0, 1, 2, 3
 EVAL_METRICS = ("ROC_AUC", "PRECISION", "PRECISION_RECALL_MIN_DEN", "RECALL", "MAP", "MRR", "NDCG", "HIT_RATE", "ARHR")
 EVAL_MAX_CUTOFFS = 8
@@ -38,7 +43,7 @@ SYMBOLS = [
     "ganmf_create", "ganmf_destroy", "ganmf_comm_unique_id", "ganmf_comm_init", "ganmf_comm_init_local", "ganmf_comm_abort", "ganmf_comm_info", "ganmf_set_urm_csr",
     "ganmf_set_tensor", "ganmf_get_tensor", "ganmf_tensor_shape", "ganmf_get_adam_powers",
     "ganmf_set_adam_powers", "ganmf_train_epoch", "ganmf_train_epoch_ragged", "ganmf_train_step", "ganmf_scores",
-    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_p3_fit", "ganmf_slim_bpr_init", "ganmf_slim_bpr_draw", "ganmf_slim_bpr_run", "ganmf_slim_bpr_epochs", "ganmf_slim_bpr_finish", "ganmf_slim_bpr_get_state", "ganmf_cfgan_init", "ganmf_cfgan_draw_masks", "ganmf_cfgan_set_masks", "ganmf_cfgan_get_masks", "ganmf_cfgan_step", "ganmf_cfgan_epoch", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
+    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_p3_fit", "ganmf_slim_bpr_init", "ganmf_slim_bpr_draw", "ganmf_slim_bpr_run", "ganmf_slim_bpr_epochs", "ganmf_slim_bpr_finish", "ganmf_slim_bpr_get_state", "ganmf_cfgan_init", "ganmf_cfgan_draw_masks", "ganmf_cfgan_set_masks", "ganmf_cfgan_get_masks", "ganmf_cfgan_step", "ganmf_cfgan_epoch", "ganmf_caae_init", "ganmf_caae_cdf", "ganmf_caae_draw_perm", "ganmf_caae_draw_negatives", "ganmf_caae_draw_batch", "ganmf_caae_get_draws", "ganmf_caae_d_step", "ganmf_caae_g_step", "ganmf_caae_epoch", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
     "ganmf_bench_scores", "ganmf_gemm_f32", "ganmf_gemm_f32_ex", "ganmf_crc32c", "ganmf_device_count", "ganmf_abi_version", "ganmf_last_error",
 ]
 
@@ -149,6 +154,15 @@ def load_library():
         "ganmf_cfgan_get_masks": (C.c_int, [vp, P(C.c_uint32), P(C.c_uint32)]),
         "ganmf_cfgan_step": (C.c_int, [vp, C.c_int, i64, i32, f32p]),
         "ganmf_cfgan_epoch": (C.c_int, [vp, i64, i32, i32, C.c_int, f32p, f32p]),
+        "ganmf_caae_init": (C.c_int, [vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_uint64, P(C.c_int32)]),
+        "ganmf_caae_cdf": (C.c_int, [vp, C.c_int, P(C.c_int32), i32, f32p, f32p]),
+        "ganmf_caae_draw_perm": (C.c_int, [vp, i64, P(C.c_int32)]),
+        "ganmf_caae_draw_negatives": (C.c_int, [vp, i64, i32, C.c_int, P(C.c_int32)]),
+        "ganmf_caae_draw_batch": (C.c_int, [vp, i64, C.c_int, i32, P(C.c_int32), P(C.c_uint32), P(C.c_int32), f32p]),
+        "ganmf_caae_get_draws": (C.c_int, [vp, C.c_int, i32, vp, i64]),
+        "ganmf_caae_d_step": (C.c_int, [vp, P(C.c_int32), P(C.c_int32), P(C.c_int32), i32, f32p]),
+        "ganmf_caae_g_step": (C.c_int, [vp, C.c_int, P(C.c_int32), P(C.c_uint32), P(C.c_int32), f32p]),
+        "ganmf_caae_epoch": (C.c_int, [vp, i64, i32, i32, i32, f32p, f32p, f32p]),
         "ganmf_crc32c": (C.c_uint32, [C.c_uint32, vp, C.c_uint64]),
         "ganmf_snapshot_best": (C.c_int, [vp]),
         "ganmf_restore_best": (C.c_int, [vp]),

@@ -52,6 +52,8 @@
 #include "slim_sched.hpp"
 #include "cfgan_masks.hpp"
 #include "cfgan_rows.hpp"
+#include "caae_sample.hpp"
+#include "caae_rows.hpp"
 #include "gemm_multi.hpp"
 #ifdef GANMF_PERSIST_DIAG_BUILD
 #include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
@@ -72,6 +74,7 @@ namespace {
 #include "lib/step_ganmf.inc"
 #include "lib/step_disganmf.inc"
 #include "lib/step_cfgan.inc"
+#include "lib/step_caae.inc"
 #include "lib/epoch.inc"
 }  // namespace
 
@@ -87,5 +90,6 @@ extern "C" {
 #include "lib/abi_p3.inc"
 #include "lib/abi_slim.inc"
 #include "lib/abi_cfgan.inc"
+#include "lib/abi_caae.inc"
 #include "lib/abi_misc.inc"
 }  // extern "C"

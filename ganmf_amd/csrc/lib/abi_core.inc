@@ -44,7 +44,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h);
 int ganmf_create(const ganmf_cfg* cfg, ganmf_handle** out) {
   if (!cfg || !out) return fail(-1, "ganmf_create: null argument");
   if (cfg->abi_version != GANMF_ABI_VERSION) return fail(-1, "ganmf_create: ABI version %d != %d", cfg->abi_version, GANMF_ABI_VERSION);
-  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF && cfg->model != GANMF_MODEL_MF && cfg->model != GANMF_MODEL_ITEMSIM && cfg->model != GANMF_MODEL_CFGAN) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
+  if (cfg->model != GANMF_MODEL_GANMF && cfg->model != GANMF_MODEL_DISGANMF && cfg->model != GANMF_MODEL_MF && cfg->model != GANMF_MODEL_ITEMSIM && cfg->model != GANMF_MODEL_CFGAN && cfg->model != GANMF_MODEL_CAAE) return fail(-1, "ganmf_create: unknown model %d", cfg->model);
   if (cfg->model == GANMF_MODEL_DISGANMF && (cfg->d_layers < 1 || cfg->d_layers > 16 || cfg->d_act < 0 || cfg->d_act > 3))
     return fail(-1, "ganmf_create: DisGANMF needs 1 <= d_layers <= 16 and a known activation");
   if (cfg->model == GANMF_MODEL_CFGAN) {
@@ -54,6 +54,12 @@ int ganmf_create(const ganmf_cfg* cfg, ganmf_handle** out) {
     if (cfg->flags & (GANMF_FLAG_MFMA_BF16 | GANMF_FLAG_MFMA_F16))
       return fail(-1, "ganmf_create: GANMF_MODEL_CFGAN runs the fp32-accurate products only (the bf16 / fp16 MFMA flags are refused)");
     if (cfg->num_items > (1LL << 29)) return fail(-1, "ganmf_create: CFGAN's discriminator input is 2 x num_items wide: dimension too large");
+  }
+  if (cfg->model == GANMF_MODEL_CAAE) {
+    if (cfg->world_size > 1) return fail(-1, "ganmf_create: GANMF_MODEL_CAAE is single-GPU (world_size %d)", cfg->world_size);
+    if (cfg->flags & (GANMF_FLAG_MFMA_BF16 | GANMF_FLAG_MFMA_F16))
+      return fail(-1, "ganmf_create: GANMF_MODEL_CAAE runs the fp32-accurate products only (the bf16 / fp16 MFMA flags are refused)");
+    if (cfg->num_factors > GANMF_CAAE_MAX_FACTORS) return fail(-1, "ganmf_create: GANMF_MODEL_CAAE holds at most %d factors", GANMF_CAAE_MAX_FACTORS);
   }
   if (cfg->num_users < 1 || cfg->num_items < 1 || cfg->num_factors < 1 || cfg->emb_dim < 1 || cfg->batch_size < 1)
     return fail(-1, "ganmf_create: non-positive dimension");
@@ -163,7 +169,9 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   const bool dis = cfg->model == GANMF_MODEL_DISGANMF;
   const bool sim = cfg->model == GANMF_MODEL_ITEMSIM;      // a weighted URM and an item similarity matrix: no tensor at all
   const bool cfgan = cfg->model == GANMF_MODEL_CFGAN;      // two MLPs: the discriminator here, the generator and the work buffers by ganmf_cfgan_init
-  const bool mf = cfg->model == GANMF_MODEL_MF || sim;      // factors only (or not even those): no discriminator, no minibatch buffers
+  const bool caae = cfg->model == GANMF_MODEL_CAAE;        // the factor tensors are its discriminator's; everything else by ganmf_caae_init
+  const bool mf = cfg->model == GANMF_MODEL_MF || sim || caae;      // factors only (or not even those): no discriminator, no minibatch buffers
+  if (caae && low_precision(h)) return fail(-1, "ganmf_create: GANMF_MODEL_CAAE runs the fp32-accurate products only (GANMF_MFMA asks for bf16 / f16)");
   // parameters; D gradients contiguous for a single all-reduce
   const int world = std::max(1, (int)cfg->world_size);
   if (!sim && !cfgan) {
@@ -299,6 +307,7 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->svd_lam); hipFree(h->svd_flag);
   hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
   cfgan_free(h);
+  caae_free(h);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   if (h->st2) hipStreamSynchronize(h->st2);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -441,6 +450,7 @@ int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* ind
   }
   h->nnz = nnz;
   h->has_urm = true;
+  h->ca.iu_src = nullptr;      // CAAE: the users of the stored interactions are formed again from this matrix (caae_prepare)
   // SURVEY 8(f)-3: below 0.5 % density (LastFM: 0.22 %) the generator step reads the real rows as CSR (GANMF only;
   // DisGANMF feeds the rows themselves to its discriminator).  GANMF_SPARSE = 0 / 1 overrides.
   const double density = (double)nnz / ((double)n_rows * (double)n_cols);

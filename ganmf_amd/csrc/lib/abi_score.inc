@@ -81,6 +81,13 @@ static int scores_device(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
     *out_dev = h->sc_out; *width = W; *ld_out = ldw;
     return 0;
   }
+  if (h->cfg.model == GANMF_MODEL_CAAE) {      // the fourth source (step_caae.inc): sigmoid(G(profile)) of the rows
+    const int W = h->N, ldw = round_up(W, LD_ALIGN);
+    TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
+    TRY(caae_scores(h, ids_dev, n, transposed, h->sc_out, ldw));
+    *out_dev = h->sc_out; *width = W; *ld_out = ldw;
+    return 0;
+  }
   Tensor& colsT = transposed ? h->Ue : h->V;   // the other factor
   const int W = colsT.rows, ldw = round_up(W, LD_ALIGN);
   TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));

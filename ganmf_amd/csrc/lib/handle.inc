@@ -81,6 +81,44 @@ struct CfganState {
   long long cache_version = -1;
 };
 
+// CAAE state of a GANMF_MODEL_CAAE handle (ganmf_caae_init; step_caae.inc).  The discriminator's embeddings P, Q are the handle's
+// factor tensors Ue [U, k] and V [N, k]; its item bias, the two generators (gen[0] = G, gen[1] = G': the generator members of a
+// CfganState each, sigmoid everywhere), the epoch's draws and the steps' work buffers live here.
+struct CaaeState {
+  bool ready = false;
+  int g = 0, Lg = 0, ldg = 0, Bm = 0, n_s = 0, words = 0, d_bsize = 0;
+  float lmbda = 0.f, beta = 0.f, lr = 0.f;
+  uint64_t seed = 0;
+  CfganState gen[2];             // Gl, Go, Hl, g, Lg, act, ldg (and the scoring scratch of gen[0])
+  Tensor bias;                   // disc_item_bias [1, N]
+  int* k_rows = nullptr;         // [U] size of Nu per user
+  // the epoch's state: both CDFs [U, ldN], the user of every stored interaction, the shuffled order and its triples
+  float* cdf[2] = {nullptr, nullptr};
+  int* iu = nullptr;             // [nnz] row of CSR position e
+  const void* iu_src = nullptr;  // the indptr it was formed from
+  int *perm = nullptr, *tu = nullptr, *ti = nullptr;      // [nnz]: CSR position, user and item of every position of the shuffled order
+  long long order_cap = 0;
+  // recorded draws of the last epoch, per pass / step slot (ganmf_caae_get_draws)
+  int* neg = nullptr;            // [passes][2][nnz]
+  size_t neg_cap = 0;
+  int* users = nullptr;          // [2][steps][Bm]
+  unsigned* nu = nullptr;        // [steps][Bm * words]
+  int* items = nullptr;          // [2][steps][Bm * n_s]
+  int step_slots = 0, rec_passes = 0, rec_steps[2] = {0, 0};
+  long long rec_nnz = 0;
+  // explicit triples of a single D-step, the gathered rows and per-triple values of the step in flight
+  int* xt = nullptr;             // [3][d_bsize]
+  int* first = nullptr;          // [U + N] CaaeDP::first: 0x7f7f7f7f between steps
+  int *xu = nullptr, *xi = nullptr;      // [Bm], [Bm * n_s]: users and policy items of a single step or draw entry
+  unsigned* xn = nullptr;        // [Bm * words]: its Nu planes
+  float *Pg = nullptr, *Qi = nullptr, *Qj = nullptr, *coef = nullptr, *lt = nullptr, *rt = nullptr;
+  // generator step: profiles, outputs of G and G', batch CDF, d loss / d z of the output layer, hidden gradients, per-row parts
+  float *C = nullptr, *R = nullptr, *Rp = nullptr, *cdfb = nullptr, *dz = nullptr, *dh0 = nullptr, *dh1 = nullptr;
+  float *lse = nullptr, *reward = nullptr, *la = nullptr, *ae = nullptr, *sq = nullptr, *loss_dev = nullptr;
+  size_t loss_cap = 0;
+  float* lse_all = nullptr;      // [U] log sum exp(r) of the all-users CDF pass
+};
+
 struct ganmf_handle {
   ganmf_cfg cfg;
   int dev = 0;
@@ -280,6 +318,7 @@ struct ganmf_handle {
   size_t knn_dense_cap = 0;
   SlimState slim;                                   // ganmf_slim_bpr_* (slim_bpr.hpp)
   CfganState cf;                                    // ganmf_cfgan_* (cfgan_masks.hpp, cfgan_rows.hpp)
+  CaaeState ca;                                     // ganmf_caae_* (caae_sample.hpp, caae_rows.hpp)
   // ganmf_pure_svd (svd_rows.hpp): the two panels [max(U, N), svd_ldl] the iteration alternates between, the Gram matrix and the
   // inverse Cholesky factor [svd_ldl, svd_ldl], the [svd_ldl, ldk] matrix W of the final products, lambda [svd_ldl] | sigma [ldk],
   // and the failure words (SvdCholP::flag).  Allocated by the first call, regrown by a call with a wider n_random.

@@ -1,0 +1,234 @@
+// step_caae.inc -- CAAE: the two generators' CDFs, the draws, the D-step, the G / G' step, scoring (CAAE.py:47-119,215-337,382-395)
+// (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
+// =================================================================================================
+// Discriminator: P = h->Ue, Q = h->V, b = CaaeState::bias; plain SGD on the touched rows (caae_rows.hpp).  Generators: CaaeState::gen[0]
+// (G) and gen[1] (G'), sigmoid on every layer.  Every dense product goes through run_gemm under the handle's planner: the forward passes
+// as CFGAN's (cfgan_generator_of with the sigmoid on the output layer), the backward pass through cfgan_bwd, and every parameter gradient
+// as a TN product that stores into the tensor's own gradient buffer (EPI_STORE); caae_sgd_kernel then applies
+// theta -= lr * (g + beta * theta).  Products that read a parameter run before the kernel that updates it.  sum(theta^2) of the loss is
+// taken at the head of the step, at the pre-update parameters like every other term of the reported loss.
+// =================================================================================================
+void caae_free(ganmf_handle* h) {
+  CaaeState& c = h->ca;
+  for (CfganState& g : c.gen) {
+    for (auto& t : g.Gl) free_tensor(t, true);
+    free_tensor(g.Go, true);
+    for (float* a : g.Hl) hipFree(a);
+    hipFree(g.sc_C); hipFree(g.sc_H0); hipFree(g.sc_H1); hipFree(g.sc_F);
+  }
+  free_tensor(c.bias, false);
+  hipFree(c.k_rows); hipFree(c.cdf[0]); hipFree(c.cdf[1]); hipFree(c.iu); hipFree(c.perm); hipFree(c.tu); hipFree(c.ti);
+  hipFree(c.neg); hipFree(c.users); hipFree(c.nu); hipFree(c.items); hipFree(c.xt); hipFree(c.first); hipFree(c.xu); hipFree(c.xi); hipFree(c.xn);
+  hipFree(c.Pg); hipFree(c.Qi); hipFree(c.Qj); hipFree(c.coef); hipFree(c.lt); hipFree(c.rt);
+  hipFree(c.C); hipFree(c.R); hipFree(c.Rp); hipFree(c.cdfb); hipFree(c.dz); hipFree(c.dh0); hipFree(c.dh1);
+  hipFree(c.lse); hipFree(c.reward); hipFree(c.la); hipFree(c.ae); hipFree(c.sq); hipFree(c.loss_dev); hipFree(c.lse_all);
+  c = CaaeState{};
+}
+
+// scoring / all-users scratch of gen[0]: `rows` dense profiles, two hidden blocks (ones column at g), one output block
+int caae_scratch(ganmf_handle* h, size_t rows) {
+  CaaeState& c = h->ca;
+  CfganState& g = c.gen[0];
+  if (rows <= g.sc_rows) return 0;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(g.sc_C); hipFree(g.sc_H0); hipFree(g.sc_H1); hipFree(g.sc_F);
+  g.sc_C = g.sc_H0 = g.sc_H1 = g.sc_F = nullptr; g.sc_rows = 0;
+  TRY(dalloc(&g.sc_C, rows * h->ldN));
+  TRY(dalloc(&g.sc_H0, rows * c.ldg));
+  TRY(dalloc(&g.sc_H1, rows * c.ldg));
+  TRY(dalloc(&g.sc_F, rows * h->ldN));
+  std::vector<float> ones(rows, 1.0f);
+  HIP_TRY(hipMemcpy2D(g.sc_H0 + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy2D(g.sc_H1 + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
+  g.sc_rows = rows;
+  return 0;
+}
+
+// out[i, :] = sigmoid(G_which(profile of ids[i])) for n rows (ids_dev == nullptr: rows row0 ..) through the scratch blocks
+int caae_forward_rows(ganmf_handle* h, int which, const int* ids_dev, int row0, int n, float* out, int ldo) {
+  CaaeState& c = h->ca;
+  TRY(caae_scratch(h, (size_t)n));
+  CfganState& s = c.gen[0];
+  std::vector<float*> H(c.Lg);
+  for (int l = 0; l < c.Lg; ++l) H[l] = (l & 1) ? s.sc_H1 : s.sc_H0;
+  GANMF_LAUNCH(cfgan_densify_kernel, dim3(n), dim3(256), 0, h->st, h->indptr, h->indices, h->data, ids_dev, row0, h->N, s.sc_C, h->ldN);
+  HIP_TRY(hipGetLastError());
+  return cfgan_generator_of(h, c.gen[which], s.sc_C, n, H.data(), out, ldo, ACT_SIGMOID);
+}
+
+// The fourth score source behind scores_device: out[i, :] = sigmoid(G(profile of ids[i])) -- the sigmoid applied, as CAAE.py:391 returns it
+int caae_scores(ganmf_handle* h, const int* ids_dev, int64_t n, int transposed, float* out, int ldw) {
+  if (!h->ca.ready) return fail(-1, "scores: ganmf_caae_init has not been called on this GANMF_MODEL_CAAE handle");
+  if (!h->has_urm) return fail(-1, "scores: ganmf_set_urm_csr has not been called");
+  if (transposed) return fail(-1, "scores: a GANMF_MODEL_CAAE handle scores users only (the reference ignores `mode`)");
+  return caae_forward_rows(h, 0, ids_dev, 0, (int)n, out, ldw);
+}
+
+constexpr int CAAE_ALL_BLOCK = 1024;
+
+// resident CDF of generator `which` over all users, block by block (CAAE.py:228-241)
+int caae_cdf_all(ganmf_handle* h, int which) {
+  CaaeState& c = h->ca;
+  const int U = h->U, blk = std::min(U, CAAE_ALL_BLOCK);
+  TRY(caae_scratch(h, (size_t)blk));
+  for (int r0 = 0; r0 < U; r0 += blk) {
+    const int nb = std::min(blk, U - r0);
+    TRY(caae_forward_rows(h, which, nullptr, r0, nb, c.gen[0].sc_F, h->ldN));
+    GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, c.gen[0].sc_F, h->ldN, h->N, c.cdf[which] + (size_t)r0 * h->ldN, h->ldN,
+                 c.lse_all + r0);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+// iu (the user of every CSR position) and the shuffled-order buffers for the URM held now
+int caae_prepare(ganmf_handle* h) {
+  CaaeState& c = h->ca;
+  if (c.iu_src == (const void*)h->indptr && c.order_cap >= h->nnz) return 0;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(c.iu); hipFree(c.perm); hipFree(c.tu); hipFree(c.ti);
+  c.iu = c.perm = c.tu = c.ti = nullptr; c.order_cap = 0; c.iu_src = nullptr;
+  const size_t n = (size_t)std::max<long long>(h->nnz, 1);
+  TRY(dalloc((float**)&c.iu, n));
+  TRY(dalloc((float**)&c.perm, n));
+  TRY(dalloc((float**)&c.tu, n));
+  TRY(dalloc((float**)&c.ti, n));
+  GANMF_LAUNCH(caae_rows_of_kernel, dim3(h->U), dim3(256), 0, h->st, h->indptr, h->U, c.iu);
+  HIP_TRY(hipGetLastError());
+  c.order_cap = h->nnz; c.iu_src = (const void*)h->indptr;
+  return 0;
+}
+
+inline int caae_grid(long long n) { return (int)std::max<long long>(1, std::min<long long>(4096, (n + 255) / 256)); }
+
+// (a) the epoch's order and its (user, item) pairs
+int caae_draw_perm(ganmf_handle* h, int64_t epoch) {
+  CaaeState& c = h->ca;
+  TRY(caae_prepare(h));
+  if (h->nnz == 0) return 0;
+  GANMF_LAUNCH(caae_perm_kernel, dim3(caae_grid(h->nnz)), dim3(256), 0, h->st, caae_base(c.seed, (unsigned long long)epoch, CAAE_S_PERM, 0),
+               h->nnz, c.iu, h->indices, c.perm, c.tu, c.ti);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// (b) one negative per position from the resident CDF of generator `which`
+int caae_draw_neg(ganmf_handle* h, int64_t epoch, int pass, int which, int* out) {
+  CaaeState& c = h->ca;
+  if (h->nnz == 0) return 0;
+  GANMF_LAUNCH(caae_cdf_draw_kernel, dim3(caae_grid(h->nnz)), dim3(256), 0, h->st,
+               caae_base(c.seed, (unsigned long long)epoch, CAAE_S_NEG + which, (unsigned long long)pass), h->nnz, c.tu, 1, c.cdf[which], h->ldN, h->N, out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// (c)
+int caae_draw_users(ganmf_handle* h, int64_t epoch, int which, int step, int* out) {
+  CaaeState& c = h->ca;
+  GANMF_LAUNCH(caae_users_kernel, dim3((c.Bm + 255) / 256), dim3(256), 0, h->st,
+               caae_base(c.seed, (unsigned long long)epoch, CAAE_S_USERS + which, (unsigned long long)step), c.Bm, h->U, which == 0 ? 1 : 0, out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// forward of generator `which` over the batch's rows into R (or Rp), hidden outputs into the generator's own blocks
+int caae_batch_forward(ganmf_handle* h, int which, const int* users_dev, float* out) {
+  CaaeState& c = h->ca;
+  GANMF_LAUNCH(cfgan_densify_kernel, dim3(c.Bm), dim3(256), 0, h->st, h->indptr, h->indices, h->data, users_dev, 0, h->N, c.C, h->ldN);
+  HIP_TRY(hipGetLastError());
+  return cfgan_generator_of(h, c.gen[which], c.C, c.Bm, c.gen[which].Hl.data(), out, h->ldN, ACT_SIGMOID);
+}
+
+// (d) the Nu planes of the batch's rows, weighted by G' at its current parameters (inside an epoch: its epoch-start parameters, because
+// G' only moves in the steps behind the generator steps)
+int caae_draw_nu(ganmf_handle* h, int64_t epoch, int step, const int* users_dev, unsigned* planes) {
+  CaaeState& c = h->ca;
+  TRY(caae_batch_forward(h, 1, users_dev, c.Rp));
+  CaaeNuP p{h->indptr, h->indices, users_dev, c.k_rows, c.Rp, h->ldN, h->N, c.words,
+            caae_base(c.seed, (unsigned long long)epoch, CAAE_S_NU, (unsigned long long)step), planes};
+  GANMF_LAUNCH(caae_nu_kernel, dim3(c.Bm), dim3(256), 0, h->st, p);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// (e) n_s items per batch row from the CDF of generator `which` over the batch's rows (left in cdfb)
+int caae_draw_items(ganmf_handle* h, int64_t epoch, int which, int step, const int* users_dev, int* items) {
+  CaaeState& c = h->ca;
+  TRY(caae_batch_forward(h, which, users_dev, c.R));
+  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(c.Bm), dim3(256), 0, h->st, c.R, h->ldN, h->N, c.cdfb, h->ldN, c.lse);
+  HIP_TRY(hipGetLastError());
+  const long long n = (long long)c.Bm * c.n_s;
+  GANMF_LAUNCH(caae_cdf_draw_kernel, dim3(caae_grid(n)), dim3(256), 0, h->st,
+               caae_base(c.seed, (unsigned long long)epoch, CAAE_S_ITEMS + which, (unsigned long long)step), n, (const int*)nullptr, c.n_s, c.cdfb,
+               h->ldN, h->N, items);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// One discriminator step on cnt triples (device arrays); the slice's loss -> *loss_dev
+int caae_d_step(ganmf_handle* h, const int* tu, const int* ti, const int* tj, int cnt, float* loss_dev) {
+  CaaeState& c = h->ca;
+  CaaeDP p{tu, ti, tj, cnt, h->k, h->ldk, h->Ue.p, h->V.p, c.bias.p, c.Pg, c.Qi, c.Qj, c.coef, c.lt, c.rt, c.rt + c.d_bsize, c.first, h->U, c.lr, c.beta};
+  GANMF_LAUNCH(caae_d_coef_kernel, dim3((cnt + 3) / 4), dim3(256), 0, h->st, p);
+  HIP_TRY(hipGetLastError());
+  GANMF_LAUNCH(cfgan_loss_kernel, dim3(1), dim3(256), 0, h->st, c.lt, (const float*)nullptr, cnt, c.rt, cnt, c.beta, (const float*)nullptr, 0.f, loss_dev);
+  HIP_TRY(hipGetLastError());
+  GANMF_LAUNCH(caae_d_update_kernel, dim3((3 * cnt + 3) / 4), dim3(256), 0, h->st, p);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// dW = A_ext^T . dz over `nrows` rows into the tensor's own gradient buffer
+int caae_wgrad(ganmf_handle* h, const float* A, int lda, const float* dz, int ldz, Tensor& W, int M, int N, int nrows) {
+  GemmP g{};
+  g.A = A; g.lda = lda; g.B = dz; g.ldb = ldz;
+  g.C = W.g; g.ldc = W.ld; g.M = M; g.N = N; g.K = nrows;
+  g.epi.kind = EPI_STORE;
+  return run_gemm(h, T_DIS_GW, T_RED_DIS_GW, g, true, true);
+}
+
+// One step of generator `which` (0: G, 1: G') on the batch's users, Nu planes (G only) and policy items (device arrays); loss -> *loss_dev
+int caae_g_step(ganmf_handle* h, int which, const int* users_dev, const unsigned* nu_dev, const int* items_dev, float* loss_dev) {
+  CaaeState& c = h->ca;
+  CfganState& gn = c.gen[which];
+  const int N = h->N, nb = c.Bm, Lg = c.Lg, g = c.g;
+  const float pc = (which == 0 ? c.lmbda : 1.0f) / ((float)nb * (float)c.n_s), ac = which == 0 ? 1.0f - c.lmbda : 0.f;
+  std::vector<Tensor*> mine;
+  for (auto& t : gn.Gl) mine.push_back(&t);
+  mine.push_back(&gn.Go);
+  if (c.beta != 0.f) {
+    for (size_t t = 0; t < mine.size(); ++t)
+      GANMF_LAUNCH(cfgan_sumsq_kernel, dim3(CFGAN_SQ_BLOCKS), dim3(256), 0, h->st, mine[t]->p, (long long)(mine[t]->padded() / 4), c.sq + t * CFGAN_SQ_BLOCKS);
+    HIP_TRY(hipGetLastError());
+  }
+  TRY(caae_batch_forward(h, which, users_dev, c.R));
+  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, c.R, h->ldN, N, (float*)nullptr, h->ldN, c.lse);
+  HIP_TRY(hipGetLastError());
+  const long long nd = (long long)nb * c.n_s;
+  GANMF_LAUNCH(caae_reward_kernel, dim3((int)((nd + 3) / 4)), dim3(256), 0, h->st, users_dev, items_dev, nb, c.n_s, h->Ue.p, h->V.p, c.bias.p,
+               h->k, h->ldk, which == 0 ? 1.0f : -1.0f, c.reward);
+  HIP_TRY(hipGetLastError());
+  CaaePolP pp{c.R, c.C, which == 0 ? nu_dev : (const unsigned*)nullptr, items_dev, c.reward, c.lse, c.dz, c.la, c.ae, h->ldN, N, c.words, c.n_s, pc, ac};
+  GANMF_LAUNCH(caae_policy_kernel, dim3(nb), dim3(256), 0, h->st, pp);
+  HIP_TRY(hipGetLastError());
+  GANMF_LAUNCH(caae_g_loss_kernel, dim3(1), dim3(256), 0, h->st, c.la, c.ae, nb, pc, ac, c.beta != 0.f ? c.sq : (const float*)nullptr,
+               (int)mine.size() * CFGAN_SQ_BLOCKS, c.beta, loss_dev);
+  HIP_TRY(hipGetLastError());
+  // backward, top down: every product reads the pre-step parameters; the updates follow
+  float* gc = c.dh0;
+  float* gnx = c.dh1;
+  TRY(cfgan_bwd(h, c.dz, h->ldN, gn.Go.p, h->ldN, gc, c.ldg, nb, g, N, ACT_SIGMOID, gn.Hl[Lg - 1], c.ldg));
+  TRY(caae_wgrad(h, gn.Hl[Lg - 1], c.ldg, c.dz, h->ldN, gn.Go, g + 1, N, nb));
+  for (int l = Lg - 1; l >= 0; --l) {
+    if (l > 0) TRY(cfgan_bwd(h, gc, c.ldg, gn.Gl[l].p, c.ldg, gnx, c.ldg, nb, g, g, ACT_SIGMOID, gn.Hl[l - 1], c.ldg));
+    TRY(caae_wgrad(h, l == 0 ? c.C : gn.Hl[l - 1], l == 0 ? h->ldN : c.ldg, gc, c.ldg, gn.Gl[l], l == 0 ? N + 1 : g + 1, g, nb));
+    if (l > 0) std::swap(gc, gnx);
+  }
+  for (Tensor* t : mine) {
+    const long long n4 = (long long)(t->padded() / 4);
+    GANMF_LAUNCH(caae_sgd_kernel, dim3(caae_grid(n4)), dim3(256), 0, h->st, t->p, t->g, n4, c.lr, c.beta);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+

@@ -39,9 +39,9 @@ void cfgan_free(ganmf_handle* h) {
   c = CfganState{};
 }
 
-// fake[nb, ldf] = G(X) for the nb dense rows X [nb, ldN] (ones column at N); hidden outputs into H[l] [nb, ldg] (ones column at g)
-int cfgan_generator(ganmf_handle* h, const float* X, int nb, float* const* H, float* fake, int ldf) {
-  const CfganState& c = h->cf;
+// fake[nb, ldf] = G(X) for the nb dense rows X [nb, ldN] (ones column at N); hidden outputs into H[l] [nb, ldg] (ones column at g).
+// c: the generator's members (CFGAN's own, or one of CAAE's two); out_act >= 0: that activation on the output layer (CAAE's sigmoid)
+int cfgan_generator_of(ganmf_handle* h, const CfganState& c, const float* X, int nb, float* const* H, float* fake, int ldf, int out_act = -1) {
   for (int l = 0; l < c.Lg; ++l) {      // h_{l+1} = act([h_l | 1] . Gl_ext)
     GemmP g{};
     g.A = l == 0 ? X : H[l - 1]; g.lda = l == 0 ? h->ldN : c.ldg;
@@ -53,7 +53,11 @@ int cfgan_generator(ganmf_handle* h, const float* X, int nb, float* const* H, fl
   GemmP g{};      // fake = [h | 1] . Go_ext
   g.A = H[c.Lg - 1]; g.lda = c.ldg; g.B = c.Go.p; g.ldb = h->ldN;
   g.C = fake; g.ldc = ldf; g.M = nb; g.N = h->N; g.K = c.g + 1; g.epi.kind = EPI_STORE;
+  if (out_act >= 0) { g.epi.kind = EPI_ACT; g.epi.act = out_act; }
   return run_gemm(h, T_GEMM_GEN, T_RED_GEN, g, false, true);
+}
+int cfgan_generator(ganmf_handle* h, const float* X, int nb, float* const* H, float* fake, int ldf) {
+  return cfgan_generator_of(h, h->cf, X, nb, H, fake, ldf);
 }
 
 // gW = A_ext^T . dz over `nrows` rows, TF-Adam in the epilogue (the plan DisGANMF's weight gradients run on)

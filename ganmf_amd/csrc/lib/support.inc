@@ -64,6 +64,8 @@ int needs_tensors(const ganmf_handle* h, const char* who) {
 int not_cfgan(const ganmf_handle* h, const char* who) {
   if (h->cfg.model == GANMF_MODEL_CFGAN)
     return fail(-1, "%s: not defined on a GANMF_MODEL_CFGAN handle (two MLPs, no factor tensors; it trains through ganmf_cfgan_* and scores through its generator)", who);
+  if (h->cfg.model == GANMF_MODEL_CAAE)      // the same entries refuse CAAE: its factor tensors are a discriminator's, trained through ganmf_caae_*
+    return fail(-1, "%s: not defined on a GANMF_MODEL_CAAE handle (a pairwise discriminator and two MLP generators; it trains through ganmf_caae_* and scores through its generator G)", who);
   return 0;
 }
 
@@ -94,6 +96,24 @@ bool find_view(ganmf_handle* h, int id, View* v) {
     const int l = gid / 2;
     if (gid & 1) return one(&h->cf.Gl[l], l == 0 ? N : g, 0, 1, g);
     return one(&h->cf.Gl[l], 0, 0, l == 0 ? N : g, g);
+  }
+  if (h->cfg.model == GANMF_MODEL_CAAE) {
+    // D: disc_user_embeddings / disc_item_embeddings under the factor ids, disc_item_bias [1, N]; G from GANMF_T_CAAE_G0 and G' from
+    // GANMF_T_CAAE_GPR0, each laid out as CFGAN's generator (2l g_layer_l/kernel, 2l+1 its bias, 2Lg reconstruction/kernel, 2Lg+1 its bias)
+    if (id == GANMF_T_USER_EMB) return one(&h->Ue, 0, 0, h->U, h->k);
+    if (id == GANMF_T_ITEM_EMB) return one(&h->V, 0, 0, h->N, h->k);
+    if (!h->ca.ready) return false;
+    if (id == GANMF_T_CAAE_ITEM_BIAS) return one(&h->ca.bias, 0, 0, 1, h->N);
+    const int which = id >= GANMF_T_CAAE_GPR0 ? 1 : 0;
+    const int gid = id - (which ? GANMF_T_CAAE_GPR0 : GANMF_T_CAAE_G0);
+    const int N = h->N, g = h->ca.g, Lg = h->ca.Lg;
+    CfganState& gn = h->ca.gen[which];
+    if (gid < 0 || gid > 2 * Lg + 1) return false;
+    if (gid == 2 * Lg) return one(&gn.Go, 0, 0, g, N);
+    if (gid == 2 * Lg + 1) return one(&gn.Go, g, 0, 1, N);
+    const int l = gid / 2;
+    if (gid & 1) return one(&gn.Gl[l], l == 0 ? N : g, 0, 1, g);
+    return one(&gn.Gl[l], 0, 0, l == 0 ? N : g, g);
   }
   if (id == GANMF_T_USER_EMB) return one(&h->Ue, 0, 0, h->U, h->k);
   if (id == GANMF_T_ITEM_EMB) return one(&h->V, 0, 0, h->N, h->k);
@@ -133,6 +153,10 @@ std::vector<Tensor*> all_tensors(ganmf_handle* h) {
     return v;
   }
   v = {&h->Ue, &h->V};
+  if (h->cfg.model == GANMF_MODEL_CAAE && h->ca.ready) {      // P, Q, then b and the layers of G and G'
+    v.push_back(&h->ca.bias);
+    for (CfganState& gn : h->ca.gen) { for (auto& t : gn.Gl) v.push_back(&t); v.push_back(&gn.Go); }
+  }
   if (h->cfg.model == GANMF_MODEL_GANMF) { v.push_back(&h->We); v.push_back(&h->Wd); }
   else if (h->cfg.model == GANMF_MODEL_DISGANMF) { for (auto& t : h->Wl) v.push_back(&t); v.push_back(&h->Wo); }
   return v;

@@ -57,6 +57,7 @@ class Engine:
         indptr = np.ascontiguousarray(urm.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(urm.indices, dtype=np.int32)
         data = np.ascontiguousarray(urm.data, dtype=np.float32)
+        self._nnz = int(indptr[-1])      # (the CAAE entries size their host buffers by the stored interactions)
         L.check(self.lib.ganmf_set_urm_csr(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices),
                                            _f32p(data), urm.shape[0], urm.shape[1]), "ganmf_set_urm_csr")
 
@@ -534,6 +535,103 @@ class Engine:
         L.check(self.lib.ganmf_cfgan_epoch(self.h, int(epoch), int(d_steps), int(g_steps), int(bool(draw)), _f32p(dl), _f32p(gl)),
                 "ganmf_cfgan_epoch")
         return dl[:nd], gl[:ng]
+
+    # -- CAAE (ganmf_caae_*, a MODEL_CAAE engine) --------------------------------------------------
+    def caae_init(self, g_units, g_layers, d_bsize, m_batch, n_s, lmbda, beta, lr, seed, k_rows):
+        """Both generators, the D slice length, the users and the policy draws per generator step, lmbda, beta, the learning rate, the
+        samplers' seed and the size of every user's subset Nu (ganmf_caae_init); once per engine."""
+        k = np.ascontiguousarray(k_rows, dtype=np.int32).ravel()
+        assert k.size == self.num_users
+        self._caae = (int(d_bsize), int(m_batch), int(n_s))
+        L.check(self.lib.ganmf_caae_init(self.h, int(g_units), int(g_layers), int(d_bsize), int(m_batch), int(n_s), float(lmbda),
+                                         float(beta), float(lr), int(seed) & (2 ** 64 - 1), _i32p(k)), "ganmf_caae_init")
+
+    def caae_cdf(self, which, users=None, n=None):
+        """(cdf [n, num_items], lse [n]) of generator `which` (0: G, 1: G') at its current parameters: of the listed users, or with
+        users=None of all users -- refreshing the resident array the negatives are drawn from -- of which rows [0, n) come back."""
+        if users is None:
+            n = self.num_users if n is None else int(n)
+            u = None
+        else:
+            u = np.ascontiguousarray(users, dtype=np.int32).ravel()
+            n = u.size
+        cdf, lse = np.zeros((n, self.num_items), dtype=np.float32), np.zeros(n, dtype=np.float32)
+        L.check(self.lib.ganmf_caae_cdf(self.h, int(which), _i32p(u) if u is not None else None, n, _f32p(cdf), _f32p(lse)),
+                "ganmf_caae_cdf")
+        return cdf, lse
+
+    def caae_draw_perm(self, epoch):
+        """the order of the stored interactions for `epoch`: CSR position per position (ganmf_caae_draw_perm)"""
+        out = np.zeros(max(self._nnz, 1), dtype=np.int32)
+        L.check(self.lib.ganmf_caae_draw_perm(self.h, int(epoch), _i32p(out)), "ganmf_caae_draw_perm")
+        return out[:self._nnz]
+
+    def caae_draw_negatives(self, epoch, pass_, which):
+        """one negative per position of the epoch's order from the resident CDF of generator `which` (ganmf_caae_draw_negatives)"""
+        out = np.zeros(max(self._nnz, 1), dtype=np.int32)
+        L.check(self.lib.ganmf_caae_draw_negatives(self.h, int(epoch), int(pass_), int(which), _i32p(out)), "ganmf_caae_draw_negatives")
+        return out[:self._nnz]
+
+    @property
+    def caae_words(self):
+        return (self.num_items + 31) // 32
+
+    def caae_draw_batch(self, epoch, which, step):
+        """(users [m], nu planes uint32 [m, words] (G; None for G'), items [m, n_s], cdf [m, num_items]) of a generator step's batch"""
+        _, m, n_s = self._caae
+        users, items = np.zeros(m, dtype=np.int32), np.zeros((m, n_s), dtype=np.int32)
+        nu = np.zeros((m, self.caae_words), dtype=np.uint32)
+        cdf = np.zeros((m, self.num_items), dtype=np.float32)
+        L.check(self.lib.ganmf_caae_draw_batch(self.h, int(epoch), int(which), int(step), _i32p(users),
+                                               nu.ctypes.data_as(C.POINTER(C.c_uint32)), _i32p(items), _f32p(cdf)), "ganmf_caae_draw_batch")
+        return users, (nu if which == 0 else None), items, cdf
+
+    def caae_draws(self, kind, index=0):
+        """what the last caae_epoch drew: kind in _lib.CAAE_DRAWS, index = pass ("neg_*"), step ("users_*", "nu", "items_*") or user
+        ("cdf_*": that row of the resident CDF)"""
+        _, m, n_s = self._caae
+        shape, dtype = {"perm": ((self._nnz,), np.int32), "neg_g": ((self._nnz,), np.int32), "neg_gpr": ((self._nnz,), np.int32),
+                        "users_g": ((m,), np.int32), "users_gpr": ((m,), np.int32), "nu": ((m, self.caae_words), np.uint32),
+                        "items_g": ((m, n_s), np.int32), "items_gpr": ((m, n_s), np.int32),
+                        "cdf_g": ((self.num_items,), np.float32), "cdf_gpr": ((self.num_items,), np.float32)}[kind]
+        out = np.zeros(shape, dtype=dtype)
+        if out.size:
+            L.check(self.lib.ganmf_caae_get_draws(self.h, L.CAAE_DRAWS[kind], int(index), out.ctypes.data_as(C.c_void_p), out.nbytes),
+                    "ganmf_caae_get_draws")
+        return out
+
+    def caae_d_step(self, users, pos_items, neg_items):
+        """one discriminator step on explicit triples; returns its loss (ganmf_caae_d_step)"""
+        u, i, j = (np.ascontiguousarray(a, dtype=np.int32).ravel() for a in (users, pos_items, neg_items))
+        assert u.size == i.size == j.size
+        loss = C.c_float()
+        L.check(self.lib.ganmf_caae_d_step(self.h, _i32p(u), _i32p(i), _i32p(j), u.size, C.byref(loss)), "ganmf_caae_d_step")
+        return np.float32(loss.value)
+
+    def caae_g_step(self, which, users, nu, items):
+        """one step of generator `which` on explicit users [m], Nu planes uint32 [m, words] (G only; None: empty) and policy items
+        [m, n_s]; returns its loss (ganmf_caae_g_step)"""
+        _, m, n_s = self._caae
+        u = np.ascontiguousarray(users, dtype=np.int32).ravel()
+        it = np.ascontiguousarray(items, dtype=np.int32).ravel()
+        assert u.size == m and it.size == m * n_s
+        p = None
+        if nu is not None and which == 0:
+            p = np.ascontiguousarray(nu, dtype=np.uint32)
+            assert p.shape == (m, self.caae_words)
+        loss = C.c_float()
+        L.check(self.lib.ganmf_caae_g_step(self.h, int(which), _i32p(u), p.ctypes.data_as(C.POINTER(C.c_uint32)) if p is not None else None,
+                                           _i32p(it), C.byref(loss)), "ganmf_caae_g_step")
+        return np.float32(loss.value)
+
+    def caae_epoch(self, epoch, d_steps=1, g_steps=1, gpr_steps=1):
+        """One epoch in one call (ganmf_caae_epoch).  Returns (d_losses, g_losses, gpr_losses), one float32 per step."""
+        d_bsize = self._caae[0]
+        nd = int(d_steps) * 2 * (-(-self._nnz // d_bsize))
+        dl, gl, pl = (np.zeros(max(n, 1), dtype=np.float32) for n in (nd, int(g_steps), int(gpr_steps)))
+        L.check(self.lib.ganmf_caae_epoch(self.h, int(epoch), int(d_steps), int(g_steps), int(gpr_steps), _f32p(dl), _f32p(gl), _f32p(pl)),
+                "ganmf_caae_epoch")
+        return dl[:nd], gl[:int(g_steps)], pl[:int(gpr_steps)]
 
     def item_similarity(self):
         """The held item similarity matrix as the reference lays W_sparse out (ganmf_itemknn_get): scipy CSR float32

@@ -53,7 +53,15 @@ typedef struct ganmf_handle ganmf_handle;
  * G(all rows), cached on the device until a parameter changes).  ganmf_train_epoch / _epoch_ragged / _step, ganmf_discriminate,
  * ganmf_als_half_sweep, ganmf_pure_svd, the item-similarity, P3 and SLIM entries, the candidate entries, ganmf_bench_scores and the two
  * communicator entries return -1 on it with a message that names the model.  The enum gained a value; no structure or signature changed: GANMF_ABI_VERSION stays. */
-enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2, GANMF_MODEL_ITEMSIM = 3, GANMF_MODEL_CFGAN = 4 };
+/* GANMF_MODEL_CAAE: CAAE (GANRec/CAAE.py): a pairwise discriminator over (user, positive item, negative item) triples -- embeddings P
+ * [U, k], Q [N, k] and an item bias, held as the handle's two factor tensors and GANMF_T_CAAE_ITEM_BIAS -- and two sigmoid MLP generators G
+ * and G' over the user's profile, all three trained by plain SGD.  Of ganmf_cfg only num_users, num_items, num_factors (at most
+ * GANMF_CAAE_MAX_FACTORS), device and flags are read (emb_dim and batch_size must still be >= 1); world_size must be 1 and the bf16 /
+ * fp16 MFMA flags are refused.  ganmf_caae_init supplies the rest (below).  The tensor, snapshot, seen / test upload, ganmf_scores,
+ * ganmf_recommend, ganmf_evaluate* (candidates = 0), score filter, ignore list and score-similarity entries work unchanged with
+ * transposed = 0: the score rows are sigmoid(G(profile of row id)).  Every entry that refuses a GANMF_MODEL_CFGAN handle refuses this one
+ * too, with a message that names the model.  The enum gained a value; no structure or signature changed: GANMF_ABI_VERSION stays. */
+enum { GANMF_MODEL_GANMF = 0, GANMF_MODEL_DISGANMF = 1, GANMF_MODEL_MF = 2, GANMF_MODEL_ITEMSIM = 3, GANMF_MODEL_CFGAN = 4, GANMF_MODEL_CAAE = 5 };
 enum { GANMF_ACT_LINEAR = 0, GANMF_ACT_TANH = 1, GANMF_ACT_RELU = 2, GANMF_ACT_SIGMOID = 3 };
 
 /* Tensor ids.  Discriminator tensors are numbered in the order of the reference's
@@ -67,6 +75,12 @@ enum { GANMF_ACT_LINEAR = 0, GANMF_ACT_TANH = 1, GANMF_ACT_RELU = 2, GANMF_ACT_S
  * 2L D_output/kernel [e,1], 2L+1 D_output/bias [1]); the generator's start here and are laid out the same way:
  * G0 + 2l G_hidden_l/kernel ([N, g] for l = 0, else [g, g]), G0 + 2l+1 its bias, G0 + 2Lg G_output/kernel [g, N], G0 + 2Lg+1 G_output/bias [N] */
 #define GANMF_T_CFGAN_G0 200
+/* CAAE: D/disc_user_embeddings and D/disc_item_embeddings are GANMF_T_USER_EMB / GANMF_T_ITEM_EMB, D/disc_item_bias [1, N] is
+ * GANMF_T_CAAE_ITEM_BIAS; the layers of G start at GANMF_T_CAAE_G0 and those of G' at GANMF_T_CAAE_GPR0, each laid out as CFGAN's generator:
+ * + 2l g_layer_l/kernel ([N, g] for l = 0, else [g, g]), + 2l+1 its bias, + 2Lg g_reconstruction/kernel [g, N], + 2Lg+1 its bias [N] */
+#define GANMF_T_CAAE_ITEM_BIAS 102
+#define GANMF_T_CAAE_G0 300
+#define GANMF_T_CAAE_GPR0 400
 
 /* which copy of a tensor */
 enum { GANMF_SLOT_PARAM = 0, GANMF_SLOT_ADAM_M = 1, GANMF_SLOT_ADAM_V = 2, GANMF_SLOT_BEST = 3 };
@@ -622,6 +636,52 @@ int ganmf_cfgan_set_masks(ganmf_handle* h, const uint32_t* zr, const uint32_t* p
 int ganmf_cfgan_get_masks(ganmf_handle* h, uint32_t* zr, uint32_t* pm);
 int ganmf_cfgan_step(ganmf_handle* h, int kind, int64_t row0, int32_t nrows, float* loss);
 int ganmf_cfgan_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g_steps, int draw, float* d_losses, float* g_losses);
+
+/* ---- CAAE (GANRec/CAAE.py) on a GANMF_MODEL_CAAE handle ----------------------------------------------------------------------
+ * `which` is 0 for G and 1 for G' throughout.  Every draw is a pure function of (seed, epoch, stream, pass / step, index) through the
+ * splitmix64 output function (caae_sample.hpp): the same arguments give the same bytes on every call and every device.
+ * init: both generators (g_layers >= 1 sigmoid hidden layers of g_units, a sigmoid output layer of width num_items; G' is built like
+ *   G, as the reference builds it), the slice length d_bsize of a discriminator step (at most GANMF_CAAE_MAX_D_BSIZE), the users per
+ *   generator step m_batch (at most num_users: G draws them distinct), the policy draws per row n_s (the reference's 2 * median profile
+ *   length), lmbda, beta, the one learning rate of the three SGD optimisers, the samplers' seed and the size k_rows[u] of every user's
+ *   subset Nu (formed by the caller: int(n_free * S)).  Once per handle.  All parameters start at zero: set_tensor.
+ * cdf: softmax(r) of generator `which` at its current parameters as an inclusive fp32 prefix sum per row, exactly non-decreasing, and
+ *   log sum exp(r).  users == NULL: all users into the handle's resident array (what the negatives are drawn from), rows [0, n)
+ *   downloaded; else the n <= m_batch listed users.  cdf_out [n, num_items] and lse_out [n] may be NULL.
+ * draw_perm: the order of the nnz stored interactions for `epoch` (position t holds CSR position out[t]); left resident.
+ * draw_negatives: draw_perm, then one negative per position for (epoch, pass, which): a 24-bit uniform in [0, 1) searched in the
+ *   resident CDF row of the position's user -- the first index whose value is >= it, clamped to num_items - 1.
+ * draw_batch: the batch of generator step (epoch, which, step): m_batch users (G: distinct; G': with replacement), for G the bit planes
+ *   [m_batch, ceil(num_items / 32)] of Nu in ganmf_cfgan_set_masks' layout -- k_rows[u] non-interactions drawn without replacement with
+ *   weights exp(r') of G' at its current parameters, as the k smallest Efraimidis-Spirakis keys -- and n_s policy items per row from
+ *   the CDF of generator `which` over the batch's rows, which cdf_out [m_batch, num_items] receives.  Every output may be NULL.
+ * get_draws: what the last epoch call drew, by kind and pass / step index (a CDF kind: by user, one row of the resident array).  draw_perm
+ *   and draw_negatives write where an epoch keeps its order and its first pass's negatives: read an epoch's draws before calling them.
+ * d_step: one discriminator step on `count` <= d_bsize explicit triples; g_step: one step of generator `which` on m_batch explicit
+ *   users, Nu planes (G only; NULL: empty) and m_batch * n_s policy items.  *loss (may be NULL): the loss at the pre-step parameters.
+ *   Contributions to one row of P, Q or b are summed in ascending position (an item's positives in front of its negatives), without
+ *   floating-point atomics: the same arguments leave the same bytes.
+ * epoch: one epoch in one call, nothing crossing the bus inside it: the order, both resident CDFs, d_steps passes (the pass's
+ *   negatives, then per slice of d_bsize positions a step with G's negatives and a step with G''s), g_steps steps of G and gpr_steps
+ *   steps of G', each on its own drawn batch.  d_losses [d_steps * 2 * ceil(nnz / d_bsize)], g_losses [g_steps], gpr_losses [gpr_steps].
+ *   The same kernels in the same order as d_step / g_step on the recorded draws: the same bytes. */
+#define GANMF_CAAE_MAX_FACTORS 256
+#define GANMF_CAAE_MAX_D_BSIZE 16384
+enum { GANMF_CAAE_DRAW_PERM = 0, GANMF_CAAE_DRAW_NEG_G = 1, GANMF_CAAE_DRAW_NEG_GPR = 2, GANMF_CAAE_DRAW_USERS_G = 3,
+       GANMF_CAAE_DRAW_USERS_GPR = 4, GANMF_CAAE_DRAW_NU = 5, GANMF_CAAE_DRAW_ITEMS_G = 6, GANMF_CAAE_DRAW_ITEMS_GPR = 7,
+       GANMF_CAAE_DRAW_CDF_G = 8, GANMF_CAAE_DRAW_CDF_GPR = 9 };
+int ganmf_caae_init(ganmf_handle* h, int32_t g_units, int32_t g_layers, int32_t d_bsize, int32_t m_batch, int32_t n_s, float lmbda,
+                    float beta, float lr, uint64_t seed, const int32_t* k_rows);
+int ganmf_caae_cdf(ganmf_handle* h, int which, const int32_t* users, int32_t n, float* cdf_out, float* lse_out);
+int ganmf_caae_draw_perm(ganmf_handle* h, int64_t epoch, int32_t* out);
+int ganmf_caae_draw_negatives(ganmf_handle* h, int64_t epoch, int32_t pass, int which, int32_t* out);
+int ganmf_caae_draw_batch(ganmf_handle* h, int64_t epoch, int which, int32_t step, int32_t* users, uint32_t* nu, int32_t* items,
+                          float* cdf_out);
+int ganmf_caae_get_draws(ganmf_handle* h, int kind, int32_t index, void* out, int64_t bytes);
+int ganmf_caae_d_step(ganmf_handle* h, const int32_t* users, const int32_t* pos_items, const int32_t* neg_items, int32_t count, float* loss);
+int ganmf_caae_g_step(ganmf_handle* h, int which, const int32_t* users, const uint32_t* nu, const int32_t* items, float* loss);
+int ganmf_caae_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g_steps, int32_t gpr_steps, float* d_losses, float* g_losses,
+                     float* gpr_losses);
 
 /* Device-resident scoring GEMM timing (no D2H): scores for the first n rows, `iters` launches;
  * returns average milliseconds per launch measured with hipEvents on the handle's stream. */
