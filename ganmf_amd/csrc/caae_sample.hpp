@@ -11,13 +11,14 @@
 //   (c) m distinct users: the first m values of bijection (a) over [0, U); m users with replacement: ((word >> 32) * U) >> 32
 //   (d) the weighted subset Nu of a row's non-interactions: the k smallest Efraimidis-Spirakis keys -log(u) / w, w = exp(r'), u =
 //       ((word >> 40) + 0.5) * 2^-24 -- successive sampling without replacement, the distribution of numpy's choice(p=, replace=False).
-//       The keys are non-negative floats, so their bit patterns order as they do: cfgan_masks_kernel's 4 x 8-bit radix select over those
-//       32 bits, the same tie rule (smaller column first) and the same bit plane layout (pack_mask_rows').
+//       The keys are non-negative floats, so their bit patterns order as they do: subset_select.hpp's selection over those 32 bits, with the
+//       tie rule (smaller column first) and the bit plane layout (pack_mask_rows') of CFGAN's masks.
 //   (e) n_s CDF draws per batch row under rule (b), index = row * n_s + draw
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "cfgan_masks.hpp"
+#include "slim_bpr.hpp"
+#include "subset_select.hpp"
 
 namespace ganmf {
 
@@ -119,73 +120,18 @@ __device__ __forceinline__ unsigned caae_nu_key(unsigned long long base, unsigne
 }
 
 __global__ __launch_bounds__(256) void caae_nu_kernel(const CaaeNuP p) {
-  __shared__ unsigned hist[256];
-  __shared__ unsigned wtot[4];
-  __shared__ unsigned sel[2];
   const int b = blockIdx.x;
   const int r = p.users[b];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   unsigned* __restrict__ out = p.planes + (size_t)b * p.words;
   const float* __restrict__ rp = p.Rp + (size_t)b * p.ld;
   const long long s = p.indptr[r], e = p.indptr[r + 1];
   const int n = p.ncols - (int)(e - s);
   const int k = min(max(p.k_rows[r], 0), n);
-  if (k == 0) {
-    for (int w = tid; w < p.words; w += 256) out[w] = 0u;
+  if (k == 0) {      // uniform over the workgroup, in front of the selector's first barrier
+    for (int w = threadIdx.x; w < p.words; w += 256) out[w] = 0u;
     return;
   }
-  unsigned prefix = 0, left = (unsigned)k;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    hist[tid] = 0u;
-    __syncthreads();
-    for (int j = tid; j < p.ncols; j += 256) {
-      if (cfgan_in_profile(p.indices, s, e, j)) continue;
-      const unsigned key = caae_nu_key(p.base, (unsigned)r, (unsigned)j, rp[j]);
-      if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const unsigned c = hist[tid];
-    unsigned incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    unsigned before = 0;
-    for (int w = 0; w < wave; ++w) before += wtot[w];
-    incl += before;
-    const unsigned excl = incl - c;
-    if (excl < left && left <= incl) { sel[0] = (unsigned)tid; sel[1] = left - excl; }
-    __syncthreads();
-    prefix |= sel[0] << shift;
-    left = sel[1];
-    __syncthreads();
-  }
-  unsigned taken = 0;
-  const int span = (p.ncols + 255) & ~255;
-  for (int j0 = 0; j0 < span; j0 += 256) {
-    const int j = j0 + tid;
-    bool below = false, tie = false;
-    if (j < p.ncols && !cfgan_in_profile(p.indices, s, e, j)) {
-      const unsigned key = caae_nu_key(p.base, (unsigned)r, (unsigned)j, rp[j]);
-      below = key < prefix;
-      tie = key == prefix;
-    }
-    const unsigned long long tb = __ballot(tie);
-    if (lane == 0) wtot[wave] = (unsigned)__popcll(tb);
-    __syncthreads();
-    unsigned rank = taken + (unsigned)__popcll(tb & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) rank += wtot[w];
-    taken += (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
-    const bool on = below || (tie && rank < left);
-    const unsigned long long ob = __ballot(on);
-    const int word = (j0 >> 5) + 2 * wave + (lane >> 5);
-    if ((lane & 31) == 0 && word < p.words) out[word] = (unsigned)(ob >> (lane & 32));
-    __syncthreads();
-  }
+  subset_select_row(p.indices, s, e, p.ncols, p.words, k, out, [&](int j) { return caae_nu_key(p.base, (unsigned)r, (unsigned)j, rp[j]); });
 }
 
 }  // namespace ganmf

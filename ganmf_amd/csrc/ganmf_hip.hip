@@ -50,6 +50,7 @@
 #include "p3_rows.hpp"
 #include "slim_bpr.hpp"
 #include "slim_sched.hpp"
+#include "subset_select.hpp"
 #include "cfgan_masks.hpp"
 #include "cfgan_rows.hpp"
 #include "caae_sample.hpp"
@@ -73,6 +74,7 @@ namespace {
 #include "lib/gemm_run.inc"
 #include "lib/step_ganmf.inc"
 #include "lib/step_disganmf.inc"
+#include "lib/profile_mlp.inc"
 #include "lib/step_cfgan.inc"
 #include "lib/step_caae.inc"
 #include "lib/epoch.inc"

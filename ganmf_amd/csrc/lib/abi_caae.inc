@@ -2,14 +2,6 @@
 // (caae_sample.hpp, caae_rows.hpp, step_caae.inc)
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
-static int caae_ready(ganmf_handle* h, const char* who, bool need_urm) {
-  if (!h) return fail(-1, "%s: null handle", who);
-  if (h->cfg.model != GANMF_MODEL_CAAE) return fail(-1, "%s: needs a GANMF_MODEL_CAAE handle", who);
-  if (!h->ca.ready) return fail(-1, "%s: ganmf_caae_init has not been called on this handle", who);
-  if (need_urm && !h->has_urm) return fail(-1, "%s: ganmf_set_urm_csr has not been called", who);
-  return 0;
-}
-
 int ganmf_caae_init(ganmf_handle* h, int32_t g_units, int32_t g_layers, int32_t d_bsize, int32_t m_batch, int32_t n_s, float lmbda,
                     float beta, float lr, uint64_t seed, const int32_t* k_rows) {
   const char* who = "ganmf_caae_init";
@@ -26,21 +18,9 @@ int ganmf_caae_init(ganmf_handle* h, int32_t g_units, int32_t g_layers, int32_t 
     if (k_rows[u] < 0 || k_rows[u] > N) return fail(-1, "%s: k_rows[%d] = %d out of range [0,%d]", who, u, k_rows[u], N);
   HIP_TRY(hipSetDevice(h->dev));
   CaaeState& c = h->ca;
-  c.g = g_units; c.Lg = g_layers; c.ldg = round_up(g_units + 1, LD_ALIGN);
   c.d_bsize = d_bsize; c.Bm = m_batch; c.n_s = n_s; c.lmbda = lmbda; c.beta = beta; c.lr = lr; c.seed = seed;
   c.words = (N + 31) / 32;
-  std::vector<float> ones((size_t)m_batch, 1.0f);
-  for (CfganState& gn : c.gen) {
-    gn.g = c.g; gn.Lg = c.Lg; gn.act = ACT_SIGMOID; gn.ldg = c.ldg;
-    gn.Gl.resize(c.Lg);
-    for (int l = 0; l < c.Lg; ++l) TRY(alloc_tensor(gn.Gl[l], l == 0 ? N + 1 : c.g + 1, c.g, true, 1));
-    TRY(alloc_tensor(gn.Go, c.g + 1, N, true, 1, h->ldN));
-    gn.Hl.assign(c.Lg, nullptr);
-    for (int l = 0; l < c.Lg; ++l) {
-      TRY(dalloc(&gn.Hl[l], (size_t)m_batch * c.ldg));
-      HIP_TRY(hipMemcpy2D(gn.Hl[l] + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, (size_t)m_batch, hipMemcpyHostToDevice));
-    }
-  }
+  for (ProfileMlp& gn : c.gen) TRY(mlp_alloc(h, gn, g_units, g_layers, ACT_SIGMOID, ACT_SIGMOID, m_batch));
   TRY(alloc_tensor(c.bias, 1, N, false, 1));
   TRY(dalloc((float**)&c.k_rows, (size_t)U));
   HIP_TRY(hipMemcpy(c.k_rows, k_rows, (size_t)U * sizeof(int), hipMemcpyHostToDevice));
@@ -65,25 +45,15 @@ int ganmf_caae_init(ganmf_handle* h, int32_t g_units, int32_t g_layers, int32_t 
   TRY(dalloc(&c.Rp, (size_t)m_batch * h->ldN));
   TRY(dalloc(&c.cdfb, (size_t)m_batch * h->ldN));
   TRY(dalloc(&c.dz, (size_t)m_batch * h->ldN));
-  TRY(dalloc(&c.dh0, (size_t)m_batch * c.ldg));
-  TRY(dalloc(&c.dh1, (size_t)m_batch * c.ldg));
+  TRY(dalloc(&c.dh0, (size_t)m_batch * c.gen[0].ldg));
+  TRY(dalloc(&c.dh1, (size_t)m_batch * c.gen[0].ldg));
   TRY(dalloc(&c.lse, (size_t)m_batch));
   TRY(dalloc(&c.reward, (size_t)m_batch * n_s));
   TRY(dalloc(&c.la, (size_t)m_batch));
   TRY(dalloc(&c.ae, (size_t)m_batch));
-  TRY(dalloc(&c.sq, (size_t)(c.Lg + 1) * CFGAN_SQ_BLOCKS));
+  TRY(dalloc(&c.sq, (size_t)(g_layers + 1) * CFGAN_SQ_BLOCKS));
   c.ready = true;
   ++h->param_version;
-  return 0;
-}
-
-static int caae_losses(ganmf_handle* h, size_t n) {
-  CaaeState& c = h->ca;
-  if (n <= c.loss_cap) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(c.loss_dev); c.loss_dev = nullptr; c.loss_cap = 0;
-  TRY(dalloc(&c.loss_dev, n));
-  c.loss_cap = n;
   return 0;
 }
 
@@ -114,7 +84,7 @@ static int* caae_items_slot(CaaeState& c, int which, int step) { return c.items 
 
 int ganmf_caae_cdf(ganmf_handle* h, int which, const int32_t* users, int32_t n, float* cdf_out, float* lse_out) {
   const char* who = "ganmf_caae_cdf";
-  TRY(caae_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, true));
   if (which != 0 && which != 1) return fail(-1, "%s: which must be 0 (G) or 1 (G')", who);
   CaaeState& c = h->ca;
   const int U = h->U, N = h->N;
@@ -133,7 +103,7 @@ int ganmf_caae_cdf(ganmf_handle* h, int which, const int32_t* users, int32_t n, 
   int* ud = c.xu;
   HIP_TRY(hipStreamSynchronize(h->st));
   HIP_TRY(hipMemcpy(ud, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-  TRY(caae_forward_rows(h, which, ud, 0, n, c.R, h->ldN));
+  TRY(mlp_forward_rows(h, c.gen[which], ud, 0, n, c.R, h->ldN));
   GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(n), dim3(256), 0, h->st, c.R, h->ldN, N, c.cdfb, h->ldN, c.lse);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->st));
@@ -144,7 +114,7 @@ int ganmf_caae_cdf(ganmf_handle* h, int which, const int32_t* users, int32_t n, 
 
 int ganmf_caae_draw_perm(ganmf_handle* h, int64_t epoch, int32_t* out) {
   const char* who = "ganmf_caae_draw_perm";
-  TRY(caae_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, true));
   if (epoch < 0) return fail(-1, "%s: negative epoch", who);
   HIP_TRY(hipSetDevice(h->dev));
   TRY(caae_draw_perm(h, epoch));
@@ -155,7 +125,7 @@ int ganmf_caae_draw_perm(ganmf_handle* h, int64_t epoch, int32_t* out) {
 
 int ganmf_caae_draw_negatives(ganmf_handle* h, int64_t epoch, int32_t pass, int which, int32_t* out) {
   const char* who = "ganmf_caae_draw_negatives";
-  TRY(caae_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, true));
   if (epoch < 0 || pass < 0) return fail(-1, "%s: negative argument", who);
   if (which != 0 && which != 1) return fail(-1, "%s: which must be 0 (G) or 1 (G')", who);
   HIP_TRY(hipSetDevice(h->dev));
@@ -170,7 +140,7 @@ int ganmf_caae_draw_negatives(ganmf_handle* h, int64_t epoch, int32_t pass, int 
 int ganmf_caae_draw_batch(ganmf_handle* h, int64_t epoch, int which, int32_t step, int32_t* users, uint32_t* nu, int32_t* items,
                           float* cdf_out) {
   const char* who = "ganmf_caae_draw_batch";
-  TRY(caae_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, true));
   if (epoch < 0 || step < 0) return fail(-1, "%s: negative argument", who);
   if (which != 0 && which != 1) return fail(-1, "%s: which must be 0 (G) or 1 (G')", who);
   CaaeState& c = h->ca;
@@ -189,7 +159,7 @@ int ganmf_caae_draw_batch(ganmf_handle* h, int64_t epoch, int which, int32_t ste
 
 int ganmf_caae_get_draws(ganmf_handle* h, int kind, int32_t index, void* out, int64_t bytes) {
   const char* who = "ganmf_caae_get_draws";
-  TRY(caae_ready(h, who, false));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, false));
   if (!out) return fail(-1, "%s: null buffer", who);
   CaaeState& c = h->ca;
   const void* src = nullptr;
@@ -226,7 +196,7 @@ int ganmf_caae_get_draws(ganmf_handle* h, int kind, int32_t index, void* out, in
 
 int ganmf_caae_d_step(ganmf_handle* h, const int32_t* users, const int32_t* pos_items, const int32_t* neg_items, int32_t count, float* loss) {
   const char* who = "ganmf_caae_d_step";
-  TRY(caae_ready(h, who, false));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, false));
   if (!users || !pos_items || !neg_items) return fail(-1, "%s: null argument", who);
   CaaeState& c = h->ca;
   if (count < 1 || count > c.d_bsize) return fail(-1, "%s: 1 to %d triples per step, got %d", who, c.d_bsize, count);
@@ -235,7 +205,7 @@ int ganmf_caae_d_step(ganmf_handle* h, const int32_t* users, const int32_t* pos_
       return fail(-1, "%s: triple %d (%d, %d, %d) out of range", who, t, users[t], pos_items[t], neg_items[t]);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(caae_losses(h, 1));
+  TRY(grow_losses(h, h->ca.loss_dev, h->ca.loss_cap, 1));
   HIP_TRY(hipStreamSynchronize(h->st));
   const int32_t* src[3] = {users, pos_items, neg_items};
   for (int q = 0; q < 3; ++q) HIP_TRY(hipMemcpy(c.xt + (size_t)q * c.d_bsize, src[q], (size_t)count * sizeof(int), hipMemcpyHostToDevice));
@@ -249,7 +219,7 @@ int ganmf_caae_d_step(ganmf_handle* h, const int32_t* users, const int32_t* pos_
 
 int ganmf_caae_g_step(ganmf_handle* h, int which, const int32_t* users, const uint32_t* nu, const int32_t* items, float* loss) {
   const char* who = "ganmf_caae_g_step";
-  TRY(caae_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, true));
   if (which != 0 && which != 1) return fail(-1, "%s: which must be 0 (G) or 1 (G')", who);
   if (!users || !items) return fail(-1, "%s: null argument", who);
   CaaeState& c = h->ca;
@@ -259,7 +229,7 @@ int ganmf_caae_g_step(ganmf_handle* h, int which, const int32_t* users, const ui
     if (items[t] < 0 || items[t] >= h->N) return fail(-1, "%s: item %d out of range", who, items[t]);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(caae_losses(h, 1));
+  TRY(grow_losses(h, h->ca.loss_dev, h->ca.loss_cap, 1));
   HIP_TRY(hipStreamSynchronize(h->st));
   int* ud = c.xu;
   int* id = c.xi;
@@ -281,7 +251,7 @@ int ganmf_caae_g_step(ganmf_handle* h, int which, const int32_t* users, const ui
 int ganmf_caae_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g_steps, int32_t gpr_steps, float* d_losses, float* g_losses,
                      float* gpr_losses) {
   const char* who = "ganmf_caae_epoch";
-  TRY(caae_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CAAE, true));
   if (d_steps < 0 || g_steps < 0 || gpr_steps < 0 || epoch < 0) return fail(-1, "%s: negative argument", who);
   CaaeState& c = h->ca;
   const long long nnz = h->nnz;
@@ -290,7 +260,7 @@ int ganmf_caae_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g_
   if ((nd && !d_losses) || (ng && !g_losses) || (np && !gpr_losses)) return fail(-1, "%s: null loss buffer", who);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(caae_losses(h, nd + ng + np + 1));
+  TRY(grow_losses(h, c.loss_dev, c.loss_cap, nd + ng + np + 1));
   TRY(caae_prepare(h));
   TRY(caae_slots(h, d_steps, std::max(1, std::max(g_steps, gpr_steps))));
   c.rec_nnz = nnz; c.rec_passes = d_steps; c.rec_steps[0] = g_steps; c.rec_steps[1] = gpr_steps;

@@ -2,14 +2,6 @@
 // (cfgan_masks.hpp, cfgan_rows.hpp, step_cfgan.inc)
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
-static int cfgan_ready(ganmf_handle* h, const char* who, bool need_urm) {
-  if (!h) return fail(-1, "%s: null handle", who);
-  if (h->cfg.model != GANMF_MODEL_CFGAN) return fail(-1, "%s: needs a GANMF_MODEL_CFGAN handle", who);
-  if (!h->cf.ready) return fail(-1, "%s: ganmf_cfgan_init has not been called on this handle", who);
-  if (need_urm && !h->has_urm) return fail(-1, "%s: ganmf_set_urm_csr has not been called", who);
-  return 0;
-}
-
 int ganmf_cfgan_init(ganmf_handle* h, int32_t g_nodes, int32_t g_layers, int g_act, int32_t d_batch, int32_t g_batch, int scheme,
                      float zr_coefficient, uint64_t seed, const int32_t* k_rows) {
   const char* who = "ganmf_cfgan_init";
@@ -28,28 +20,19 @@ int ganmf_cfgan_init(ganmf_handle* h, int32_t g_nodes, int32_t g_layers, int g_a
     if (k_rows[u] < 0 || k_rows[u] > N) return fail(-1, "%s: k_rows[%d] = %d out of range [0,%d]", who, u, k_rows[u], N);
   HIP_TRY(hipSetDevice(h->dev));
   CfganState& c = h->cf;
-  c.g = g_nodes; c.Lg = g_layers; c.act = g_act; c.ldg = round_up(g_nodes + 1, LD_ALIGN);
   c.d_batch = std::min(d_batch, U); c.g_batch = std::min(g_batch, U); c.Bm = Bm; c.scheme = scheme;
   c.zr_coef = zr_coefficient; c.seed = seed;
   c.ldx = round_up(2 * N + 2, LD_ALIGN); c.words = (N + 31) / 32;
-  c.Gl.resize(c.Lg);
-  for (int l = 0; l < c.Lg; ++l) TRY(alloc_tensor(c.Gl[l], l == 0 ? N + 1 : c.g + 1, c.g, true, 1));
-  TRY(alloc_tensor(c.Go, c.g + 1, N, true, 1, h->ldN));
-  std::vector<float> ones((size_t)Bm, 1.0f);
-  c.Hl.assign(c.Lg, nullptr);
-  for (int l = 0; l < c.Lg; ++l) {
-    TRY(dalloc(&c.Hl[l], (size_t)Bm * c.ldg));
-    HIP_TRY(hipMemcpy2D(c.Hl[l] + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, (size_t)Bm, hipMemcpyHostToDevice));
-  }
+  TRY(mlp_alloc(h, c.gen, g_nodes, g_layers, g_act, -1, Bm));
   TRY(dalloc(&c.C, (size_t)Bm * h->ldN));
   TRY(dalloc(&c.fake, (size_t)Bm * h->ldN));
   TRY(dalloc(&c.dfake, (size_t)Bm * h->ldN));
   TRY(dalloc(&c.DX, (size_t)2 * Bm * c.ldx));
-  TRY(dalloc(&c.dh0, (size_t)Bm * c.ldg));
-  TRY(dalloc(&c.dh1, (size_t)Bm * c.ldg));
+  TRY(dalloc(&c.dh0, (size_t)Bm * c.gen.ldg));
+  TRY(dalloc(&c.dh1, (size_t)Bm * c.gen.ldg));
   TRY(dalloc(&c.zr_part, (size_t)Bm));
   TRY(dalloc(&c.loss_rows, (size_t)2 * Bm));
-  TRY(dalloc(&c.sq, (size_t)(std::max(h->L, c.Lg) + 1) * CFGAN_SQ_BLOCKS));
+  TRY(dalloc(&c.sq, (size_t)(std::max(h->L, g_layers) + 1) * CFGAN_SQ_BLOCKS));
   TRY(dalloc((float**)&c.planes, (size_t)2 * U * c.words));
   TRY(dalloc((float**)&c.k_rows, (size_t)U));
   HIP_TRY(hipMemcpy(c.k_rows, k_rows, (size_t)U * sizeof(int), hipMemcpyHostToDevice));
@@ -69,7 +52,7 @@ static int cfgan_draw(ganmf_handle* h, int64_t epoch) {
 
 int ganmf_cfgan_draw_masks(ganmf_handle* h, int64_t epoch) {
   const char* who = "ganmf_cfgan_draw_masks";
-  TRY(cfgan_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CFGAN, true));
   if (epoch < 0) return fail(-1, "%s: negative epoch", who);
   HIP_TRY(hipSetDevice(h->dev));
   TRY(cfgan_draw(h, epoch));
@@ -78,7 +61,7 @@ int ganmf_cfgan_draw_masks(ganmf_handle* h, int64_t epoch) {
 }
 
 int ganmf_cfgan_set_masks(ganmf_handle* h, const uint32_t* zr, const uint32_t* pm) {
-  TRY(cfgan_ready(h, "ganmf_cfgan_set_masks", false));
+  TRY(model_ready(h, "ganmf_cfgan_set_masks", GANMF_MODEL_CFGAN, false));
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   const size_t n = (size_t)h->U * h->cf.words;
@@ -91,7 +74,7 @@ int ganmf_cfgan_set_masks(ganmf_handle* h, const uint32_t* zr, const uint32_t* p
 }
 
 int ganmf_cfgan_get_masks(ganmf_handle* h, uint32_t* zr, uint32_t* pm) {
-  TRY(cfgan_ready(h, "ganmf_cfgan_get_masks", false));
+  TRY(model_ready(h, "ganmf_cfgan_get_masks", GANMF_MODEL_CFGAN, false));
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   const size_t n = (size_t)h->U * h->cf.words;
@@ -100,25 +83,15 @@ int ganmf_cfgan_get_masks(ganmf_handle* h, uint32_t* zr, uint32_t* pm) {
   return 0;
 }
 
-static int cfgan_losses(ganmf_handle* h, size_t n) {
-  CfganState& c = h->cf;
-  if (n <= c.loss_cap) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(c.loss_dev); c.loss_dev = nullptr; c.loss_cap = 0;
-  TRY(dalloc(&c.loss_dev, n));
-  c.loss_cap = n;
-  return 0;
-}
-
 int ganmf_cfgan_step(ganmf_handle* h, int kind, int64_t row0, int32_t nrows, float* loss) {
   const char* who = "ganmf_cfgan_step";
-  TRY(cfgan_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CFGAN, true));
   if (kind != 0 && kind != 1) return fail(-1, "%s: kind must be 0 (D) or 1 (G)", who);
   if (nrows < 1 || nrows > h->cf.Bm || row0 < 0 || row0 + nrows > h->U)
     return fail(-1, "%s: rows [%lld, %lld) of %d, at most %d per step", who, (long long)row0, (long long)row0 + nrows, h->U, h->cf.Bm);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(cfgan_losses(h, 1));
+  TRY(grow_losses(h, h->cf.loss_dev, h->cf.loss_cap, 1));
   TRY(cfgan_step(h, kind, (int)row0, nrows, h->cf.loss_dev));
   float l = 0.f;
   HIP_TRY(hipMemcpyAsync(&l, h->cf.loss_dev, sizeof(float), hipMemcpyDeviceToHost, h->st));
@@ -129,7 +102,7 @@ int ganmf_cfgan_step(ganmf_handle* h, int kind, int64_t row0, int32_t nrows, flo
 
 int ganmf_cfgan_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g_steps, int draw, float* d_losses, float* g_losses) {
   const char* who = "ganmf_cfgan_epoch";
-  TRY(cfgan_ready(h, who, true));
+  TRY(model_ready(h, who, GANMF_MODEL_CFGAN, true));
   if (d_steps < 0 || g_steps < 0 || epoch < 0) return fail(-1, "%s: negative argument", who);
   CfganState& c = h->cf;
   const int U = h->U;
@@ -137,7 +110,7 @@ int ganmf_cfgan_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g
   if ((nd && !d_losses) || (ng && !g_losses)) return fail(-1, "%s: null loss buffer", who);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(cfgan_losses(h, nd + ng + 1));
+  TRY(grow_losses(h, c.loss_dev, c.loss_cap, nd + ng + 1));
   if (draw) TRY(cfgan_draw(h, epoch));
   float* out = c.loss_dev;
   for (int pass = 0; pass < d_steps; ++pass)

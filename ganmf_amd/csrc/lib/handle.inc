@@ -58,38 +58,52 @@ struct SlimState {
   int n_eligible = 0;
 };
 
+// The generator CFGAN and CAAE share (profile_mlp.inc): an MLP from a dense profile row [N] through Lg hidden layers of g units back to
+// [N], every bias folded into its tensor as the last row and fed by a ones column of the layer's input.
+struct ProfileMlp {
+  int g = 0, Lg = 0, act = 0, ldg = 0;      // width, depth, hidden activation
+  int out_act = -1;                         // activation of the output layer (-1: none; CAAE: the sigmoid)
+  std::vector<Tensor> Gl;        // l = 0: [N + 1, g] (row N the bias); l > 0: [g + 1, g]
+  Tensor Go;                     // [g + 1, N] (row g the bias), leading dimension ldN
+  std::vector<float*> Hl;        // hidden outputs of a training batch [rows, ldg] with the ones column at g
+  // scratch of a block of sc_rows scored rows: dense profiles, two hidden blocks (the layers alternate), one output block
+  float *sc_C = nullptr, *sc_H0 = nullptr, *sc_H1 = nullptr, *sc_F = nullptr;
+  size_t sc_rows = 0;
+  std::vector<Tensor*> tensors() {
+    std::vector<Tensor*> v;
+    for (auto& t : Gl) v.push_back(&t);
+    v.push_back(&Go);
+    return v;
+  }
+};
+
 // CFGAN state of a GANMF_MODEL_CFGAN handle (ganmf_cfgan_init; step_cfgan.inc).  The discriminator lives in the handle's DisGANMF
 // members (Wl, Wo, Al, dz0, dz1, dlogit; Wl[0] is [2N + 1, e]: condition rows, input rows, bias row); the generator, the masks and the
 // step's work buffers live here.  Bm = max(d_batch, g_batch) rows.
 struct CfganState {
   bool ready = false;
-  int g = 0, Lg = 0, act = 0, ldg = 0;      // generator width, depth, activation
   int d_batch = 0, g_batch = 0, scheme = 0, Bm = 0, ldx = 0, words = 0;
   float zr_coef = 0.f;
   uint64_t seed = 0;
-  std::vector<Tensor> Gl;        // l = 0: [N + 1, g] (row N the bias); l > 0: [g + 1, g]
-  Tensor Go;                     // [g + 1, N] (row g the bias), leading dimension ldN
-  std::vector<float*> Hl;        // hidden outputs [Bm, ldg] with the ones column at g
+  ProfileMlp gen;
   float *C = nullptr, *fake = nullptr, *dfake = nullptr, *DX = nullptr, *dh0 = nullptr, *dh1 = nullptr;
   float *zr_part = nullptr, *loss_rows = nullptr, *sq = nullptr, *loss_dev = nullptr;
   size_t loss_cap = 0;
   unsigned* planes = nullptr;    // [2][U][words]: CFGAN_PLANE_ZR, CFGAN_PLANE_PM
   int* k_rows = nullptr;         // [U]
-  // scoring: scratch of a block of scored rows, and (item mode) the transposed G(all rows) [N, ld(U)] as of cache_version
-  float *sc_C = nullptr, *sc_H0 = nullptr, *sc_H1 = nullptr, *sc_F = nullptr, *cache = nullptr;
-  size_t sc_rows = 0;
+  float* cache = nullptr;        // item-mode scoring: the transposed G(all rows) [N, ld(U)] as of cache_version
   long long cache_version = -1;
 };
 
 // CAAE state of a GANMF_MODEL_CAAE handle (ganmf_caae_init; step_caae.inc).  The discriminator's embeddings P, Q are the handle's
-// factor tensors Ue [U, k] and V [N, k]; its item bias, the two generators (gen[0] = G, gen[1] = G': the generator members of a
-// CfganState each, sigmoid everywhere), the epoch's draws and the steps' work buffers live here.
+// factor tensors Ue [U, k] and V [N, k]; its item bias, the two generators (gen[0] = G, gen[1] = G': built alike, sigmoid on every
+// layer), the epoch's draws and the steps' work buffers live here.
 struct CaaeState {
   bool ready = false;
-  int g = 0, Lg = 0, ldg = 0, Bm = 0, n_s = 0, words = 0, d_bsize = 0;
+  int Bm = 0, n_s = 0, words = 0, d_bsize = 0;
   float lmbda = 0.f, beta = 0.f, lr = 0.f;
   uint64_t seed = 0;
-  CfganState gen[2];             // Gl, Go, Hl, g, Lg, act, ldg (and the scoring scratch of gen[0])
+  ProfileMlp gen[2];
   Tensor bias;                   // disc_item_bias [1, N]
   int* k_rows = nullptr;         // [U] size of Nu per user
   // the epoch's state: both CDFs [U, ldN], the user of every stored interaction, the shuffled order and its triples

@@ -2,20 +2,15 @@
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 // =================================================================================================
 // Discriminator: P = h->Ue, Q = h->V, b = CaaeState::bias; plain SGD on the touched rows (caae_rows.hpp).  Generators: CaaeState::gen[0]
-// (G) and gen[1] (G'), sigmoid on every layer.  Every dense product goes through run_gemm under the handle's planner: the forward passes
-// as CFGAN's (cfgan_generator_of with the sigmoid on the output layer), the backward pass through cfgan_bwd, and every parameter gradient
+// (G) and gen[1] (G'), sigmoid on every layer.  Every dense product goes through run_gemm under the handle's planner: the forward and
+// backward passes are the shared generator's (profile_mlp.inc, the sigmoid on the output layer too), and every parameter gradient runs
 // as a TN product that stores into the tensor's own gradient buffer (EPI_STORE); caae_sgd_kernel then applies
 // theta -= lr * (g + beta * theta).  Products that read a parameter run before the kernel that updates it.  sum(theta^2) of the loss is
 // taken at the head of the step, at the pre-update parameters like every other term of the reported loss.
 // =================================================================================================
 void caae_free(ganmf_handle* h) {
   CaaeState& c = h->ca;
-  for (CfganState& g : c.gen) {
-    for (auto& t : g.Gl) free_tensor(t, true);
-    free_tensor(g.Go, true);
-    for (float* a : g.Hl) hipFree(a);
-    hipFree(g.sc_C); hipFree(g.sc_H0); hipFree(g.sc_H1); hipFree(g.sc_F);
-  }
+  for (ProfileMlp& g : c.gen) mlp_free(g);
   free_tensor(c.bias, false);
   hipFree(c.k_rows); hipFree(c.cdf[0]); hipFree(c.cdf[1]); hipFree(c.iu); hipFree(c.perm); hipFree(c.tu); hipFree(c.ti);
   hipFree(c.neg); hipFree(c.users); hipFree(c.nu); hipFree(c.items); hipFree(c.xt); hipFree(c.first); hipFree(c.xu); hipFree(c.xi); hipFree(c.xn);
@@ -25,43 +20,12 @@ void caae_free(ganmf_handle* h) {
   c = CaaeState{};
 }
 
-// scoring / all-users scratch of gen[0]: `rows` dense profiles, two hidden blocks (ones column at g), one output block
-int caae_scratch(ganmf_handle* h, size_t rows) {
-  CaaeState& c = h->ca;
-  CfganState& g = c.gen[0];
-  if (rows <= g.sc_rows) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(g.sc_C); hipFree(g.sc_H0); hipFree(g.sc_H1); hipFree(g.sc_F);
-  g.sc_C = g.sc_H0 = g.sc_H1 = g.sc_F = nullptr; g.sc_rows = 0;
-  TRY(dalloc(&g.sc_C, rows * h->ldN));
-  TRY(dalloc(&g.sc_H0, rows * c.ldg));
-  TRY(dalloc(&g.sc_H1, rows * c.ldg));
-  TRY(dalloc(&g.sc_F, rows * h->ldN));
-  std::vector<float> ones(rows, 1.0f);
-  HIP_TRY(hipMemcpy2D(g.sc_H0 + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy2D(g.sc_H1 + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
-  g.sc_rows = rows;
-  return 0;
-}
-
-// out[i, :] = sigmoid(G_which(profile of ids[i])) for n rows (ids_dev == nullptr: rows row0 ..) through the scratch blocks
-int caae_forward_rows(ganmf_handle* h, int which, const int* ids_dev, int row0, int n, float* out, int ldo) {
-  CaaeState& c = h->ca;
-  TRY(caae_scratch(h, (size_t)n));
-  CfganState& s = c.gen[0];
-  std::vector<float*> H(c.Lg);
-  for (int l = 0; l < c.Lg; ++l) H[l] = (l & 1) ? s.sc_H1 : s.sc_H0;
-  GANMF_LAUNCH(cfgan_densify_kernel, dim3(n), dim3(256), 0, h->st, h->indptr, h->indices, h->data, ids_dev, row0, h->N, s.sc_C, h->ldN);
-  HIP_TRY(hipGetLastError());
-  return cfgan_generator_of(h, c.gen[which], s.sc_C, n, H.data(), out, ldo, ACT_SIGMOID);
-}
-
 // The fourth score source behind scores_device: out[i, :] = sigmoid(G(profile of ids[i])) -- the sigmoid applied, as CAAE.py:391 returns it
 int caae_scores(ganmf_handle* h, const int* ids_dev, int64_t n, int transposed, float* out, int ldw) {
   if (!h->ca.ready) return fail(-1, "scores: ganmf_caae_init has not been called on this GANMF_MODEL_CAAE handle");
   if (!h->has_urm) return fail(-1, "scores: ganmf_set_urm_csr has not been called");
   if (transposed) return fail(-1, "scores: a GANMF_MODEL_CAAE handle scores users only (the reference ignores `mode`)");
-  return caae_forward_rows(h, 0, ids_dev, 0, (int)n, out, ldw);
+  return mlp_forward_rows(h, h->ca.gen[0], ids_dev, 0, (int)n, out, ldw);
 }
 
 constexpr int CAAE_ALL_BLOCK = 1024;
@@ -69,12 +33,13 @@ constexpr int CAAE_ALL_BLOCK = 1024;
 // resident CDF of generator `which` over all users, block by block (CAAE.py:228-241)
 int caae_cdf_all(ganmf_handle* h, int which) {
   CaaeState& c = h->ca;
+  ProfileMlp& gn = c.gen[which];
   const int U = h->U, blk = std::min(U, CAAE_ALL_BLOCK);
-  TRY(caae_scratch(h, (size_t)blk));
+  TRY(mlp_scratch(h, gn, (size_t)blk));      // grown here: sc_F is named as the output below, before mlp_forward_rows would grow it
   for (int r0 = 0; r0 < U; r0 += blk) {
     const int nb = std::min(blk, U - r0);
-    TRY(caae_forward_rows(h, which, nullptr, r0, nb, c.gen[0].sc_F, h->ldN));
-    GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, c.gen[0].sc_F, h->ldN, h->N, c.cdf[which] + (size_t)r0 * h->ldN, h->ldN,
+    TRY(mlp_forward_rows(h, gn, nullptr, r0, nb, gn.sc_F, h->ldN));
+    GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, gn.sc_F, h->ldN, h->N, c.cdf[which] + (size_t)r0 * h->ldN, h->ldN,
                  c.lse_all + r0);
     HIP_TRY(hipGetLastError());
   }
@@ -133,10 +98,7 @@ int caae_draw_users(ganmf_handle* h, int64_t epoch, int which, int step, int* ou
 
 // forward of generator `which` over the batch's rows into R (or Rp), hidden outputs into the generator's own blocks
 int caae_batch_forward(ganmf_handle* h, int which, const int* users_dev, float* out) {
-  CaaeState& c = h->ca;
-  GANMF_LAUNCH(cfgan_densify_kernel, dim3(c.Bm), dim3(256), 0, h->st, h->indptr, h->indices, h->data, users_dev, 0, h->N, c.C, h->ldN);
-  HIP_TRY(hipGetLastError());
-  return cfgan_generator_of(h, c.gen[which], c.C, c.Bm, c.gen[which].Hl.data(), out, h->ldN, ACT_SIGMOID);
+  return mlp_forward_rows(h, h->ca.gen[which], users_dev, 0, h->ca.Bm, out, h->ldN, h->ca.C);
 }
 
 // (d) the Nu planes of the batch's rows, weighted by G' at its current parameters (inside an epoch: its epoch-start parameters, because
@@ -190,17 +152,11 @@ int caae_wgrad(ganmf_handle* h, const float* A, int lda, const float* dz, int ld
 // One step of generator `which` (0: G, 1: G') on the batch's users, Nu planes (G only) and policy items (device arrays); loss -> *loss_dev
 int caae_g_step(ganmf_handle* h, int which, const int* users_dev, const unsigned* nu_dev, const int* items_dev, float* loss_dev) {
   CaaeState& c = h->ca;
-  CfganState& gn = c.gen[which];
-  const int N = h->N, nb = c.Bm, Lg = c.Lg, g = c.g;
+  ProfileMlp& gn = c.gen[which];
+  const int N = h->N, nb = c.Bm;
   const float pc = (which == 0 ? c.lmbda : 1.0f) / ((float)nb * (float)c.n_s), ac = which == 0 ? 1.0f - c.lmbda : 0.f;
-  std::vector<Tensor*> mine;
-  for (auto& t : gn.Gl) mine.push_back(&t);
-  mine.push_back(&gn.Go);
-  if (c.beta != 0.f) {
-    for (size_t t = 0; t < mine.size(); ++t)
-      GANMF_LAUNCH(cfgan_sumsq_kernel, dim3(CFGAN_SQ_BLOCKS), dim3(256), 0, h->st, mine[t]->p, (long long)(mine[t]->padded() / 4), c.sq + t * CFGAN_SQ_BLOCKS);
-    HIP_TRY(hipGetLastError());
-  }
+  const std::vector<Tensor*> mine = gn.tensors();
+  if (c.beta != 0.f) TRY(sumsq_tensors(h, mine, c.sq));
   TRY(caae_batch_forward(h, which, users_dev, c.R));
   GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, c.R, h->ldN, N, (float*)nullptr, h->ldN, c.lse);
   HIP_TRY(hipGetLastError());
@@ -215,15 +171,9 @@ int caae_g_step(ganmf_handle* h, int which, const int* users_dev, const unsigned
                (int)mine.size() * CFGAN_SQ_BLOCKS, c.beta, loss_dev);
   HIP_TRY(hipGetLastError());
   // backward, top down: every product reads the pre-step parameters; the updates follow
-  float* gc = c.dh0;
-  float* gnx = c.dh1;
-  TRY(cfgan_bwd(h, c.dz, h->ldN, gn.Go.p, h->ldN, gc, c.ldg, nb, g, N, ACT_SIGMOID, gn.Hl[Lg - 1], c.ldg));
-  TRY(caae_wgrad(h, gn.Hl[Lg - 1], c.ldg, c.dz, h->ldN, gn.Go, g + 1, N, nb));
-  for (int l = Lg - 1; l >= 0; --l) {
-    if (l > 0) TRY(cfgan_bwd(h, gc, c.ldg, gn.Gl[l].p, c.ldg, gnx, c.ldg, nb, g, g, ACT_SIGMOID, gn.Hl[l - 1], c.ldg));
-    TRY(caae_wgrad(h, l == 0 ? c.C : gn.Hl[l - 1], l == 0 ? h->ldN : c.ldg, gc, c.ldg, gn.Gl[l], l == 0 ? N + 1 : g + 1, g, nb));
-    if (l > 0) std::swap(gc, gnx);
-  }
+  TRY(mlp_backward(h, gn, c.C, c.dz, c.dh0, c.dh1, nb, [&](const float* A, int lda, const float* dz, int ldz, Tensor& W, int Mw, int Nw) {
+    return caae_wgrad(h, A, lda, dz, ldz, W, Mw, Nw, nb);
+  }));
   for (Tensor* t : mine) {
     const long long n4 = (long long)(t->padded() / 4);
     GANMF_LAUNCH(caae_sgd_kernel, dim3(caae_grid(n4)), dim3(256), 0, h->st, t->p, t->g, n4, c.lr, c.beta);

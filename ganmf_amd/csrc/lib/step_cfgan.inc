@@ -3,10 +3,10 @@
 // =================================================================================================
 // Discriminator: the handle's DisGANMF members.  Its input block DX [2B, ldx] holds [c | x | 1]: Wl[0] is [2N + 1, e] (condition rows,
 // input rows, bias row), so layer 0 is ONE K = 2N + 1 product and both bias and the concat of CFGAN.py:57 ride in it.  Generator:
-// CfganState.  Every dense product goes through run_gemm under the handle's planner; every parameter gradient is a TN product that ends
+// CfganState::gen (profile_mlp.inc).  Every dense product goes through run_gemm under the handle's planner; every parameter gradient is a TN product that ends
 // in the fused TF-Adam epilogue (EPI_ADAM) -- the output unit's rides in dis_dz_top_kernel as in DisGANMF -- so no gradient is stored.
 // Products that read a parameter run before the product that updates it.  sum(theta^2) of the loss is taken at the head of the step
-// (cfgan_sumsq_kernel), at the pre-update parameters like every other term of the reported loss.
+// (sumsq_tensors), at the pre-update parameters like every other term of the reported loss.
 // =================================================================================================
 int cfgan_create(ganmf_handle* h) {
   const int N = h->N, e = h->e, B = h->B;
@@ -29,35 +29,12 @@ int cfgan_create(ganmf_handle* h) {
 
 void cfgan_free(ganmf_handle* h) {
   CfganState& c = h->cf;
-  for (auto& t : c.Gl) free_tensor(t, true);
-  free_tensor(c.Go, true);
+  mlp_free(c.gen);
   if (h->cfg.model == GANMF_MODEL_CFGAN) { for (auto& t : h->Wl) hipFree(t.g); hipFree(h->Wo.g); }
-  for (float* a : c.Hl) hipFree(a);
   hipFree(c.C); hipFree(c.fake); hipFree(c.dfake); hipFree(c.DX); hipFree(c.dh0); hipFree(c.dh1);
   hipFree(c.zr_part); hipFree(c.loss_rows); hipFree(c.sq); hipFree(c.loss_dev); hipFree(c.planes); hipFree(c.k_rows);
-  hipFree(c.sc_C); hipFree(c.sc_H0); hipFree(c.sc_H1); hipFree(c.sc_F); hipFree(c.cache);
+  hipFree(c.cache);
   c = CfganState{};
-}
-
-// fake[nb, ldf] = G(X) for the nb dense rows X [nb, ldN] (ones column at N); hidden outputs into H[l] [nb, ldg] (ones column at g).
-// c: the generator's members (CFGAN's own, or one of CAAE's two); out_act >= 0: that activation on the output layer (CAAE's sigmoid)
-int cfgan_generator_of(ganmf_handle* h, const CfganState& c, const float* X, int nb, float* const* H, float* fake, int ldf, int out_act = -1) {
-  for (int l = 0; l < c.Lg; ++l) {      // h_{l+1} = act([h_l | 1] . Gl_ext)
-    GemmP g{};
-    g.A = l == 0 ? X : H[l - 1]; g.lda = l == 0 ? h->ldN : c.ldg;
-    g.B = c.Gl[l].p; g.ldb = c.ldg;
-    g.C = H[l]; g.ldc = c.ldg; g.M = nb; g.N = c.g; g.K = l == 0 ? h->N + 1 : c.g + 1;
-    g.epi.kind = EPI_ACT; g.epi.act = c.act;
-    TRY(run_gemm(h, T_DIS_FWD, T_RED_DIS_FWD, g, false, true));
-  }
-  GemmP g{};      // fake = [h | 1] . Go_ext
-  g.A = H[c.Lg - 1]; g.lda = c.ldg; g.B = c.Go.p; g.ldb = h->ldN;
-  g.C = fake; g.ldc = ldf; g.M = nb; g.N = h->N; g.K = c.g + 1; g.epi.kind = EPI_STORE;
-  if (out_act >= 0) { g.epi.kind = EPI_ACT; g.epi.act = out_act; }
-  return run_gemm(h, T_GEMM_GEN, T_RED_GEN, g, false, true);
-}
-int cfgan_generator(ganmf_handle* h, const float* X, int nb, float* const* H, float* fake, int ldf) {
-  return cfgan_generator_of(h, h->cf, X, nb, H, fake, ldf);
 }
 
 // gW = A_ext^T . dz over `nrows` rows, TF-Adam in the epilogue (the plan DisGANMF's weight gradients run on)
@@ -74,40 +51,23 @@ int cfgan_wgrad(ganmf_handle* h, const float* A, int lda, const float* dz, int l
   return run_gemm(h, T_DIS_GW, T_RED_DIS_GW, g, true, true, nullptr, 24.0 * W.count(), 0, &ft);
 }
 
-// dst = (src . W[0:n_out]^T) * act'(aux): one layer of a backward pass over nrows rows
-int cfgan_bwd(ganmf_handle* h, const float* src, int lds, const float* W, int ldw, float* dst, int ldd, int nrows, int n_out, int K,
-              int act, const float* aux, int ldaux) {
-  GemmP g{};
-  g.A = src; g.lda = lds; g.B = W; g.ldb = ldw;
-  g.C = dst; g.ldc = ldd; g.M = nrows; g.N = n_out; g.K = K;
-  g.epi.kind = aux ? EPI_MUL_ACTGRAD : EPI_STORE; g.epi.act = act;
-  g.epi.aux = aux; g.epi.ldaux = ldaux;
-  return run_gemm(h, T_DIS_BWD, T_RED_DIS_BWD, g, false, false);
-}
-
 // One optimiser step on rows [row0, row0 + nb): kind 0 the discriminator's, 1 the generator's.  The step's loss -> *loss_dev.
 int cfgan_step(ganmf_handle* h, int kind, int row0, int nb, float* loss_dev) {
   CfganState& c = h->cf;
-  const int N = h->N, e = h->e, L = h->L, Lg = c.Lg, g = c.g;
+  const int N = h->N, e = h->e, L = h->L;
   const bool gstep = kind == 1;
   const int alpha = gstep ? S_ALPHA_G : S_ALPHA_D;
   const float reg = gstep ? h->cfg.g_reg : h->cfg.d_reg;
   const unsigned* pm = c.scheme != 0 ? c.planes + (size_t)CFGAN_PLANE_PM * h->U * c.words : nullptr;      // ZR: the train mask is c
   const unsigned* zr = (gstep && c.scheme != 1 && c.zr_coef != 0.f) ? c.planes + (size_t)CFGAN_PLANE_ZR * h->U * c.words : nullptr;
   std::vector<Tensor*> mine;
-  if (gstep) { for (auto& t : c.Gl) mine.push_back(&t); mine.push_back(&c.Go); }
+  if (gstep) mine = c.gen.tensors();
   else { for (auto& t : h->Wl) mine.push_back(&t); mine.push_back(&h->Wo); }
   GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal, kind, alpha, gstep ? h->cfg.g_lr : h->cfg.d_lr);
   HIP_TRY(hipGetLastError());
-  if (reg != 0.f) {
-    for (size_t t = 0; t < mine.size(); ++t)
-      GANMF_LAUNCH(cfgan_sumsq_kernel, dim3(CFGAN_SQ_BLOCKS), dim3(256), 0, h->st, mine[t]->p, (long long)(mine[t]->padded() / 4), c.sq + t * CFGAN_SQ_BLOCKS);
-    HIP_TRY(hipGetLastError());
-  }
+  if (reg != 0.f) TRY(sumsq_tensors(h, mine, c.sq));
   // rows, generator, masked rows into the discriminator's input block
-  GANMF_LAUNCH(cfgan_densify_kernel, dim3(nb), dim3(256), 0, h->st, h->indptr, h->indices, h->data, (const int*)nullptr, row0, N, c.C, h->ldN);
-  HIP_TRY(hipGetLastError());
-  TRY(cfgan_generator(h, c.C, nb, c.Hl.data(), c.fake, h->ldN));
+  TRY(mlp_forward_rows(h, c.gen, nullptr, row0, nb, c.fake, h->ldN, c.C));
   CfganRowP rp{c.C, c.fake, c.dfake, h->ldN, N, nb, row0, pm, zr, c.words, c.DX, c.ldx, gstep ? 0 : 1, zr ? c.zr_part : nullptr,
                2.0f * c.zr_coef / (float)nb};
   GANMF_LAUNCH(cfgan_mask_fwd_kernel, dim3(nb), dim3(256), 0, h->st, rp);
@@ -139,72 +99,37 @@ int cfgan_step(ganmf_handle* h, int kind, int row0, int nb, float* loss_dev) {
   float* cur = h->dz0;
   float* nxt = h->dz1;
   for (int l = L - 1; l >= 0; --l) {
-    if (l > 0) TRY(cfgan_bwd(h, cur, h->lde, h->Wl[l].p, h->lde, nxt, h->lde, M, e, e, h->act, h->Al[l - 1], h->lde));
+    if (l > 0) TRY(mlp_bwd(h, cur, h->lde, h->Wl[l].p, h->lde, nxt, h->lde, M, e, e, h->act, h->Al[l - 1], h->lde));
     if (!gstep) TRY(cfgan_wgrad(h, l == 0 ? c.DX : h->Al[l - 1], l == 0 ? c.ldx : h->lde, cur, h->lde, h->Wl[l], l == 0 ? 2 * N + 1 : e + 1, e, M, alpha, reg));
     if (l > 0) std::swap(cur, nxt);
   }
   if (!gstep) return 0;
   // d loss / d g_out = dz_0 . W_0[N:2N]^T, then dfake through the masks
-  TRY(cfgan_bwd(h, cur, h->lde, h->Wl[0].p + (size_t)N * h->lde, h->lde, c.dfake, h->ldN, nb, N, e, 0, nullptr, 0));
+  TRY(mlp_bwd(h, cur, h->lde, h->Wl[0].p + (size_t)N * h->lde, h->lde, c.dfake, h->ldN, nb, N, e, 0, nullptr, 0));
   GANMF_LAUNCH(cfgan_mask_bwd_kernel, dim3(nb), dim3(256), 0, h->st, rp);
   HIP_TRY(hipGetLastError());
-  // generator, top down
-  float* gc = c.dh0;
-  float* gn = c.dh1;
-  TRY(cfgan_bwd(h, c.dfake, h->ldN, c.Go.p, h->ldN, gc, c.ldg, nb, g, N, c.act, c.Hl[Lg - 1], c.ldg));
-  TRY(cfgan_wgrad(h, c.Hl[Lg - 1], c.ldg, c.dfake, h->ldN, c.Go, g + 1, N, nb, alpha, reg));
-  for (int l = Lg - 1; l >= 0; --l) {
-    if (l > 0) TRY(cfgan_bwd(h, gc, c.ldg, c.Gl[l].p, c.ldg, gn, c.ldg, nb, g, g, c.act, c.Hl[l - 1], c.ldg));
-    TRY(cfgan_wgrad(h, l == 0 ? c.C : c.Hl[l - 1], l == 0 ? h->ldN : c.ldg, gc, c.ldg, c.Gl[l], l == 0 ? N + 1 : g + 1, g, nb, alpha, reg));
-    if (l > 0) std::swap(gc, gn);
-  }
-  return 0;
+  return mlp_backward(h, c.gen, c.C, c.dfake, c.dh0, c.dh1, nb, [&](const float* A, int lda, const float* dz, int ldz, Tensor& W, int Mw, int Nw) {
+    return cfgan_wgrad(h, A, lda, dz, ldz, W, Mw, Nw, nb, alpha, reg);
+  });
 }
 
 // The third score source behind scores_device.  transposed = 0: out[i, :] = G(c[ids[i]]) (user mode).  transposed = 1: row ids[i] of the
 // TRANSPOSED G(all rows) (item mode: training rows are items), formed in blocks into a device cache keyed by param_version.
-int cfgan_scratch(ganmf_handle* h, size_t rows) {
-  CfganState& c = h->cf;
-  if (rows <= c.sc_rows) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(c.sc_C); hipFree(c.sc_H0); hipFree(c.sc_H1); hipFree(c.sc_F);
-  c.sc_C = c.sc_H0 = c.sc_H1 = c.sc_F = nullptr; c.sc_rows = 0;
-  TRY(dalloc(&c.sc_C, rows * h->ldN));
-  TRY(dalloc(&c.sc_H0, rows * c.ldg));
-  TRY(dalloc(&c.sc_H1, rows * c.ldg));
-  TRY(dalloc(&c.sc_F, rows * h->ldN));
-  std::vector<float> ones(rows, 1.0f);
-  HIP_TRY(hipMemcpy2D(c.sc_H0 + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy2D(c.sc_H1 + c.g, (size_t)c.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
-  c.sc_rows = rows;
-  return 0;
-}
-
 int cfgan_scores(ganmf_handle* h, const int* ids_dev, int64_t n, int transposed, float* out, int ldw) {
   CfganState& c = h->cf;
   if (!c.ready) return fail(-1, "scores: ganmf_cfgan_init has not been called on this GANMF_MODEL_CFGAN handle");
   if (!h->has_urm) return fail(-1, "scores: ganmf_set_urm_csr has not been called");
   const int N = h->N, U = h->U;
-  std::vector<float*> H(c.Lg);
-  if (!transposed) {
-    TRY(cfgan_scratch(h, (size_t)n));
-    for (int l = 0; l < c.Lg; ++l) H[l] = (l & 1) ? c.sc_H1 : c.sc_H0;
-    GANMF_LAUNCH(cfgan_densify_kernel, dim3((int)n), dim3(256), 0, h->st, h->indptr, h->indices, h->data, ids_dev, 0, N, c.sc_C, h->ldN);
-    HIP_TRY(hipGetLastError());
-    return cfgan_generator(h, c.sc_C, (int)n, H.data(), out, ldw);
-  }
+  if (!transposed) return mlp_forward_rows(h, c.gen, ids_dev, 0, (int)n, out, ldw);
   const int ldu = round_up(U, LD_ALIGN);      // == ldw
   if (c.cache_version != h->param_version || !c.cache) {
     if (!c.cache) TRY(dalloc(&c.cache, (size_t)N * ldu));
     const int blk = std::min(U, 1024);
-    TRY(cfgan_scratch(h, (size_t)blk));
-    for (int l = 0; l < c.Lg; ++l) H[l] = (l & 1) ? c.sc_H1 : c.sc_H0;
+    TRY(mlp_scratch(h, c.gen, (size_t)blk));      // grown here: sc_F is named as the output below, before mlp_forward_rows would grow it
     for (int r0 = 0; r0 < U; r0 += blk) {
       const int nb = std::min(blk, U - r0);
-      GANMF_LAUNCH(cfgan_densify_kernel, dim3(nb), dim3(256), 0, h->st, h->indptr, h->indices, h->data, (const int*)nullptr, r0, N, c.sc_C, h->ldN);
-      HIP_TRY(hipGetLastError());
-      TRY(cfgan_generator(h, c.sc_C, nb, H.data(), c.sc_F, h->ldN));
-      GANMF_LAUNCH(cfgan_transpose_kernel, dim3((N + 31) / 32, (nb + 31) / 32), dim3(256), 0, h->st, c.sc_F, h->ldN, nb, N, c.cache, ldu, r0);
+      TRY(mlp_forward_rows(h, c.gen, nullptr, r0, nb, c.gen.sc_F, h->ldN));
+      GANMF_LAUNCH(cfgan_transpose_kernel, dim3((N + 31) / 32, (nb + 31) / 32), dim3(256), 0, h->st, c.gen.sc_F, h->ldN, nb, N, c.cache, ldu, r0);
       HIP_TRY(hipGetLastError());
     }
     c.cache_version = h->param_version;

@@ -69,6 +69,27 @@ int not_cfgan(const ganmf_handle* h, const char* who) {
   return 0;
 }
 
+// the gate of the ganmf_cfgan_* / ganmf_caae_* entries behind their _init: a handle of `model`, initialised, with a URM where needed
+int model_ready(ganmf_handle* h, const char* who, int model, bool need_urm) {
+  const bool cfgan = model == GANMF_MODEL_CFGAN;
+  if (!h) return fail(-1, "%s: null handle", who);
+  if (h->cfg.model != model) return fail(-1, "%s: needs a GANMF_MODEL_%s handle", who, cfgan ? "CFGAN" : "CAAE");
+  if (!(cfgan ? h->cf.ready : h->ca.ready))
+    return fail(-1, "%s: ganmf_%s_init has not been called on this handle", who, cfgan ? "cfgan" : "caae");
+  if (need_urm && !h->has_urm) return fail(-1, "%s: ganmf_set_urm_csr has not been called", who);
+  return 0;
+}
+
+// room for n step losses in a model's device buffer
+int grow_losses(ganmf_handle* h, float*& buf, size_t& cap, size_t n) {
+  if (n <= cap) return 0;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  hipFree(buf); buf = nullptr; cap = 0;
+  TRY(dalloc(&buf, n));
+  cap = n;
+  return 0;
+}
+
 // A reference variable as up to two row segments of a folded tensor.
 struct Seg { Tensor* t; int row0, col0, rows, cols, host_row0; };
 struct View { int rows, cols, nseg; Seg seg[2]; };
@@ -81,7 +102,7 @@ bool find_view(ganmf_handle* h, int id, View* v) {
   if (h->cfg.model == GANMF_MODEL_CFGAN) {
     // discriminator ids as DisGANMF's (layer 0 is [2N, e]: condition rows then input rows, the bias is row 2N of the folded tensor);
     // generator ids from GANMF_T_CFGAN_G0, laid out the same way (G_output/kernel [g, N], G_output/bias [N])
-    const int N = h->N, e = h->e, g = h->cf.g, L = h->L, Lg = h->cf.Lg;
+    const int N = h->N, e = h->e, g = h->cf.gen.g, L = h->L, Lg = h->cf.gen.Lg;
     if (id >= 0 && id <= 2 * L + 1) {
       if (id == 2 * L) { v->rows = e; v->cols = 1; v->nseg = 1; v->seg[0] = {&h->Wo, 0, 0, 1, e, 0}; return true; }
       if (id == 2 * L + 1) return one(&h->Wo, 0, e, 1, 1);
@@ -91,11 +112,11 @@ bool find_view(ganmf_handle* h, int id, View* v) {
     }
     const int gid = id - GANMF_T_CFGAN_G0;
     if (!h->cf.ready || gid < 0 || gid > 2 * Lg + 1) return false;
-    if (gid == 2 * Lg) return one(&h->cf.Go, 0, 0, g, N);
-    if (gid == 2 * Lg + 1) return one(&h->cf.Go, g, 0, 1, N);
+    if (gid == 2 * Lg) return one(&h->cf.gen.Go, 0, 0, g, N);
+    if (gid == 2 * Lg + 1) return one(&h->cf.gen.Go, g, 0, 1, N);
     const int l = gid / 2;
-    if (gid & 1) return one(&h->cf.Gl[l], l == 0 ? N : g, 0, 1, g);
-    return one(&h->cf.Gl[l], 0, 0, l == 0 ? N : g, g);
+    if (gid & 1) return one(&h->cf.gen.Gl[l], l == 0 ? N : g, 0, 1, g);
+    return one(&h->cf.gen.Gl[l], 0, 0, l == 0 ? N : g, g);
   }
   if (h->cfg.model == GANMF_MODEL_CAAE) {
     // D: disc_user_embeddings / disc_item_embeddings under the factor ids, disc_item_bias [1, N]; G from GANMF_T_CAAE_G0 and G' from
@@ -106,8 +127,8 @@ bool find_view(ganmf_handle* h, int id, View* v) {
     if (id == GANMF_T_CAAE_ITEM_BIAS) return one(&h->ca.bias, 0, 0, 1, h->N);
     const int which = id >= GANMF_T_CAAE_GPR0 ? 1 : 0;
     const int gid = id - (which ? GANMF_T_CAAE_GPR0 : GANMF_T_CAAE_G0);
-    const int N = h->N, g = h->ca.g, Lg = h->ca.Lg;
-    CfganState& gn = h->ca.gen[which];
+    ProfileMlp& gn = h->ca.gen[which];
+    const int N = h->N, g = gn.g, Lg = gn.Lg;
     if (gid < 0 || gid > 2 * Lg + 1) return false;
     if (gid == 2 * Lg) return one(&gn.Go, 0, 0, g, N);
     if (gid == 2 * Lg + 1) return one(&gn.Go, g, 0, 1, N);
@@ -148,14 +169,13 @@ std::vector<Tensor*> all_tensors(ganmf_handle* h) {
   if (h->cfg.model == GANMF_MODEL_CFGAN) {      // no factor tensors: the discriminator's layers, then the generator's
     for (auto& t : h->Wl) v.push_back(&t);
     v.push_back(&h->Wo);
-    for (auto& t : h->cf.Gl) v.push_back(&t);
-    if (h->cf.ready) v.push_back(&h->cf.Go);
+    if (h->cf.ready) for (Tensor* t : h->cf.gen.tensors()) v.push_back(t);
     return v;
   }
   v = {&h->Ue, &h->V};
   if (h->cfg.model == GANMF_MODEL_CAAE && h->ca.ready) {      // P, Q, then b and the layers of G and G'
     v.push_back(&h->ca.bias);
-    for (CfganState& gn : h->ca.gen) { for (auto& t : gn.Gl) v.push_back(&t); v.push_back(&gn.Go); }
+    for (ProfileMlp& gn : h->ca.gen) for (Tensor* t : gn.tensors()) v.push_back(t);
   }
   if (h->cfg.model == GANMF_MODEL_GANMF) { v.push_back(&h->We); v.push_back(&h->Wd); }
   else if (h->cfg.model == GANMF_MODEL_DISGANMF) { for (auto& t : h->Wl) v.push_back(&t); v.push_back(&h->Wo); }

@@ -1,10 +1,12 @@
 """CAAE on the device: the CDF rows against float64, the samplers against their uint64 restatement, the weighted subset Nu against its
-sizes and against numpy's own choice(p=, replace=False), one D-step and one G / G' step per row against the float64 restatement, the
+sizes, against numpy's own choice(p=, replace=False) and against planes recorded on the device, one D-step and one G / G' step per row against the float64 restatement, the
 one-call epoch against its own recorded draws fed step by step and against float64, and the class (fit with both samplers, scoring,
 device evaluation, early stopping, the Saver bundle, the refusals).
 
 Shapes: 65 rows, I = 64 / 70 / 400 (and 5000 for the CDF rows: a second 4096-column tile), profiles of 0, 1, 63, 64, 65, I - 1 and I
 items among the first rows (helpers_cfgan.make_case): the row with I items has no non-interaction, the row with 0 an empty profile."""
+import os
+
 import numpy as np
 import pytest
 import scipy.sparse as sps
@@ -208,6 +210,50 @@ def test_nu_statistics_against_numpy_choice():
         worst = max(worst, z_.max())
         assert z_.max() <= 5.0, (r, z_.max())
     print("Nu statistics: worst inclusion frequency %.2f sigma from numpy's" % worst)
+
+
+# Nu's keys go through the device's fast log and exp, so no host restatement is exact: its bytes are pinned by a recording instead
+NU_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "caae_nu_planes.npz")
+NU_CASES = [(64, 0.1), (70, 0.5), (400, 0.9)]
+NU_DRAWS = [(3, 0), (3, 1), (1000, 0)]
+
+
+def _nu_engine(I, S, bias):
+    """m_batch = 65, seed 2; every kernel and every hidden bias of G' zero, its output bias `bias`: r'_j = sigmoid(bias_j) exactly, in
+    whatever order a product sums, so the planes do not depend on the GEMM planner"""
+    from ganmf_amd.CAAE import init_weights
+    eng = _engine(H.make_case(I), g_units=3, m_batch=ROWS, S=S, seed=2)
+    w = init_weights(0, ROWS, I, 4, 1, 3)
+    w["G_prime"] = [np.zeros_like(a) for a in w["G_prime"][:-1]] + [np.asarray(bias, dtype=np.float32)]
+    _set_state(eng, w, 1)
+    return eng
+
+
+def record_nu_planes(path=NU_GOLDEN):
+    """Run by hand on the device, never by the suite:
+    python -c "from tests.test_gpu_caae import record_nu_planes; record_nu_planes()" """
+    out = {"I": np.array([I for I, _ in NU_CASES]), "S": np.array([S for _, S in NU_CASES]), "draws": np.array(NU_DRAWS)}
+    for I, S in NU_CASES:
+        out["bias_%d" % I] = np.linspace(-6, 6, I).astype(np.float32)[np.random.RandomState(0).permutation(I)]
+        eng = _nu_engine(I, S, out["bias_%d" % I])
+        for epoch, step in NU_DRAWS:
+            out["users_%d_%d_%d" % (I, epoch, step)], out["nu_%d_%d_%d" % (I, epoch, step)], _, _ = eng.caae_draw_batch(epoch, 0, step)
+        eng.close()
+    np.savez_compressed(path, **out)
+
+
+def test_nu_planes_equal_the_recorded_bytes():
+    with np.load(NU_GOLDEN) as f:
+        rec = {k: f[k] for k in f.files}
+    assert list(zip(rec["I"].tolist(), rec["S"].tolist())) == NU_CASES and [tuple(d) for d in rec["draws"].tolist()] == NU_DRAWS
+    for I, S in NU_CASES:
+        assert len(set(rec["bias_%d" % I].tolist())) == I      # not constant: every column its own weight
+        eng = _nu_engine(I, S, rec["bias_%d" % I])
+        for epoch, step in NU_DRAWS:
+            us, nu, _, _ = eng.caae_draw_batch(epoch, 0, step)
+            assert us.tobytes() == rec["users_%d_%d_%d" % (I, epoch, step)].tobytes(), (I, S, epoch, step)
+            assert nu.tobytes() == rec["nu_%d_%d_%d" % (I, epoch, step)].tobytes(), (I, S, epoch, step)
+        eng.close()
 
 
 # ---- one D-step ----------------------------------------------------------------------------------------------------------------------
