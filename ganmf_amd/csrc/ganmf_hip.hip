@@ -56,9 +56,6 @@
 #include "caae_sample.hpp"
 #include "caae_rows.hpp"
 #include "gemm_multi.hpp"
-#ifdef GANMF_PERSIST_DIAG_BUILD
-#include "wgrad_stream.hpp"      // experiment (profiles/r04_wgrad_stream.md)
-#endif
 
 using namespace ganmf;
 

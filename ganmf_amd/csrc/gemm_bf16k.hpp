@@ -209,12 +209,6 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
     const f32x4k v[2] = {rg[s][0], rg[s][1]};
     const int tok = bf16k_wait_vm(nwait, v[0], v[1]);
     u32x4 pc[3];
-#ifdef GANMF_PERSIST_DIAG_BUILD
-    if ((p.diag & 32) && stage_a) {      // timing only: the A-staging waves store unsplit bits (what pre-split activation planes would save)
-      pc[0] = __builtin_bit_cast(u32x4, v[0]); pc[1] = __builtin_bit_cast(u32x4, v[1]); pc[2] = pc[0];
-      pc[0][0] += (unsigned)tok;
-    } else
-#endif
     it.template split<NPIECE, F16>(v, pc, tok, my_scale);
     if (it.km) {      // (wave-uniform) K-major image: the item's two k-rows are two 8-byte stores per piece
       typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -238,9 +232,6 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
   static_assert(PD == 4 || PD == 2, "the wait above names every prefetch register");      // (PD even: K-tile t of slot s lies in buffer s & 1)
   at_entry();
   __syncthreads();
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps && tid == 0) p.stamps[(size_t)blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();      // first K-tile split into LDS
-#endif
 
   auto step = [&](auto ss, int t) {      // K-tile t, whose registers were slot s = t % PD (consumed in iteration t - 1)
     constexpr int s = decltype(ss)::value, s1 = (s + 1) % PD;
@@ -251,14 +242,8 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
 #pragma unroll
     for (int q = 0; q < NPIECE; ++q) pb[q] = FB::frag_at(frag_b[b] + 4u * (unsigned)(q * FB::PLANE));
     // the registers of tile t are free: request tile t + PD into them (before the MFMAs: the longer the fetch has)
-#ifdef GANMF_PERSIST_DIAG_BUILD
-    if (p.diag & 16) { if (t + PD < nt) kleft -= BK; } else      // timing only: no operand fetches after the prologue
-#endif
     if (t + PD < nt) load_tile(ss);
     constexpr int ta[6] = {1, 0, 2, 1, 0, 0}, tb[6] = {1, 2, 0, 0, 1, 0};   // (mid,mid) (hi,lo) (lo,hi) (mid,hi) (hi,mid) (hi,hi): gemm_bf16s_body
-#ifdef GANMF_PERSIST_DIAG_BUILD
-    if (!(p.diag & 4))             // timing only: no MFMAs
-#endif
     {
       if constexpr (NPIECE == 3) {
 #pragma unroll
@@ -274,9 +259,6 @@ __device__ __forceinline__ void bf16k_mainloop(const GemmP& p, const int tm, con
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pa[0]), __builtin_bit_cast(bf16x8, pb[0]), acc, 0, 0, 0);
       }
     }
-#ifdef GANMF_PERSIST_DIAG_BUILD
-    if (!(p.diag & 2))             // timing only: no split / plane stores after the prologue
-#endif
     // under the MFMAs: split K-tile t + 1 into the other buffer.  Issued after its two loads: those of tiles t + 2 .. min(t + PD, nt - 1),
     // and the entry hook's EXTRA loads if tile t + 1 was requested in the prologue
     if (t + 1 < nt) store_tile(std::integral_constant<int, s1>{}, std::integral_constant<int, (s1 & 1)>{}, 2 * (min(t + PD, nt - 1) - (t + 1)) + (t + 1 < PD ? EXTRA : 0));
@@ -297,18 +279,9 @@ __device__ __forceinline__ void gemm_bf16k_body(const GemmP& p, const int bid, c
   int tm, tn, sp, bz;
   tile_coords(p, bid, nblk, tm, tn, sp, bz);
   f32x16 acc[1][1];
-#ifdef GANMF_PERSIST_DIAG_BUILD      // (GANMF_GEMM_STAMPS: only stand-alone launches hand out a stamp buffer, one slot per block of the grid)
-  if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memrealtime();
-#endif
   bf16k_mainloop<AKM, BKM, NPIECE, F16, 0>(p, tm, tn, sp, bz, smem, acc[0][0], [] {});
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-#endif
   static_assert(4 * 64 * 64 <= bf16k_smem_dw<NPIECE>(), "the workgroup's LDS must hold the four staged partial tiles");
   gemm_epilogue<64, 64, 1, 1, 4, AKM && BKM>(p, acc, smem, TileCoord{tm, tn, sp, bz, tm * 64, tn * 64});
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); if (threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memrealtime(); }
-#endif
 }
 
 // (one-piece forms: 64 KiB of LDS, so two workgroups fit a CU -- if the CU admits their 32 waves: floor(800 / (ceil(sgpr / 16) * 16 + 16)) waves per SIMD
@@ -322,23 +295,13 @@ __global__ __launch_bounds__(1024) void gemm_bf16k_mfma(const GemmP p) {
 // (Round 6: the one-piece forms with their scalar registers capped at 80 -- two 64-KiB workgroups per CU admitted, as for pair_kernel -- measured 0.5-1 % SLOWER
 // on configs[4]: their grids are one round anyway except the per-pass batched generator launch, and the spills cost the loop.  Not kept.)
 template <int NPIECE, bool F16>
-inline hipError_t gemm_bf16k_launch(hipStream_t st, const GemmP& p0, bool akm, bool bkm) {
-  GemmP p = p0;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (getenv("GANMF_BF16K_DIAG")) p.diag = atoi(getenv("GANMF_BF16K_DIAG"));      // 2 no splits, 4 no MFMAs, 16 no fetches (wrong results)
-#endif
+inline hipError_t gemm_bf16k_launch(hipStream_t st, const GemmP& p, bool akm, bool bkm) {
   const int grid = p.tiles_m * p.tiles_n * p.nsplit * p.nbatch;
   if (grid <= 0) return hipSuccess;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  const bool stamping = gemm_stamps_on() && gemm_stamps_begin(p, grid, st);
-  struct Report { const GemmP& p; int grid; hipStream_t st; bool akm, bkm, on; ~Report() { if (on) gemm_stamps_report(p, grid, st, akm, bkm, NPIECE == 3 ? "gemm_bf16k_mfma (split-bf16, 16 waves)" : "gemm_bf16k_mfma (one piece)"); } } report{p, grid, st, akm, bkm, stamping};
-#endif
-  {
-    if (!akm && !bkm) GANMF_LAUNCH((gemm_bf16k_mfma<false, false, NPIECE, F16>), dim3(grid), dim3(1024), 0, st, p);
-    else if (!akm && bkm) GANMF_LAUNCH((gemm_bf16k_mfma<false, true, NPIECE, F16>), dim3(grid), dim3(1024), 0, st, p);
-    else if (akm && bkm) GANMF_LAUNCH((gemm_bf16k_mfma<true, true, NPIECE, F16>), dim3(grid), dim3(1024), 0, st, p);
-    else return hipErrorInvalidValue;
-  }
+  if (!akm && !bkm) GANMF_LAUNCH((gemm_bf16k_mfma<false, false, NPIECE, F16>), dim3(grid), dim3(1024), 0, st, p);
+  else if (!akm && bkm) GANMF_LAUNCH((gemm_bf16k_mfma<false, true, NPIECE, F16>), dim3(grid), dim3(1024), 0, st, p);
+  else if (akm && bkm) GANMF_LAUNCH((gemm_bf16k_mfma<true, true, NPIECE, F16>), dim3(grid), dim3(1024), 0, st, p);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

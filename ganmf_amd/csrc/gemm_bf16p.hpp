@@ -72,8 +72,6 @@ struct Bf16pP {
   int ldc, M, N;          // rows >= M and columns >= ldc of a tile are not written
   int tiles_m, tiles_n, nt;      // nt = K-tiles per output tile (kp2 / 16)
   int xb_m, xb_n, wgs_per_xcd;
-  int late_mask;                 // experiment: which waves take the MFMA-first order (0: waves NW/2 ..)
-  unsigned long long* dbg;       // diagnostic builds (make DIAG=1, GANMF_BF16P_STAMPS=1): s_memtime sums per loop phase of workgroup 0
 };
 
 template <int WGM, int WGN>
@@ -172,7 +170,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16p_persist(const Bf16p
       for (int q = 0; q < 3; ++q) pb[set][b][q] = SF::frag(tile + OPER + q * PLANE, wc * WN + b * 32, c, li, lh);
   };
   // The MFMAs of one chunk (piece products in increasing weight, blocks innermost: (mid,mid) (hi,lo) (lo,hi) (mid,hi) (hi,mid) ->
-  // accl, (hi,hi) -> acc); side(i) is issued behind MFMA i and pinned there.  In-kernel stamps (make DIAG=1, GANMF_BF16P_STAMPS):
+  // accl, (hi,hi) -> acc); side(i) is issued behind MFMA i and pinned there.  In-kernel stamps (of a diagnostic build, since removed):
   // per K-step 555 + 837 cycles of LDS issue phases (fragment reads; plane writes + fragment reads) and 840 of barrier skew beside
   // 855 of MFMA -- the two waves of a SIMD move in lockstep behind the workgroup's one barrier, so nothing covers the LDS phases
   // (208 KiB per K-step at the 128 B/clk the CU's LDS delivers).  Dealing the fragment reads, plane writes and operand loads out
@@ -247,15 +245,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16p_persist(const Bf16p
   load_frags(0, smem, 0);
 
   int slot = 0, cur_l = j, kstep = 0;
-  const bool late = p.late_mask ? ((p.late_mask >> wave) & 1) != 0 : wave >= NW / 2;            // (uniform per wave: a scalar branch)
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-  const bool stamping = p.dbg != nullptr && blockIdx.x == 8 && (tid == 0 || tid == 64);
-#define BF16P_STAMP(i) if (stamping) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph[i] += t_ - tprev; tprev = t_; }
-  if (stamping) tprev = __builtin_amdgcn_s_memtime();
-#else
-#define BF16P_STAMP(i)
-#endif
+  const bool late = wave >= NW / 2;            // (uniform per wave: a scalar branch)
   for (int s = 0; s < total; ++s) {
     const unsigned* __restrict__ cur = smem + slot * BUF;
     const int nslot = slot ^ 1;
@@ -269,15 +259,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16p_persist(const Bf16p
     piece_read();
     if (!late) load_frags(1, cur, 1);
     __builtin_amdgcn_sched_barrier(0);
-    BF16P_STAMP(0)
     mfmas_with(std::integral_constant<int, 0>{}, [](auto) {});
     if (late) { load_frags(1, cur, 1); __builtin_amdgcn_sched_barrier(0); }
-    BF16P_STAMP(1)
     // chunk 1 (k 16..31): once its fragments are in registers nothing reads slot `slot` any more
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    BF16P_STAMP(2)
     __builtin_amdgcn_s_barrier();              // every wave is done with slot `slot`; K-tile s+1 (written one K-step ago) is visible
-    BF16P_STAMP(3)
     auto refill = [&]() {
       if (s + 2 < total) {                     // K-tile s+2 has been in flight for a whole K-step: into the freed slot ...
         write_tile(smem + slot * BUF);
@@ -287,10 +273,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16p_persist(const Bf16p
     };
     if (!late) refill();
     __builtin_amdgcn_sched_barrier(0);
-    BF16P_STAMP(4)
     mfmas_with(std::integral_constant<int, 1>{}, [](auto) {});
     if (late) { refill(); __builtin_amdgcn_sched_barrier(0); }
-    BF16P_STAMP(5)
     slot = nslot;
     if (++kstep == nt) {
       // ---- output tile complete: hi + corrections -> staging; its stores ride under the next tile's K-steps
@@ -317,9 +301,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16p_persist(const Bf16p
     }
   }
   flush_pieces();           // the last tile
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (stamping) { for (int i = 0; i < 6; ++i) p.dbg[(tid ? 8 : 0) + i] = ph[i]; p.dbg[(tid ? 8 : 0) + 6] = total; }
-#endif
 }
 
 inline bool bf16p_eligible(int M, int N, int K) {
@@ -339,36 +320,7 @@ inline hipError_t gemm_bf16p_launch(hipStream_t st, const unsigned* a_planes, in
   if (q.tiles_m * BF16P_TILE > a_rows_pad || q.tiles_n * BF16P_TILE > b_rows_pad || kp2 % (BF16P_BK / 2)) return hipErrorInvalidValue;
   const PersistPlan pp = persist_plan(M, N, 2 * kp2, BF16P_TILE, GEMM_CUS);
   q.xb_m = pp.xb_m; q.xb_n = pp.xb_n; q.wgs_per_xcd = pp.grid / 8;
-#ifdef GANMF_PERSIST_DIAG_BUILD      // experiment switches (make DIAG=1): the 4-wave form and the per-wave phase order were measured and not kept
-  static const int waves = [] { const char* e = getenv("GANMF_BF16P_WAVES"); return e ? atoi(e) : 8; }();
-  static const int late_mask = [] { const char* e = getenv("GANMF_BF16P_LATE"); return e ? (int)strtol(e, nullptr, 0) : 0; }();
-#else
-  constexpr int waves = 8, late_mask = 0;
-#endif
-  q.late_mask = late_mask;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  static unsigned long long* dbg = nullptr;
-  static int printed = 0;
-  if (getenv("GANMF_BF16P_STAMPS")) {
-    if (!dbg) { if (hipMalloc((void**)&dbg, 16 * 8) != hipSuccess) return hipErrorOutOfMemory; }
-    (void)hipMemset(dbg, 0, 16 * 8);
-    q.dbg = dbg;
-  }
-#endif
-  if (waves == 4) GANMF_LAUNCH((gemm_bf16p_persist<2, 2>), dim3(pp.grid), dim3(256), 0, st, q);
-  else GANMF_LAUNCH((gemm_bf16p_persist<2, 4>), dim3(pp.grid), dim3(512), 0, st, q);
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (q.dbg && printed++ < 3) {
-    (void)hipDeviceSynchronize();
-    unsigned long long hs[16];
-    (void)hipMemcpy(hs, dbg, sizeof hs, hipMemcpyDeviceToHost);
-    for (int w = 0; w < 2; ++w)
-      fprintf(stderr, "[bf16p stamps wave %d, %llu K-steps] per K-step: top->frags issued %llu | mfmas(0) %llu | lgkm wait %llu | barrier %llu | "
-              "write+load+frags %llu | mfmas(1) %llu   (s_memtime ticks)\n", w, hs[8 * w + 6],
-              hs[8 * w + 0] / hs[8 * w + 6], hs[8 * w + 1] / hs[8 * w + 6], hs[8 * w + 2] / hs[8 * w + 6], hs[8 * w + 3] / hs[8 * w + 6],
-              hs[8 * w + 4] / hs[8 * w + 6], hs[8 * w + 5] / hs[8 * w + 6]);
-  }
-#endif
+  GANMF_LAUNCH((gemm_bf16p_persist<2, 4>), dim3(pp.grid), dim3(512), 0, st, q);
   return hipGetLastError();
 }
 

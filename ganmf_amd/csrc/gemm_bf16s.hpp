@@ -81,7 +81,7 @@ struct SplitStage {
   // K-major: XOR on the chunk index of k-row k.  A transposing read covers k-rows k0 .. k0 + 3 (k0 a multiple of four) x 16 rows per
   // 16-lane group, two groups per 32-lane half: with 128-byte k-rows (R = 64) rows k0 + 2, k0 + 3 fall on the banks of k0, k0 + 1 and
   // move to the other half of their 128 bytes; with 256-byte k-rows (R = 128) all four share their banks and take four different
-  // 64-byte groups (the layout of round 4's wgrad_stream.hpp, SQ_LDS_BANK_CONFLICT 0)
+  // 64-byte groups (SQ_LDS_BANK_CONFLICT 0)
   __device__ static inline int swzk(int k) { return R == 64 ? ((k & 3) >> 1) << 2 : (k & 3) << 2; }
   static_assert(NW % 256 == 0 && NI >= 1, "tile too small for 256 threads");
   static_assert(BK == 32 || BK == 64, "BK must be 32 or 64");
@@ -155,7 +155,6 @@ struct SplitStage {
 
   // split / round and write the pieces to this operand's planes of the buffer `buf_bytes` behind the one init() was given
   // (piece q at + q * PLANE dwords: buffer and piece are constants of the instruction)
-  bool diag_nosplit = false;
   template <int NPIECE, bool F16 = false>
   __device__ inline void store(const float4 (&v)[NI][2], float scale = 1.f, unsigned buf_bytes = 0u) const {
 #pragma unroll
@@ -168,9 +167,6 @@ struct SplitStage {
         constexpr int q = decltype(qq)::value;
         if constexpr (NPIECE == 3) {
           unsigned h, m, l;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-          if (diag_nosplit) { h = cvt_pk_bf16(x0, x1); m = h; l = h; } else      // timing only: one conversion instead of the 3-way split
-#endif
           split_bf16x3(x0, x1, h, m, l);
           pc[0][q] = h; pc[1][q] = m; pc[2][q] = l;
         } else if constexpr (F16) {
@@ -288,14 +284,6 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
   const int kbeg = sp * p.k_per_split;
   const int kend = min(p.K, kbeg + p.k_per_split);
   const int nt = (kend - kbeg + BK - 1) / BK;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  // diagnostic build: 64 stamps per workgroup (thread 0): [0] entry, [1 + 5 it + j] K-tile `it` (it < 12): loads issued, MFMAs issued,
-  // past the barrier, next planes stored, past the second barrier; [62] K loop done, [63] exit
-#define GANMF_S_STAMP(i) do { if (p.stamps && tid == 0) p.stamps[(size_t)bid * 64 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define GANMF_S_STAMP(i) do { } while (0)
-#endif
-  GANMF_S_STAMP(0);
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -309,9 +297,6 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
   SB lb;
   la.init(p.A + (size_t)bz * p.a_batch_stride, p.lda, m0, p.M, kbeg, p.zero_page, tid, lds_a);
   lb.init(p.B, p.ldb, n0, p.N, kbeg, p.zero_page, tid, lds_b);
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  la.diag_nosplit = lb.diag_nosplit = (p.diag & 2) != 0;
-#endif
 
   float4 ra[SA::NI][2], rb[SB::NI][2];
   int kleft = kend - kbeg;
@@ -387,37 +372,23 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
   for (int it = 0; it < nt; ++it) {
     const bool more = it + 1 < nt;
     if (more) {                      // next K-tile into registers while this one is multiplied
-#ifdef GANMF_PERSIST_DIAG_BUILD
-      if (!(p.diag & 16))            // timing only: the first K-tile's registers are reused (no operand traffic after the prologue)
-#endif
-      {
       la.load(ra, kleft);
       lb.load(rb, kleft);
-      }
       kleft -= BK;
     }
-    if (it < 12) GANMF_S_STAMP(1 + 5 * it);
     load_frags(0, 0);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       if (c + 1 < NC) load_frags((c + 1) & 1, c + 1);
-#ifdef GANMF_PERSIST_DIAG_BUILD
-      if (p.diag & 4) { if (c == 0) mfmas(0); continue; }      // timing only: one MFMA step per K-tile instead of NC
-#endif
       mfmas(c & 1);
     }
-    if (it < 12) GANMF_S_STAMP(2 + 5 * it);
     __syncthreads();                 // every wave has read its fragments: the planes may be overwritten
-    if (it < 12) GANMF_S_STAMP(3 + 5 * it);
     if (more) {
       la.template store<NPIECE, F16>(ra, sa);
       lb.template store<NPIECE, F16>(rb, sb);
-      if (it < 12) GANMF_S_STAMP(4 + 5 * it);
       __syncthreads();
-      if (it < 12) GANMF_S_STAMP(5 + 5 * it);
     }
   }
-  GANMF_S_STAMP(62);
   if constexpr (NPIECE == 3) {
 #pragma unroll
     for (int a = 0; a < TM; ++a)
@@ -441,10 +412,6 @@ __device__ __forceinline__ void gemm_bf16s_body(const GemmP& p, const int bid, c
     rowsq_epilogue<BM, BN, TM, TN>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
   } else
   gemm_epilogue<BM, BN, TM, TN, 1, AKM && BKM>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
-#endif
-  GANMF_S_STAMP(63);
 }
 
 template <int BM, int BN, int BK, bool AKM, bool BKM, int NPIECE, bool F16 = false>
@@ -467,13 +434,8 @@ inline hipError_t gemm_bf16s_launch(hipStream_t st, const GemmP& p, bool akm, bo
 template <int NPIECE, bool F16>
 inline hipError_t gemm_bf16k_launch(hipStream_t st, const GemmP& p, bool akm, bool bkm);      // gemm_bf16k.hpp: the 16-wave form
 
-inline hipError_t gemm_planes_launch(hipStream_t st, const GemmP& p, bool bkm);      // gemm_planes.hpp: the same plan on pre-split operands
-
 inline hipError_t gemm_dispatch_staged(hipStream_t st, const GemmP& p, bool akm, bool bkm, const GemmPlan& pl) {
   if (pl.tile == 64 && pl.kg == 4) {
-#ifdef GANMF_PERSIST_DIAG_BUILD      // experiment (profiles/r04_wgrad_stream.md): measured level with the in-loop split, not used by the step
-    if (pl.mode == MFMA_BF16X3 && p.a_planes && p.b_planes && !akm && !p.a_gather) return gemm_planes_launch(st, p, bkm);
-#endif
     if (pl.mode == MFMA_BF16X3) return gemm_bf16k_launch<3, false>(st, p, akm, bkm);
     if (pl.mode == MFMA_F16) return gemm_bf16k_launch<1, true>(st, p, akm, bkm);
     if (pl.mode == MFMA_BF16) return gemm_bf16k_launch<1, false>(st, p, akm, bkm);

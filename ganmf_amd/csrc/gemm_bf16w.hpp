@@ -171,9 +171,6 @@ __device__ __forceinline__ void bf16w_mainloop(const GemmP& p, const int tm, con
   asm volatile("s_waitcnt vmcnt(0)" :: "v"(rg[0][0]), "v"(rg[0][1]), "v"(rg[0][2]), "v"(rg[1][0]), "v"(rg[1][1]), "v"(rg[1][2]));
   static_assert(PD == 2, "the wait above names every prefetch register");      // (PD even: K-tile t of slot s lies in buffer s & 1)
   __syncthreads();
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps && tid == 0) p.stamps[(size_t)blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();      // first K-tile split into LDS
-#endif
 
   // this lane's fragment of an A plane / of a B plane: LDS byte addresses in piece plane 0 of buffer 0
   unsigned fa[2], fb[2];
@@ -249,13 +246,7 @@ __device__ __forceinline__ void gemm_bf16w_body(const GemmP& p, const int bid, c
   int tm, tn, sp, bz;
   tile_coords(p, bid, nblk, tm, tn, sp, bz);
   f32x16 acc[1][1];
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memrealtime();
-#endif
   bf16w_mainloop<BKM, NPIECE, F16>(p, tm, tn, bz, smem, acc[0][0]);
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-#endif
   // the eight K groups' 64 x 32 images (the loop's last barrier is behind every fragment read)
   static_assert(BF16W_KG * BF16W_BM * BF16W_BN <= bf16w_smem_dw<NPIECE>(), "the workgroup's LDS must hold the staged partial tiles");
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -264,9 +255,6 @@ __device__ __forceinline__ void gemm_bf16w_body(const GemmP& p, const int bid, c
 #pragma unroll
   for (int r = 0; r < 16; ++r) ct[(wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * BF16W_BN + li] = acc[0][0][r];
   gemm_epilogue<BF16W_BM, BF16W_BN, 1, 1, 4, false, BF16W_KG, true>(p, acc, smem, TileCoord{tm, tn, sp, bz, tm * BF16W_BM, tn * BF16W_BN});
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); if (threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memrealtime(); }
-#endif
 }
 
 template <bool BKM, int NPIECE = 3, bool F16 = false>
@@ -279,7 +267,7 @@ __global__ __launch_bounds__(1024) void gemm_bf16w_mfma(const GemmP p) {
 inline bool gemm_bf16w_eligible(const GemmP& p, bool akm, bool bkm) {
   // leading dimensions: the kernel issues 16-byte loads at A + row * lda + 8 c and B + row * ldb + 4 c, and its K-tail logic reads up to the next
   // multiple of 64 past K inside a row (zero pads, as every matrix of the library has them, handle.inc LD_ALIGN) -- anything else stays on 64 x 64
-  return !akm && std::max(p.nbatch, 1) == 1 && !p.a_gather && !p.a_planes && !p.b_planes && !p.epi.csr_indptr && !p.epi.sp_rows &&
+  return !akm && std::max(p.nbatch, 1) == 1 && !p.a_gather && !p.epi.csr_indptr && !p.epi.sp_rows &&
          p.epi.kind != EPI_ADAM && p.K >= 1 && (p.lda % 64) == 0 && (p.ldb % 64) == 0;      // (the zero page is checked at dispatch: plans are drawn before it is filled in)
 }
 // out-of-range rows read zero_page + (tid & 255) * 8 + 0..7: the page must hold at least this many floats (the handle's: 2048 + 64, abi_core.inc)
@@ -316,10 +304,6 @@ inline hipError_t gemm_dispatch_bf16w(hipStream_t st, const GemmP& p0, bool bkm,
   GemmP p = p0;
   const int grid = p.tiles_m * p.tiles_n * std::max(p.nbatch, 1);
   if (grid <= 0) return hipSuccess;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  const bool stamping = gemm_stamps_on() && gemm_stamps_begin(p, grid, st);
-  struct Report { const GemmP& p; int grid; hipStream_t st; bool bkm, on; ~Report() { if (on) gemm_stamps_report(p, grid, st, false, bkm, "gemm_bf16w_mfma (64 x 32 tiles, 128-deep K-tiles)"); } } report{p, grid, st, bkm, stamping};
-#endif
   if (p.nsplit != 1 || p.tiles_m != (p.M + BF16W_BM - 1) / BF16W_BM || p.tiles_n != (p.N + BF16W_BN - 1) / BF16W_BN) return hipErrorInvalidValue;
   if (!p.zero_page || (p.lda % 64) != 0 || (p.ldb % 64) != 0) return hipErrorInvalidValue;      // (gemm_bf16w_eligible: never a silent out-of-bounds read)
   if (mode == MFMA_F16) {

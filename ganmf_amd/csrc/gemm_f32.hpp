@@ -233,10 +233,6 @@ struct EpiD {
   // sp_bias_row of the gradient.
   const float* sp_rows;    // S [sp_bias_row + sp_bias_parts, sp_ld]; nullptr: dense path
   int sp_ld, sp_bias_row, sp_bias_parts;
-  // the slab-sum kernel only (splitk_reduce_body): the finished values are ALSO filed as their three bf16 pieces, row-major with C's
-  // geometry, piece q at planes + q * plane_stride -- the operand form of wgrad_stream.hpp (nullptr: no planes)
-  unsigned short* planes;
-  long long plane_stride;
   double* gram_partials;   // EPI_GRAM_STATS: [tiles of the upper triangle][2] = (sum d, sum d^2) of each tile's in-range elements
                            // rowsq_epilogue (disc_rows.hpp): [M][tiles_n] = each row's sum of d^2 over a column tile's in-range elements
 };
@@ -342,11 +338,6 @@ struct GemmP {
   long long a_batch_stride, c_batch_stride;
   EpiD epi;
   int tiles_m, tiles_n;
-  // split-K finished inside the launch: the last workgroup to arrive at a tile (agent-scope
-  // arrival counter) sums the slabs in split order and applies the epilogue into Cf
-  unsigned* counters;      // [nbatch * tiles]; zero between launches (the reducer re-zeroes its word)
-  float* Cf;               // final output [M, ldc] per batch
-  long long cf_batch_stride;
   int c_pad_writable;           // columns N .. ldc-1 of C hold nothing the caller needs (gemm_persist.hpp writes zeros there)
   const int* a_gather;          // K-contiguous A only: row r of A is A + a_gather[r] * lda (embedding lookup folded into the
                                 // operand fetch, GANMF.py:82); nullptr: row r is A + r * lda
@@ -357,14 +348,6 @@ struct GemmP {
   // is walked in bands of xb_band tile rows, M-innermost, so an XCD's L2 keeps its A band and streams its B panels once per
   // band (tile_coords below; speed only, any order is correct).
   int xb_m, xb_n, xb_band;
-  int diag;                     // diagnostic builds only (make DIAG=1): timing experiments of the staged kernel's K loop
-  unsigned long long* stamps;   // diagnostic builds only: four s_memrealtime stamps per workgroup (entry, first K-tile landed, K loop done, exit)
-  // Operands split ahead of the launch (gemm_planes.hpp): the three bf16 pieces of A / B as row-major matrices of the fp32 operand's
-  // geometry (same lda / ldb, in elements), piece q at base + q * stride.  Both set (and A K-contiguous, no a_gather): the 16-wave
-  // split-bf16 plan runs its DMA form -- no split in the K loop, bit-identical results.  nullptr: the fp32 operand is split in the loop.
-  const unsigned short* a_planes;
-  const unsigned short* b_planes;
-  long long a_pstride, b_pstride;
   int n_fastest;                // list order with the tile COLUMN fastest (default: tile row fastest).  For the fused-Adam weight-gradient
                                 // products: workgroups that run at the same time then update neighbouring 256-byte segments of the same
                                 // parameter rows, i.e. whole DRAM pages of theta / m / v instead of one segment per 4-15 KiB row
@@ -604,17 +587,6 @@ __device__ inline void gemm_epilogue(const GemmP& p, const f32x16 (&acc)[TM][TN]
   const bool adam = ADAM_OK && !deferred && e.kind == EPI_ADAM;
   const float alpha = adam ? *e.adam_alpha : 0.f;
   float* __restrict__ theta_out = e.adam_theta_out ? e.adam_theta_out : e.adam_theta;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  const bool inlaunch = deferred && p.counters != nullptr;      // in-launch split-K reduction: an experiment (measured level / slower)
-#else
-  constexpr bool inlaunch = false;
-#endif
-  const bool publish = inlaunch;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const __amdgpu_buffer_rsrc_t slab_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)C, (short)0, 0x7fffffff, 0x00020000);
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (adam && (p.diag & 8)) return;      // timing only: the K phase without the Adam streams
-#endif
   if (adam && GANMF_ADAM_HOIST) {
     // The tile is a gradient: parameter and moments are updated in place, the gradient is never stored.  theta / m / v of up to
     // four row steps are fetched BEFORE the first of them is written back: written as one loop the stores of step j and the
@@ -713,20 +685,7 @@ __device__ inline void gemm_epilogue(const GemmP& p, const f32x16 (&acc)[TM][TN]
         }
         continue;
       }
-      if (publish) {
-        // slab tile handed to another workgroup inside this launch: WRITE-THROUGH (sc1) stores,
-        // so no release fence is needed (cdna guide §6 Guideline 16, R1)
-        const int boff = (int)(((size_t)row * p.ldc + col) * sizeof(float));
-        if (col + 3 < p.N) {
-          u32x4 bits;
-          bits[0] = __float_as_uint(o[0]); bits[1] = __float_as_uint(o[1]);
-          bits[2] = __float_as_uint(o[2]); bits[3] = __float_as_uint(o[3]);
-          __builtin_amdgcn_raw_buffer_store_b128(bits, slab_rsrc, boff, 0, 16 /* sc1 */);
-        } else {
-          for (int q = 0; q < 4 && col + q < p.N; ++q)
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[q]), slab_rsrc, boff + 4 * q, 0, 16);
-        }
-      } else if (col + 3 < p.N) {
+      if (col + 3 < p.N) {
         if (aux_pre) {      // (the auxiliary values arrived while the partial tiles met in LDS: epi_apply's three cases on them)
           const float a4[4] = {auxv.x, auxv.y, auxv.z, auxv.w};
 #pragma unroll
@@ -746,61 +705,11 @@ __device__ inline void gemm_epilogue(const GemmP& p, const f32x16 (&acc)[TM][TN]
       }
     }
   }
-  bool write_sq = !deferred && e.sq_partials;
-  if (inlaunch) {
-    // ---- in-launch split-K reduction (cdna guide §5 "In-launch split-K reduction", sc1 form):
-    // write-through slab stores -> every wave drains vmcnt -> workgroup barrier -> lane 0 relaxed
-    // agent fetch_add; the workgroup that draws nsplit-1 acquires (L1 invalidate) and reduces.
-    // Correct for any placement of a tile's slices over XCDs; the sum runs in split order.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(smem);
-    if (tid == 0) {
-      unsigned* cnt = p.counters + (size_t)bz * p.tiles_m * p.tiles_n + tn * p.tiles_m + tm;
-      const unsigned prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = prev == (unsigned)(p.nsplit - 1);
-      if (last) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-    const float* __restrict__ slab = p.C + (size_t)bz * p.c_batch_stride;
-    float* __restrict__ Cf = p.Cf + (size_t)bz * p.cf_batch_stride;
-#pragma unroll 2
-    for (int j = 0; j < BM / RPP; ++j) {
-      const int row = m0 + tr + j * RPP;
-      if (row < p.M && col < p.N && (!SPARE || tr + j * RPP < BM)) {
-        const size_t off = (size_t)row * p.ldc + col;
-        float4 s4 = *reinterpret_cast<const float4*>(slab + off);
-#pragma unroll 4
-        for (int k = 1; k < p.nsplit; ++k) {
-          const float4 q = *reinterpret_cast<const float4*>(slab + (size_t)k * p.c_split_stride + off);
-          s4.x += q.x; s4.y += q.y; s4.z += q.z; s4.w += q.w;
-        }
-        if (csr0) {
-          const float4 x = csr_quad(e, row, col);
-          s4.x -= x.x; s4.y -= x.y; s4.z -= x.z; s4.w -= x.w;
-        }
-        float o[4] = {s4.x, s4.y, s4.z, s4.w};
-        if (col + 3 < p.N) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[q] = epi_apply(e, o[q], row, col + q, p.ldc, aux, sq);
-          *reinterpret_cast<float4*>(Cf + off) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-          for (int q = 0; q < 4 && col + q < p.N; ++q) Cf[off + q] = epi_apply(e, o[q], row, col + q, p.ldc, aux, sq);
-        }
-      }
-    }
-    write_sq = e.sq_partials != nullptr;
-  }
+  const bool write_sq = !deferred && e.sq_partials;
   if (write_sq) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-    __syncthreads();   // every wave is done reading the staged tile / the flag
+    __syncthreads();   // every wave is done reading the staged tile
     if (lane == 0) smem[wave] = sq;
     __syncthreads();
     if (tid == 0) {
@@ -843,12 +752,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, con
   int tm, tn, sp = 0, bz = 0;
   if constexpr (GRAM) gram_tile_coords(p, bid, nblk, tm, tn);
   else tile_coords(p, bid, nblk, tm, tn, sp, bz);
-#ifdef GANMF_PERSIST_DIAG_BUILD
-#define GANMF_GEMM_STAMP(i) do { if (p.stamps && tid == 0) p.stamps[(size_t)bid * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define GANMF_GEMM_STAMP(i) do { } while (0)
-#endif
-  GANMF_GEMM_STAMP(0);
 
   const int m0 = tm * BM, n0 = tn * BN;
   const int kbeg = sp * p.k_per_split;
@@ -914,7 +817,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, con
   if (nt >= NS) GANMF_WAIT_VMCNT((NS - 1) * LOADS);   // tile 0 of this wave has landed ...
   else GANMF_WAIT_VMCNT(0);
   __builtin_amdgcn_s_barrier();                        // ... and of every other wave
-  GANMF_GEMM_STAMP(1);
   load_frags(0, smem, 0);
 
   // The refill of a freed ring slot is spread over the chunks of the FOLLOWING tile, LOADS / NC glds per
@@ -982,17 +884,12 @@ __device__ __forceinline__ void gemm_f32_body(const GemmP& p, const int bid, con
     if (touch) adam_touch_keep<BM, BN, NTHR>(touched);
   }
 
-  GANMF_GEMM_STAMP(2);
   static_assert(KG * BM * BN <= NS * BUF, "the ring must hold the KG staged partial tiles");
   if constexpr (GRAM) {
     static_assert(KG == 1 && !AKM && !BKM, "the symmetric product is an NT product on one K group");
     gram_epilogue<BM, BN, TM, TN>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
   } else
   gemm_epilogue<BM, BN, TM, TN, KG, AKM && BKM>(p, acc, smem, TileCoord{tm, tn, sp, bz, m0, n0});
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
-#endif
-  GANMF_GEMM_STAMP(3);
 }
 
 template <int BM, int BN, int BK, int NS, bool AKM, bool BKM, int KG = 1>
@@ -1001,32 +898,8 @@ __global__ __launch_bounds__(256 * KG) void gemm_f32_mfma(const GemmP p) {
   gemm_f32_body<BM, BN, BK, NS, AKM, BKM, KG>(p, (int)blockIdx.x, (int)gridDim.x, smem);
 }
 
-typedef unsigned short bf16raw;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-// ---- planes: x = hi + mid + lo exactly (split_bf16x3), three row-major bf16 matrices of the fp32 matrix's geometry -----------
-struct PlaneRef {
-  bf16raw* p;             // piece q at p + q * pstride
-  long long pstride;      // elements
-};
-
-__device__ inline void planes_store4(const PlaneRef& pl, size_t off, float x, float y, float z, float w) {
-  unsigned h0, m0, l0, h1, m1, l1;
-  split_bf16x3(x, y, h0, m0, l0);
-  split_bf16x3(z, w, h1, m1, l1);
-  *reinterpret_cast<uint2*>(pl.p + off) = make_uint2(h0, h1);
-  *reinterpret_cast<uint2*>(pl.p + pl.pstride + off) = make_uint2(m0, m1);
-  *reinterpret_cast<uint2*>(pl.p + 2 * pl.pstride + off) = make_uint2(l0, l1);
-}
-__device__ inline void planes_store1(const PlaneRef& pl, size_t off, float x) {
-  unsigned h, m, l;
-  split_bf16x3(x, 0.f, h, m, l);
-  pl.p[off] = (bf16raw)(h & 0xffffu);
-  pl.p[pl.pstride + off] = (bf16raw)(m & 0xffffu);
-  pl.p[2 * pl.pstride + off] = (bf16raw)(l & 0xffffu);
-}
-
 
 // Reduce split-K slabs and apply the deferred epilogue: out[m,n] = epi(sum_s part[s][m,n]).
 // grid = (gx, nbatch); columns >= N are never written (ones / pad columns keep their values).
@@ -1039,7 +912,6 @@ struct RedP {
   int M, N;
   long long batch_stride;   // of part and out
   EpiD epi;
-  int sc1 = 0;              // 1: the sums are handed to OTHER workgroups of the same launch (wgrad_seam_kernel): write-through (sc1) 16-byte stores
 };
 
 // Slab groups of the reduce: a small output behind a deep split (the reference's defaults on LastFM: 64 x 32 outputs, K = 17 632,
@@ -1070,25 +942,9 @@ __device__ __forceinline__ void splitk_reduce_body(const RedP& p, const int bx, 
     if (c + 3 < p.N) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = epi_apply(e, o[j], m, c + j, p.ld, aux, sq);
-      if (p.sc1) {      // (cdna guide section 6, Guideline 16 R1: payload stored write-through, the storing waves drain before the arrival is counted)
-        typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)out, (short)0, 0x7fffffff, 0x00020000);
-        u32x4s bits;
-        bits[0] = __float_as_uint(o[0]); bits[1] = __float_as_uint(o[1]); bits[2] = __float_as_uint(o[2]); bits[3] = __float_as_uint(o[3]);
-        __builtin_amdgcn_raw_buffer_store_b128(bits, rs, (int)(off * sizeof(float)), 0, 16 /* sc1 */);
-      } else
       *reinterpret_cast<float4*>(out + off) = make_float4(o[0], o[1], o[2], o[3]);
-      if (e.planes) planes_store4(PlaneRef{e.planes, e.plane_stride}, off, o[0], o[1], o[2], o[3]);
     } else {
-      for (int j = 0; j < 4 && c + j < p.N; ++j) {
-        const float r = epi_apply(e, o[j], m, c + j, p.ld, aux, sq);
-        if (p.sc1) {
-          const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)out, (short)0, 0x7fffffff, 0x00020000);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), rs, (int)((off + j) * sizeof(float)), 0, 16);
-        } else
-        out[off + j] = r;
-        if (e.planes) planes_store1(PlaneRef{e.planes, e.plane_stride}, off + j, r);
-      }
+      for (int j = 0; j < 4 && c + j < p.N; ++j) out[off + j] = epi_apply(e, o[j], m, c + j, p.ld, aux, sq);
     }
   };
   const int G = reduce_groups(total, p.nsplit);
@@ -1233,7 +1089,7 @@ inline GemmPlan gemm_plan(int M, int N, int K, int nbatch, bool wants_sq, const 
       const double per_wg = ts.fixed + k_tiles * cyc_tile;   // prologue + epilogue + K walk (K sweep, MI355X)
       const double rounds = std::ceil((double)wgs / GEMM_CUS);
       double us = rounds * per_wg / 2100.0;
-      if (ns > 1) us += 1.5 + (double)(ns + 1) * M * N * nbatch * 4.0 / 3.0e6;   // in-launch reduce tail + slab traffic at ~3 TB/s
+      if (ns > 1) us += 1.5 + (double)(ns + 1) * M * N * nbatch * 4.0 / 3.0e6;   // reduce tail + slab traffic at ~3 TB/s
       if (us < best.est_us) {
         best.est_us = us; best.tile = tile; best.nsplit = ns; best.kps = kps; best.tiles_m = tm; best.tiles_n = tn;
       }
@@ -1259,14 +1115,12 @@ inline GemmPlan gemm_plan(int M, int N, int K, int nbatch, bool wants_sq, const 
   // 6130 -> 6660 steps/s with two per SIMD, 6760-6830 with four); co-resident ring-2 workgroups already interleave
   best.kg = (best.tile == 64 && best.mode == MFMA_F32 && best.ring <= 3) ? (tune.kg ? tune.kg : (best.ring == 3 ? 4 : 1)) : 1;
   if (best.kg == 4 && best.ring != 3) best.kg = 2;
-#ifndef GANMF_PERSIST_DIAG_BUILD
   // the product build carries two fp32 64 x 64 points: one K group on a 2-slot ring (co-resident workgroups) and four K groups on a 3-slot
   // ring (a CU to itself); overrides that name another point (GANMF_TUNE kg = 2, ring = 4, ring = 3 with kg = 1) land on the nearest one
   if (best.tile == 64 && best.mode == MFMA_F32) {
     if (best.kg >= 2 && best.ring >= 3) { best.kg = 4; best.ring = 3; }
     else { best.kg = 1; best.ring = 2; }
   }
-#endif
   best.sq_count = wants_sq ? best.tiles_m * best.tiles_n : 0;   // (separate reduce kernel: GEMM_RED_GRID, set by gemm_run)
   return best;
 }
@@ -1292,14 +1146,12 @@ inline hipError_t gemm_dispatch(hipStream_t st, const GemmP& p, bool akm, bool b
 // Logical GEMM: C[bz] = epi(op(A[bz]) . op(B)).  `p` carries the operands, shapes, batch strides
 // and the epilogue; C/ldc/c_batch_stride describe the FINAL output.  slab: workspace for split-K.
 inline hipError_t gemm_run(hipStream_t st, GemmP p, bool akm, bool bkm, const GemmPlan& pl, float* slab,
-                           size_t slab_elems, unsigned* counters = nullptr, size_t n_counters = 0, int red_blocks = GEMM_RED_GRID) {
+                           size_t slab_elems, int red_blocks = GEMM_RED_GRID) {
   if (p.nbatch < 1) p.nbatch = 1;
   if (!p.zero_page || (p.lda % LD_ALIGN) || (p.ldb % LD_ALIGN)) return hipErrorInvalidValue;
   p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
   p.nsplit = pl.nsplit; p.k_per_split = pl.kps;
   p.epi.sq_stride = pl.sq_count;
-  p.counters = nullptr;
-  const bool in_launch = pl.nsplit > 1 && counters && (size_t)pl.tiles_m * pl.tiles_n * p.nbatch <= n_counters;
   RedP r{};
   if (pl.nsplit > 1) {
     if (gemm_slab_elems(pl, p.M, p.ldc, p.nbatch) > slab_elems) return hipErrorOutOfMemory;
@@ -1308,13 +1160,12 @@ inline hipError_t gemm_run(hipStream_t st, GemmP p, bool akm, bool bkm, const Ge
     // slab layout [split][batch][M, ldc]
     r.split_stride = (long long)p.nbatch * p.M * p.ldc;
     if (p.nbatch > 1 && p.c_batch_stride != (long long)p.M * p.ldc) return hipErrorInvalidValue;
-    if (in_launch) { p.counters = counters; p.Cf = p.C; p.cf_batch_stride = p.c_batch_stride; }
-    else if (p.epi.sq_partials) { p.epi.sq_stride = red_blocks; r.epi.sq_stride = red_blocks; }
+    if (p.epi.sq_partials) { p.epi.sq_stride = red_blocks; r.epi.sq_stride = red_blocks; }
     p.C = slab; p.c_split_stride = r.split_stride; p.c_batch_stride = (long long)p.M * p.ldc;
   }
   hipError_t e;
   e = gemm_dispatch(st, p, akm, bkm, pl);
-  if (e != hipSuccess || pl.nsplit == 1 || in_launch) return e;
+  if (e != hipSuccess || pl.nsplit == 1) return e;
   GANMF_LAUNCH(splitk_reduce_kernel, dim3(red_blocks, p.nbatch), dim3(256), 0, st, r);
   return hipGetLastError();
 }
@@ -1350,44 +1201,6 @@ inline void choose_tile_order(GemmP& p, const GemmPlan& pl) {
   p.xb_band = band;
 }
 
-#ifdef GANMF_PERSIST_DIAG_BUILD
-// (make DIAG=1, GANMF_GEMM_STAMPS=1) four s_memrealtime stamps per workgroup of a 16-wave GEMM launch -- entry, first K-tile landed, K loop done,
-// stores drained -- and their distribution over the launch's workgroups, for the first three launches of every shape: gemm_f32_mfma<.., 4>,
-// gemm_bf16k_mfma and gemm_bf16w_mfma (profiles/r03_gemm_stamps.md, profiles/r06_launch_fixed_part.md)
-inline bool gemm_stamps_on() { const char* v = getenv("GANMF_GEMM_STAMPS"); return v && atoi(v) != 0; }
-inline bool gemm_stamps_begin(GemmP& p, int grid, hipStream_t st) {
-  static unsigned long long* dbg = nullptr;
-  static int cap = 0;
-  if (grid > cap) { if (dbg) (void)hipFree(dbg); if (hipMalloc((void**)&dbg, (size_t)grid * 32) != hipSuccess) return false; cap = grid; }
-  (void)hipMemsetAsync(dbg, 0, (size_t)grid * 32, st);
-  p.stamps = dbg;
-  return true;
-}
-inline void gemm_stamps_report(const GemmP& p, int grid, hipStream_t st, bool akm, bool bkm, const char* kernel) {
-  (void)hipStreamSynchronize(st);
-  static std::vector<long long> seen;
-  const long long key = ((long long)p.M << 40) ^ ((long long)p.N << 20) ^ p.K ^ ((long long)akm << 62) ^ ((long long)bkm << 61) ^ ((long long)p.epi.kind << 56);
-  if (std::count(seen.begin(), seen.end(), key) >= 3) return;
-  seen.push_back(key);
-  std::vector<unsigned long long> hs((size_t)grid * 4);
-  (void)hipMemcpy(hs.data(), p.stamps, hs.size() * 8, hipMemcpyDeviceToHost);
-  unsigned long long t_min = ~0ull, t_max = 0;
-  for (int b = 0; b < grid; ++b) { t_min = std::min(t_min, hs[4 * b]); t_max = std::max(t_max, hs[4 * b + 3]); }
-  auto stat = [&](auto f, const char* name) {
-    std::vector<double> v(grid);
-    for (int b = 0; b < grid; ++b) v[b] = f(b) * 0.01;      // 100 MHz ticks -> us
-    std::sort(v.begin(), v.end());
-    fprintf(stderr, "  %-34s min %6.2f  median %6.2f  p90 %6.2f  max %6.2f us\n", name, v[0], v[grid / 2], v[(size_t)(grid * 0.9)], v[grid - 1]);
-  };
-  fprintf(stderr, "[gemm stamps] %s M=%d N=%d K=%d nsplit %d epi %d akm %d bkm %d: %d workgroups, first entry -> last exit %.2f us\n", kernel, p.M, p.N, p.K, p.nsplit,
-          (int)p.epi.kind, (int)akm, (int)bkm, grid, (t_max - t_min) * 0.01);
-  stat([&](int b) { return (double)(hs[4 * b] - t_min); }, "entry after the first entry");
-  stat([&](int b) { return (double)(hs[4 * b + 1] - hs[4 * b]); }, "entry -> first K-tile in LDS");
-  stat([&](int b) { return (double)(hs[4 * b + 2] - hs[4 * b + 1]); }, "K loop");
-  stat([&](int b) { return (double)(hs[4 * b + 3] - hs[4 * b + 2]); }, "epilogue + store drain");
-  stat([&](int b) { return (double)(t_max - hs[4 * b + 3]); }, "exit before the last exit");
-}
-#endif
 
 inline hipError_t gemm_dispatch_skinny(hipStream_t st, const GemmP& p0, bool bkm, int rt);
 inline hipError_t gemm_dispatch_skinny_n(hipStream_t st, const GemmP& p0, bool bkm);
@@ -1404,25 +1217,7 @@ inline hipError_t gemm_dispatch(hipStream_t st, const GemmP& p0, bool akm, bool 
   choose_tile_order(p, pl);
   if (pl.mode == MFMA_BF16 || pl.mode == MFMA_BF16X3 || pl.mode == MFMA_F16) return gemm_dispatch_staged(st, p, akm, bkm, pl);
   if (pl.tile == 128) return pl.ring >= 3 ? gemm_launch_t<128, 128, 32, 3>(st, p, akm, bkm) : gemm_launch_t<128, 128, 32, 2>(st, p, akm, bkm);
-#ifdef GANMF_PERSIST_DIAG_BUILD      // two K groups: between the planner's two points (one group on a shared CU, four on a CU of its own); sweeps only
-  if (pl.kg == 2) return pl.ring == 3 ? gemm_launch_t<64, 64, 64, 3, 2>(st, p, akm, bkm) : gemm_launch_t<64, 64, 64, 2, 2>(st, p, akm, bkm);
-#endif
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  // diagnostic build (make DIAG=1), GANMF_GEMM_STAMPS=1: where the time of a 16-wave launch goes -- dispatch ramp, first K-tile,
-  // K loop, epilogue + store drain -- from four 100 MHz stamps per workgroup, printed for the first launches of every shape
-  if (pl.kg == 4 && gemm_stamps_on()) {
-    const int grid = p.tiles_m * p.tiles_n * p.nsplit * p.nbatch;
-    if (!gemm_stamps_begin(p, grid, st)) return hipErrorOutOfMemory;
-    const hipError_t e = gemm_launch_t<64, 64, 64, 3, 4>(st, p, akm, bkm);
-    gemm_stamps_report(p, grid, st, akm, bkm, "fp32 ring, 16 waves");
-    return e;
-  }
-#endif
   if (pl.kg == 4) return gemm_launch_t<64, 64, 64, 3, 4>(st, p, akm, bkm);
-#ifdef GANMF_PERSIST_DIAG_BUILD      // a 4-slot ring and a 3-slot ring with one K group: measured level, sweeps only
-  if (pl.ring == 4) return gemm_launch_t<64, 64, 64, 4>(st, p, akm, bkm);   // 128 KiB ring: three K-tiles (96 KiB) in flight
-  if (pl.ring == 3) return gemm_launch_t<64, 64, 64, 3>(st, p, akm, bkm);
-#endif
   return gemm_launch_t<64, 64, 64, 2>(st, p, akm, bkm);
 }
 

@@ -329,10 +329,10 @@ __global__ __launch_bounds__(512) void gemm_skinny_n_kernel(const GemmP p) {
 }
 
 // Which products: N <= 32 behind a long K (an A of at least 16 MB) with a K-contiguous A, no batches, nothing that only the tiled kernels' operand fetch
-// does (row gather, planes); the epilogue is applied by the slab sum, so every kind the reduce kernel knows is fine.
+// does (row gather); the epilogue is applied by the slab sum, so every kind the reduce kernel knows is fine.
 inline bool gemm_skinny_n_eligible(const GemmP& p, bool akm) {
   return !akm && p.N >= 1 && p.N <= SKN_NMAX && p.K >= 2048 && (long long)p.M * p.K >= (4LL << 20) &&      // (below 16 MB of A the tiled kernels' fewer slabs win: 64 x 17 633 13.5 vs 10.7 us)
-         std::max(p.nbatch, 1) == 1 && p.a_gather == nullptr && p.a_planes == nullptr &&
+         std::max(p.nbatch, 1) == 1 && p.a_gather == nullptr &&
          p.epi.csr_indptr == nullptr && p.epi.sp_rows == nullptr && p.epi.sq_m_half == 0 && p.epi.kind != EPI_ADAM &&
          (p.lda % 4) == 0 && (p.ldb % 4) == 0;
 }

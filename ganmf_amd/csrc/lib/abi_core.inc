@@ -99,7 +99,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   h->tune.nsplit = std::max(0, tune_env_int("nsplit", 0));
   h->tune.mode = env_mfma_mode((cfg->flags & GANMF_FLAG_MFMA_F16) ? MFMA_F16 : (cfg->flags & GANMF_FLAG_MFMA_BF16) ? MFMA_BF16 : (cfg->flags & GANMF_FLAG_MFMA_F32) ? MFMA_F32 : MFMA_DEFAULT);
   h->tune.persist = tune_env_int("persist", -1);
-  if (h->tune.persist > 1) h->tune.persist = experiment_int("GANMF_PERSIST_WAVES", 1);      // (2 / 3: the one-workgroup-per-CU forms, measured slower)
+  if (h->tune.persist > 1) h->tune.persist = 1;
   h->tune.kg = tune_env_int("kg", 0);
   h->tune.tile_order = tune_env_int("tile_order", 0);
   h->pass_stage = tune_env_int("pass_stage", 1) != 0;
@@ -115,20 +115,11 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
 #endif
   h->bf16w = tune_env_int("bf16w", kAsmPrefetchDefault);
   h->wgrad_xb = std::max(0, tune_env_int("wgrad_xb", 16));
-  h->wd_lane = std::max(0, tune_env_int("wd_lane", 0));
   h->g_rows_staged = std::max(0, std::min(2, tune_env_int("g_rows_staged", 1)));
-  h->pair_kg = tune_env_int("pair_kg", 4) == 1 ? 1 : 4;
-  h->wgrad_seam = tune_env_int("wgrad_seam", 0);
   h->adam_touch = tune_env_int("adam_touch", 1) != 0 ? 1 : 0;
   h->gram_arith = tune_env_int("gram", 1) == 0 ? 0 : 1;
-  HIP_TRY(hipMalloc((void**)&h->seam_cnt, 2 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(h->seam_cnt, 0, 2 * sizeof(unsigned long long)));
   if (h->tune.kg != 0 && h->tune.kg != 1 && h->tune.kg != 2 && h->tune.kg != 4) h->tune.kg = 0;
   h->debug_plan = env_int("GANMF_DEBUG_PLAN", 0) != 0;
-  h->fused_mode = experiment_int("GANMF_FUSED_X3", 1) ? MFMA_BF16X3 : MFMA_F32;
-  h->fused_tile = experiment_int("GANMF_FUSED_TILE", 64) == 128 ? 128 : 64;
-  h->fused_bk = experiment_int("GANMF_FUSED_BK", 32);   // 24 KiB of LDS per workgroup: six co-resident workgroups hide the
-                                                 // theta / m / v round trip of each other (33.6 / 28.8 us against 37.2 / 32.0 at 64)
   HIP_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
   HIP_TRY(hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking));
   // lane events order two streams of THIS device only: no system-scope fence when they are recorded (the cache write-back /
@@ -144,7 +135,6 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   HIP_TRY(hipEventCreateWithFlags(&h->ev_mid, lane_flags));
   HIP_TRY(hipEventCreateWithFlags(&h->ev_we, lane_flags));
   HIP_TRY(hipEventCreateWithFlags(&h->ev_wd, lane_flags));
-  h->fuse_adam = experiment_int("GANMF_FUSE_ADAM", 1) != 0;
   // GANMF_MULTI: bits 0-4 the combined launches (gemm_multi.hpp), bit 5 (32) gUb's split-K slabs summed by adam_rows_kernel,
   // bit 6 (64) DisGANMF: the hidden layers' TF-Adam in the epilogue of their gradient GEMMs
   const int multi_env = env_int("GANMF_MULTI", 127);
@@ -152,19 +142,8 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   h->defer_gub = (multi_env & 32) != 0;
   h->dis_fuse_hidden = (multi_env & 64) != 0;
   h->x3kg = env_int("GANMF_X3KG", kAsmPrefetchDefault ? 7 : 0);      // +10 % steps/s at the ML-1M shape (profiles/r03_gemm_stamps.md)
-  h->dcoef_spread = experiment_int("GANMF_DCOEF_SPREAD", 1) != 0;
-  h->pair_ring = experiment_int("GANMF_PAIR_RING", 2) == 3 ? 3 : 2;
-  h->inkernel_reduce = experiment_int("GANMF_INKERNEL_REDUCE", 0) != 0;   // measured slower than the chip-wide reduce kernel (DESIGN.md §4)
-  h->inlaunch_max = experiment_int("GANMF_INLAUNCH_MAX", 4);
-  h->inlaunch_tags = experiment_int("GANMF_INLAUNCH_TAGS", 0);
   h->force_coll = env_int("GANMF_FORCE_COLLECTIVES", 0) != 0;
   h->score_presplit = env_int("GANMF_SCORE_PRESPLIT", 1) != 0;
-  h->fork_attach = experiment_int("GANMF_FORK_ATTACH", 1) != 0;
-  h->adam_nfast = experiment_int("GANMF_ADAM_NFAST", 3);
-  h->red_elems = experiment_int("GANMF_RED_ELEMS", 0);
-  h->merge_decode = experiment_int("GANMF_MERGE_DECODE", 1) != 0;
-  TRY(dalloc((float**)&h->counters, COUNTER_CAP));
-  TRY(dalloc((float**)&h->counters2, COUNTER_CAP));
   const int U = h->U, N = h->N, k = h->k, e = h->e, B = h->B;
   const bool dis = cfg->model == GANMF_MODEL_DISGANMF;
   const bool sim = cfg->model == GANMF_MODEL_ITEMSIM;      // a weighted URM and an item similarity matrix: no tensor at all
@@ -227,17 +206,6 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
       TRY(dalloc(&h->Dl, (size_t)2 * B * h->ldN));
       TRY(dalloc(&h->dE, (size_t)2 * B * h->lde));
       HIP_TRY(hipMemcpy2D(h->E + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
-#ifdef GANMF_PERSIST_DIAG_BUILD
-      h->wgrad_stream = env_int("GANMF_WGRAD_STREAM", 0) != 0;
-#endif
-      if (h->wgrad_stream) {      // three bf16 pieces per activation element (dalloc counts floats: two bf16 each)
-        h->ps_N = (long long)2 * B * h->ldN; h->ps_e = (long long)2 * B * h->lde;
-        TRY(dalloc((float**)&h->pl_XF, (size_t)(3 * h->ps_N + 1) / 2));
-        TRY(dalloc((float**)&h->pl_Dl, (size_t)(3 * h->ps_N + 1) / 2));
-        TRY(dalloc((float**)&h->pl_Es, (size_t)(3 * h->ps_e + 1) / 2));
-        TRY(dalloc((float**)&h->pl_dE, (size_t)(3 * h->ps_e + 1) / 2));
-        TRY(dalloc(&h->wgs_dump, 2048 + 64));
-      }
     } else {
       h->Al.resize(h->L, nullptr);
       for (int l = 0; l < h->L; ++l) {
@@ -276,7 +244,7 @@ int ganmf_destroy(ganmf_handle* h) {
     h->local->failed = true;            // a group does not outlive any of its members
     h->local->cv.notify_all();
   }
-  free_tensor(h->We, false); free_tensor(h->Wd, false); hipFree(h->zero_page); hipFree(h->Es); hipFree(h->seam_cnt);
+  free_tensor(h->We, false); free_tensor(h->Wd, false); hipFree(h->zero_page); hipFree(h->Es);
   for (auto& t : h->Wl) free_tensor(t, false);
   free_tensor(h->Wo, false);
   for (float* a : h->Al) hipFree(a);
@@ -319,8 +287,7 @@ int ganmf_destroy(ganmf_handle* h) {
   if (h->ev_wd) hipEventDestroy(h->ev_wd);
   if (h->st2) hipStreamDestroy(h->st2);
   if (h->st) hipStreamDestroy(h->st);
-  hipFree(h->slab2); hipFree(h->counters); hipFree(h->counters2);
-  hipFree(h->pl_XF); hipFree(h->pl_Dl); hipFree(h->pl_Es); hipFree(h->pl_dE); hipFree(h->wgs_dump); hipFree(h->wgs_table);
+  hipFree(h->slab2);
   delete h;
   return 0;
 }

@@ -111,12 +111,12 @@ static int gemm_f32_entry(int device, const float* A, const float* B, float* C, 
   tune.ring = tune_env_int("ring", 0);
   if (tune.ring != 0 && tune.ring != 2 && tune.ring != 3 && tune.ring != 4) tune.ring = 0;
   tune.persist = tune_env_int("persist", -1);
-  if (tune.persist > 1) tune.persist = experiment_int("GANMF_PERSIST_WAVES", 1);
+  if (tune.persist > 1) tune.persist = 1;
   tune.kg = tune_env_int("kg", 0);
   tune.tile_order = tune_env_int("tile_order", 0);
   if (tune.kg != 0 && tune.kg != 1 && tune.kg != 2 && tune.kg != 4) tune.kg = 0;
   GemmPlan pl = gemm_plan(g.M, g.N, g.K, 1, false, tune, adam_m != nullptr);
-  pl.persist = gemm_persist_eligible(g, a_kmajor, b_kmajor, pl, tune.persist) ? (tune.persist >= 2 ? tune.persist : 1) : 0;
+  pl.persist = gemm_persist_eligible(g, a_kmajor, b_kmajor, pl, tune.persist) ? 1 : 0;
   if (tune_env_int("skinny", 1) && tile == 0 && nsplit == 0) { if (!plan_skinny(pl, g, a_kmajor != 0) && tune_env_int("skinny_n", 1)) plan_skinny_n(pl, g, a_kmajor != 0); }
   if (env_int("GANMF_X3KG", 0) && pl.mode == MFMA_F32 && pl.tile == 64 && pl.kg == 4 && pl.ring == 3 && !pl.persist) pl.mode = MFMA_BF16X3;      // (tests: the 16-wave split-bf16 kernel)
   if (tune_env_int("bf16w", 0) && tile == 0 && nsplit == 0) plan_bf16w(pl, g, a_kmajor != 0, b_kmajor != 0, tune_env_int("bf16w", 0) >= 2);      // (tests: 2 = wherever eligible)
@@ -128,33 +128,16 @@ static int gemm_f32_entry(int device, const float* A, const float* B, float* C, 
   // (the row list is read by the 16-wave kernels' operand fetch only: any other plan would silently multiply the ungathered rows)
   if (a_gather && !(pl.tile == 64 && pl.kg == 4 && !pl.persist && !pl.skinny && !pl.skinny_n && !pl.wide32))
     return fail(-1, "ganmf_gemm_f32_ex: a row list needs a 16-wave 64 x 64 plan (tile = 64, GANMF_TUNE kg=4,ring=3)");
-  // GANMF_TUNE planes=1 (tests): both operands split into bf16 x 3 planes ahead of the launch -- the 16-wave plan then runs its DMA
-  // form (gemm_planes.hpp), which must reproduce the in-loop split bit for bit
-  bf16raw *plA = nullptr, *plB = nullptr;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  if (tune_env_int("planes", 0) && !a_kmajor) {
-    const size_t ea = (size_t)ar * lda, eb = (size_t)br * ldb;
-    TRY(dalloc((float**)&plA, (3 * ea + 1) / 2 + 64));
-    TRY(dalloc((float**)&plB, (3 * eb + 1) / 2 + 64));
-    GANMF_LAUNCH(planes_of_kernel, dim3(512), dim3(256), 0, (hipStream_t) nullptr, (const float*)dA, plA, (long long)ea, (long long)(ea / 4));
-    GANMF_LAUNCH(planes_of_kernel, dim3(512), dim3(256), 0, (hipStream_t) nullptr, (const float*)dB, plB, (long long)eb, (long long)(eb / 4));
-    HIP_TRY(hipDeviceSynchronize());
-    g.a_planes = plA; g.a_pstride = (long long)ea; g.b_planes = plB; g.b_pstride = (long long)eb;
-  }
-#endif
   const size_t slab_elems = gemm_slab_elems(pl, g.M, ldc, 1);
   if (slab_elems) TRY(dalloc(&slab, slab_elems));
-  unsigned* counters = nullptr;
-  const bool inl = experiment_int("GANMF_INKERNEL_REDUCE", 0) != 0;
-  if (inl) TRY(dalloc((float**)&counters, COUNTER_CAP));
   hipStream_t st = nullptr;
-  HIP_TRY(gemm_run(st, g, a_kmajor, b_kmajor, pl, slab, slab_elems, counters, COUNTER_CAP));
+  HIP_TRY(gemm_run(st, g, a_kmajor, b_kmajor, pl, slab, slab_elems));
   HIP_TRY(hipDeviceSynchronize());
   if (iters > 1 || ms) {
     hipEvent_t a, b;
     hipEventCreate(&a); hipEventCreate(&b);
     hipEventRecord(a, st);
-    for (int i = 0; i < std::max(iters, 1); ++i) gemm_run(st, g, a_kmajor, b_kmajor, pl, slab, slab_elems, counters, COUNTER_CAP);
+    for (int i = 0; i < std::max(iters, 1); ++i) gemm_run(st, g, a_kmajor, b_kmajor, pl, slab, slab_elems);
     hipEventRecord(b, st);
     hipEventSynchronize(b);
     float t = 0.f;
@@ -164,9 +147,8 @@ static int gemm_f32_entry(int device, const float* A, const float* B, float* C, 
   }
   HIP_TRY(hipMemcpy2D(C, (size_t)N * 4, dC, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
   if (adam_m) HIP_TRY(hipMemcpy2D(adam_m, (size_t)N * 4, dMom, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
-  hipFree(dA); hipFree(dB); hipFree(dC); hipFree(zp); hipFree(plA); hipFree(plB); hipFree(dIds); hipFree(dMom); hipFree(dAlpha);
+  hipFree(dA); hipFree(dB); hipFree(dC); hipFree(zp); hipFree(dIds); hipFree(dMom); hipFree(dAlpha);
   if (slab) hipFree(slab);
-  if (counters) hipFree(counters);
   return 0;
 }
 

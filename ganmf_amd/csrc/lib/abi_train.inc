@@ -21,10 +21,6 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
   prealloc_pass_buffers(h, local_batch_rows != nullptr);
-  static const bool time_it = experiment_int("GANMF_TIME_EPOCH", 0) != 0;
-  const auto tp0 = std::chrono::steady_clock::now();
-  auto since = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp0).count(); };
-  double t_prep = 0, t_first = 0, t_enq = 0, t_sync = 0;
   const int B = h->B;
   const int64_t local_steps = local_batch_rows ? n_steps_per_pass : (n + B - 1) / B;
   const int64_t per_pass = std::max(local_steps, n_steps_per_pass);
@@ -70,11 +66,9 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
     bglob[i] = global_batch_rows ? global_batch_rows[i] : nb;
     if (bglob[i] < nb || bglob[i] < 1) return fail(-1, "ganmf_train_epoch: global_batch_rows[%lld]=%d < local %d", (long long)i, bglob[i], nb);
   }
-  t_prep = since();
   HIP_TRY(hipMemcpyAsync(h->perm, stage_perm, (size_t)3 * h->U * sizeof(int), hipMemcpyHostToDevice, h->st));   // perm | pos | pos_step, contiguous on both sides
   const int64_t nd = (int64_t)d_steps * per_pass, ng = (int64_t)g_steps * per_pass;
   TRY(parts_begin(h, nd, ng));
-  t_first = since();
   // Discriminator passes.  U, V and the URM do not change while they run: the row expansion and the generated rows of every full
   // minibatch are formed once, in front of them (stage_pass); minibatch i then reads its [real ; generated] block and its own lr_t slot.
   const int64_t nfull = (local_batch_rows || d_steps == 0) ? 0 : n / B;
@@ -173,23 +167,11 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
   }
   if (dist && ng > 0) TRY(allreduce(h, h->g_parts, (size_t)ng * 4));
   const size_t ndp = (size_t)std::max<int64_t>(nd, 1) * 4, ngp = (size_t)std::max<int64_t>(ng, 1) * 4;
-  TRY(ensure_stage(h, 0, ndp + ngp + 4));
+  TRY(ensure_stage(h, 0, ndp + ngp));
   HIP_TRY(hipMemcpyAsync(h->stage_f, h->d_parts, (ndp + ngp) * sizeof(float), hipMemcpyDeviceToHost, h->st));   // d_parts | g_parts, contiguous
-  const size_t seam_at = (ndp + ngp + 1) & ~(size_t)1;      // (8-byte aligned slot behind the loss parts)
-  if (h->wgrad_seam) HIP_TRY(hipMemcpyAsync(h->stage_f + seam_at, h->seam_cnt + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
-  t_enq = since();
   HIP_TRY(hipStreamSynchronize(h->st));
-  t_sync = since();
-  if (h->wgrad_seam) {
-    unsigned long long gave_up = 0;
-    memcpy(&gave_up, h->stage_f + seam_at, sizeof gave_up);
-    if (gave_up) return fail(-2, "wgrad_seam_kernel: a weight-gradient block gave up waiting for the slab sum of dE (results of this call are invalid)");
-  }
   const std::vector<float> dp(h->stage_f, h->stage_f + ndp), gp(h->stage_f + ndp, h->stage_f + ndp + ngp);
   finish_losses(h, dp, gp, bglob, nd, ng, per_pass, d_losses, g_losses);
-  if (time_it)
-    fprintf(stderr, "[ganmf epoch] %lld D + %lld G steps: host prep %.0f us, first step enqueued at %.0f, all enqueued at %.0f, synced at %.0f, done at %.0f us\n",
-            (long long)nd, (long long)ng, t_prep, t_first, t_enq, t_sync, since());
   return 0;
 }
 

@@ -42,8 +42,8 @@ int env_int(const char* name, int dflt) {
 // GEMM-plan overrides the kernel tests use to reach a variant at a small shape: tile (64 | 128), ring (2 | 3 | 4), kg (1 | 2 | 4),
 // nsplit, tile_order (0 | 1 | 2), persist (-1 auto | 0 | 1), score_product (ganmf_bench_scores times the whole product),
 // gram (K loop of ganmf_score_similarity's Gram product: 1 exact three-way bf16 split, the default | 0 plain fp32 MFMA).
-// Everything else that ever selected a path -- the alternatives that were measured slower and that no planner picks -- is an
-// EXPERIMENT switch: read only by a library built with `make DIAG=1`, a constant in the product build.
+// The alternatives that were measured slower and that no planner picks are not in the library (profiles/one_path.md lists them with
+// the notes that hold their measurements).
 int tune_env_int(const char* key, int dflt) {
   const char* s = getenv("GANMF_TUNE");
   if (!s) return dflt;
@@ -55,15 +55,6 @@ int tune_env_int(const char* key, int dflt) {
   }
   return dflt;
 }
-int experiment_int(const char* name, int dflt) {
-#ifdef GANMF_PERSIST_DIAG_BUILD
-  return env_int(name, dflt);
-#else
-  (void)name;
-  return dflt;
-#endif
-}
-
 // K-loop arithmetic: GANMF_MFMA = f32 | bf16x3 | bf16 overrides the handle's choice (tests, A/B timing)
 constexpr int MFMA_DEFAULT = MFMA_AUTO;
 int env_mfma_mode(int dflt) {
@@ -78,7 +69,10 @@ int env_mfma_mode(int dflt) {
 }
 
 constexpr int ADAM_GRID = 1024;
-constexpr int COUNTER_CAP = 1 << 16;
+// The fused-Adam weight-gradient GEMMs under MFMA_AUTO: 64 x 64 tiles on the staged split-bf16 loop (the two [~1000 x ~3700 x 2B] TN
+// GEMMs run 10 % faster there than on the fp32 MFMA, +2.7 % steps/s) with 32-deep K-tiles -- 24 KiB of LDS per workgroup: six co-resident
+// workgroups hide the theta / m / v round trip of each other (33.6 / 28.8 us against 37.2 / 32.0 at 64)
+constexpr int FUSED_MODE = MFMA_BF16X3, FUSED_TILE = 64, FUSED_BK = 32;
 
 struct Tensor {
   int rows = 0, cols = 0, ld = 0;

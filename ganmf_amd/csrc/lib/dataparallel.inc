@@ -84,12 +84,12 @@ int lane_fork(ganmf_handle* h) {
 }
 // The same fork in two halves around the LAST main-lane launch the side lane has to wait for: fork_arm() before it (that launch
 // then carries ev_fork as its completion event: no marker packet on the main lane), fork_wait() after it.  While the library's
-// profiler is on (its scopes hand their own events to the launches) and with GANMF_FORK_ATTACH=0 the plain fork is used.
+// profiler is on (its scopes hand their own events to the launches) the plain fork is used.
 // The attached event marks the FIRST launch after fork_arm(): the fork is only taken as attached when exactly one kernel was
 // launched in between (a plan that adds a stand-alone reduce or an attached slab sum falls back to the marker-packet fork, which
 // covers everything enqueued so far -- never a silent wait for the wrong kernel).
 bool fork_arm(ganmf_handle* h) {
-  if (!h->fork_attach || h->prof) return false;
+  if (h->prof) return false;
   launch_stop_event() = h->ev_fork;
   h->fork_armed_at = launch_count();
   return true;

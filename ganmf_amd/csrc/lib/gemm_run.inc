@@ -1,14 +1,5 @@
 // gemm_run.inc -- one logical GEMM of the step: plan, launch, split-K reduce (run_gemm)
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
-// Blocks of a stand-alone slab sum over an [M, N] output: one float4 of output per thread (GANMF_RED_ELEMS per thread), at most
-// GEMM_RED_GRID.  The step's outputs are 32 k - 118 k float4: a fixed 512-block grid left up to 3/4 of its threads without work
-// and the launch paid their dispatch.  (Also the number of sum-of-squares partials such a launch writes.)
-int red_grid(const ganmf_handle* h, long long M, long long N, int nsplit) {
-  const long long total4 = M * ((N + 3) / 4);
-  // (a deep split behind a small output is summed by reduce_groups() threads per element: 256 / G elements per block and pass)
-  const long long per_block = 256LL / reduce_groups(total4, nsplit) * std::max(1, h->red_elems);
-  return (int)std::max<long long>(1, std::min<long long>(GEMM_RED_GRID, (total4 + per_block - 1) / per_block));
-}
 
 int ensure_slab(ganmf_handle* h, size_t elems, int lane) {
   float*& slab = lane ? h->slab2 : h->slab;
@@ -37,12 +28,7 @@ struct SlabRef { const float* p; int nsplit; long long split_stride; };
 GemmPlan plan_gemm(const ganmf_handle* h, int tag_gemm, const GemmP& g, bool akm, bool bkm, const GemmTune* force) {
   const GemmTune& tn = force ? *force : h->tune;
   GemmPlan pl = gemm_plan(g.M, g.N, g.K, std::max(g.nbatch, 1), g.epi.sq_partials != nullptr, tn, g.epi.kind == EPI_ADAM);
-  pl.persist = gemm_persist_eligible(g, akm, bkm, pl, tn.persist) ? (tn.persist >= 2 ? tn.persist : 1) : 0;
-  // gUb / gV where the pair launch would take them (pair_kernel<1, 2>, gen_update): the stand-alone products run the same 4-wave body on the
-  // 2-slot ring, so that paired and separate launches stay bit-identical (GANMF_TUNE pair_kg=4: the 16-wave forms of rounds 2-5)
-  if (!force && h->pair_kg == 1 && (tag_gemm == T_GEMM_GUB || tag_gemm == T_GEMM_GV) && !h->gub_x3 && h->tune.mode == MFMA_AUTO && plan_is_f32_64_kg(pl, 4)) {
-    pl.kg = 1; pl.ring = 2;
-  }
+  pl.persist = gemm_persist_eligible(g, akm, bkm, pl, tn.persist) ? 1 : 0;
   // a plan for the 16-wave fp32 ring kernel (one 64 x 64 tile per CU) runs the 16-wave split-bf16 loop instead: same grid, same split,
   // same epilogue, 6 / 16 of the MFMA cycles (gemm_bf16k.hpp)
   // (only under MFMA_AUTO: a handle created with GANMF_FLAG_MFMA_F32 / mfma="f32" runs the fp32 MFMA everywhere, as documented)
@@ -65,7 +51,7 @@ int run_gemm(ganmf_handle* h, int tag_gemm, int tag_red, GemmP g, bool akm, bool
              RedP* defer_red = nullptr, const RedP* attach = nullptr, const GemmPlan* plan = nullptr) {
   if (g.nbatch < 1) g.nbatch = 1;
   g.zero_page = h->zero_page;
-  if (g.epi.kind == EPI_ADAM && (h->adam_nfast & 2)) g.n_fastest = 1;      // (GANMF_ADAM_NFAST bit 1: every fused-Adam product, not only the paired launch)
+  if (g.epi.kind == EPI_ADAM) g.n_fastest = 1;      // (every fused-Adam product, not only the paired launch)
   hipStream_t st = lane ? h->st2 : h->st;
   GemmPlan pl = plan ? *plan : plan_gemm(h, tag_gemm, g, akm, bkm, force);
   if (defer) *defer = SlabRef{g.C, 1, 0};
@@ -76,17 +62,9 @@ int run_gemm(ganmf_handle* h, int tag_gemm, int tag_red, GemmP g, bool akm, bool
   if (pl.nsplit > 1) TRY(ensure_slab(h, gemm_slab_elems(pl, g.M, g.ldc, g.nbatch), slab_lane));
   float* slab = slab_lane ? h->slab2 : h->slab;
   const size_t slab_elems = slab_lane ? h->slab2_elems : h->slab_elems;
-  // in-launch split-K reduction (the last workgroup to arrive at a tile sums its slabs, gemm_f32.hpp): for every product
-  // (GANMF_INKERNEL_REDUCE=1) or for the classes of GANMF_INLAUNCH_TAGS (1 encode, 2 decode, 4 dF, 8 dE of the generator step)
-  const int tag_bit = tag_gemm == T_GEMM_ENC ? 1 : tag_gemm == T_GEMM_DEC ? 2 : tag_gemm == T_GEMM_DF ? 4 : tag_gemm == T_GEMM_DE ? 8 : 0;
-  unsigned* counters = (h->inkernel_reduce || (h->inlaunch_tags & tag_bit)) ? (lane ? h->counters2 : h->counters) : nullptr;
-  const size_t n_tiles = (size_t)pl.tiles_m * pl.tiles_n * g.nbatch;
-  // the last-arriving workgroup reads nsplit slab tiles alone (~60-120 GB/s per block): in-launch
-  // reduction only pays for shallow splits; deep splits keep the chip-wide reduce kernel
-  const bool in_launch = !deferred && pl.nsplit > 1 && pl.nsplit <= h->inlaunch_max && counters && n_tiles <= (size_t)COUNTER_CAP;
   const bool wants_sq = g.epi.sq_partials != nullptr;
-  const int nredg = h->red_elems > 0 ? red_grid(h, g.M, g.N, pl.nsplit) : GEMM_RED_GRID;      // blocks (and partials) of a stand-alone slab sum
-  const int sqc = !wants_sq ? 0 : (pl.nsplit > 1 && !in_launch ? nredg : pl.sq_count);
+  const int nredg = GEMM_RED_GRID;      // blocks (and partials) of a stand-alone slab sum
+  const int sqc = !wants_sq ? 0 : (pl.nsplit > 1 ? nredg : pl.sq_count);
   if (sq_count) *sq_count = sqc;
   if (h->debug_plan) {
     const long long key = ((long long)tag_gemm << 48) ^ ((long long)g.M << 32) ^ ((long long)g.N << 16) ^ g.K;
@@ -96,7 +74,7 @@ int run_gemm(ganmf_handle* h, int tag_gemm, int tag_red, GemmP g, bool akm, bool
               kTagName[tag_gemm], g.M, g.N, g.K, g.nbatch, pl.tile, pl.ring, pl.kg, pl.nsplit, pl.kps,
               pl.mode == MFMA_BF16X3 ? "bf16x3" : pl.mode == MFMA_BF16 ? "bf16" : pl.mode == MFMA_F16 ? "f16" : "f32",
               pl.tiles_m * pl.tiles_n * pl.nsplit * g.nbatch, pl.est_us,
-              pl.skinny ? " (skinny-K stream)" : pl.skinny_n ? " (skinny-N stream)" : pl.wide32 ? " (64 x 32 tiles, 128-deep K-tiles)" : pl.persist ? " (persistent tile walk)" : in_launch ? " (in-launch reduce)" : "");
+              pl.skinny ? " (skinny-K stream)" : pl.skinny_n ? " (skinny-N stream)" : pl.wide32 ? " (64 x 32 tiles, 128-deep K-tiles)" : pl.persist ? " (persistent tile walk)" : "");
     }
   }
   const double fl = g.nbatch * gemm_flops(g.M, g.N, g.K), by = gemm_bytes((double)g.nbatch * g.M, g.N, g.K) + extra_bytes;
@@ -118,11 +96,11 @@ int run_gemm(ganmf_handle* h, int tag_gemm, int tag_red, GemmP g, bool akm, bool
     {
       Scope s(h, tag_red, 0, 4.0 * (attach->nsplit + 1) * attach->M * attach->N, st);
       RedP r = *attach;
-      GANMF_LAUNCH(splitk_reduce_kernel, dim3(h->red_elems > 0 ? red_grid(h, r.M, r.N, r.nsplit) : GEMM_RED_GRID, 1), dim3(256), 0, st, r);
+      GANMF_LAUNCH(splitk_reduce_kernel, dim3(GEMM_RED_GRID, 1), dim3(256), 0, st, r);
       HIP_TRY(hipGetLastError());
     }
   }
-  if (defer_red && pl.nsplit > 1 && !in_launch && !deferred && g.nbatch == 1) {    // GEMM now, its reduce rides in a later launch
+  if (defer_red && pl.nsplit > 1 && !deferred && g.nbatch == 1) {    // GEMM now, its reduce rides in a later launch
     Scope s(h, tag_gemm, fl, by, st);
     GemmP q = g;
     fill_plan(q, pl);
@@ -139,21 +117,21 @@ int run_gemm(ganmf_handle* h, int tag_gemm, int tag_red, GemmP g, bool akm, bool
   if (deferred) {     // slabs only: the consumer sums them
     Scope s(h, tag_gemm, fl, by + 4.0 * pl.nsplit * g.M * g.N, st);
     GemmP q = g;
-    q.tiles_m = pl.tiles_m; q.tiles_n = pl.tiles_n; q.nsplit = pl.nsplit; q.k_per_split = pl.kps; q.counters = nullptr;
+    q.tiles_m = pl.tiles_m; q.tiles_n = pl.tiles_n; q.nsplit = pl.nsplit; q.k_per_split = pl.kps;
     q.C = slab; q.c_split_stride = (long long)g.M * g.ldc; q.c_batch_stride = (long long)g.M * g.ldc;
     HIP_TRY(gemm_dispatch(st, q, akm, bkm, pl));
     *defer = SlabRef{slab, pl.nsplit, (long long)g.M * g.ldc};
     return 0;
   }
-  if (!h->prof || pl.nsplit == 1 || in_launch) {
+  if (!h->prof || pl.nsplit == 1) {
     Scope s(h, tag_gemm, fl, by + (pl.nsplit > 1 ? 8.0 * pl.nsplit * g.nbatch * g.M * g.N : 0), st);
-    HIP_TRY(gemm_run(st, g, akm, bkm, pl, slab, slab_elems, in_launch ? counters : nullptr, COUNTER_CAP, nredg));
+    HIP_TRY(gemm_run(st, g, akm, bkm, pl, slab, slab_elems, nredg));
     return 0;
   }
   {  // profiled, separate reduce kernel: bracket the GEMM and the reduce separately
     Scope s(h, tag_gemm, fl, by, st);
     GemmP q = g;
-    q.tiles_m = pl.tiles_m; q.tiles_n = pl.tiles_n; q.nsplit = pl.nsplit; q.k_per_split = pl.kps; q.counters = nullptr;
+    q.tiles_m = pl.tiles_m; q.tiles_n = pl.tiles_n; q.nsplit = pl.nsplit; q.k_per_split = pl.kps;
     q.C = slab; q.c_split_stride = (long long)g.nbatch * g.M * g.ldc; q.c_batch_stride = (long long)g.M * g.ldc;
     hipError_t e;
     e = gemm_dispatch(st, q, akm, bkm, pl);

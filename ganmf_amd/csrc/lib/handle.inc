@@ -211,17 +211,12 @@ struct ganmf_handle {
   size_t slab_elems = 0;
   float* slab2 = nullptr;                // split-K workspace of the side lane
   size_t slab2_elems = 0;
-  unsigned *counters = nullptr, *counters2 = nullptr;   // split-K arrival counters (zero between launches)
   int x3kg = 7;                   // GANMF_X3KG bits: 16-wave split-bf16 loop for the plans of the 16-wave fp32 ring kernel (1 NT, 2 K-major B), 4: its one-piece form for bf16 / fp16 plans
-  bool inkernel_reduce = true;
-  int inlaunch_tags = 0;
-  int inlaunch_max = 4;
   float* rs = nullptr;
   float* scal = nullptr;
   float *sqp = nullptr;  // [2][max_tiles]
   int sqp_stride = 0;
   int reg_cap = 0;
-  int pair_ring = 2;      // LDS ring depth of the gUb + gV launch (GANMF_PAIR_RING)
   bool dis_colsum_pending = false;      // this discriminator step's column sums (ColSumP dis_colsum) ride in the layer-0 gradient GEMM's launch (dis_d_step)
   ColSumP dis_colsum{};
   bool dis_uid_done = false;    // this discriminator step's dis_dz_top_kernel formed the gradient of W_0_ext's float(uid) row and updated it (dis_d_step)
@@ -235,9 +230,7 @@ struct ganmf_handle {
                           // bit 4 (with bit 2): gWd + gWe in one launch behind a stand-alone slab sum of dE (GANMF_MULTI)
   float* V_alt = nullptr; // second parameter buffer of item_embeddings: the fused gV update is written there while gUb
                           // still reads the old V in the same launch; swapped with V.p after the launch
-  bool fuse_adam = true;  // single GPU: Adam runs in the epilogue of the weight-gradient GEMMs
   bool dis_fuse_hidden = true;   // DisGANMF: also for the hidden layers l > 0 (GANMF_DIS_FUSE_HIDDEN)
-  bool dcoef_spread = true;      // de_dcoef_kernel: d_coef shared out over the GEMM's workgroups instead of extra ones (GANMF_DCOEF_SPREAD)
   float* parts_all = nullptr;                    // ONE allocation: [d_parts | g_parts | d_arena | g_arena], packed per call (parts_begin)
   float *d_parts = nullptr, *g_parts = nullptr;  // [steps][4]
   float* colbuf = nullptr;                       // [cap] one column of d_parts on its way through an all-reduce
@@ -354,41 +347,18 @@ struct ganmf_handle {
   int d_alpha = S_ALPHA_D;             // scalar slot holding lr_t of the discriminator step in flight (alternates in data-parallel runs)
   int side_pending = 0;                // data-parallel: PEND_* bits of the replicated tensors the side lane still updates (dp_join
                                        // before their next use on the main lane)
-  bool merge_decode = true;            // GANMF_MERGE_DECODE: the discriminator step's two decode batches as one product (d_step)
-  int red_elems = 0;                   // GANMF_RED_ELEMS: float4 outputs per thread of the stand-alone slab sum (0: the fixed 512-block grid)
-  // (experiment, make DIAG=1) bf16 x 3 planes of the discriminator step's activations (wgrad_stream.hpp): [2B][ld] per piece, piece stride ps_N / ps_e elements
-  bf16raw *pl_XF = nullptr, *pl_Dl = nullptr, *pl_Es = nullptr, *pl_dE = nullptr;
-  long long ps_N = 0, ps_e = 0;
-  float* wgs_dump = nullptr;           // 8 KiB the stream kernel's out-of-matrix lanes store to
-  int* wgs_table = nullptr;            // its tile schedule (wgs_build_schedule), rebuilt when the tile grid changes
-  int wgs_key[5] = {0, 0, 0, 0, 0}, wgs_rounds = 0;
-  size_t wgs_table_cap = 0;
-  bool wgrad_stream = false;           // GANMF_WGRAD_STREAM=1 (make DIAG=1 only): the two fused-Adam weight-gradient products as the persistent role-split launch
-  int adam_nfast = 3;                  // GANMF_ADAM_NFAST: tile order of the fused-Adam weight-gradient launch (GemmP::n_fastest)
   int wgrad_xb = 16;                   // GANMF_TUNE wgrad_xb: gWd of the paired launch in XCD-blocked tile order, bands of this many tile rows (0: list order)
-  int wgrad_seam = 0;                  // GANMF_TUNE wgrad_seam: the slab sum of dE as the first block range of the fused weight-gradient launch (wgrad_seam_kernel)
   int adam_touch = 1;                  // GANMF_TUNE adam_touch: gV + Adam(V) touches its tile's theta / m / v lines in front of the K loop (GemmP::adam_touch, adam_touch_for)
-  unsigned long long* seam_cnt = nullptr;      // [2] device words: arrivals of the reduce blocks (monotonic over the handle's life), timeout flag
-  unsigned long long seam_target = 0;          // arrivals every launch so far has added up to
-  int pair_kg = 4;                     // GANMF_TUNE pair_kg: K groups of the gUb + gV pair launch (4: the 16-wave form, two per CU now that its SGPRs are capped at 80; 1: 4-wave workgroups)
   bool gub_x3 = false;                 // gV runs on the staged kernel (wide V: >= two tiles per CU), so gUb can never pair with it: its stand-alone plan may take
                                        // the 16-wave split-bf16 loop like every other NN product (gen_update; 46 -> 38 us at the configs[3] shard)
   int g_rows_staged = 1;               // GANMF_TUNE g_rows_staged: the generator passes read their real rows from the blocks staged in front of the call
                                        // (1: where the per-step row expansion is a launch of its own, 2: wherever possible, 0: never)
-  int wd_lane = 0;                     // GANMF_TUNE wd_lane: single GPU, fused Adam: gWd_ext + Adam(Wd) of a discriminator step on the side lane under the NEXT step's
-                                       // encode GEMM (which reads only We); joined before that step's decode GEMM.  1: forked behind gWe_ext, 2: behind the slab sum of dE,
-                                       // 0: both products in one launch on the main lane (wgrad_pair_kernel)
   long long fork_armed_at = 0;         // launch_count() when fork_arm() handed ev_fork to the next launch
-  bool fork_attach = true;             // GANMF_FORK_ATTACH: forks ride on the producing kernel's completion event (fork_arm / fork_wait)
   bool force_coll = false;             // GANMF_FORCE_COLLECTIVES=1: a one-rank communicator still issues its (in-place) reduce-scatter /
                                        // all-gather calls, so that the RCCL call sites execute on a one-GPU box (tests, bench)
   // tuning knobs (environment: GANMF_TILE, GANMF_RING, GANMF_NSPLIT; 0 = cost model decides)
   GemmTune tune;
   bool debug_plan = false;
-  int fused_bk = 0;               // K-tile depth of those GEMMs (GANMF_FUSED_BK)
-  int fused_tile = 64;            // their output tile (GANMF_FUSED_TILE: 64 | 128)
-  int fused_mode = MFMA_BF16X3;   // K-loop arithmetic of the fused-Adam weight-gradient GEMMs under MFMA_AUTO: the two
-                                  // [~1000 x ~3700 x 2B] TN GEMMs run 10 % faster on the split-bf16 loop (+2.7 % steps/s)
   std::vector<long long> seen_plans;
   // profiling
   bool prof = false;

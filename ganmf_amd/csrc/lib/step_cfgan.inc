@@ -46,8 +46,8 @@ int cfgan_wgrad(ganmf_handle* h, const float* A, int lda, const float* dz, int l
   g.epi.adam_alpha = h->scal + alpha_idx; g.epi.adam_reg = reg;
   GemmTune ft;
   ft.tile = 64; ft.ring = 2; ft.nsplit = 1;
-  ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : h->fused_mode;
-  ft.bk = h->fused_bk;
+  ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : FUSED_MODE;
+  ft.bk = FUSED_BK;
   return run_gemm(h, T_DIS_GW, T_RED_DIS_GW, g, true, true, nullptr, 24.0 * W.count(), 0, &ft);
 }
 

@@ -74,7 +74,7 @@ int dis_backprop_hidden(ganmf_handle* h, int row0, int nrows, bool param_grads, 
       // in this step; a hidden layer's W_l is read once more, by the backward product dz_{l-1} = dz_l . W_l^T, which therefore
       // goes FIRST (below).  Not with a communicator (the gradient must be reduced first).  In the low-precision modes the
       // float(uid) row of layer 0 is left out of the GEMM and updated by the fp32 kernel below.
-      const bool fuse = h->fuse_adam && !h->has_comm && (l == 0 || h->dis_fuse_hidden);
+      const bool fuse = !h->has_comm && (l == 0 || h->dis_fuse_hidden);
       h->dis_fused[l] = 0;
       if (l > 0 && fuse) TRY(backward(l));
       if (fuse) {
@@ -84,15 +84,15 @@ int dis_backprop_hidden(ganmf_handle* h, int row0, int nrows, bool param_grads, 
         g.epi.sq_partials = regD ? h->dis_slot + (size_t)(4 + l) * h->dis_cap : nullptr;
         GemmTune ft;
         ft.tile = 64; ft.ring = 2; ft.nsplit = 1;
-        ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : h->fused_mode;
-        ft.bk = h->fused_bk;
+        ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : FUSED_MODE;
+        ft.bk = FUSED_BK;
         int regn = ADAM_GRID;
         if (l == 0 && h->dis_colsum_pending) {
           // the column sums of the top of the backward pass (output-layer gradient + Adam, the fp32 float(uid) row) as extra blocks of this
           // launch: gemm_bf16s_colsum (the plan was checked by dis_d_step: the staged 64 x 64 kernel, unsplit)
           h->dis_colsum_pending = false;
           g.nbatch = 1; g.zero_page = h->zero_page;
-          if (h->adam_nfast & 2) g.n_fastest = 1;
+          g.n_fastest = 1;
           const GemmPlan pl = gemm_plan(g.M, g.N, g.K, 1, g.epi.sq_partials != nullptr, ft, true);
           fill_plan(g, pl);
           regn = pl.sq_count;
@@ -135,7 +135,7 @@ int dis_backprop_hidden(ganmf_handle* h, int row0, int nrows, bool param_grads, 
 int dis_d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* parts) {
   const int e = h->e;
   const float inv_b = 1.0f / (float)b_global;
-  const bool fuse_wo = h->fuse_adam && !h->has_comm && h->dis_fuse_hidden;      // output layer updated by the kernel that forms its gradient
+  const bool fuse_wo = !h->has_comm && h->dis_fuse_hidden;      // output layer updated by the kernel that forms its gradient
   h->dis_colsum_pending = false;
   h->dis_uid_done = false;
   if (nb > 0) {
@@ -148,8 +148,8 @@ int dis_d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float
     if (top_gw) {
       GemmTune ft;
       ft.tile = 64; ft.ring = 2; ft.nsplit = 1;
-      ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : h->fused_mode;
-      ft.bk = h->fused_bk;
+      ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : FUSED_MODE;
+      ft.bk = FUSED_BK;
       const GemmPlan pl = gemm_plan(low_precision(h) ? h->N + 1 : h->N + 2, e, 2 * nb, 1, h->cfg.d_reg != 0.f, ft, true);
       top_gw = pl.tile == 64 && pl.nsplit == 1 && !pl.persist &&
                ((pl.mode == MFMA_BF16X3 && pl.bk == 32) || pl.mode == MFMA_F16 || pl.mode == MFMA_BF16) &&
@@ -177,7 +177,7 @@ int dis_d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float
     // gets its gradient and its TF-Adam update in that launch (dis_uid_grad_kernel's launch leaves the step; GANMF_TUNE dis_uid_top=0 keeps it).
     // Its sum(theta^2) partials go behind the output layer's in the same arena segment (finish_dis_parts_kernel sums whole segments).
     const int ntop = dis_dz_top_blocks(e);
-    const bool uid_top = h->L == 1 && low_precision(h) && h->fuse_adam && !h->has_comm && 2 * ntop <= h->dis_cap && tune_env_int("dis_uid_top", 1);
+    const bool uid_top = h->L == 1 && low_precision(h) && !h->has_comm && 2 * ntop <= h->dis_cap && tune_env_int("dis_uid_top", 1);
     h->dis_uid_done = uid_top;
     {
       Scope s(h, T_DIS_HEAD, 0, 4.0 * 2 * nb * e * 3);

@@ -267,7 +267,7 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
   const int N = h->N, e = h->e;
   const bool dist = h->has_comm;
   // (a staged step has a slot of its own; else the slot alternates: the side lane may still read lr_t of the step before)
-  if ((dist || h->wd_lane) && !h->front_staged) h->d_alpha = h->d_alpha == S_ALPHA_D ? S_ALPHA_D_ALT : S_ALPHA_D;
+  if (dist && !h->front_staged) h->d_alpha = h->d_alpha == S_ALPHA_D ? S_ALPHA_D_ALT : S_ALPHA_D;
   const int aslot = h->d_alpha;
   const float inv_bn = 1.0f / ((float)b_global * (float)N);
   int sqn = 0;
@@ -291,7 +291,7 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
       // the decoder panel is fetched once instead of once per batch (rocprofv3 FETCH_SIZE: 42.5 MB per launch as two batches
       // against 23.3 MB algorithmic, profiles/r02_traffic.json).  Same tiles, same K order, partial sums filed per path as before.
       bool merged = false;
-      if (!h->sparse_d && nb % 64 == 0 && h->merge_decode) {
+      if (!h->sparse_d && nb % 64 == 0) {
         const GemmPlan p1 = gemm_plan(2 * nb, g.N, g.K, 1, true, h->tune), p2 = gemm_plan(g.M, g.N, g.K, 2, true, h->tune);
         if (p1.tile == 64 && p2.tile == 64 && p1.nsplit == 1 && p2.nsplit == 1 && p1.mode == p2.mode && p1.kg == p2.kg && p1.ring == p2.ring) {
           GemmP q = g;
@@ -339,14 +339,14 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
     pde.persist = 0;
     GemmPlan pskn = pde;
     const bool de_stream = h->skinny_n && plan_skinny_n(pskn, gde, false);      // (emb_dim <= 32: dE is a stream over Delta, gemm_skinny.hpp)
-    if (!de_stream && plan_is_f32_64_kg(pde, 4) && pde.nsplit > 1 && !(h->inkernel_reduce && pde.nsplit <= h->inlaunch_max)) {
+    if (!de_stream && plan_is_f32_64_kg(pde, 4) && pde.nsplit > 1) {
       TRY(ensure_slab(h, gemm_slab_elems(pde, gde.M, gde.ldc, 1), 0));
       Scope s(h, T_DE_DCOEF, gemm_flops(gde.M, gde.N, gde.K), gemm_bytes(gde.M, gde.N, gde.K) + 8.0 * 2 * nb * e);
       GemmP q = gde;
       fill_plan(q, pde);
       q.C = h->slab; q.c_split_stride = (long long)gde.M * gde.ldc; q.c_batch_stride = (long long)gde.M * gde.ldc;
       const int ng = pde.tiles_m * pde.tiles_n * pde.nsplit;
-      const int nd = h->dcoef_spread ? 0 : (int)std::max<long long>(1, std::min<long long>(32, (dc_total + 4095) / 4096));
+      const int nd = 0;      // (d_coef is shared out over the GEMM's workgroups, no extra ones)
       if (combined_x3(h)) GANMF_LAUNCH((de_dcoef_kernel<4, true>), dim3(ng + nd), dim3(1024), 0, h->st, q, dc, nd);
       else GANMF_LAUNCH(de_dcoef_kernel<4>, dim3(ng + nd), dim3(1024), 0, h->st, q, dc, nd);
       HIP_TRY(hipGetLastError());
@@ -361,11 +361,11 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
   }
   if (nb > 0) {
     const bool regD = h->cfg.d_reg != 0.f;
-    fused = h->fuse_adam && !dist;
+    fused = !dist;      // single GPU: Adam runs in the epilogue of the weight-gradient GEMMs
     GemmTune ft;
-    ft.tile = h->fused_tile; ft.ring = 2; ft.nsplit = 1;
-    ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : h->fused_mode;
-    ft.bk = h->fused_bk;
+    ft.tile = FUSED_TILE; ft.ring = 2; ft.nsplit = 1;
+    ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : FUSED_MODE;
+    ft.bk = FUSED_BK;
     // the data-parallel path runs the same two GEMMs with a plain store epilogue: same tile, split and arithmetic,
     // so that it stays bitwise equal to the fused single-GPU path (tests/test_gpu_parity.py, one-rank RCCL)
     const GemmTune* wg_tune = &ft;
@@ -422,117 +422,7 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
     // applies TF-Adam to theta/m/v in place (after dE, which reads the old decoder).
     // Data-parallel: the gradients are stored, reduce-scattered, and each rank updates its slice (dp_update).
     bool wpair = false;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-    if (!dist && fused && h->wgrad_stream && h->pl_XF && ft.mode == MFMA_BF16X3) {
-      // Both weight-gradient products with TF-Adam in place as ONE persistent launch fed from bf16 x 3 planes (wgrad_stream.hpp).
-      // In front of it, one launch: the slab sum of dE (+ its row scale; also files dE's planes) next to the planes of the three
-      // operands that are final by now.
-      const int K2 = 2 * nb;
-      PlaneJobs js{};
-      auto job = [&](const float* src, bf16raw* dst, long long ps, int rows, int ld) {
-        js.j[js.count++] = PlaneJob{src, PlaneRef{dst, ps}, (long long)rows * ld / 4};
-      };
-      if (h->sparse_d) job(h->XF + (size_t)nb * h->ldN, h->pl_XF + (size_t)nb * h->ldN, h->ps_N, nb, h->ldN);      // (the real rows stay CSR)
-      else job(h->XF, h->pl_XF, h->ps_N, K2, h->ldN);
-      job(h->Dl, h->pl_Dl, h->ps_N, K2, h->ldN);
-      job(h->Es, h->pl_Es, h->ps_e, K2, h->lde);
-      RedPlanes rp{};
-      RedP rr{};
-      int nred = 0;
-      long long n4 = 0;
-      if (dE_red.part) {
-        rr = dE_red; rp.pl = PlaneRef{h->pl_dE, h->ps_e}; rp.on = 1;
-        nred = h->red_elems > 0 ? red_grid(h, dE_red.M, dE_red.N, dE_red.nsplit) : GEMM_RED_GRID;
-        rr.epi.sq_stride = nred;
-      } else job(h->dE, h->pl_dE, h->ps_e, K2, h->lde);
-      for (int i = 0; i < js.count; ++i) n4 += js.j[i].n4;
-      const int nsp = (int)std::max<long long>(1, std::min<long long>(1024, (n4 + 1023) / 1024));
-      {
-        Scope s(h, T_RED_DE, 0, (dE_red.part ? 4.0 * (dE_red.nsplit + 1) * dE_red.M * dE_red.N : 0.0) + 10.0 * 4.0 * (double)n4);
-        GANMF_LAUNCH(presplit_red_kernel, dim3(nred + nsp), dim3(256), 0, h->st, rr, rp, nred, js);
-        HIP_TRY(hipGetLastError());
-      }
-      TRY(sparse_rows());
-      WgsP w{};
-      w.zero_page = h->zero_page;
-      w.dump = h->wgs_dump;
-      WgsProd& w0 = w.g[0];
-      w0.a_pl = h->pl_Es; w0.a_ps = h->ps_e; w0.lda = h->lde; w0.b_pl = h->pl_Dl; w0.b_ps = h->ps_N; w0.ldb = h->ldN; w0.ldc = h->ldN;
-      w0.M = e + 1; w0.N = N; w0.K = K2;
-      w0.epi.kind = EPI_ADAM; w0.epi.adam_theta = h->Wd.p; w0.epi.adam_m = h->Wd.m; w0.epi.adam_v = h->Wd.v;
-      w0.epi.adam_alpha = h->scal + aslot; w0.epi.adam_reg = h->cfg.d_reg; w0.epi.sq_partials = regD ? regWd : nullptr;
-      WgsProd& w1 = w.g[1];
-      const size_t r1 = h->sparse_d ? (size_t)nb : 0;      // sparse regime: the generated rows only, the real rows' share comes from the CSC matrix
-      w1.a_pl = h->pl_XF + r1 * h->ldN; w1.a_ps = h->ps_N; w1.lda = h->ldN; w1.b_pl = h->pl_dE + r1 * h->lde; w1.b_ps = h->ps_e; w1.ldb = h->lde;
-      w1.ldc = h->lde; w1.M = N + 1; w1.N = e; w1.K = h->sparse_d ? nb : K2;
-      w1.epi.kind = EPI_ADAM; w1.epi.adam_theta = h->We.p; w1.epi.adam_m = h->We.m; w1.epi.adam_v = h->We.v;
-      w1.epi.adam_alpha = h->scal + aslot; w1.epi.adam_reg = h->cfg.d_reg; w1.epi.sq_partials = regD ? regWe : nullptr;
-      if (h->sparse_d) { w1.epi.sp_rows = h->sp_rows; w1.epi.sp_ld = h->lde; w1.epi.sp_bias_row = N; w1.epi.sp_bias_parts = CSC_BIAS_PARTS; }
-      for (int i = 0; i < 2; ++i) { w.g[i].tiles_m = (w.g[i].M + WGS_BM - 1) / WGS_BM; w.g[i].tiles_n = (w.g[i].N + WGS_BN - 1) / WGS_BN; }
-      w.tiles0 = w0.tiles_m * w0.tiles_n;
-      w.tiles_total = w.tiles0 + w1.tiles_m * w1.tiles_n;
-      regn[1] = w.tiles0; regn[0] = w.tiles_total - w.tiles0;
-      const int grid = std::min(GEMM_CUS, round_up(w.tiles_total, 8));
-      {
-        const int key[5] = {w0.tiles_m, w0.tiles_n, w1.tiles_m, w1.tiles_n, grid};
-        if (memcmp(key, h->wgs_key, sizeof key) != 0) {
-          const int tms[2] = {w0.tiles_m, w1.tiles_m}, tns[2] = {w0.tiles_n, w1.tiles_n};
-          std::vector<int> tab;
-          const int rounds = wgs_build_schedule(tms, tns, 2, grid, tab);
-          HIP_TRY(hipStreamSynchronize(h->st));
-          if (tab.size() > h->wgs_table_cap) {
-            hipFree(h->wgs_table); h->wgs_table = nullptr;
-            HIP_TRY(hipMalloc((void**)&h->wgs_table, tab.size() * sizeof(int)));
-            h->wgs_table_cap = tab.size();
-          }
-          HIP_TRY(hipMemcpy(h->wgs_table, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-          memcpy(h->wgs_key, key, sizeof key);
-          h->wgs_rounds = rounds;
-        }
-        w.table = h->wgs_table; w.rounds = h->wgs_rounds;
-      }
-      w.diag = env_int("GANMF_WGS_DIAG", 0);
-      static unsigned long long* wst = nullptr;
-      static int wst_n = 0;
-      const bool stamping = env_int("GANMF_WGS_STAMPS", 0) != 0 && wst_n < 40;
-      if (stamping) {
-        if (!wst) HIP_TRY(hipMalloc((void**)&wst, (size_t)GEMM_CUS * 64 * 8));
-        HIP_TRY(hipMemsetAsync(wst, 0, (size_t)GEMM_CUS * 64 * 8, h->st));
-        w.stamps = wst;
-      }
-      {
-        Scope s(h, T_WPAIR, gemm_flops(w0.M, w0.N, w0.K) + gemm_flops(w1.M, w1.N, w1.K),
-                // operands once (as planes: 6 bytes per element) + the six Adam streams; the gradients themselves never reach HBM
-                6.0 * ((double)w0.K * (w0.M + w0.N) + (double)w1.K * (w1.M + w1.N)) + 24.0 * ((double)w0.M * w0.N + (double)w1.M * w1.N));
-        GANMF_LAUNCH(wgrad_stream_kernel, dim3(grid), dim3(1024), 0, h->st, w);
-        HIP_TRY(hipGetLastError());
-      }
-      if (stamping && ++wst_n == 40) {      // (a warm launch)
-        HIP_TRY(hipStreamSynchronize(h->st));
-        std::vector<unsigned long long> hs((size_t)grid * 64);
-        HIP_TRY(hipMemcpy(hs.data(), wst, hs.size() * 8, hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull;
-        for (int b = 0; b < grid; ++b) if (hs[(size_t)b * 64]) t0 = std::min(t0, hs[(size_t)b * 64]);
-        auto med = [&](int role, int i) {
-          std::vector<double> v;
-          for (int b = 0; b < grid; ++b) { const unsigned long long x = hs[((size_t)b * 2 + role) * 32 + i]; if (x) v.push_back((double)(x - t0) * 0.01); }
-          if (v.empty()) return -1.0;
-          std::sort(v.begin(), v.end());
-          return v[v.size() / 2];
-        };
-        fprintf(stderr, "[wgs stamps] diag %d, %d workgroups, medians in us after the first GEMM-wave entry\n", w.diag, grid);
-        for (int role = 0; role < 2; ++role) {
-          fprintf(stderr, "  %s: start %.2f |", role ? "Adam" : "GEMM", med(role, 0));
-          for (int r = 0; r < 6; ++r) fprintf(stderr, " r%d: work done %.2f, past Y %.2f, past X %.2f |", r, med(role, 1 + 3 * r), med(role, 2 + 3 * r), med(role, 3 + 3 * r));
-          fprintf(stderr, "\n   detail:");
-          for (int i = 19; i < 32; ++i) fprintf(stderr, " %.2f", med(role, i));
-          fprintf(stderr, "\n");
-        }
-      }
-      wpair = true;
-    }
-#endif
-    if (!wpair && !dist && fused && (h->multi & 16) && dE_red.part) {
+    if (fused && (h->multi & 16) && dE_red.part) {
       // both weight-gradient products in ONE launch (wgrad_pair_kernel); the slab sum of dE, which gWe reads, gets its own
       // launch in front
       GemmP g0{}, g1{};
@@ -549,115 +439,34 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
       sparse_gWe(g1);
       GemmPlan p0 = gemm_plan(g0.M, g0.N, g0.K, 1, regD, ft, true), p1 = gemm_plan(g1.M, g1.N, g1.K, 1, regD, ft, true);
       auto staged = [](const GemmPlan& pl) { return pl.mode == MFMA_BF16X3 && pl.tile == 64 && pl.bk == 32 && pl.nsplit == 1; };
-      const bool seam = h->wgrad_seam && !h->wd_lane && !h->sparse_d;      // the slab sum of dE rides in the launch below (wgrad_seam_kernel)
       if (staged(p0) && staged(p1)) {
-        if (!seam) {
+        {
           Scope s(h, T_RED_DE, 0, 4.0 * (dE_red.nsplit + 1) * dE_red.M * dE_red.N);
-          GANMF_LAUNCH(splitk_reduce_kernel, dim3(h->red_elems > 0 ? red_grid(h, dE_red.M, dE_red.N, dE_red.nsplit) : GEMM_RED_GRID, 1), dim3(256), 0, h->st, dE_red);
+          GANMF_LAUNCH(splitk_reduce_kernel, dim3(GEMM_RED_GRID, 1), dim3(256), 0, h->st, dE_red);
           HIP_TRY(hipGetLastError());
         }
         TRY(sparse_rows());
         fill_plan(g0, p0);
         fill_plan(g1, p1);
-        g0.n_fastest = g1.n_fastest = (h->adam_nfast & 1);
+        g0.n_fastest = g1.n_fastest = 1;
         // gWd's tiles in XCD-blocked order (tile_coords): an XCD takes a band of tile COLUMNS -- its eighth of Delta instead of all of it
         // through its L2 -- and walks it tile row fastest; gWe's column-fastest list already gives every XCD a band of X rows
         if (h->wgrad_xb > 0) { g0.n_fastest = 0; g0.xb_m = 1; g0.xb_n = 8; g0.xb_band = h->wgrad_xb; }
-#ifdef GANMF_PERSIST_DIAG_BUILD
-        // diagnostic build only (make DIAG=1; wrong results): GANMF_WGRAD_DIAG=1 empties the K range, i.e. the launch becomes its
-        // tile-wise Adam pass on a zero gradient -- how long do the twelve Adam streams take in THIS access pattern and occupancy
-        if (env_int("GANMF_WGRAD_DIAG", 0) & 1) { g0.K = 0; g1.K = 0; g0.k_per_split = g1.k_per_split = 0; }
-        g0.diag = g1.diag = env_int("GANMF_WGRAD_DIAG", 0);      // bit 1 (2): no 3-way split, bit 2 (4): 1/NC of the MFMAs, bit 3 (8): no Adam streams
-#endif
         regn[1] = p0.sq_count; regn[0] = p1.sq_count;
         const int n0 = p0.tiles_m * p0.tiles_n, n1 = p1.tiles_m * p1.tiles_n;
-#ifdef GANMF_PERSIST_DIAG_BUILD
-        // diagnostic build, GANMF_WGRAD_STAMPS=1: the launch's workgroup timelines (64 stamps each, gemm_bf16s.hpp), summarised for the
-        // first launches: lifetimes, and per K-tile the five phases averaged over the workgroups
-        static unsigned long long* wst = nullptr;
-        static int wst_printed = 0;
-        const bool stamping = env_int("GANMF_WGRAD_STAMPS", 0) != 0 && wst_printed < 3;
-        if (stamping) {
-          if (!wst) HIP_TRY(hipMalloc((void**)&wst, (size_t)(n0 + n1) * 64 * 8));
-          HIP_TRY(hipMemsetAsync(wst, 0, (size_t)(n0 + n1) * 64 * 8, h->st));
-          g0.stamps = wst; g1.stamps = wst + (size_t)n0 * 64;
-        }
-#endif
-        if (h->wd_lane) {
-          // Wd is first read by the NEXT step's decode GEMM, We already by its encode GEMM: gWe_ext + Adam(We) stays on the main lane, gWd_ext +
-          // Adam(Wd) -- HBM-bound, 24 KiB of LDS and four waves per workgroup -- goes to the side lane, where it runs beside the next step's
-          // MFMA-bound encode GEMM (96 KiB, sixteen waves: two of these workgroups fit next to one of its).  Same kernel, same tiles, same sums
-          // (an empty block range for the other product): bit-identical to the paired launch.  Joined in front of the next reader of Wd
-          // (dp_join(PEND_WD): the next decode GEMM, or the end of the call).
-          GemmP none{};
-          const bool armed = h->wd_lane == 1 && fork_arm(h);
-          if (h->wd_lane != 1) TRY(lane_fork(h));      // (behind the slab sum of dE: gWd_ext starts beside gWe_ext)
-          {
-            Scope s1(h, T_GEMM_GWE, gemm_flops(g1.M, g1.N, g1.K), 4.0 * (double)g1.K * (g1.M + g1.N) + 24.0 * (double)g1.M * g1.N);
-            GANMF_LAUNCH(wgrad_pair_kernel, dim3(n1), dim3(256), 0, h->st, none, g1);
-            HIP_TRY(hipGetLastError());
-          }
-          if (h->wd_lane == 1) TRY(fork_wait(h, armed));
-          {
-            Scope s0(h, T_GEMM_GWD, gemm_flops(g0.M, g0.N, g0.K), 4.0 * (double)g0.K * (g0.M + g0.N) + 24.0 * (double)g0.M * g0.N, h->st2);
-            GANMF_LAUNCH(wgrad_pair_kernel, dim3(n0), dim3(256), 0, h->st2, g0, none);
-            HIP_TRY(hipGetLastError());
-          }
-          TRY(dp_mark(h, PEND_WD));
-        } else if (seam) {
-          const int nred = h->red_elems > 0 ? red_grid(h, dE_red.M, dE_red.N, dE_red.nsplit) : GEMM_RED_GRID;
-          RedP rr = dE_red;
-          rr.sc1 = 1;
-          h->seam_target += (unsigned long long)nred;
-          Scope s(h, T_WPAIR, gemm_flops(g0.M, g0.N, g0.K) + gemm_flops(g1.M, g1.N, g1.K),
-                  4.0 * ((double)g0.K * (g0.M + g0.N) + (double)g1.K * (g1.M + g1.N)) + 24.0 * ((double)g0.M * g0.N + (double)g1.M * g1.N) +
-                      4.0 * (dE_red.nsplit + 1) * dE_red.M * dE_red.N);
-          GANMF_LAUNCH(wgrad_seam_kernel, dim3(nred + n0 + n1), dim3(256), 0, h->st, g0, g1, rr, nred, h->seam_cnt, h->seam_target);
-          HIP_TRY(hipGetLastError());
-        } else {
+        {
           Scope s(h, T_WPAIR, gemm_flops(g0.M, g0.N, g0.K) + gemm_flops(g1.M, g1.N, g1.K),
                   // operands once + the six Adam streams; the gradients themselves never reach HBM
                   4.0 * ((double)g0.K * (g0.M + g0.N) + (double)g1.K * (g1.M + g1.N)) + 24.0 * ((double)g0.M * g0.N + (double)g1.M * g1.N));
           GANMF_LAUNCH(wgrad_pair_kernel, dim3(n0 + n1), dim3(256), 0, h->st, g0, g1);
           HIP_TRY(hipGetLastError());
         }
-#ifdef GANMF_PERSIST_DIAG_BUILD
-        if (stamping && ++wst_printed >= 2) {      // (the second launch: warm)
-          HIP_TRY(hipStreamSynchronize(h->st));
-          const int nw = n0 + n1;
-          std::vector<unsigned long long> hs((size_t)nw * 64);
-          HIP_TRY(hipMemcpy(hs.data(), wst, hs.size() * 8, hipMemcpyDeviceToHost));
-          unsigned long long t0 = ~0ull, t1 = 0;
-          for (int b = 0; b < nw; ++b) { t0 = std::min(t0, hs[(size_t)b * 64]); t1 = std::max(t1, hs[(size_t)b * 64 + 63]); }
-          auto med = [&](auto f) { std::vector<double> v(nw); for (int b = 0; b < nw; ++b) v[b] = f(b) * 0.01; std::sort(v.begin(), v.end()); return std::make_pair(v[nw / 2], v[(size_t)(nw * 0.9)]); };
-          auto pr = [&](const char* name, std::pair<double, double> m) { fprintf(stderr, "  %-44s median %6.2f  p90 %6.2f us\n", name, m.first, m.second); };
-          fprintf(stderr, "[wgrad stamps] %d + %d workgroups, first entry -> last exit %.2f us\n", n0, n1, (t1 - t0) * 0.01);
-          pr("entry after the first entry", med([&](int b) { return (double)(hs[(size_t)b * 64] - t0); }));
-          pr("entry -> first K-tile's loads issued", med([&](int b) { return (double)(hs[(size_t)b * 64 + 1] - hs[(size_t)b * 64]); }));
-          pr("K loop (8 K-tiles)", med([&](int b) { return (double)(hs[(size_t)b * 64 + 62] - hs[(size_t)b * 64 + 1]); }));
-          pr("epilogue (Adam streams) + store drain", med([&](int b) { return (double)(hs[(size_t)b * 64 + 63] - hs[(size_t)b * 64 + 62]); }));
-          for (int it = 0; it < 8; ++it) {
-            const int o = 1 + 5 * it;
-            fprintf(stderr, "  K-tile %d:", it);
-            auto m1 = med([&](int b) { return (double)(hs[(size_t)b * 64 + o + 1] - hs[(size_t)b * 64 + o]); });
-            auto m2 = med([&](int b) { return (double)(hs[(size_t)b * 64 + o + 2] - hs[(size_t)b * 64 + o + 1]); });
-            fprintf(stderr, " fragments + MFMA issue %5.2f (p90 %5.2f)  barrier %5.2f (%5.2f)", m1.first, m1.second, m2.first, m2.second);
-            if (it < 7) {
-              auto m3 = med([&](int b) { return (double)(hs[(size_t)b * 64 + o + 3] - hs[(size_t)b * 64 + o + 2]); });
-              auto m4 = med([&](int b) { return (double)(hs[(size_t)b * 64 + o + 4] - hs[(size_t)b * 64 + o + 3]); });
-              auto m5 = med([&](int b) { return (double)(hs[(size_t)b * 64 + o + 5] - hs[(size_t)b * 64 + o + 4]); });
-              fprintf(stderr, "  wait for loads + split + plane stores %5.2f (%5.2f)  barrier %5.2f (%5.2f)  next loads issued %5.2f", m3.first, m3.second, m4.first, m4.second, m5.first);
-            }
-            fprintf(stderr, " us\n");
-          }
-        }
-#endif
         wpair = true;
       }
     }
     if (dist && dE_red.part) {     // (dcoef_done: the slabs of dE are waiting for their sum)
       Scope s(h, T_RED_DE, 0, 4.0 * (dE_red.nsplit + 1) * dE_red.M * dE_red.N);
-      GANMF_LAUNCH(splitk_reduce_kernel, dim3(h->red_elems > 0 ? red_grid(h, dE_red.M, dE_red.N, dE_red.nsplit) : GEMM_RED_GRID, 1), dim3(256), 0, h->st, dE_red);
+      GANMF_LAUNCH(splitk_reduce_kernel, dim3(GEMM_RED_GRID, 1), dim3(256), 0, h->st, dE_red);
       HIP_TRY(hipGetLastError());
       dE_red.part = nullptr;      // (summed: nothing to attach to the gWd launch)
     }
@@ -810,10 +619,10 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
   const int N = h->N, k = h->k;
   const bool reg = h->cfg.g_reg != 0.f;
   const bool dist = h->has_comm;
-  const bool fused = h->fuse_adam && !dist && nb > 0;
+  const bool fused = !dist && nb > 0;
   *regn_v = ADAM_GRID;
   const bool lazy = h->lazy_pass;      // the step's gUb (or its slabs) stays in the pass arena until the pass's flush (lazy_pass_end)
-  h->gub_x3 = (long long)((N + 63) / 64) * ((k + 63) / 64) >= 2 * GEMM_CUS && experiment_int("GANMF_GV_STAGED", 1) != 0;      // (= staged_gv below)
+  h->gub_x3 = (long long)((N + 63) / 64) * ((k + 63) / 64) >= 2 * GEMM_CUS;      // (= staged_gv below)
   SlabRef gub{h->gUb, 1, 0};
   auto gemm_gUb = [&]() -> int {  // gUb = dF . V     (reads the OLD V)
     GemmP g{};
@@ -852,13 +661,13 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
     }
     GemmTune ft;
     ft.tile = 64; ft.ring = 2; ft.nsplit = 1;
-    ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : h->fused_mode;
-    ft.bk = h->fused_bk;
+    ft.mode = h->tune.mode != MFMA_AUTO ? h->tune.mode : FUSED_MODE;
+    ft.bk = FUSED_BK;
     // the half-depth staged split-bf16 kernel of the other fused-Adam GEMMs once the output has at least two 64 x 64 tiles per
     // CU (C4 width, N = 50 000: 136 -> 102 us, +2 .. 5 % steps/s); below that the fp32 ring kernel (C2: 17.2 vs 18.1 us, and it
-    // pairs with gUb in one launch).  GANMF_GV_STAGED = 0 / 1 forces either.
+    // pairs with gUb in one launch).
     const long long gv_tiles = (long long)((N + 63) / 64) * ((k + 63) / 64);
-    const bool staged_gv = experiment_int("GANMF_GV_STAGED", gv_tiles >= 2 * GEMM_CUS ? 1 : 0) != 0;
+    const bool staged_gv = gv_tiles >= 2 * GEMM_CUS;
     TRY(run_gemm(h, T_GEMM_GV, T_RED_GV, g, true, true, regn_v, fused ? 24.0 * h->V.count() : 0, 0, staged_gv ? &ft : nullptr));
     if (!fused) *regn_v = ADAM_GRID;
     return 0;
@@ -909,7 +718,7 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
       g0.c_batch_stride = (long long)g0.M * g0.ldc;
       fill_plan(g0, p0);
       fill_plan(g1, p1);
-      if (fused && (h->adam_nfast & 2)) g1.n_fastest = 1;
+      if (fused) g1.n_fastest = 1;
       if (fused) g1.adam_touch = adam_touch_for(h, g1.M, g1.ldc);
       if (fused) *regn_v = p1.sq_count;
       const int n0 = p0.tiles_m * p0.tiles_n * p0.nsplit, n1 = p1.tiles_m * p1.tiles_n;
@@ -917,40 +726,10 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
         Scope s(h, T_PAIR, gemm_flops(g0.M, g0.N, g0.K) + gemm_flops(g1.M, g1.N, g1.K),
                 gemm_bytes(g0.M, g0.N, g0.K) + gemm_bytes(g1.M, g1.N, g1.K) + (fused ? 24.0 * h->V.count() : 0));
         pair_armed = dist && !v_inline && fork_arm(h);
-#ifdef GANMF_PERSIST_DIAG_BUILD
-        // diagnostic build, GANMF_PAIR_STAMPS=1: do the two halves of the pair launch run side by side?  entry / exit stamps of both block ranges
-        static unsigned long long* pst = nullptr;
-        static int pst_n = 0;
-        const bool pstamp = !pair_lp && env_int("GANMF_PAIR_STAMPS", 0) != 0 && pst_n < 30;
-        if (pstamp) {
-          if (!pst) HIP_TRY(hipMalloc((void**)&pst, (size_t)4096 * 32));
-          HIP_TRY(hipMemsetAsync(pst, 0, (size_t)(n0 + n1) * 32, h->st));
-          g0.stamps = pst; g1.stamps = pst + (size_t)n0 * 4;
-        }
-#endif
         if (pair_lp && p0.mode == MFMA_F16) GANMF_LAUNCH(pair_lp_kernel<true>, dim3(n0 + n1), dim3(1024), 0, h->st, g0, g1);
         else if (pair_lp) GANMF_LAUNCH(pair_lp_kernel<false>, dim3(n0 + n1), dim3(1024), 0, h->st, g0, g1);
-        // (round 6) 4-wave workgroups, several per CU: in-kernel stamps showed the two block ranges of the 16-wave form running one AFTER the other --
-        // two 1024-thread workgroups do not share a CU whatever their LDS -- i.e. two rounds of prologue + two K-tiles + epilogue (profiles/r06_pair_kernel.md)
-        else if (h->pair_kg == 1) GANMF_LAUNCH((pair_kernel<1, 2>), dim3(n0 + n1), dim3(256), 0, h->st, g0, g1);
-        else if (h->pair_ring == 2) GANMF_LAUNCH((pair_kernel<4, 2>), dim3(n0 + n1), dim3(1024), 0, h->st, g0, g1);
-        else GANMF_LAUNCH((pair_kernel<4, 3>), dim3(n0 + n1), dim3(1024), 0, h->st, g0, g1);
+        else GANMF_LAUNCH((pair_kernel<4, 2>), dim3(n0 + n1), dim3(1024), 0, h->st, g0, g1);
         HIP_TRY(hipGetLastError());
-#ifdef GANMF_PERSIST_DIAG_BUILD
-        if (pstamp && ++pst_n >= 28) {
-          HIP_TRY(hipStreamSynchronize(h->st));
-          std::vector<unsigned long long> hs((size_t)(n0 + n1) * 4);
-          HIP_TRY(hipMemcpy(hs.data(), pst, hs.size() * 8, hipMemcpyDeviceToHost));
-          unsigned long long t0 = ~0ull;
-          for (int b = 0; b < n0 + n1; ++b) if (hs[(size_t)b * 4]) t0 = std::min(t0, hs[(size_t)b * 4]);
-          auto med = [&](int lo, int hi, int i) { std::vector<double> v; for (int b = lo; b < hi; ++b) v.push_back((double)(hs[(size_t)b * 4 + i] - t0) * 0.01); std::sort(v.begin(), v.end()); return std::make_pair(v[v.size() / 2], v.back()); };
-          for (int half = 0; half < 2; ++half) {
-            const int lo = half ? n0 : 0, hi = half ? n0 + n1 : n0;
-            fprintf(stderr, "[pair stamps] %s (%d workgroups): entry median %.2f max %.2f | first K-tile %.2f | K loop done %.2f | exit median %.2f max %.2f us after the launch's first entry\n",
-                    half ? "gV + Adam" : "gUb", hi - lo, med(lo, hi, 0).first, med(lo, hi, 0).second, med(lo, hi, 1).first, med(lo, hi, 2).first, med(lo, hi, 3).first, med(lo, hi, 3).second);
-          }
-        }
-#endif
       }
       if (fused) std::swap(h->V.p, h->V_alt);
       paired = true;

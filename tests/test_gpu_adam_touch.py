@@ -68,10 +68,13 @@ def test_adam_touch_bit_identical(shape, monkeypatch):
 
 @pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[4]])
 def test_adam_touch_bit_identical_four_wave_pair(shape, monkeypatch):
-    """GANMF_TUNE pair_kg=1: gUb + gV on 256-thread workgroups (pair_kernel<1, 2>), where a thread touches up to two lines."""
-    ref = _run(monkeypatch, 0, *shape, tune="pair_kg=1,")
-    got = _run(monkeypatch, 1, *shape, tune="pair_kg=1,")
-    _same(got, ref, "pair_kg=1, adam_touch=1 vs 0 at %r" % (shape,))
+    """The touch on 256-thread workgroups, where a thread touches up to two lines: gUb and gV as separate launches (GANMF_MULTI bit 1 clear)
+    on a one-K-group plan (GANMF_TUNE kg=1), so gV + Adam(V) runs gemm_f32_mfma<64, 64, 64, 2, true, true, 1> (GANMF_DEBUG_PLAN=1 prints
+    "kg 1" for gemm_gV at both shapes)."""
+    monkeypatch.setenv("GANMF_MULTI", str(127 & ~2))
+    ref = _run(monkeypatch, 0, *shape, tune="kg=1,")
+    got = _run(monkeypatch, 1, *shape, tune="kg=1,")
+    _same(got, ref, "separate gV launch, kg=1, adam_touch=1 vs 0 at %r" % (shape,))
 
 
 def test_adam_touch_inert_under_forced_collectives(monkeypatch):

@@ -76,7 +76,7 @@ def test_gemm_persistent_tile_walk(shape, monkeypatch):
     rng = np.random.RandomState(M + 3 * N + 7 * K)
     A, B, ref, bound = _mk(rng, M, N, K, False, False)
     monkeypatch.setenv("GANMF_MFMA", "f32")
-    monkeypatch.setenv("GANMF_TUNE", "persist=1")      # two 4-wave workgroups per CU (the one-workgroup forms are experiment builds)
+    monkeypatch.setenv("GANMF_TUNE", "persist=1")      # two 4-wave workgroups per CU (the one-workgroup-per-CU forms were measured slower and removed)
     out, _ = gemm_f32(A, B, False, False, tile=128)
     err = np.abs(out - ref)
     assert np.all(err <= 4e-7 * bound * np.sqrt(K) + 1e-30), float((err / (bound + 1e-30)).max())
