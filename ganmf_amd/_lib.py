@@ -15,6 +15,10 @@ ITEMKNN_PRODUCT, ITEMKNN_TANIMOTO, ITEMKNN_DICE, ITEMKNN_TVERSKY, ITEMKNN_SHRINK
 # include/ganmf_hip.h GANMF_SLIM_*: the optimiser of ganmf_slim_bpr_init and the route of ganmf_slim_bpr_run
 SLIM_SGD_MODES = {"sgd": 0, "adagrad": 1, "rmsprop": 2, "adam": 3}
 SLIM_AUTO, SLIM_SEQUENTIAL, SLIM_LEVELLED = 0, 1, 2
+# include/ganmf_hip.h GANMF_MF_SGD_*: the algorithm of ganmf_mf_sgd_init, the route of ganmf_mf_sgd_run and the two limits
+MF_SGD_ALGORITHMS = {"MF_BPR": 0, "FUNK_SVD": 1}
+MF_SGD_AUTO, MF_SGD_SEQUENTIAL, MF_SGD_LEVELLED = 0, 1, 2
+MF_SGD_MAX_FACTORS, MF_SGD_MAX_BATCH = 1024, 1 << 20
 ALS_MAX_FACTORS = 256              # include/ganmf_hip.h GANMF_ALS_MAX_FACTORS
 SVD_MAX_RANDOM = 280               # include/ganmf_hip.h GANMF_SVD_MAX_RANDOM
 FLAG_MFMA_F32, FLAG_MFMA_BF16, FLAG_MFMA_F16 = 1, 2, 4     # include/ganmf_hip.h GANMF_FLAG_*
@@ -43,7 +47,7 @@ SYMBOLS = [
     "ganmf_create", "ganmf_destroy", "ganmf_comm_unique_id", "ganmf_comm_init", "ganmf_comm_init_local", "ganmf_comm_abort", "ganmf_comm_info", "ganmf_set_urm_csr",
     "ganmf_set_tensor", "ganmf_get_tensor", "ganmf_tensor_shape", "ganmf_get_adam_powers",
     "ganmf_set_adam_powers", "ganmf_train_epoch", "ganmf_train_epoch_ragged", "ganmf_train_step", "ganmf_scores",
-    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_p3_fit", "ganmf_slim_bpr_init", "ganmf_slim_bpr_draw", "ganmf_slim_bpr_run", "ganmf_slim_bpr_epochs", "ganmf_slim_bpr_finish", "ganmf_slim_bpr_get_state", "ganmf_cfgan_init", "ganmf_cfgan_draw_masks", "ganmf_cfgan_set_masks", "ganmf_cfgan_get_masks", "ganmf_cfgan_step", "ganmf_cfgan_epoch", "ganmf_caae_init", "ganmf_caae_cdf", "ganmf_caae_draw_perm", "ganmf_caae_draw_negatives", "ganmf_caae_draw_batch", "ganmf_caae_get_draws", "ganmf_caae_d_step", "ganmf_caae_g_step", "ganmf_caae_epoch", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
+    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_p3_fit", "ganmf_slim_bpr_init", "ganmf_slim_bpr_draw", "ganmf_slim_bpr_run", "ganmf_slim_bpr_epochs", "ganmf_slim_bpr_finish", "ganmf_slim_bpr_get_state", "ganmf_mf_sgd_init", "ganmf_mf_sgd_draw", "ganmf_mf_sgd_run", "ganmf_mf_sgd_epochs", "ganmf_mf_sgd_publish", "ganmf_mf_sgd_get_state", "ganmf_mf_sgd_set_state", "ganmf_cfgan_init", "ganmf_cfgan_draw_masks", "ganmf_cfgan_set_masks", "ganmf_cfgan_get_masks", "ganmf_cfgan_step", "ganmf_cfgan_epoch", "ganmf_caae_init", "ganmf_caae_cdf", "ganmf_caae_draw_perm", "ganmf_caae_draw_negatives", "ganmf_caae_draw_batch", "ganmf_caae_get_draws", "ganmf_caae_d_step", "ganmf_caae_g_step", "ganmf_caae_epoch", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
     "ganmf_bench_scores", "ganmf_gemm_f32", "ganmf_gemm_f32_ex", "ganmf_crc32c", "ganmf_device_count", "ganmf_abi_version", "ganmf_last_error",
 ]
 
@@ -148,6 +152,14 @@ def load_library():
         "ganmf_slim_bpr_epochs": (C.c_int, [vp, i64, C.c_int, P(C.c_int64)]),
         "ganmf_slim_bpr_finish": (C.c_int, [vp, i32, P(C.c_int64)]),
         "ganmf_slim_bpr_get_state": (C.c_int, [vp, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_int64)]),
+        "ganmf_mf_sgd_init": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, C.c_uint64, P(C.c_int64), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double)]),
+        "ganmf_mf_sgd_draw": (C.c_int, [vp, i64, i64, i64, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
+        "ganmf_mf_sgd_run": (C.c_int, [vp, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double), i64, i64, C.c_int, P(C.c_int64)]),
+        "ganmf_mf_sgd_epochs": (C.c_int, [vp, i64, i64, C.c_int, P(C.c_int64)]),
+        "ganmf_mf_sgd_publish": (C.c_int, [vp]),
+        "ganmf_mf_sgd_get_state": (C.c_int, [vp, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_int64)]),
+        "ganmf_mf_sgd_set_state": (C.c_int, [vp, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), i64]),
         "ganmf_cfgan_init": (C.c_int, [vp, i32, i32, C.c_int, i32, i32, C.c_int, C.c_float, C.c_uint64, P(C.c_int32)]),
         "ganmf_cfgan_draw_masks": (C.c_int, [vp, i64]),
         "ganmf_cfgan_set_masks": (C.c_int, [vp, P(C.c_uint32), P(C.c_uint32)]),

@@ -50,6 +50,8 @@
 #include "p3_rows.hpp"
 #include "slim_bpr.hpp"
 #include "slim_sched.hpp"
+#include "mf_sgd.hpp"
+#include "mf_sched.hpp"
 #include "subset_select.hpp"
 #include "cfgan_masks.hpp"
 #include "cfgan_rows.hpp"
@@ -88,6 +90,7 @@ extern "C" {
 #include "lib/abi_itemknn.inc"
 #include "lib/abi_p3.inc"
 #include "lib/abi_slim.inc"
+#include "lib/abi_mf_sgd.inc"
 #include "lib/abi_cfgan.inc"
 #include "lib/abi_caae.inc"
 #include "lib/abi_misc.inc"

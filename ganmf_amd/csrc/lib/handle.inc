@@ -58,6 +58,28 @@ struct SlimState {
   int n_eligible = 0;
 };
 
+// SGD matrix-factorisation training state of a GANMF_MODEL_MF handle (ganmf_mf_sgd_init; mf_sgd.hpp).  P holds three blocks of `block`
+// float64 values -- the parameters, st0, st1 -- each laid out [W: U k | H: N k | USER_bias: U | ITEM_bias: N | GLOBAL_bias: 1]; the
+// profiles the samples are drawn from with their stored values, the eligible users, phase 1's per-sample terms of one batch, and what
+// the host carries from call to call: the epoch counter of the sampler and Adam's beta powers (one multiplication per BATCH)
+struct MfSgdState {
+  bool ready = false;
+  int algo = 0, k = 0, use_bias = 0, sgd = 0;
+  double lr = 0, user_reg = 0, item_reg = 0, pos_reg = 0, neg_reg = 0, bias_reg = 0, quota = 0;
+  double gamma = 0.995, b1 = 0.9, b2 = 0.999, b1_pow = 0.9, b2_pow = 0.999;      // (fit() never forwards them: fixed)
+  uint64_t seed = 0;
+  int64_t epoch = 0, nnz = 0;
+  size_t block = 0;
+  double* P = nullptr;
+  long long* indptr = nullptr;
+  int* items = nullptr;
+  double* ratings = nullptr;
+  int* eligible = nullptr;
+  int n_eligible = 0;
+  double* terms = nullptr;
+  size_t terms_cap = 0;
+};
+
 // The generator CFGAN and CAAE share (profile_mlp.inc): an MLP from a dense profile row [N] through Lg hidden layers of g units back to
 // [N], every bias folded into its tensor as the last row and fed by a ones column of the layer's input.
 struct ProfileMlp {
@@ -324,6 +346,7 @@ struct ganmf_handle {
   float* knn_dense = nullptr;
   size_t knn_dense_cap = 0;
   SlimState slim;                                   // ganmf_slim_bpr_* (slim_bpr.hpp)
+  MfSgdState mfs;                                   // ganmf_mf_sgd_* (mf_sgd.hpp)
   CfganState cf;                                    // ganmf_cfgan_* (cfgan_masks.hpp, cfgan_rows.hpp)
   CaaeState ca;                                     // ganmf_caae_* (caae_sample.hpp, caae_rows.hpp)
   // ganmf_pure_svd (svd_rows.hpp): the two panels [max(U, N), svd_ldl] the iteration alternates between, the Gram matrix and the

@@ -36,6 +36,7 @@
 // rounds with ties to the smaller id); the non-zero picks are rounded to float32 and stored in the layout itemknn_pack_kernel reads.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "counter_draw.hpp"
 #include "itemknn_rows.hpp"
 
 namespace ganmf {
@@ -66,11 +67,6 @@ __host__ __device__ __forceinline__ size_t slim_cell(int symmetric, int n, int a
     return r * (r + 1) / 2 + c;
   }
   return (size_t)a * (size_t)n + (size_t)b;
-}
-
-__device__ __forceinline__ bool slim_in_profile(const int* __restrict__ items, long long a, long long b, int item) {
-  const long long q = knn_lower_bound(items, a, b, item);
-  return q < b && items[q] == item;
 }
 
 __device__ __forceinline__ void slim_sample(const SlimP& p, long long t, double* red, double* sh_upd) {
@@ -164,19 +160,7 @@ __global__ __launch_bounds__(SLIM_THREADS) void slim_update_kernel(const SlimP p
 }
 
 // ---- the sampler ------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ unsigned long long slim_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ __forceinline__ unsigned long long slim_word(unsigned long long key, unsigned stream, unsigned attempt) {
-  return slim_mix(key ^ (((unsigned long long)stream << 32) | attempt));
-}
-__host__ __device__ __forceinline__ unsigned slim_below(unsigned long long w, unsigned m) {
-  return (unsigned)(((w >> 32) * (unsigned long long)m) >> 32);
-}
-
+// (the generator and the three picks: counter_draw.hpp)
 struct SlimDrawP {
   const long long* indptr;
   const int* items;
@@ -193,31 +177,11 @@ __global__ __launch_bounds__(SLIM_THREADS) void slim_draw_kernel(const SlimDrawP
   const long long g = (long long)blockIdx.x * SLIM_THREADS + threadIdx.x;
   if (g >= p.n) return;
   const unsigned long long epoch = (unsigned long long)(p.epoch0 + g / p.per_epoch), index = (unsigned long long)(g % p.per_epoch);
-  const unsigned long long key = slim_mix(slim_mix(slim_mix(p.seed) ^ epoch) ^ index);
-  int u = -1;
+  const unsigned long long key = slim_key(p.seed, epoch, index);
   long long a = 0, b = 0;
-  for (unsigned at = 0; at < (unsigned)SLIM_ATTEMPTS; ++at) {
-    const int c = (int)slim_below(slim_word(key, 0, at), (unsigned)p.n_users);
-    a = p.indptr[c];
-    b = p.indptr[c + 1];
-    if (b > a && b - a < p.n_items) { u = c; break; }
-  }
-  if (u < 0) {
-    u = p.eligible[slim_below(slim_word(key, 0, SLIM_ATTEMPTS), (unsigned)p.n_eligible)];
-    a = p.indptr[u];
-    b = p.indptr[u + 1];
-  }
-  const int len = (int)(b - a);
-  const int i = p.items[a + slim_below(slim_word(key, 1, 0), (unsigned)len)];
-  int j = -1;
-  for (unsigned at = 0; at < (unsigned)SLIM_ATTEMPTS; ++at) {
-    const int c = (int)slim_below(slim_word(key, 2, at), (unsigned)p.n_items);
-    if (!slim_in_profile(p.items, a, b, c)) { j = c; break; }
-  }
-  if (j < 0) {      // the k-th item outside the (ascending) profile
-    j = (int)slim_below(slim_word(key, 2, SLIM_ATTEMPTS), (unsigned)(p.n_items - len));
-    for (long long q = a; q < b && p.items[q] <= j; ++q) ++j;
-  }
+  const int u = slim_draw_user(key, SLIM_ATTEMPTS, p.indptr, p.eligible, p.n_users, p.n_items, p.n_eligible, &a, &b);
+  const int i = p.items[slim_draw_positive(key, a, b)];
+  const int j = slim_draw_negative(key, SLIM_ATTEMPTS, p.items, a, b, p.n_items);
   p.users[g] = u;
   p.pos[g] = i;
   p.neg[g] = j;

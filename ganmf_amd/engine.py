@@ -481,6 +481,119 @@ class Engine:
                 "ganmf_slim_bpr_get_state")
         return {"S": S, "state0": s0, "state1": s1, "beta_powers": pw, "epoch": int(epoch.value)}
 
+    # -- MF-BPR / FunkSVD (ganmf_mf_sgd_*, a MODEL_MF engine) ---------------------------------------
+    def mf_sgd_init(self, algorithm, profiles, user_factors, item_factors, use_bias=False, sgd_mode="sgd", learning_rate=1e-3,
+                    user_reg=0.0, item_reg=0.0, positive_reg=0.0, negative_reg=0.0, bias_reg=0.0, negative_interactions_quota=0.0, seed=0):
+        """The float64 training state on the device (ganmf_mf_sgd_init).  profiles: the users x items CSR the samples are drawn from,
+        with its stored values (canonical form).  The engine has num_factors + 2 columns when use_bias.  The rates are passed on as
+        given: the caller rounds them."""
+        if algorithm not in L.MF_SGD_ALGORITHMS:
+            raise ValueError("Value for 'algorithm_name' not recognized. Acceptable values are {}, provided was '{}'".format(
+                list(L.MF_SGD_ALGORITHMS), algorithm))
+        if sgd_mode not in L.SLIM_SGD_MODES:
+            raise ValueError("Value for 'sgd_mode' not recognized. Acceptable values are {}, provided was '{}'".format(
+                ["sgd", "adam", "adagrad", "rmsprop"], sgd_mode))
+        m = profiles.tocsr()
+        if m.shape != (self.num_users, self.num_items):
+            raise ValueError("mf_sgd_init: profiles must be %d x %d, given %r" % (self.num_users, self.num_items, m.shape))
+        indptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(m.indices, dtype=np.int32)
+        data = np.ascontiguousarray(m.data, dtype=np.float64)
+        U = np.ascontiguousarray(user_factors, dtype=np.float64)
+        V = np.ascontiguousarray(item_factors, dtype=np.float64)
+        k = self.cfg.num_factors - 2 * int(bool(use_bias))
+        if U.shape != (self.num_users, k) or V.shape != (self.num_items, k):
+            raise ValueError("mf_sgd_init: the initial factors must be %d x %d and %d x %d, given %r and %r" % (
+                self.num_users, k, self.num_items, k, U.shape, V.shape))
+        L.check(self.lib.ganmf_mf_sgd_init(self.h, L.MF_SGD_ALGORITHMS[algorithm], int(bool(use_bias)), L.SLIM_SGD_MODES[sgd_mode],
+                                           float(learning_rate), float(user_reg), float(item_reg), float(positive_reg), float(negative_reg),
+                                           float(bias_reg), float(negative_interactions_quota), int(seed) & (2 ** 64 - 1),
+                                           indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices), _f64p(data), _f64p(U), _f64p(V)),
+                "ganmf_mf_sgd_init")
+        self._mf_sgd_info = (algorithm, k, bool(use_bias), int(indptr[-1]))
+
+    @property
+    def _mf_sgd(self):
+        """(algorithm, num_factors, use_bias, nnz of the profiles) of the last mf_sgd_init; without one the library's own refusal"""
+        if self._mf_sgd_info is None:
+            L.check(self.lib.ganmf_mf_sgd_get_state(self.h, None, None, None, None, None), "ganmf_mf_sgd_get_state")
+            raise L.GanmfError("ganmf_mf_sgd_init was not called through this Engine")
+        return self._mf_sgd_info
+
+    _mf_sgd_info = None
+
+    def _mf_sgd_per_epoch(self, batch_size):
+        algorithm, _, _, nnz = self._mf_sgd
+        return ((self.num_users if algorithm == "MF_BPR" else nnz) // int(batch_size) + 1) * int(batch_size)
+
+    def mf_sgd_draw(self, epoch, n_epochs=1, batch_size=1000):
+        """(users, items, neg_items) int32 for MF_BPR, (users, items, ratings float64) for FUNK_SVD: the samples of the epochs
+        [epoch, epoch + n_epochs) (ganmf_mf_sgd_draw)"""
+        n = int(n_epochs) * self._mf_sgd_per_epoch(batch_size)
+        bpr = self._mf_sgd[0] == "MF_BPR"
+        users, items = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        third = np.zeros(n, dtype=np.int32 if bpr else np.float64)
+        L.check(self.lib.ganmf_mf_sgd_draw(self.h, int(epoch), int(n_epochs), int(batch_size), _i32p(users), _i32p(items),
+                                           _i32p(third) if bpr else None, None if bpr else _f64p(third)), "ganmf_mf_sgd_draw")
+        return users, items, third
+
+    def mf_sgd_run(self, users, items, third, batch_size, route=L.MF_SGD_AUTO):
+        """Applies the samples in mini-batches of batch_size, in list order (ganmf_mf_sgd_run); `third` is neg_items for MF_BPR and
+        the ratings for FUNK_SVD.  Returns the largest level count of a batch (0 on the sequential route)."""
+        bpr = self._mf_sgd[0] == "MF_BPR"
+        u, i = (np.ascontiguousarray(v, dtype=np.int32).ravel() for v in (users, items))
+        t = np.ascontiguousarray(third, dtype=np.int32 if bpr else np.float64).ravel()
+        assert u.size == i.size == t.size
+        levels = C.c_int64(0)
+        L.check(self.lib.ganmf_mf_sgd_run(self.h, _i32p(u), _i32p(i), _i32p(t) if bpr else None, None if bpr else _f64p(t), u.size,
+                                          int(batch_size), int(route), C.byref(levels)), "ganmf_mf_sgd_run")
+        return int(levels.value)
+
+    def mf_sgd_epochs(self, n_epochs=1, batch_size=1000, route=L.MF_SGD_AUTO):
+        """Draws and applies the next n_epochs epochs (ganmf_mf_sgd_epochs); returns the largest level count of a batch."""
+        levels = C.c_int64(0)
+        L.check(self.lib.ganmf_mf_sgd_epochs(self.h, int(n_epochs), int(batch_size), int(route), C.byref(levels)), "ganmf_mf_sgd_epochs")
+        return int(levels.value)
+
+    def mf_sgd_publish(self):
+        """the float64 state rounded into the factor tensors, the biases as two more columns (ganmf_mf_sgd_publish)"""
+        L.check(self.lib.ganmf_mf_sgd_publish(self.h), "ganmf_mf_sgd_publish")
+
+    def _mf_sgd_split(self, block):
+        _, k, _, _ = self._mf_sgd
+        U, N = self.num_users, self.num_items
+        a, b, c, d = U * k, U * k + N * k, U * k + N * k + U, U * k + N * k + U + N
+        return {"USER_factors": block[:a].reshape(U, k), "ITEM_factors": block[a:b].reshape(N, k), "USER_bias": block[b:c],
+                "ITEM_bias": block[c:d], "GLOBAL_bias": block[d:d + 1]}
+
+    def mf_sgd_state(self):
+        """dict: params / state0 / state1, each a dict of float64 USER_factors, ITEM_factors, USER_bias, ITEM_bias, GLOBAL_bias [1];
+        beta_powers [2]; epoch (ganmf_mf_sgd_get_state)"""
+        _, k, _, _ = self._mf_sgd
+        size = (self.num_users + self.num_items) * (k + 1) + 1
+        blocks = [np.zeros(size, dtype=np.float64) for _ in range(3)]
+        pw, epoch = np.zeros(2), C.c_int64(0)
+        L.check(self.lib.ganmf_mf_sgd_get_state(self.h, _f64p(blocks[0]), _f64p(blocks[1]), _f64p(blocks[2]), _f64p(pw), C.byref(epoch)),
+                "ganmf_mf_sgd_get_state")
+        return {"params": self._mf_sgd_split(blocks[0]), "state0": self._mf_sgd_split(blocks[1]), "state1": self._mf_sgd_split(blocks[2]),
+                "beta_powers": pw, "epoch": int(epoch.value)}
+
+    def mf_sgd_set_state(self, params=None, state0=None, state1=None, beta_powers=None, epoch=-1):
+        """the reverse of mf_sgd_state: each of params / state0 / state1 a dict with all five members, or None to keep the block"""
+        def join(d):
+            if d is None:
+                return None
+            flat = np.concatenate([np.asarray(d[n], dtype=np.float64).ravel() for n in
+                                   ("USER_factors", "ITEM_factors", "USER_bias", "ITEM_bias", "GLOBAL_bias")])
+            _, k, _, _ = self._mf_sgd
+            if flat.size != (self.num_users + self.num_items) * (k + 1) + 1:
+                raise ValueError("mf_sgd_set_state: a block has %d values" % flat.size)
+            return np.ascontiguousarray(flat)
+        blocks = [join(d) for d in (params, state0, state1)]
+        pw = None if beta_powers is None else np.ascontiguousarray(beta_powers, dtype=np.float64)
+        L.check(self.lib.ganmf_mf_sgd_set_state(self.h, *[_f64p(b) if b is not None else None for b in blocks],
+                                                _f64p(pw) if pw is not None else None, int(epoch)), "ganmf_mf_sgd_set_state")
+
     # -- CFGAN (ganmf_cfgan_*, a MODEL_CFGAN engine) ------------------------------------------------
     def cfgan_init(self, g_nodes, g_layers, g_act, d_batch, g_batch, scheme, zr_coefficient, seed, k_rows):
         """The generator, the two batch sizes, the scheme ("ZR" | "PM" | "ZP"), the zero-reconstruction coefficient, the mask

@@ -714,6 +714,54 @@ int ganmf_device_count(void);
 int ganmf_abi_version(void);
 const char* ganmf_last_error(void);
 
+/* ---- MF-BPR and FunkSVD trained on the device (MatrixFactorization/Cython/MatrixFactorization_Cython_Epoch.pyx: the epochs :287-389
+ * and :614-696, adaptive_gradient :760-798, the samplers :803-910) on a GANMF_MODEL_MF handle.  float64, as in the reference;
+ * ganmf_amd/csrc/mf_sgd.hpp states the kernels, the summation orders and the sampler in full.  New entries; no structure or signature
+ * changed: GANMF_ABI_VERSION stays.
+ * init: allocates W [num_users, k], H [num_items, k], the three biases and two optimiser values per element, in float64, with
+ *   k = the handle's num_factors - 2 use_bias (a biased model publishes two more columns, see publish); W and H start as
+ *   user_factors / item_factors, everything else as zero.  (indptr, indices, ratings) is the users x items CSR the samples are drawn
+ *   from: indices ascending without repeats inside a row (-1 otherwise), every rating finite.  The rates are used as the doubles
+ *   given (the caller rounds them to float32, as the reference's C float members do); gamma = 0.995, beta_1 = 0.9, beta_2 = 0.999.
+ *   item_reg is stored and never read (the reference's item gradient uses positive_reg).  GANMF_MF_SGD_BPR refuses use_bias.  Errors
+ *   (-1, nothing allocated, a state held before is kept): unknown algorithm or mode, a value that is not finite, a quota outside
+ *   [0, 1), more than GANMF_MF_SGD_MAX_FACTORS columns, no user whose profile is neither empty nor full.  -2 "out of memory: ...
+ *   needs N bytes" when an allocation fails; the handle stays usable.
+ * draw: the samples of the epochs [epoch, epoch + n_epochs): (num_users / batch_size + 1) batch_size per epoch for BPR,
+ *   (nnz / batch_size + 1) batch_size for FunkSVD.  A pure function of (seed, epoch, index) and the profiles.  BPR fills neg_items,
+ *   FunkSVD ratings (the other may be NULL).  Nothing of the state moves.
+ * run: applies the n samples in mini-batches of batch_size (the last one may be shorter) with the reference's semantics: per batch
+ *   one scalar, the mean over the batch of 1 / (1 + exp(x_uij)) or of rating - prediction at frozen parameters, then the samples in
+ *   list order, each reading the current rows.  GANMF_MF_SGD_SEQUENTIAL: one wave walks a batch in order (2 launches per batch).
+ *   GANMF_MF_SGD_LEVELLED (and AUTO): the host sorts every batch into levels (ganmf_amd/csrc/mf_sched.hpp) and launches one grid
+ *   per level; the bytes are those of the sequential route.  *n_levels (may be NULL): the largest level count of a batch (0 on the
+ *   sequential route).  Errors (-1, nothing enqueued): an id out of range, a BPR sample with equal items, a rating that is not
+ *   finite, batch_size outside [1, GANMF_MF_SGD_MAX_BATCH].
+ * epochs: draw of the next n_epochs epochs followed by run of them, the samples staying on the device (the levelled route copies
+ *   their ids back once per epoch); advances the epoch counter.  *n_levels as for run, over all batches.
+ * publish: rounds the float64 state into the handle's float32 factor tensors, with use_bias as U' = [W | USER_bias + GLOBAL_bias | 1]
+ *   and V' = [H | 1 | ITEM_bias]: every scoring, ranking, evaluation and best-slot entry then serves W H^T + the three biases.
+ * get_state / set_state: the three blocks (parameters, state0, state1), each num_users k + num_items k + num_users + num_items + 1
+ *   values laid out [W | H | USER_bias | ITEM_bias | GLOBAL_bias], Adam's two beta powers and the epoch counter.  A NULL pointer is
+ *   skipped; set_state keeps the counter for epoch = -1. */
+#define GANMF_MF_SGD_MAX_FACTORS 1024
+#define GANMF_MF_SGD_MAX_BATCH (1 << 20)
+enum { GANMF_MF_SGD_BPR = 0, GANMF_MF_SGD_FUNK = 1 };
+enum { GANMF_MF_SGD_AUTO = 0, GANMF_MF_SGD_SEQUENTIAL = 1, GANMF_MF_SGD_LEVELLED = 2 };
+int ganmf_mf_sgd_init(ganmf_handle* h, int algorithm, int use_bias, int sgd_mode, double learning_rate, double user_reg, double item_reg,
+                      double positive_reg, double negative_reg, double bias_reg, double negative_interactions_quota, uint64_t seed,
+                      const int64_t* indptr, const int32_t* indices, const double* ratings, const double* user_factors,
+                      const double* item_factors);
+int ganmf_mf_sgd_draw(ganmf_handle* h, int64_t epoch, int64_t n_epochs, int64_t batch_size, int32_t* users, int32_t* items,
+                      int32_t* neg_items, double* ratings);
+int ganmf_mf_sgd_run(ganmf_handle* h, const int32_t* users, const int32_t* items, const int32_t* neg_items, const double* ratings, int64_t n,
+                     int64_t batch_size, int route, int64_t* n_levels);
+int ganmf_mf_sgd_epochs(ganmf_handle* h, int64_t n_epochs, int64_t batch_size, int route, int64_t* n_levels);
+int ganmf_mf_sgd_publish(ganmf_handle* h);
+int ganmf_mf_sgd_get_state(ganmf_handle* h, double* params, double* state0, double* state1, double* beta_powers, int64_t* epoch);
+int ganmf_mf_sgd_set_state(ganmf_handle* h, const double* params, const double* state0, const double* state1, const double* beta_powers,
+                           int64_t epoch);
+
 #ifdef __cplusplus
 }
 #endif
