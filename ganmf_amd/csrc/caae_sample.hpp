@@ -1,7 +1,7 @@
 // CAAE's samplers (CAAE.py:220,244,270-293,312-321), all counter-based in the manner of cfgan_masks.hpp: every draw is a pure function
 // of (seed, epoch, stream, pass / step, index), so nothing depends on the grid, the workgroup size or the order in which anything runs.
-//     base  = slim_mix(slim_mix(slim_mix(slim_mix(seed) ^ epoch) ^ stream) ^ step)
-//     word  = slim_mix(base ^ index)
+//     base  = draw_mix(draw_mix(draw_mix(draw_mix(seed) ^ epoch) ^ stream) ^ step)
+//     word  = draw_mix(base ^ index)
 //   (a) the epoch's order of the nnz stored interactions: position t holds CSR position caae_perm_index(base, nnz, t), a keyed
 //       bijection of [0, nnz) -- a balanced Feistel network of CAAE_FEISTEL_ROUNDS rounds over the smallest even number of bits that
 //       covers nnz, walked until it lands below nnz (cycle walking: a bijection of the power-of-two domain restricted to [0, nnz) is a
@@ -17,7 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "slim_bpr.hpp"
+#include "counter_draw.hpp"
 #include "subset_select.hpp"
 
 namespace ganmf {
@@ -29,10 +29,10 @@ constexpr int CAAE_FEISTEL_ROUNDS = 6;
 
 __host__ __device__ __forceinline__ unsigned long long caae_base(unsigned long long seed, unsigned long long epoch, unsigned stream,
                                                                  unsigned long long step) {
-  return slim_mix(slim_mix(slim_mix(slim_mix(seed) ^ epoch) ^ (unsigned long long)stream) ^ step);
+  return draw_mix(draw_mix(draw_mix(draw_mix(seed) ^ epoch) ^ (unsigned long long)stream) ^ step);
 }
 __host__ __device__ __forceinline__ unsigned caae_u24(unsigned long long base, unsigned long long index) {
-  return (unsigned)(slim_mix(base ^ index) >> 40);
+  return (unsigned)(draw_mix(base ^ index) >> 40);
 }
 
 // position t of the keyed bijection of [0, n), n >= 1
@@ -44,7 +44,7 @@ __host__ __device__ __forceinline__ unsigned long long caae_perm_index(unsigned 
   do {
     unsigned long long l = x >> half, r = x & mask;
     for (int q = 0; q < CAAE_FEISTEL_ROUNDS; ++q) {
-      const unsigned long long f = slim_mix(base ^ (((unsigned long long)(q + 1) << 40) | r)) & mask;
+      const unsigned long long f = draw_mix(base ^ (((unsigned long long)(q + 1) << 40) | r)) & mask;
       const unsigned long long nl = r;
       r = l ^ f;
       l = nl;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void caae_users_kernel(unsigned long long base
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= m) return;
   out[b] = distinct ? (int)caae_perm_index(base, (unsigned long long)U, (unsigned long long)b)
-                    : (int)(((slim_mix(base ^ (unsigned long long)b) >> 32) * (unsigned long long)U) >> 32);
+                    : (int)(((draw_mix(base ^ (unsigned long long)b) >> 32) * (unsigned long long)U) >> 32);
 }
 
 // (d)

@@ -3,7 +3,7 @@
 // (np.packbits(..., bitorder='little') over 32-bit little-endian words).
 //
 // Every eligible column j of row r (j not stored in the row's sorted CSR) gets the 32-bit key
-//     key(j) = slim_mix(base ^ (r << 32 | j)) >> 32,     base = slim_mix(slim_mix(slim_mix(seed) ^ epoch) ^ plane)
+//     key(j) = draw_mix(base ^ (r << 32 | j)) >> 32,     base = draw_mix(draw_mix(draw_mix(seed) ^ epoch) ^ plane)
 // and the chosen set is the k smallest (key, column) pairs: ties go to the smaller column.  The result is a pure function of
 // (seed, epoch, plane, row): nothing depends on the grid, the workgroup size or the order in which anything runs.
 //
@@ -11,7 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "slim_bpr.hpp"
+#include "counter_draw.hpp"
 #include "subset_select.hpp"
 
 namespace ganmf {
@@ -19,10 +19,10 @@ namespace ganmf {
 constexpr int CFGAN_PLANE_ZR = 0, CFGAN_PLANE_PM = 1;
 
 __host__ __device__ __forceinline__ unsigned long long cfgan_mask_base(unsigned long long seed, unsigned long long epoch, unsigned plane) {
-  return slim_mix(slim_mix(slim_mix(seed) ^ epoch) ^ (unsigned long long)plane);
+  return draw_mix(draw_mix(draw_mix(seed) ^ epoch) ^ (unsigned long long)plane);
 }
 __host__ __device__ __forceinline__ unsigned cfgan_mask_key(unsigned long long base, unsigned row, unsigned col) {
-  return (unsigned)(slim_mix(base ^ (((unsigned long long)row << 32) | col)) >> 32);
+  return (unsigned)(draw_mix(base ^ (((unsigned long long)row << 32) | col)) >> 32);
 }
 
 struct CfganMaskP {

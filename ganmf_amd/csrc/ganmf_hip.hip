@@ -48,10 +48,9 @@
 #include "svd_rows.hpp"
 #include "itemknn_rows.hpp"
 #include "p3_rows.hpp"
+#include "level_sched.hpp"
 #include "slim_bpr.hpp"
-#include "slim_sched.hpp"
 #include "mf_sgd.hpp"
-#include "mf_sched.hpp"
 #include "subset_select.hpp"
 #include "cfgan_masks.hpp"
 #include "cfgan_rows.hpp"
@@ -77,6 +76,7 @@ namespace {
 #include "lib/step_cfgan.inc"
 #include "lib/step_caae.inc"
 #include "lib/epoch.inc"
+#include "lib/sgd_train.inc"
 }  // namespace
 
 // =================================================================================================

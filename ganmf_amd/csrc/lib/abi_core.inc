@@ -270,8 +270,8 @@ int ganmf_destroy(ganmf_handle* h) {
   for (AlsSide& s : h->als) { hipFree(s.indptr); hipFree(s.indices); hipFree(s.conf); }
   hipFree(h->als_G); hipFree(h->als_bad);
   hipFree(h->knn_indptr); hipFree(h->knn_nbr); hipFree(h->knn_val); hipFree(h->knn_dense);
-  hipFree(h->slim.S); hipFree(h->slim.st0); hipFree(h->slim.st1); hipFree(h->slim.indptr); hipFree(h->slim.items); hipFree(h->slim.eligible);
-  hipFree(h->mfs.P); hipFree(h->mfs.indptr); hipFree(h->mfs.items); hipFree(h->mfs.ratings); hipFree(h->mfs.eligible); hipFree(h->mfs.terms);
+  hipFree(h->slim.S); hipFree(h->slim.st0); hipFree(h->slim.st1); profiles_drop(h->slim.profiles);
+  hipFree(h->mfs.P); hipFree(h->mfs.terms); profiles_drop(h->mfs.profiles);
   hipFree(h->svd_P[0]); hipFree(h->svd_P[1]); hipFree(h->svd_G); hipFree(h->svd_X); hipFree(h->svd_Wl);
   hipFree(h->svd_lam); hipFree(h->svd_flag);
   hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);

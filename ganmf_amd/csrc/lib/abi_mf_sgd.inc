@@ -1,12 +1,13 @@
 // abi_mf_sgd.inc -- C ABI: MF-BPR and FunkSVD trained on a GANMF_MODEL_MF handle: ganmf_mf_sgd_init / _draw / _run / _epochs /
-// _publish / _get_state / _set_state (mf_sgd.hpp, mf_sched.hpp).  _publish rounds the float64 state into the handle's factor tensors.
+// _publish / _get_state / _set_state (mf_sgd.hpp; the list path: sgd_train.inc).  _publish rounds the float64 state into the handle's
+// factor tensors.
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
 static_assert(MF_SGD_BPR == GANMF_MF_SGD_BPR && MF_SGD_FUNK == GANMF_MF_SGD_FUNK, "algorithms of the kernels and of the header");
 
 static void mf_sgd_drop(ganmf_handle* h) {
   MfSgdState& s = h->mfs;
-  hipFree(s.P); hipFree(s.indptr); hipFree(s.items); hipFree(s.ratings); hipFree(s.eligible); hipFree(s.terms);
+  hipFree(s.P); hipFree(s.terms); profiles_drop(s.profiles);
   s = MfSgdState();
 }
 
@@ -41,7 +42,7 @@ int ganmf_mf_sgd_init(ganmf_handle* h, int algorithm, int use_bias, int sgd_mode
   if (!h || !indptr || !user_factors || !item_factors) return fail(-1, "%s: null argument", who);
   TRY(mf_sgd_handle(h, who));
   if (algorithm < 0 || algorithm >= MF_SGD_ALGOS) return fail(-1, "%s: unknown algorithm %d", who, algorithm);
-  if (sgd_mode < 0 || sgd_mode >= SLIM_SGD_MODES) return fail(-1, "%s: unknown sgd mode %d", who, sgd_mode);
+  if (sgd_mode < 0 || sgd_mode >= SGD_MODES) return fail(-1, "%s: unknown sgd mode %d", who, sgd_mode);
   use_bias = use_bias ? 1 : 0;
   if (use_bias && algorithm == MF_SGD_BPR) return fail(-1, "%s: MF_BPR has no biases (the reference's class forces use_bias = False)", who);
   const int U = h->U, n = h->N, k = h->k - 2 * use_bias;
@@ -62,36 +63,24 @@ int ganmf_mf_sgd_init(ganmf_handle* h, int algorithm, int use_bias, int sgd_mode
     if (!std::isfinite(user_factors[q])) return fail(-1, "%s: the initial user factors are not finite", who);
   for (size_t q = 0; q < (size_t)n * k; ++q)
     if (!std::isfinite(item_factors[q])) return fail(-1, "%s: the initial item factors are not finite", who);
-  std::vector<int> eligible;
-  for (int u = 0; u < U; ++u) {
-    const int64_t len = indptr[(size_t)u + 1] - indptr[(size_t)u];
-    if (len > 0 && len < n) eligible.push_back(u);
-  }
-  if (eligible.empty()) return fail(-1, "%s: no user has a profile that is neither empty nor full: there is nothing to sample", who);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
+  SampleProfiles profiles;      // a refusal leaves the state held as it is
+  TRY(profiles_upload(profiles, who, U, n, indptr, indices, ratings, nullptr, nullptr));
 
   mf_sgd_drop(h);
   MfSgdState& s = h->mfs;
+  s.profiles = profiles;
   s.k = k;
   s.block = (size_t)U * k + (size_t)n * k + (size_t)U + (size_t)n + 1;
-  static_assert(sizeof(long long) == sizeof(int64_t), "indptr words");
-  int rc = slim_alloc(who, "the factors, the biases and their optimiser state (float64)", (void**)&s.P, 3 * s.block * sizeof(double));
-  if (!rc) rc = slim_alloc(who, "the profiles", (void**)&s.indptr, ((size_t)U + 1) * sizeof(long long));
-  if (!rc) rc = slim_alloc(who, "the profiles", (void**)&s.items, nnz * sizeof(int));
-  if (!rc) rc = slim_alloc(who, "the profiles", (void**)&s.ratings, nnz * sizeof(double));
-  if (!rc) rc = slim_alloc(who, "the eligible users", (void**)&s.eligible, eligible.size() * sizeof(int));
-  if (rc) { mf_sgd_drop(h); return rc; }
+  if (int rc = named_alloc(who, "the factors, the biases and their optimiser state (float64)", (void**)&s.P, 3 * s.block * sizeof(double))) {
+    mf_sgd_drop(h);
+    return rc;
+  }
   hipError_t e = hipMemset(s.P, 0, 3 * s.block * sizeof(double));
   if (e == hipSuccess) e = hipMemcpy(s.P, user_factors, (size_t)U * k * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(s.P + (size_t)U * k, item_factors, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(s.indptr, indptr, ((size_t)U + 1) * sizeof(long long), hipMemcpyHostToDevice);
-  if (e == hipSuccess && nnz) e = hipMemcpy(s.items, indices, nnz * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess && nnz) e = hipMemcpy(s.ratings, ratings, nnz * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(s.eligible, eligible.data(), eligible.size() * sizeof(int), hipMemcpyHostToDevice);
   if (e != hipSuccess) { mf_sgd_drop(h); return fail(-2, "%s: %s", who, hipGetErrorString(e)); }
-  s.n_eligible = (int)eligible.size();
-  s.nnz = (int64_t)nnz;
   s.algo = algorithm; s.use_bias = use_bias; s.sgd = sgd_mode;
   s.lr = learning_rate; s.user_reg = user_reg; s.item_reg = item_reg; s.pos_reg = positive_reg; s.neg_reg = negative_reg;
   s.bias_reg = bias_reg; s.quota = negative_interactions_quota;
@@ -105,48 +94,14 @@ int ganmf_mf_sgd_init(ganmf_handle* h, int algorithm, int use_bias, int sgd_mode
 static int mf_sgd_per_epoch(ganmf_handle* h, const char* who, int64_t batch_size, int64_t* per) {
   if (batch_size < 1 || batch_size > GANMF_MF_SGD_MAX_BATCH)
     return fail(-1, "%s: batch_size must be in [1, %d]", who, GANMF_MF_SGD_MAX_BATCH);
-  const int64_t base = h->mfs.algo == MF_SGD_BPR ? (int64_t)h->U : h->mfs.nnz;
+  const int64_t base = h->mfs.algo == MF_SGD_BPR ? (int64_t)h->U : h->mfs.profiles.nnz;
   *per = (base / batch_size + 1) * batch_size;
-  if (*per > SLIM_MAX_SAMPLES) return fail(-1, "%s: more than 2^30 samples in one epoch", who);
-  return 0;
-}
-
-struct MfSgdTmp {
-  int *users = nullptr, *pos = nullptr, *neg = nullptr;
-  double* rating = nullptr;
-  long long* order = nullptr;
-  ~MfSgdTmp() { hipFree(users); hipFree(pos); hipFree(neg); hipFree(rating); hipFree(order); }
-  int alloc(const char* who, int algo, int64_t n) {
-    TRY(slim_alloc(who, "the samples", (void**)&users, (size_t)n * sizeof(int)));
-    TRY(slim_alloc(who, "the samples", (void**)&pos, (size_t)n * sizeof(int)));
-    if (algo == MF_SGD_BPR) TRY(slim_alloc(who, "the samples", (void**)&neg, (size_t)n * sizeof(int)));
-    else TRY(slim_alloc(who, "the samples", (void**)&rating, (size_t)n * sizeof(double)));
-    return 0;
-  }
-};
-
-// n samples of the epochs [epoch, ...) with `per` samples each, into device arrays: one launch
-static int mf_sgd_draw_device(ganmf_handle* h, int64_t epoch, int64_t per, int64_t n, MfSgdTmp& t) {
-  const MfSgdState& s = h->mfs;
-  MfDrawP p{};
-  p.indptr = s.indptr; p.items = s.items; p.ratings = s.ratings; p.eligible = s.eligible;
-  p.n_users = h->U; p.n_items = h->N; p.n_eligible = s.n_eligible; p.algo = s.algo; p.quota = s.quota;
-  p.seed = s.seed; p.epoch0 = epoch; p.per_epoch = per; p.n = n;
-  p.users = t.users; p.pos = t.pos; p.neg = t.neg; p.rating = t.rating;
-  const unsigned blocks = (unsigned)((n + MF_SGD_THREADS - 1) / MF_SGD_THREADS);
-  GANMF_LAUNCH(mf_draw_kernel, dim3(blocks), dim3(MF_SGD_THREADS), 0, h->st, p);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-static int mf_sgd_route_ok(const char* who, int route) {
-  if (route != GANMF_MF_SGD_AUTO && route != GANMF_MF_SGD_SEQUENTIAL && route != GANMF_MF_SGD_LEVELLED)
-    return fail(-1, "%s: unknown route %d", who, route);
+  if (*per > SGD_MAX_SAMPLES) return fail(-1, "%s: more than 2^30 samples in one epoch", who);
   return 0;
 }
 
 // the list is on the device (t) and, for the levelled route, its ids on the host (checked by the caller)
-static int mf_sgd_run_device(ganmf_handle* h, const char* who, MfSgdTmp& t, const int32_t* users, const int32_t* pos, const int32_t* neg,
+static int mf_sgd_run_device(ganmf_handle* h, const char* who, SampleList& t, const int32_t* users, const int32_t* pos, const int32_t* neg,
                              int64_t n, int64_t batch_size, int route, int64_t* n_levels) {
   MfSgdState& s = h->mfs;
   const bool levelled = route != GANMF_MF_SGD_SEQUENTIAL;
@@ -156,7 +111,7 @@ static int mf_sgd_run_device(ganmf_handle* h, const char* who, MfSgdTmp& t, cons
     HIP_TRY(hipStreamSynchronize(h->st));
     hipFree(s.terms);
     s.terms = nullptr; s.terms_cap = 0;
-    TRY(slim_alloc(who, "the per-sample terms of a batch", (void**)&s.terms, (size_t)batch_size * sizeof(double)));
+    TRY(named_alloc(who, "the per-sample terms of a batch", (void**)&s.terms, (size_t)batch_size * sizeof(double)));
     s.terms_cap = (size_t)batch_size;
   }
   MfSgdP p{};
@@ -173,11 +128,13 @@ static int mf_sgd_run_device(ganmf_handle* h, const char* who, MfSgdTmp& t, cons
   int64_t top = 0;
   if (levelled) {
     order.resize((size_t)n);
-    MfScheduler scheduler(h->U, h->N);
-    MfSchedule sched;
+    LevelScheduler scheduler((int64_t)h->U + h->N);      // users, then items at base U: one table through every batch
+    LevelSchedule sched;
     for (int64_t b = 0; b < n_batches; ++b) {
       const int64_t first = b * batch_size, count = std::min(batch_size, n - first);
-      const int64_t levels = scheduler.schedule(users + first, pos + first, neg ? neg + first : nullptr, count, sched);
+      std::vector<LevelColumn> cols = {{users + first, 0, h->U}, {pos + first, h->U, h->N}};
+      if (neg) cols.push_back({neg + first, h->U, h->N});
+      const int64_t levels = scheduler.schedule(cols, count, sched);
       if (levels < 0) return fail(-2, "%s: the schedule met an id out of range", who);
       top = std::max(top, levels);
       batch_at[(size_t)b] = (int64_t)starts.size();
@@ -185,8 +142,7 @@ static int mf_sgd_run_device(ganmf_handle* h, const char* who, MfSgdTmp& t, cons
       for (int64_t q = 0; q < count; ++q) order[(size_t)(first + q)] = first + sched.order[(size_t)q];
     }
     batch_at[(size_t)n_batches] = (int64_t)starts.size();
-    TRY(slim_alloc(who, "the level order", (void**)&t.order, (size_t)n * sizeof(long long)));
-    HIP_TRY(hipMemcpyAsync(t.order, order.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice, h->st));
+    TRY(t.upload_order(who, h->st, order));
     p.order = t.order;
   }
   constexpr int per_wg = MF_SGD_THREADS / MF_SGD_WAVE;
@@ -207,7 +163,7 @@ static int mf_sgd_run_device(ganmf_handle* h, const char* who, MfSgdTmp& t, cons
         HIP_TRY(hipGetLastError());
       }
     }
-    if (s.sgd == SLIM_ADAM) {      // once per batch (:393-397, :699-703)
+    if (s.sgd == SGD_ADAM) {      // once per batch (:393-397, :699-703)
       b1p *= s.b1;
       b2p *= s.b2;
     }
@@ -229,19 +185,16 @@ int ganmf_mf_sgd_draw(ganmf_handle* h, int64_t epoch, int64_t n_epochs, int64_t 
   if (epoch < 0 || n_epochs < 0) return fail(-1, "%s: epoch and n_epochs must be >= 0", who);
   int64_t per = 0;
   TRY(mf_sgd_per_epoch(h, who, batch_size, &per));
-  if (n_epochs > SLIM_MAX_SAMPLES / per) return fail(-1, "%s: more than 2^30 samples in one call", who);
-  const int64_t n = n_epochs * per;
+  int64_t n = 0;
+  TRY(sample_count(who, n_epochs, per, &n));
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(h->dev));
-  MfSgdTmp t;
-  TRY(t.alloc(who, algo, n));
-  TRY(mf_sgd_draw_device(h, epoch, per, n, t));
-  HIP_TRY(hipMemcpyAsync(users, t.users, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(items, t.pos, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->st));
-  if (algo == MF_SGD_BPR) HIP_TRY(hipMemcpyAsync(neg_items, t.neg, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->st));
-  else HIP_TRY(hipMemcpyAsync(ratings, t.rating, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  return 0;
+  const MfSgdState& s = h->mfs;
+  const bool rated = algo == MF_SGD_FUNK;
+  SampleList t;
+  TRY(t.alloc(who, n, rated));
+  TRY(sample_draw(h, s.profiles, rated, s.quota, s.seed, epoch, per, n, t));
+  return t.download(h->st, n, users, items, rated ? nullptr : neg_items, rated ? ratings : nullptr);
 }
 
 int ganmf_mf_sgd_run(ganmf_handle* h, const int32_t* users, const int32_t* items, const int32_t* neg_items, const double* ratings, int64_t n,
@@ -251,29 +204,15 @@ int ganmf_mf_sgd_run(ganmf_handle* h, const int32_t* users, const int32_t* items
   TRY(mf_sgd_ready(h, who));
   const bool bpr = h->mfs.algo == MF_SGD_BPR;
   if (n > 0 && (!users || !items || (bpr ? !neg_items : !ratings))) return fail(-1, "%s: null argument", who);
-  TRY(mf_sgd_route_ok(who, route));
-  if (n < 0 || n > SLIM_MAX_SAMPLES) return fail(-1, "%s: n out of range", who);
+  TRY(sgd_route_ok(who, route));
+  TRY(sample_n_ok(who, n));
   if (batch_size < 1 || batch_size > GANMF_MF_SGD_MAX_BATCH) return fail(-1, "%s: batch_size must be in [1, %d]", who, GANMF_MF_SGD_MAX_BATCH);
-  for (int64_t q = 0; q < n; ++q) {
-    if (users[q] < 0 || users[q] >= h->U) return fail(-1, "%s: sample %lld names user %d of %d", who, (long long)q, users[q], h->U);
-    if (items[q] < 0 || items[q] >= h->N) return fail(-1, "%s: sample %lld names item %d of %d", who, (long long)q, items[q], h->N);
-    if (bpr) {
-      if (neg_items[q] < 0 || neg_items[q] >= h->N) return fail(-1, "%s: sample %lld names item %d of %d", who, (long long)q, neg_items[q], h->N);
-      if (items[q] == neg_items[q]) return fail(-1, "%s: sample %lld has the same positive and negative item %d", who, (long long)q, items[q]);
-    } else if (!std::isfinite(ratings[q])) {
-      return fail(-1, "%s: sample %lld has a rating that is not finite", who, (long long)q);
-    }
-  }
+  TRY(sample_list_ok(h, who, users, items, neg_items, bpr ? nullptr : ratings, n));
   if (n_levels) *n_levels = 0;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(h->dev));
-  MfSgdTmp t;
-  TRY(t.alloc(who, h->mfs.algo, n));
-  HIP_TRY(hipMemcpyAsync(t.users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->st));
-  HIP_TRY(hipMemcpyAsync(t.pos, items, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->st));
-  if (bpr) HIP_TRY(hipMemcpyAsync(t.neg, neg_items, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->st));
-  else HIP_TRY(hipMemcpyAsync(t.rating, ratings, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));      // (pageable sources: the copies are done before the caller's arrays may change)
+  SampleList t;
+  TRY(t.upload(who, h->st, n, users, items, neg_items, bpr ? nullptr : ratings));
   return mf_sgd_run_device(h, who, t, users, items, bpr ? neg_items : nullptr, n, batch_size, route, n_levels);
 }
 
@@ -281,7 +220,7 @@ int ganmf_mf_sgd_epochs(ganmf_handle* h, int64_t n_epochs, int64_t batch_size, i
   const char* who = "ganmf_mf_sgd_epochs";
   if (!h) return fail(-1, "%s: null argument", who);
   TRY(mf_sgd_ready(h, who));
-  TRY(mf_sgd_route_ok(who, route));
+  TRY(sgd_route_ok(who, route));
   if (n_epochs < 0) return fail(-1, "%s: n_epochs must be >= 0", who);
   int64_t per = 0;
   TRY(mf_sgd_per_epoch(h, who, batch_size, &per));
@@ -291,20 +230,10 @@ int ganmf_mf_sgd_epochs(ganmf_handle* h, int64_t n_epochs, int64_t batch_size, i
   std::vector<int32_t> users, pos, neg;
   int64_t top = 0;
   for (int64_t e = 0; e < n_epochs; ++e) {
-    MfSgdTmp t;
-    TRY(t.alloc(who, h->mfs.algo, per));
-    TRY(mf_sgd_draw_device(h, h->mfs.epoch, per, per, t));
-    if (levelled) {      // the one copy back of the epoch: the ids the schedule is formed from
-      users.resize((size_t)per);
-      pos.resize((size_t)per);
-      HIP_TRY(hipMemcpyAsync(users.data(), t.users, (size_t)per * sizeof(int), hipMemcpyDeviceToHost, h->st));
-      HIP_TRY(hipMemcpyAsync(pos.data(), t.pos, (size_t)per * sizeof(int), hipMemcpyDeviceToHost, h->st));
-      if (bpr) {
-        neg.resize((size_t)per);
-        HIP_TRY(hipMemcpyAsync(neg.data(), t.neg, (size_t)per * sizeof(int), hipMemcpyDeviceToHost, h->st));
-      }
-      HIP_TRY(hipStreamSynchronize(h->st));
-    }
+    SampleList t;
+    TRY(t.alloc(who, per, !bpr));
+    TRY(sample_draw(h, h->mfs.profiles, !bpr, h->mfs.quota, h->mfs.seed, h->mfs.epoch, per, per, t));
+    if (levelled) TRY(t.ids_to_host(h->st, per, true, users, pos, neg));
     int64_t levels = 0;
     TRY(mf_sgd_run_device(h, who, t, users.data(), pos.data(), bpr ? neg.data() : nullptr, per, batch_size, route, &levels));
     top = std::max(top, levels);

@@ -41,9 +41,20 @@ struct AlsSide {
   bool canonical = false;      // every row's columns ascend without repeats (what the GANMF_MODEL_ITEMSIM entries need)
 };
 
+// The profiles an SGD trainer draws its samples from, on the device (profiles_upload / profiles_drop of lib/sgd_train.inc; draw_kernel):
+// users x items in CSR with ascending items, the stored values where the trainer reads them, and the users with 0 < |profile| < n_items
+struct SampleProfiles {
+  long long* indptr = nullptr;
+  int* items = nullptr;
+  double* ratings = nullptr;      // FunkSVD's; else null
+  int* eligible = nullptr;        // [n_eligible] ascending
+  int n_eligible = 0;
+  int64_t nnz = 0;
+};
+
 // SLIM-BPR training state of a GANMF_MODEL_ITEMSIM handle (ganmf_slim_bpr_init; slim_bpr.hpp): S and the optimiser state in float64,
-// the profiles the samples are drawn from and summed over (a copy of side 0's pattern, or the caller's), the eligible users, and what
-// the host carries from call to call: the epoch counter of the sampler and Adam's beta powers
+// the profiles the samples are drawn from and summed over (a copy of side 0's pattern, or the caller's), and what the host carries
+// from call to call: the epoch counter of the sampler and Adam's beta powers
 struct SlimState {
   bool ready = false;
   int symmetric = 0, sgd = 0;
@@ -52,30 +63,23 @@ struct SlimState {
   int64_t epoch = 0;
   size_t cells = 0;
   double *S = nullptr, *st0 = nullptr, *st1 = nullptr;
-  long long* indptr = nullptr;
-  int* items = nullptr;
-  int* eligible = nullptr;
-  int n_eligible = 0;
+  SampleProfiles profiles;
 };
 
 // SGD matrix-factorisation training state of a GANMF_MODEL_MF handle (ganmf_mf_sgd_init; mf_sgd.hpp).  P holds three blocks of `block`
 // float64 values -- the parameters, st0, st1 -- each laid out [W: U k | H: N k | USER_bias: U | ITEM_bias: N | GLOBAL_bias: 1]; the
-// profiles the samples are drawn from with their stored values, the eligible users, phase 1's per-sample terms of one batch, and what
-// the host carries from call to call: the epoch counter of the sampler and Adam's beta powers (one multiplication per BATCH)
+// profiles the samples are drawn from with their stored values, phase 1's per-sample terms of one batch, and what the host carries
+// from call to call: the epoch counter of the sampler and Adam's beta powers (one multiplication per BATCH)
 struct MfSgdState {
   bool ready = false;
   int algo = 0, k = 0, use_bias = 0, sgd = 0;
   double lr = 0, user_reg = 0, item_reg = 0, pos_reg = 0, neg_reg = 0, bias_reg = 0, quota = 0;
   double gamma = 0.995, b1 = 0.9, b2 = 0.999, b1_pow = 0.9, b2_pow = 0.999;      // (fit() never forwards them: fixed)
   uint64_t seed = 0;
-  int64_t epoch = 0, nnz = 0;
+  int64_t epoch = 0;
   size_t block = 0;
   double* P = nullptr;
-  long long* indptr = nullptr;
-  int* items = nullptr;
-  double* ratings = nullptr;
-  int* eligible = nullptr;
-  int n_eligible = 0;
+  SampleProfiles profiles;
   double* terms = nullptr;
   size_t terms_cap = 0;
 };

@@ -17,26 +17,24 @@
 //     l, l + 64, ...; lane 0 owns the two bias scalars of the sample; nothing crosses lanes.  Per factor (mf_apply):
 //       MF_BPR:   g_i = s W_u - positive_reg H_i;  g_j = s (-W_u) - negative_reg H_j;  g_u = s (H_i - H_j) - user_reg W_u
 //       FUNK_SVD: g_i = s W_u - positive_reg H_i;  g_u = s H_i - user_reg W_u      (the two biases first: g = s - bias_reg b)
-//     each through mf_adapt with the element's own state, then x += lr g.  FUNK_SVD with use_bias updates GLOBAL_bias once per batch in
-//     front of the samples (head != 0: lane 0 of the first wave).  Adam divides by 1 - the beta powers of the BATCH (b1p, b2p: formed
-//     on the host by repeated multiplication, one per batch).
+//     each through sgd_adapt (sgd_adapt.hpp) with the element's own state, then x += lr g.  FUNK_SVD with use_bias updates GLOBAL_bias
+//     once per batch in front of the samples (head != 0: lane 0 of the first wave).  Adam divides by 1 - the beta powers of the BATCH
+//     (b1p, b2p: formed on the host by repeated multiplication, one per batch).
 //
 // Routes (mf_update_kernel).  walk = 1: ONE wave applies the batch in list order; an element is always read and written by the same
 // lane, so program order is all the ordering there is.  walk = 0: wave w applies list[order[lvl_first + w]]; the caller launches one
-// grid per level of mf_sched.hpp, whose samples share no row.  Both routes run mf_apply, so they write the same bytes.  No atomics, no
-// workgroup waits for another inside a kernel.
+// grid per level of level_sched.hpp, whose samples share no row.  Both routes run mf_apply, so they write the same bytes.  No atomics,
+// no workgroup waits for another inside a kernel.
 //
-// Sampler (mf_draw_kernel), one thread per sample, counter-based: the generator and the picks of counter_draw.hpp with the key and
-// the streams of slim_bpr.hpp.  MF_BPR: slim_draw_kernel's triple unchanged.  FUNK_SVD: the same user; a coin on stream 3 -- a
-// positive iff quota == 0 or double(below(word(3, 0), 2^31)) <= quota (2^31 - 1) -- then the positive pick of stream 1 with its
-// stored rating, or the negative pick of stream 2 with rating 0.
+// Sampler: draw_kernel of counter_draw.hpp, which states the scheme in full.  MF_BPR draws the triple (rated = 0), FUNK_SVD one item
+// with its rating (rated = 1).
 //
 // Publish (mf_publish_kernel): the float64 state rounded into the handle's float32 factor tensors; with use_bias two more columns,
 // U' = [W | USER_b + GLOBAL | 1], V' = [H | 1 | ITEM_b], so that U' V'^T is W H^T + ITEM_b + GLOBAL + USER_b[u].
 #pragma once
 #include <hip/hip_runtime.h>
 #include "counter_draw.hpp"
-#include "slim_bpr.hpp"
+#include "sgd_adapt.hpp"
 
 namespace ganmf {
 
@@ -48,7 +46,7 @@ struct MfSgdP {
   double *W, *H, *ub, *ib, *gb;              // parameters
   double *W0, *H0, *ub0, *ib0, *gb0;         // st0 of each
   double *W1, *H1, *ub1, *ib1, *gb1;         // st1 of each
-  int k, algo, use_bias, sgd;                // sgd: SlimSgd
+  int k, algo, use_bias, sgd;                // sgd: SgdMode
   double lr, user_reg, pos_reg, neg_reg, bias_reg, gamma, b1, b2;
   const int* users;                          // the sample list
   const int* pos;
@@ -95,36 +93,11 @@ __global__ __launch_bounds__(MF_SGD_THREADS) void mf_predict_kernel(const MfSgdP
   if (lane == 0) p.terms[w] = term;
 }
 
-// adaptive_gradient (:760-798) on one element's state
-__device__ __forceinline__ double mf_adapt(const MfSgdP& p, double g, double* c0, double* c1, double b1p, double b2p) {
-#pragma clang fp contract(off)
-  if (p.sgd == SLIM_ADAGRAD) {
-    const double c = *c0 + g * g;
-    *c0 = c;
-    return g / (sqrt(c) + 1e-8);
-  }
-  if (p.sgd == SLIM_RMSPROP) {
-    const double c = *c0 * p.gamma + (1.0 - p.gamma) * (g * g);
-    *c0 = c;
-    return g / (sqrt(c) + 1e-8);
-  }
-  if (p.sgd == SLIM_ADAM) {
-    const double m1 = *c0 * p.b1 + (1.0 - p.b1) * g;
-    const double m2 = *c1 * p.b2 + (1.0 - p.b2) * (g * g);
-    *c0 = m1;
-    *c1 = m2;
-    const double h1 = m1 / (1.0 - b1p);
-    const double h2 = m2 / (1.0 - b2p);
-    return h1 / (sqrt(h2) + 1e-8);
-  }
-  return g;
-}
-
 // GLOBAL_bias, once per batch (:338-347); lane 0 of one wave
 __device__ __forceinline__ void mf_global_bias(const MfSgdP& p, double s, double b1p, double b2p) {
 #pragma clang fp contract(off)
   double g = s - p.bias_reg * p.gb[0];
-  g = mf_adapt(p, g, p.gb0, p.gb1, b1p, b2p);
+  g = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, g, p.gb0, p.gb1, b1p, b2p);
   p.gb[0] = p.gb[0] + p.lr * g;
 }
 
@@ -140,9 +113,9 @@ __device__ __forceinline__ void mf_apply(const MfSgdP& p, long long t, double s,
       double gi = s * Wu - p.pos_reg * Hi;
       double gj = s * (-Wu) - p.neg_reg * Hj;
       double gu = s * (Hi - Hj) - p.user_reg * Wu;
-      gi = mf_adapt(p, gi, p.H0 + ri + f, p.H1 + ri + f, b1p, b2p);
-      gj = mf_adapt(p, gj, p.H0 + rj + f, p.H1 + rj + f, b1p, b2p);
-      gu = mf_adapt(p, gu, p.W0 + ru + f, p.W1 + ru + f, b1p, b2p);
+      gi = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, gi, p.H0 + ri + f, p.H1 + ri + f, b1p, b2p);
+      gj = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, gj, p.H0 + rj + f, p.H1 + rj + f, b1p, b2p);
+      gu = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, gu, p.W0 + ru + f, p.W1 + ru + f, b1p, b2p);
       p.W[ru + f] = Wu + p.lr * gu;
       p.H[ri + f] = Hi + p.lr * gi;
       p.H[rj + f] = Hj + p.lr * gj;
@@ -152,8 +125,8 @@ __device__ __forceinline__ void mf_apply(const MfSgdP& p, long long t, double s,
   if (p.use_bias && lane == 0) {
     double gbi = s - p.bias_reg * p.ib[i];
     double gbu = s - p.bias_reg * p.ub[u];
-    gbi = mf_adapt(p, gbi, p.ib0 + i, p.ib1 + i, b1p, b2p);
-    gbu = mf_adapt(p, gbu, p.ub0 + u, p.ub1 + u, b1p, b2p);
+    gbi = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, gbi, p.ib0 + i, p.ib1 + i, b1p, b2p);
+    gbu = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, gbu, p.ub0 + u, p.ub1 + u, b1p, b2p);
     p.ib[i] = p.ib[i] + p.lr * gbi;
     p.ub[u] = p.ub[u] + p.lr * gbu;
   }
@@ -161,8 +134,8 @@ __device__ __forceinline__ void mf_apply(const MfSgdP& p, long long t, double s,
     const double Hi = p.H[ri + f], Wu = p.W[ru + f];
     double gi = s * Wu - p.pos_reg * Hi;
     double gu = s * Hi - p.user_reg * Wu;
-    gi = mf_adapt(p, gi, p.H0 + ri + f, p.H1 + ri + f, b1p, b2p);
-    gu = mf_adapt(p, gu, p.W0 + ru + f, p.W1 + ru + f, b1p, b2p);
+    gi = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, gi, p.H0 + ri + f, p.H1 + ri + f, b1p, b2p);
+    gu = sgd_adapt(p.sgd, p.gamma, p.b1, p.b2, gu, p.W0 + ru + f, p.W1 + ru + f, b1p, b2p);
     p.H[ri + f] = Hi + p.lr * gi;
     p.W[ru + f] = Wu + p.lr * gu;
   }
@@ -182,48 +155,6 @@ __global__ __launch_bounds__(MF_SGD_THREADS) void mf_update_kernel(const MfSgdP 
     for (long long t = first; t < first + count; ++t) mf_apply(p, t, s, b1p, b2p, lane);
   } else {
     mf_apply(p, p.order[lvl_first + w], s, b1p, b2p, lane);
-  }
-}
-
-// ---- the sampler ------------------------------------------------------------------------------------------------------------------
-struct MfDrawP {
-  const long long* indptr;     // the profiles: users x items, items ascending without repeats inside a user
-  const int* items;
-  const double* ratings;       // the stored value of every profile entry
-  const int* eligible;         // [n_eligible] the users with 0 < |profile| < n_items, ascending
-  int n_users, n_items, n_eligible, algo;
-  double quota;
-  unsigned long long seed;
-  long long epoch0, per_epoch, n;      // sample g of the call: epoch epoch0 + g / per_epoch, index g % per_epoch
-  int* users;
-  int* pos;
-  int* neg;                    // MF_BPR
-  double* rating;              // FUNK_SVD
-};
-
-__global__ __launch_bounds__(MF_SGD_THREADS) void mf_draw_kernel(const MfDrawP p) {
-#pragma clang fp contract(off)
-  const long long g = (long long)blockIdx.x * MF_SGD_THREADS + threadIdx.x;
-  if (g >= p.n) return;
-  const unsigned long long epoch = (unsigned long long)(p.epoch0 + g / p.per_epoch), index = (unsigned long long)(g % p.per_epoch);
-  const unsigned long long key = slim_key(p.seed, epoch, index);
-  long long a = 0, b = 0;
-  const int u = slim_draw_user(key, SLIM_ATTEMPTS, p.indptr, p.eligible, p.n_users, p.n_items, p.n_eligible, &a, &b);
-  p.users[g] = u;
-  if (p.algo == MF_SGD_BPR) {
-    p.pos[g] = p.items[slim_draw_positive(key, a, b)];
-    p.neg[g] = slim_draw_negative(key, SLIM_ATTEMPTS, p.items, a, b, p.n_items);
-    return;
-  }
-  bool positive = true;
-  if (p.quota != 0.0) positive = (double)slim_below(slim_word(key, 3, 0), 0x80000000u) <= p.quota * 2147483647.0;
-  if (positive) {
-    const long long q = slim_draw_positive(key, a, b);
-    p.pos[g] = p.items[q];
-    p.rating[g] = p.ratings[q];
-  } else {
-    p.pos[g] = slim_draw_negative(key, SLIM_ATTEMPTS, p.items, a, b, p.n_items);
-    p.rating[g] = 0.0;
   }
 }
 

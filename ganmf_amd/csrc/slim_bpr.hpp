@@ -10,7 +10,7 @@
 //       order, then the 256 partial sums are added by a fixed binary tree in LDS.  The same bytes on every run.
 //   g = 1 / (1 + exp(x)); thread 0 updates the state of i and j and forms the step `upd` (sgd: g; adagrad / rmsprop: g / (sqrt(c_i) +
 //       1e-8); adam: the bias-corrected moments of i ONLY, with the beta powers of this sample, pows[2 t], pows[2 t + 1], formed on
-//       the host by repeated multiplication).
+//       the host by repeated multiplication): the expressions of sgd_adapt.hpp, written out for the two entries together.
 //   every s of the profile, one thread each: s != i: cell(i, s) += lr (upd - li cell(i, s));  s != j: cell(j, s) -= lr (upd - lj cell(j, s)).
 //   No two of these touch one cell, with one exception: symmetric storage and a list that names a j INSIDE the profile (the sampler
 //   never does; an injected list may): cell(i, j) is then written at s = j and at s = i.  Thread 0 applies that pair alone, in the
@@ -18,18 +18,11 @@
 //   Floating-point contraction is off: every product and sum rounds once, as on the reference's x86-64 build.
 //
 // Routes (slim_update_kernel).  walk = 1: ONE workgroup applies list[first, first + count) in order, a barrier between samples.
-// walk = 0: workgroup b applies list[order[first + b]]; the caller launches one grid per level of slim_sched.hpp, whose samples
+// walk = 0: workgroup b applies list[order[first + b]]; the caller launches one grid per level of level_sched.hpp, whose samples
 // share no item.  Both routes run slim_sample, so they write the same bytes.  No workgroup waits for another inside a kernel.
 //
-// Sampler (slim_draw_kernel), one thread per sample, counter-based.  With mix() the output function of splitmix64,
-//     mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
-//     key = mix(mix(mix(seed) ^ epoch) ^ index);   word(stream, attempt) = mix(key ^ (stream << 32 | attempt));
-//     below(w, m) = ((w >> 32) * m) >> 32          (a value in [0, m), m < 2^32)
-//   user:     u = below(word(0, a), n_users) for a = 0, 1, ... until 0 < |profile(u)| < n_items; after SLIM_ATTEMPTS refusals
-//             u = eligible[below(word(0, SLIM_ATTEMPTS), n_eligible)] (the eligible users ascending): uniform over them either way;
-//   positive: i = profile(u)[below(word(1, 0), |profile(u)|)];
-//   negative: j = below(word(2, a), n_items) for a = 0, 1, ... until j is not in the profile (binary search); after SLIM_ATTEMPTS
-//             refusals the k-th item outside the profile, k = below(word(2, SLIM_ATTEMPTS), n_items - |profile(u)|).
+// Sampler: draw_kernel of counter_draw.hpp, which states the scheme in full; SLIM-BPR draws the triple (rated = 0), num_users + 1
+// samples per epoch.
 //
 // get_S (slim_rows_kernel): one workgroup per row; the row is copied (from the triangle when symmetric) into a private float64 row,
 // its diagonal entry zero, and the topk largest are selected in float64 by select_topk_nonzero<double> (topk_rounds.hpp: arg-max
@@ -38,13 +31,12 @@
 #include <hip/hip_runtime.h>
 #include "counter_draw.hpp"
 #include "itemknn_rows.hpp"
+#include "sgd_adapt.hpp"
 
 namespace ganmf {
 
 constexpr int SLIM_THREADS = 256;
 static_assert(SLIM_THREADS == TOPK_THREADS, "slim_rows_kernel selects with the rounds of topk_rounds.hpp");
-constexpr int SLIM_ATTEMPTS = 64;
-enum SlimSgd : int { SLIM_SGD = 0, SLIM_ADAGRAD = 1, SLIM_RMSPROP = 2, SLIM_ADAM = 3, SLIM_SGD_MODES = 4 };
 
 struct SlimP {
   const long long* indptr;     // the profiles: users x items, items ascending without repeats inside a user
@@ -52,7 +44,7 @@ struct SlimP {
   double* S;
   double* st0;
   double* st1;
-  int n_items, symmetric, sgd;
+  int n_items, symmetric, sgd;      // sgd: SgdMode
   double lr, li, lj, gamma, b1, b2;
   const int* users;            // the sample list
   const int* pos;
@@ -89,18 +81,21 @@ __device__ __forceinline__ void slim_sample(const SlimP& p, long long t, double*
   if (tid == 0) {
     const double x = red[0];
     const double g = 1.0 / (1.0 + exp(x));
+    // sgd_adapt's expressions (sgd_adapt.hpp) written out for the PAIR of entries i and j: one test of the mode serves both, j's step
+    // is never formed, and the beta powers are read inside the adam branch.  Two calls of sgd_adapt leave the same bytes and cost the
+    // sequential walk 3 - 8 % (profiles/sgd_shared.md): this section stands between two barriers of every sample.
     double upd = g;
-    if (p.sgd == SLIM_ADAGRAD) {
+    if (p.sgd == SGD_ADAGRAD) {
       const double ci = p.st0[i] + g * g;
       p.st0[i] = ci;
       p.st0[j] = p.st0[j] + g * g;
       upd = g / (sqrt(ci) + 1e-8);
-    } else if (p.sgd == SLIM_RMSPROP) {
+    } else if (p.sgd == SGD_RMSPROP) {
       const double ci = p.st0[i] * p.gamma + (1.0 - p.gamma) * (g * g);
       p.st0[i] = ci;
       p.st0[j] = p.st0[j] * p.gamma + (1.0 - p.gamma) * (g * g);
       upd = g / (sqrt(ci) + 1e-8);
-    } else if (p.sgd == SLIM_ADAM) {
+    } else if (p.sgd == SGD_ADAM) {
       const double m1 = p.st0[i] * p.b1 + (1.0 - p.b1) * g;
       const double m2 = p.st1[i] * p.b2 + (1.0 - p.b2) * (g * g);
       p.st0[i] = m1;
@@ -116,7 +111,7 @@ __device__ __forceinline__ void slim_sample(const SlimP& p, long long t, double*
   __syncthreads();
   const double upd = *sh_upd;
   // symmetric storage and both i and j inside the profile: cell(i, j) is written twice, by thread 0 below
-  const bool pair = sym && slim_in_profile(p.items, a, b, j) && slim_in_profile(p.items, a, b, i);
+  const bool pair = sym && in_profile(p.items, a, b, j) && in_profile(p.items, a, b, i);
   for (long long q = a + tid; q < b; q += SLIM_THREADS) {
     const int s = p.items[q];
     if (s != i && !(pair && s == j)) {
@@ -157,34 +152,6 @@ __global__ __launch_bounds__(SLIM_THREADS) void slim_update_kernel(const SlimP p
     if ((long long)blockIdx.x >= count) return;
     slim_sample(p, p.order[first + blockIdx.x], red, &sh_upd);
   }
-}
-
-// ---- the sampler ------------------------------------------------------------------------------------------------------------------
-// (the generator and the three picks: counter_draw.hpp)
-struct SlimDrawP {
-  const long long* indptr;
-  const int* items;
-  const int* eligible;         // [n_eligible] the users with 0 < |profile| < n_items, ascending
-  int n_users, n_items, n_eligible;
-  unsigned long long seed;
-  long long epoch0, per_epoch, n;      // sample g of the call: epoch epoch0 + g / per_epoch, index g % per_epoch
-  int* users;
-  int* pos;
-  int* neg;
-};
-
-__global__ __launch_bounds__(SLIM_THREADS) void slim_draw_kernel(const SlimDrawP p) {
-  const long long g = (long long)blockIdx.x * SLIM_THREADS + threadIdx.x;
-  if (g >= p.n) return;
-  const unsigned long long epoch = (unsigned long long)(p.epoch0 + g / p.per_epoch), index = (unsigned long long)(g % p.per_epoch);
-  const unsigned long long key = slim_key(p.seed, epoch, index);
-  long long a = 0, b = 0;
-  const int u = slim_draw_user(key, SLIM_ATTEMPTS, p.indptr, p.eligible, p.n_users, p.n_items, p.n_eligible, &a, &b);
-  const int i = p.items[slim_draw_positive(key, a, b)];
-  const int j = slim_draw_negative(key, SLIM_ATTEMPTS, p.items, a, b, p.n_items);
-  p.users[g] = u;
-  p.pos[g] = i;
-  p.neg[g] = j;
 }
 
 // ---- get_S: the diagonal, and the top-k of every row in float64 ---------------------------------------------------------------------

@@ -564,7 +564,7 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
 
 /* SLIM-BPR trained on the device (SLIM_BPR/Cython/SLIM_BPR_Cython_Epoch.pyx: the epoch :198-347, the sampler :427-471, get_S
  * :373-421; dense and symmetric storage, not the tree-CSR mode).  All entries need a GANMF_MODEL_ITEMSIM handle; everything is
- * float64, as in the reference.  ganmf_amd/csrc/slim_bpr.hpp states the kernels, the storage and the generator in full.
+ * float64, as in the reference.  ganmf_amd/csrc/slim_bpr.hpp states the kernels and the storage in full, counter_draw.hpp the sampler.
  * ganmf_slim_bpr_init: allocates S -- [num_items, num_items], or with symmetric != 0 one cell per unordered pair of items, S[a, b]
  *   and S[b, a] being one value -- and the per-item optimiser state (state0: the AdaGrad / RMSprop cache or Adam's first moment;
  *   state1: Adam's second moment), all zero, and resets the epoch counter and Adam's beta powers (beta_1, beta_2).  The profiles the
@@ -584,7 +584,7 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
  *     S[j, s] -= lr (upd - lambda_j S[j, s]) for s != j.
  *   One workgroup per sample; the sum is a fixed tree: the same bytes on every run.  mode GANMF_SLIM_SEQUENTIAL: one workgroup walks
  *   the list in order.  GANMF_SLIM_LEVELLED (symmetric = 0 only): a sample touches rows i and j of S and the state of i and j only, so
- *   the host sorts the list into levels (ganmf_amd/csrc/slim_sched.hpp: level = 1 + the larger level of the last earlier samples that
+ *   the host sorts the list into levels (ganmf_amd/csrc/level_sched.hpp: level = 1 + the larger level of the last earlier samples that
  *   named i or j) and launches one grid per level; the bytes are those of the sequential route.  GANMF_SLIM_AUTO: levelled when
  *   symmetric = 0.  *n_levels (may be NULL) receives the number of levels, 0 on the sequential route.  n = 0 is allowed.  Errors (-1,
  *   nothing enqueued): ids out of range, pos[t] == neg[t], an unknown mode, LEVELLED with symmetric storage, no training state.
@@ -716,7 +716,7 @@ const char* ganmf_last_error(void);
 
 /* ---- MF-BPR and FunkSVD trained on the device (MatrixFactorization/Cython/MatrixFactorization_Cython_Epoch.pyx: the epochs :287-389
  * and :614-696, adaptive_gradient :760-798, the samplers :803-910) on a GANMF_MODEL_MF handle.  float64, as in the reference;
- * ganmf_amd/csrc/mf_sgd.hpp states the kernels, the summation orders and the sampler in full.  New entries; no structure or signature
+ * ganmf_amd/csrc/mf_sgd.hpp states the kernels and the summation orders in full, counter_draw.hpp the sampler.  New entries; no structure or signature
  * changed: GANMF_ABI_VERSION stays.
  * init: allocates W [num_users, k], H [num_items, k], the three biases and two optimiser values per element, in float64, with
  *   k = the handle's num_factors - 2 use_bias (a biased model publishes two more columns, see publish); W and H start as
@@ -733,7 +733,7 @@ const char* ganmf_last_error(void);
  * run: applies the n samples in mini-batches of batch_size (the last one may be shorter) with the reference's semantics: per batch
  *   one scalar, the mean over the batch of 1 / (1 + exp(x_uij)) or of rating - prediction at frozen parameters, then the samples in
  *   list order, each reading the current rows.  GANMF_MF_SGD_SEQUENTIAL: one wave walks a batch in order (2 launches per batch).
- *   GANMF_MF_SGD_LEVELLED (and AUTO): the host sorts every batch into levels (ganmf_amd/csrc/mf_sched.hpp) and launches one grid
+ *   GANMF_MF_SGD_LEVELLED (and AUTO): the host sorts every batch into levels (ganmf_amd/csrc/level_sched.hpp) and launches one grid
  *   per level; the bytes are those of the sequential route.  *n_levels (may be NULL): the largest level count of a batch (0 on the
  *   sequential route).  Errors (-1, nothing enqueued): an id out of range, a BPR sample with equal items, a rating that is not
  *   finite, batch_size outside [1, GANMF_MF_SGD_MAX_BATCH].

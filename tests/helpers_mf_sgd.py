@@ -1,6 +1,6 @@
 """MF-BPR and FunkSVD restated on the host in float64, for the tests of ganmf_mf_sgd_* and of the MatrixFactorization_*_Cython
 classes: the reference's two epochs (MatrixFactorization/Cython/MatrixFactorization_Cython_Epoch.pyx:287-389, :614-696) with its
-adaptive_gradient (:760-798), in two summation orders; the device's counter-based sampler (csrc/mf_sgd.hpp); glibc's rand() with
+adaptive_gradient (:760-798), in two summation orders; the device's counter-based sampler (csrc/counter_draw.hpp); glibc's rand() with
 the reference's own two samplers on top of it (:803-910), which is how tools/make_mf_sgd_fixture.py predicts the sample list of a
 seeded reference run; and a stand-in for the engine.
 Plain Python floats: every product and sum rounds once."""
@@ -189,7 +189,7 @@ def per_epoch(algorithm, profiles, batch_size):
 
 
 def draw(algorithm, seed, epoch, n_epochs, profiles, batch_size, quota=0.0):
-    """the samples of the epochs [epoch, epoch + n_epochs) as mf_draw_kernel draws them: (users, items, neg_items) int32 for MF_BPR,
+    """the samples of the epochs [epoch, epoch + n_epochs) as draw_kernel (csrc/counter_draw.hpp) draws them: (users, items, neg_items) int32 for MF_BPR,
     (users, items, ratings float64) for FUNK_SVD"""
     m = sps.csr_matrix(profiles)
     m.sort_indices()

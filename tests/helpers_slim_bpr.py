@@ -1,6 +1,6 @@
 """SLIM-BPR restated on the host in float64, for the tests of ganmf_slim_bpr_* and of the SLIM_BPR_Cython class: the reference's epoch
 (SLIM_BPR/Cython/SLIM_BPR_Cython_Epoch.pyx:198-347: four optimisers x dense / symmetric storage), get_S with the class's column top-K
-(:373-421, SLIM_BPR_Cython.py:188-197) under the device's tie rule, and the device's counter-based sampler (csrc/slim_bpr.hpp).
+(:373-421, SLIM_BPR_Cython.py:188-197) under the device's tie rule, and the device's counter-based sampler (csrc/counter_draw.hpp).
 Plain Python floats: every product and sum rounds once, in the reference's order."""
 import math
 
@@ -10,7 +10,7 @@ import scipy.sparse as sps
 from tests import helpers_itemknn as HK
 
 M64 = (1 << 64) - 1
-ATTEMPTS = 64      # csrc/slim_bpr.hpp SLIM_ATTEMPTS
+ATTEMPTS = 64      # csrc/counter_draw.hpp DRAW_ATTEMPTS
 THREADS = 256      # csrc/slim_bpr.hpp SLIM_THREADS
 
 

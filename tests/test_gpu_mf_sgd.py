@@ -208,6 +208,26 @@ def test_sampler_equals_its_restatement_and_respects_the_profiles(algorithm, quo
     other.close()
 
 
+def test_mf_bpr_and_slim_bpr_draw_the_same_triples():
+    """there is ONE sampler (draw_kernel of counter_draw.hpp): with the same profiles, the same seed and the same samples per epoch
+    -- SLIM-BPR's is num_users + 1, MF-BPR's at batch_size = num_users + 1 is (num_users // batch_size + 1) * batch_size, the same --
+    the two entries return the same arrays"""
+    from ganmf_amd import _lib as L
+    from ganmf_amd.engine import Engine
+    urm = _urm(40, 70)
+    U0, V0 = _factors(urm, 4)
+    mf = _engine(urm, "MF_BPR", False, "sgd", U0, V0, seed=31)
+    slim = Engine(40, 70, 1, 1, 1, model=L.MODEL_ITEMSIM)
+    slim.slim_bpr_init(symmetric=False, sgd_mode="sgd", seed=31, profiles=sps.csr_matrix(urm, dtype=np.float32))
+    a, b = mf.mf_sgd_draw(0, 2, batch_size=41), slim.slim_bpr_draw(0, 2)
+    assert a[0].size == b[0].size == 2 * 41
+    for x, y in zip(a, b):
+        assert x.dtype == y.dtype == np.int32 and np.array_equal(x, y)
+    assert len(set(a[0])) > 10 and not np.any(np.isin(a[0], [0, 1]))      # (a real draw: many users, never the empty or the full one)
+    mf.close()
+    slim.close()
+
+
 @pytest.mark.parametrize("algorithm,use_bias", CONFIGS)
 def test_epochs_is_draw_followed_by_run(algorithm, use_bias):
     from ganmf_amd import _lib as L

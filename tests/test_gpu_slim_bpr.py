@@ -226,7 +226,7 @@ def test_sampler_equals_its_restatement_and_respects_the_profiles(n_items):
 
 
 def test_sampler_user_fallback_and_given_profiles():
-    """one eligible user among 500 (further than SLIM_ATTEMPTS draws away for most samples), and profiles that are not side 0"""
+    """one eligible user among 500 (further than DRAW_ATTEMPTS draws away for most samples), and profiles that are not side 0"""
     rows = np.zeros((500, 6), dtype=np.float32)
     rows[499, 3] = 1
     rows[7] = 1

@@ -90,12 +90,14 @@ def test_the_entries_are_declared_and_bound():
     assert int(re.search(r"#define GANMF_ABI_VERSION (\d+)", text).group(1)) == L.ABI_VERSION == 2
     for method in ("mf_sgd_init", "mf_sgd_draw", "mf_sgd_run", "mf_sgd_epochs", "mf_sgd_publish", "mf_sgd_state", "mf_sgd_set_state"):
         assert callable(getattr(Engine, method))
-    # the generator is shared with SLIM-BPR, not copied
+    # the generator and the sampler kernel are shared with SLIM-BPR, not copied
     csrc = os.path.join(ROOT, "ganmf_amd", "csrc")
-    assert "slim_mix(" not in open(os.path.join(csrc, "mf_sgd.hpp")).read().split("#pragma once")[1]
-    assert open(os.path.join(csrc, "counter_draw.hpp")).read().count("unsigned long long slim_mix(unsigned long long z) {") == 1
+    draw = open(os.path.join(csrc, "counter_draw.hpp")).read()
+    assert draw.count("unsigned long long draw_mix(unsigned long long z) {") == 1 and draw.count("void draw_kernel(const DrawP p) {") == 1
     for header in ("slim_bpr.hpp", "mf_sgd.hpp"):
-        assert '#include "counter_draw.hpp"' in open(os.path.join(csrc, header)).read()
+        text = open(os.path.join(csrc, header)).read()
+        assert '#include "counter_draw.hpp"' in text
+        assert "draw_mix(" not in text.split("#pragma once")[1] and "__global__" in text and "draw_kernel(const" not in text
 
 
 def test_driver_import_sequence_with_reference_tree_behind(tmp_path):

@@ -1,11 +1,9 @@
 """MF-BPR and FunkSVD without a device: the float64 restatement (tests/helpers_mf_sgd.py) against cases worked out by hand and against
-what the reference's compiled epoch recorded (tests/golden/mf_sgd_tiny.npz), the level scheduler (ganmf_amd/csrc/mf_sched.hpp) in a
-stand-alone sanitized program, and the host logic of the MatrixFactorization_*_Cython classes on a helper engine."""
+what the reference's compiled epoch recorded (tests/golden/mf_sgd_tiny.npz), and the host logic of the MatrixFactorization_*_Cython classes on a
+helper engine.  (The level scheduler: tests/test_level_sched_host.py.)"""
 import json
 import math
 import os
-import shutil
-import subprocess
 import zipfile
 
 import numpy as np
@@ -182,34 +180,8 @@ def test_restatement_reproduces_the_reference(golden, n):
     assert np.abs(final["USER_factors"] - U0).max() > 1e-2
 
 
-# ---- the scheduler -------------------------------------------------------------------------------------------------------------------------
-def _compiler():
-    for c in (os.environ.get("CXX"), "g++", "clang++", "c++"):
-        if c and shutil.which(c):
-            return shutil.which(c)
-    raise AssertionError("no host C++ compiler found")
-
-
-def test_scheduler_program_sanitized(tmp_path):
-    exe = str(tmp_path / "mf_sched_check")
-    src = os.path.join(ROOT, "tests", "mf_sched_check.cpp")
-    base = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe]
-    cc = subprocess.run(base + ["-static-libasan", "-static-libubsan"], capture_output=True, text=True)
-    if cc.returncode != 0:
-        cc = subprocess.run(base, capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, (run.stdout[-3000:] + run.stderr[-3000:])
-    assert "all schedules clean" in run.stdout and "FAIL" not in run.stdout
-    for name in ("empty", "independent", "shared user", "shared positive", "j becomes i", "i becomes j", "j ignored by funk",
-                 "one user in every sample", "two chains", "clean after a refusal", "out of range"):
-        assert "ok   " + name in run.stdout
-    assert "ok   one user in every sample: 40 samples, 40 levels" in run.stdout and "ok   independent funk: 4 samples, 1 levels" in run.stdout
-
-
-def test_the_scheduler_header_has_no_hip_in_it():
-    text = open(os.path.join(ROOT, "ganmf_amd", "csrc", "mf_sched.hpp")).read()
-    assert "hip" not in text.lower().replace("relationship", "")
+# ---- the restated constant -----------------------------------------------------------------------------------------------------------------
+def test_the_restated_wave_width_is_the_kernels():
     assert open(os.path.join(ROOT, "ganmf_amd", "csrc", "mf_sgd.hpp")).read().count("constexpr int MF_SGD_WAVE = %d;" % H.WAVE) == 1
 
 

@@ -84,6 +84,6 @@ def test_the_entries_are_declared_and_bound():
         assert callable(getattr(Engine, method))
     # the restated constants are the kernels'
     from tests import helpers_slim_bpr as H
-    hpp = open(os.path.join(ROOT, "ganmf_amd", "csrc", "slim_bpr.hpp")).read()
-    assert int(re.search(r"constexpr int SLIM_ATTEMPTS = (\d+);", hpp).group(1)) == H.ATTEMPTS
-    assert int(re.search(r"constexpr int SLIM_THREADS = (\d+);", hpp).group(1)) == H.THREADS
+    csrc = os.path.join(ROOT, "ganmf_amd", "csrc")
+    assert int(re.search(r"constexpr int DRAW_ATTEMPTS = (\d+);", open(os.path.join(csrc, "counter_draw.hpp")).read()).group(1)) == H.ATTEMPTS
+    assert int(re.search(r"constexpr int SLIM_THREADS = (\d+);", open(os.path.join(csrc, "slim_bpr.hpp")).read()).group(1)) == H.THREADS

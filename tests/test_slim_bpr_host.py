@@ -1,9 +1,7 @@
-"""SLIM-BPR without a device: the float64 restatement (tests/helpers_slim_bpr.py) against cases worked out by hand, the level scheduler
-(ganmf_amd/csrc/slim_sched.hpp) in a stand-alone sanitized program, and the host logic of SLIM_BPR_Cython on a helper engine."""
+"""SLIM-BPR without a device: the float64 restatement (tests/helpers_slim_bpr.py) against cases worked out by hand, and the
+host logic of SLIM_BPR_Cython on a helper engine.  (The level scheduler: tests/test_level_sched_host.py.)"""
 import math
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -141,7 +139,7 @@ def test_sampler_restatement_properties():
     # epochs are addressed, not streamed: epoch 7 alone is the eighth block of epochs 0..7
     e7 = H.draw(11, 7, 1, m)
     assert np.array_equal(e7[2], neg[7 * 7:8 * 7])
-    # the user fall-back: one eligible user among 500, further than SLIM_ATTEMPTS draws away for most samples
+    # the user fall-back: one eligible user among 500, further than DRAW_ATTEMPTS draws away for most samples
     lone = _profiles([[]] * 499 + [[3]], 6)
     u2, p2, n2 = H.draw(1, 0, 1, lone)
     assert set(u2) == {499} and set(p2) == {3} and 3 not in set(n2) and len(set(n2)) == 5
@@ -151,35 +149,6 @@ def test_generator_words_by_hand():
     # splitmix64's first outputs for the state 0 are published: mix(0) is the first one
     assert H.mix(0) == 0xE220A8397B1DCDAF
     assert H.below(0xFFFFFFFF00000000, 10) == 9 and H.below(0, 10) == 0 and H.below(0x8000000000000000, 7) == 3
-
-
-# ---- the scheduler -------------------------------------------------------------------------------------------------------------------------
-def _compiler():
-    for c in (os.environ.get("CXX"), "g++", "clang++", "c++"):
-        if c and shutil.which(c):
-            return shutil.which(c)
-    raise AssertionError("no host C++ compiler found")
-
-
-def test_scheduler_program_sanitized(tmp_path):
-    exe = str(tmp_path / "slim_sched_check")
-    src = os.path.join(ROOT, "tests", "slim_sched_check.cpp")
-    base = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe]
-    cc = subprocess.run(base + ["-static-libasan", "-static-libubsan"], capture_output=True, text=True)
-    if cc.returncode != 0:
-        cc = subprocess.run(base, capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, (run.stdout[-3000:] + run.stderr[-3000:])
-    assert "all schedules clean" in run.stdout and "FAIL" not in run.stdout
-    for name in ("empty", "independent", "repeated i", "i becomes j", "j becomes i", "two chains", "out of range"):
-        assert "ok   " + name in run.stdout
-    assert "ok   repeated i: 40 samples, 40 levels" in run.stdout and "ok   independent: 5 samples, 1 levels" in run.stdout
-
-
-def test_the_scheduler_header_has_no_hip_in_it():
-    text = open(os.path.join(ROOT, "ganmf_amd", "csrc", "slim_sched.hpp")).read()
-    assert "hip" not in text.replace("slim_bpr.hpp", "").replace("No HIP", "").replace("no HIP", "").lower().replace("relationship", "")
 
 
 # ---- the class on a helper engine ------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ num_factors 10 and 250.
 How the numbers are taken: every timed region is a host clock around ganmf_mf_sgd_epochs(1), which blocks until the device is done.
 One untimed warm-up epoch, then `reps` epochs; the median, the minimum and the maximum are reported.  The time of an epoch includes
 the sampler launch, and on the levelled route the copy of the samples' ids to the host and the schedule.  The launch count is formed
-on the host from the epoch's own samples (ganmf_mf_sgd_draw) with the rule of csrc/mf_sched.hpp: one sampler launch, per batch one
+on the host from the epoch's own samples (ganmf_mf_sgd_draw) with the rule of csrc/level_sched.hpp: one sampler launch, per batch one
 predict launch and one update launch per level (sequential route: one).  A run without a GPU fails: there is no fallback.
 
 --host compiles the reference's .pyx as tools/make_mf_sgd_fixture.py does (into a temporary directory) and times its epoch on the
@@ -43,7 +43,7 @@ def _train():
 
 
 def batch_levels(users, items, neg, batch_size):
-    """levels of every batch of the list, by the rule of csrc/mf_sched.hpp"""
+    """levels of every batch of the list, by the rule of csrc/level_sched.hpp"""
     out = []
     for first in range(0, users.size, batch_size):
         lu, li, top = {}, {}, 0
