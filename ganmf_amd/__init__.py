@@ -6,7 +6,8 @@ fallback: without the HIP library and a GPU the classes raise.
 """
 from ._lib import build_library, library_path, load_library  # noqa: F401
 
-__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "CFGAN", "CAAE", "IALSRecommender", "PureSVDRecommender"]
+__all__ = ["build_library", "library_path", "load_library", "GANMF", "DisGANMF", "CFGAN", "CAAE", "IALSRecommender", "PureSVDRecommender",
+           "NMFRecommender"]
 
 
 def __getattr__(name):
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name == "PureSVDRecommender":
         from .PureSVD import PureSVDRecommender
         return PureSVDRecommender
+    if name == "NMFRecommender":
+        from .NMF import NMFRecommender
+        return NMFRecommender
     raise AttributeError(name)

@@ -21,6 +21,8 @@ MF_SGD_AUTO, MF_SGD_SEQUENTIAL, MF_SGD_LEVELLED = 0, 1, 2
 MF_SGD_MAX_FACTORS, MF_SGD_MAX_BATCH = 1024, 1 << 20
 ALS_MAX_FACTORS = 256              # include/ganmf_hip.h GANMF_ALS_MAX_FACTORS
 SVD_MAX_RANDOM = 280               # include/ganmf_hip.h GANMF_SVD_MAX_RANDOM
+NMF_MAX_FACTORS = 270              # include/ganmf_hip.h GANMF_NMF_MAX_FACTORS
+NMF_FROBENIUS, NMF_KULLBACK_LEIBLER = 0, 1      # include/ganmf_hip.h GANMF_NMF_*: the beta_loss of ganmf_nmf_mu / ganmf_nmf_error
 FLAG_MFMA_F32, FLAG_MFMA_BF16, FLAG_MFMA_F16 = 1, 2, 4     # include/ganmf_hip.h GANMF_FLAG_*
 MFMA_FLAGS = {None: 0, "auto": 0, "f32": FLAG_MFMA_F32, "bf16": FLAG_MFMA_BF16, "f16": FLAG_MFMA_F16}
 ACT = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
@@ -38,7 +40,7 @@ EVAL_MAX_CUTOFFS = 8
 EVAL_MAX_GROUPS = 256             # include/ganmf_hip.h GANMF_EVAL_MAX_GROUPS
 # ganmf_evaluate_full's sums per cut-off (GANMF_EVAL_FULL_METRICS): NON_EMPTY = number of non-empty lists
 EVAL_FULL_METRICS = EVAL_METRICS + ("RMSE", "NOVELTY", "AVERAGE_POPULARITY", "NON_EMPTY")
-PROF_MAX = 64
+PROF_MAX = 80
 RECOMMEND_MAX_CUTOFF = 1024        # include/ganmf_hip.h GANMF_RECOMMEND_MAX_CUTOFF
 CANDIDATES_MAX_PER_ROW = 8192     # include/ganmf_hip.h GANMF_CANDIDATES_MAX_PER_ROW
 
@@ -47,7 +49,7 @@ SYMBOLS = [
     "ganmf_create", "ganmf_destroy", "ganmf_comm_unique_id", "ganmf_comm_init", "ganmf_comm_init_local", "ganmf_comm_abort", "ganmf_comm_info", "ganmf_set_urm_csr",
     "ganmf_set_tensor", "ganmf_get_tensor", "ganmf_tensor_shape", "ganmf_get_adam_powers",
     "ganmf_set_adam_powers", "ganmf_train_epoch", "ganmf_train_epoch_ragged", "ganmf_train_step", "ganmf_scores",
-    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_p3_fit", "ganmf_slim_bpr_init", "ganmf_slim_bpr_draw", "ganmf_slim_bpr_run", "ganmf_slim_bpr_epochs", "ganmf_slim_bpr_finish", "ganmf_slim_bpr_get_state", "ganmf_mf_sgd_init", "ganmf_mf_sgd_draw", "ganmf_mf_sgd_run", "ganmf_mf_sgd_epochs", "ganmf_mf_sgd_publish", "ganmf_mf_sgd_get_state", "ganmf_mf_sgd_set_state", "ganmf_cfgan_init", "ganmf_cfgan_draw_masks", "ganmf_cfgan_set_masks", "ganmf_cfgan_get_masks", "ganmf_cfgan_step", "ganmf_cfgan_epoch", "ganmf_caae_init", "ganmf_caae_cdf", "ganmf_caae_draw_perm", "ganmf_caae_draw_negatives", "ganmf_caae_draw_batch", "ganmf_caae_get_draws", "ganmf_caae_d_step", "ganmf_caae_g_step", "ganmf_caae_epoch", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
+    "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_nmf_mu", "ganmf_nmf_cd", "ganmf_nmf_error", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_p3_fit", "ganmf_slim_bpr_init", "ganmf_slim_bpr_draw", "ganmf_slim_bpr_run", "ganmf_slim_bpr_epochs", "ganmf_slim_bpr_finish", "ganmf_slim_bpr_get_state", "ganmf_mf_sgd_init", "ganmf_mf_sgd_draw", "ganmf_mf_sgd_run", "ganmf_mf_sgd_epochs", "ganmf_mf_sgd_publish", "ganmf_mf_sgd_get_state", "ganmf_mf_sgd_set_state", "ganmf_cfgan_init", "ganmf_cfgan_draw_masks", "ganmf_cfgan_set_masks", "ganmf_cfgan_get_masks", "ganmf_cfgan_step", "ganmf_cfgan_epoch", "ganmf_caae_init", "ganmf_caae_cdf", "ganmf_caae_draw_perm", "ganmf_caae_draw_negatives", "ganmf_caae_draw_batch", "ganmf_caae_get_draws", "ganmf_caae_d_step", "ganmf_caae_g_step", "ganmf_caae_epoch", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
     "ganmf_bench_scores", "ganmf_gemm_f32", "ganmf_gemm_f32_ex", "ganmf_crc32c", "ganmf_device_count", "ganmf_abi_version", "ganmf_last_error",
 ]
 
@@ -141,6 +143,9 @@ def load_library():
         "ganmf_als_set_confidence": (C.c_int, [vp, C.c_int, P(C.c_int64), P(C.c_int32), f32p, i64, i64]),
         "ganmf_als_half_sweep": (C.c_int, [vp, C.c_int, C.c_float]),
         "ganmf_pure_svd": (C.c_int, [vp, f32p, C.c_int, C.c_int, f32p]),
+        "ganmf_nmf_mu": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, P(C.c_double)]),
+        "ganmf_nmf_cd": (C.c_int, [vp, P(C.c_int32), C.c_int, C.c_int, P(C.c_double)]),
+        "ganmf_nmf_error": (C.c_int, [vp, C.c_int, P(C.c_double)]),
         "ganmf_itemknn_fit": (C.c_int, [vp, C.c_int, i32, C.c_float, C.c_float, C.c_float, f32p, f32p, P(C.c_int64)]),
         "ganmf_itemknn_get": (C.c_int, [vp, P(C.c_int64), P(C.c_int32), f32p]),
         "ganmf_set_item_similarity": (C.c_int, [vp, P(C.c_int64), P(C.c_int32), f32p, i64]),

@@ -46,6 +46,7 @@
 #include "disc_rows.hpp"
 #include "als_rows.hpp"
 #include "svd_rows.hpp"
+#include "nmf_rows.hpp"
 #include "itemknn_rows.hpp"
 #include "p3_rows.hpp"
 #include "level_sched.hpp"
@@ -87,6 +88,7 @@ extern "C" {
 #include "lib/abi_disc.inc"
 #include "lib/abi_als.inc"
 #include "lib/abi_svd.inc"
+#include "lib/abi_nmf.inc"
 #include "lib/abi_itemknn.inc"
 #include "lib/abi_p3.inc"
 #include "lib/abi_slim.inc"

@@ -274,6 +274,8 @@ int ganmf_destroy(ganmf_handle* h) {
   hipFree(h->mfs.P); hipFree(h->mfs.terms); profiles_drop(h->mfs.profiles);
   hipFree(h->svd_P[0]); hipFree(h->svd_P[1]); hipFree(h->svd_G); hipFree(h->svd_X); hipFree(h->svd_Wl);
   hipFree(h->svd_lam); hipFree(h->svd_flag);
+  hipFree(h->nmf_den); hipFree(h->nmf_num); hipFree(h->nmf_G); hipFree(h->nmf_q); hipFree(h->nmf_vec); hipFree(h->nmf_rowd); hipFree(h->nmf_part);
+  hipFree(h->nmf_scal); hipFree(h->nmf_perm); hipFree(h->nmf_rowidx); hipFree(h->nmf_errp);
   hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
   cfgan_free(h);
   caae_free(h);

@@ -22,16 +22,17 @@ static int svd_ensure(ganmf_handle* h, int ldl) {
   return 0;
 }
 
-// Y[rows of the side, l] = side . Q
-static int svd_spmm(ganmf_handle* h, const AlsSide& s, const float* Q, float* Y, int l, int ldl) {
+// Y[rows of the side, l] = side . Q, with the side's own values or (ganmf_nmf_*) another value array over the same pattern
+static int svd_spmm(ganmf_handle* h, const AlsSide& s, const float* Q, float* Y, int l, int ldl, const float* val = nullptr,
+                    int tag = T_SVD_SPMM) {
   SvdSpmmP p{};
-  p.indptr = s.indptr; p.indices = s.indices; p.val = s.conf; p.Q = Q; p.Y = Y; p.ldq = ldl; p.ldy = ldl; p.n_rows = (int)s.rows;
+  p.indptr = s.indptr; p.indices = s.indices; p.val = val ? val : s.conf; p.Q = Q; p.Y = Y; p.ldq = ldl; p.ldy = ldl; p.n_rows = (int)s.rows;
   p.nc4 = (l + 3) / 4;
   const int groups = SVD_SPMM_THREADS / p.nc4;
   p.gpr = groups >= 8 ? 4 : groups;
   p.rows_per_wg = groups >= 8 ? groups / 4 : 1;
   if (s.rows == 0) return 0;
-  Scope sc(h, T_SVD_SPMM, 2.0 * s.nnz * l, 4.0 * s.nnz * l + 8.0 * s.nnz + 4.0 * s.rows * l);
+  Scope sc(h, tag, 2.0 * s.nnz * l, 4.0 * s.nnz * l + 8.0 * s.nnz + 4.0 * s.rows * l);
   GANMF_LAUNCH(svd_spmm_kernel, dim3((unsigned)((s.rows + p.rows_per_wg - 1) / p.rows_per_wg)), dim3(SVD_SPMM_THREADS), 0, h->st, p);
   HIP_TRY(hipGetLastError());
   return 0;

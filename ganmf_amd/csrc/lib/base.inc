@@ -90,6 +90,7 @@ enum Tag : int {
   T_DIS_GW, T_RED_DIS_GW, T_DIS_BWD, T_RED_DIS_BWD, T_FRONT, T_GWD_RED, T_PAIR, T_DE_DCOEF, T_WPAIR,
   T_COLL_WE, T_COLL_WD, T_COLL_V, T_JOIN_WE, T_JOIN_WD, T_JOIN_V, T_SIM_GRAM, T_SIM_AUX, T_EVAL_GROUPS,
   T_SVD_SPMM, T_SVD_GRAM, T_SVD_GRAM_RED, T_SVD_APPLY, T_SVD_APPLY_RED, T_SVD_CHOL, T_SVD_EIG, T_SVD_GLUE,
+  T_NMF_SPMM, T_NMF_GRAM, T_NMF_GRAM_RED, T_NMF_MU_ROWS, T_NMF_CD_ROWS, T_NMF_SAMPLED, T_NMF_REDUCE,
   T_KNN_FIT, T_KNN_PACK, T_KNN_SCORE, T_P3_ROWS, T_P3_NORMALIZE, T_P3_COLUMNS, T_COUNT
 };
 const char* const kTagName[T_COUNT] = {
@@ -113,6 +114,10 @@ const char* const kTagName[T_COUNT] = {
   // ganmf_pure_svd: sparse x dense panel, Gram and apply products with their split-K sums, Cholesky + inverse, Jacobi, select / finish
   "svd_spmm[rows,nnz]x[cols,l]", "svd_gram[n,l]^Tx[n,l]", "reduce_svd_gram", "svd_apply[n,l]x[l,.]", "reduce_svd_apply",
   "svd_cholesky_inverse[l,l]", "svd_jacobi[l,l]", "svd_select / finish",
+  // ganmf_nmf_*: sparse x factor, the Gram matrix of a factor with its split-K sum, the two row solvers, the sampled products of the
+  // Kullback-Leibler loss, column sums / traces / totals (the item-similarity classes keep the end of the enum: tests/test_p3_dropin.py)
+  "nmf_spmm[rows,nnz]x[cols,k]", "nmf_gram[n,k]^Tx[n,k]", "reduce_nmf_gram", "nmf_mu_rows", "nmf_cd_rows", "nmf_sampled[nnz]",
+  "nmf_colsum / dot / sum",
   // ganmf_itemknn_fit: one similarity row and its top-k per item, the columns packed by neighbour id; the sparse scoring product
   "itemknn_fit: similarity row + top-k", "itemknn_pack", "itemknn_scores[n,items]x W",
   // ganmf_p3_fit: one row of the random walk and its top-k per source item, the row normalisation, the top-k per target item

@@ -360,6 +360,14 @@ struct ganmf_handle {
   float *svd_G = nullptr, *svd_X = nullptr, *svd_Wl = nullptr, *svd_lam = nullptr;
   int* svd_flag = nullptr;
   int svd_ldl = 0;
+  // ganmf_nmf_* (nmf_rows.hpp): the denominator and numerator panels [max(U, N), ldk], the Gram matrices of both factors [2][ldk, ldk], the value
+  // array of the sampled products [nnz], the two column-sum vectors [2][ldk], the per-row float64 values [2 max(U, N)], the partial
+  // sums [NMF_PARTS], the scalars [4 + iterations] and the permutations of a call; allocated by the first call, grown on demand
+  float *nmf_den = nullptr, *nmf_num = nullptr, *nmf_G = nullptr, *nmf_q = nullptr, *nmf_vec = nullptr;
+  double *nmf_rowd = nullptr, *nmf_part = nullptr, *nmf_scal = nullptr;
+  int *nmf_perm = nullptr, *nmf_rowidx = nullptr;      // nmf_rowidx [2][nnz]: the row of every CSR position of both sides
+  double* nmf_errp = nullptr;                          // [chunks, 2] divergence sums of nmf_sampled_kernel
+  size_t nmf_q_cap = 0, nmf_scal_cap = 0, nmf_perm_cap = 0;
   int gram_arith = 1;                               // GANMF_TUNE gram: 1 (default, the faster one measured) the exact three-way bf16 split, 0 the plain fp32 MFMA body
   bool score_presplit = true;                       // GANMF_SCORE_PRESPLIT: many-tile scoring products on the pre-split persistent kernel
   // RCCL

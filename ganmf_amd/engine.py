@@ -392,6 +392,30 @@ class Engine:
         L.check(self.lib.ganmf_pure_svd(self.h, _f32p(om), int(om.shape[1]), int(n_iter), _f32p(sigma)), "ganmf_pure_svd")
         return sigma
 
+    # -- NMF (ganmf_nmf_*): W = T_USER_EMB, H^T = T_ITEM_EMB as set_tensor left them, X from set_confidence ----------
+    def nmf_mu(self, beta_loss, n_iter, update_H=True, error=True):
+        """n_iter iterations of sklearn's multiplicative update on the device (ganmf_nmf_mu); beta_loss is L.NMF_FROBENIUS or
+        L.NMF_KULLBACK_LEIBLER, update_H=False runs the W half only.  Returns the error after the last iteration (float), or None."""
+        err = C.c_double(0.0)
+        L.check(self.lib.ganmf_nmf_mu(self.h, int(beta_loss), int(n_iter), int(bool(update_H)), C.byref(err) if error else None),
+                "ganmf_nmf_mu")
+        return float(err.value) if error else None
+
+    def nmf_cd(self, perms, update_H=True):
+        """One coordinate-descent iteration per row of perms [n_iter, 2 if update_H else 1, num_factors] on the device (ganmf_nmf_cd):
+        a permutation per half, W half first.  Returns every iteration's violation (float64 [n_iter])."""
+        k, halves = int(self.cfg.num_factors), 2 if update_H else 1
+        pm = np.ascontiguousarray(perms, dtype=np.int32).reshape(-1, halves, k)
+        viol = np.zeros(max(pm.shape[0], 1), dtype=np.float64)
+        L.check(self.lib.ganmf_nmf_cd(self.h, _i32p(pm), int(pm.shape[0]), int(bool(update_H)), _f64p(viol)), "ganmf_nmf_cd")
+        return viol[:pm.shape[0]]
+
+    def nmf_error(self, beta_loss):
+        """sklearn's _beta_divergence(X, W, H, beta_loss, square_root=True) of the factors as they stand (ganmf_nmf_error)"""
+        err = C.c_double(0.0)
+        L.check(self.lib.ganmf_nmf_error(self.h, int(beta_loss), C.byref(err)), "ganmf_nmf_error")
+        return float(err.value)
+
     # -- item-based nearest neighbours (ganmf_itemknn_*, a MODEL_ITEMSIM engine) ------------------
     def itemknn_fit(self, kind, topk, shrink=0.0, p0=1.0, p1=1.0, den_a=None, den_b=None):
         """The item similarity matrix from the matrix uploaded by set_confidence (side 0 the weighted URM, side 1 its transpose),

@@ -256,8 +256,9 @@ int ganmf_restore_best(ganmf_handle* h);
 /* GANMF_PROF_MAX: an upper bound of the number of kernel classes, for sizing the caller's array.  It was 48 until the library had 48
  * classes and is 64 since ganmf_pure_svd added eight; ganmf_profile_read returns only the classes that were launched and never
  * writes more than `cap` entries, so a caller compiled against the earlier value cannot be overrun; it loses entries only if more
- * than 48 classes ran in one profile.  No structure or signature changed: GANMF_ABI_VERSION stays. */
-#define GANMF_PROF_MAX 64
+ * than 48 classes ran in one profile.  No structure or signature changed: GANMF_ABI_VERSION stays.  It is 80 since the ganmf_nmf_*
+ * entries added seven, under the same rule. */
+#define GANMF_PROF_MAX 80
 typedef struct ganmf_prof_entry {
   char name[48];
   int64_t launches;
@@ -488,6 +489,38 @@ int ganmf_als_half_sweep(ganmf_handle* h, int side, float reg);
  *   they were. */
 #define GANMF_SVD_MAX_RANDOM 280
 int ganmf_pure_svd(ganmf_handle* h, const float* omega, int n_random, int n_iter, float* sigma);
+
+/* NMF on the device: the two solvers of sklearn.decomposition.NMF as the reference's NMFRecommender runs them
+ * (MatrixFactorization/NMFRecommender.py:65-78: alpha_W = alpha_H = 0, so no regularisation term; float32).  The entries act on
+ * W = GANMF_T_USER_EMB [num_users, k] and H^T = GANMF_T_ITEM_EMB [num_items, k] of ANY single-GPU handle, a GANMF_MODEL_MF one
+ * included, as the caller set them (ganmf_set_tensor: the initial factors are the caller's, like every random number), and read X
+ * from the two uploads of ganmf_als_set_confidence (side 0 the URM, side 1 its transpose, the URM's data as the values).  The host
+ * decides when to stop: every entry runs the number of iterations it is given.  EPS = 2^-23.
+ * ganmf_nmf_mu: n_iter iterations of the multiplicative update (sklearn's _fit_multiplicative_update, gamma = 1).
+ *   GANMF_NMF_FROBENIUS: W *= (X H^T) / (W (H H^T)); H *= (W^T X) / ((W^T W) H); a denominator of exactly 0 becomes EPS.
+ *   GANMF_NMF_KULLBACK_LEIBLER: with q_ij = x_ij / max(w_i . h_j, EPS) at the stored entries, W *= (Q H^T) / rowsum(H) (0 -> EPS); Q
+ *   again from the new W; H *= (W^T Q) / colsum(W) (0 -> 1); entries of H below 2^-52 become 0.
+ *   update_H = 0 runs the W half only (sklearn's transform): X H^T, H H^T and rowsum(H) are then formed once per call.
+ *   error (may be NULL) receives ganmf_nmf_error of the factors after the last iteration.
+ * ganmf_nmf_cd: n_iter iterations of coordinate descent on the Frobenius loss (sklearn's _update_cdnmf_fast): a W half, then with
+ *   update_H an H half, the same routine on X^T, H^T, W.  A half forms G = H H^T and B = X H^T and, for every row i and every t in the
+ *   order of its permutation: grad = G[t, :] . W[i, :] - B[i, t]; the violation grows by |min(0, grad)| if W[i, t] == 0, else by |grad|;
+ *   W[i, t] = max(W[i, t] - grad / G[t, t], 0) if G[t, t] != 0.  perms: host array [n_iter, update_H ? 2 : 1, k], one permutation of
+ *   0 .. k - 1 per half in the order the halves run; violation [n_iter] receives every iteration's sum over its halves (float64).
+ * ganmf_nmf_error: sklearn's _beta_divergence(X, W, H, beta_loss, square_root=True) of the factors as they stand:
+ *   sqrt(max(|X|^2 + tr((W^T W)(H H^T)) - 2 tr((X H^T) W^T), 0)), or sqrt(2 max(r, 0)) with r = sum_{x > EPS} x log(x / max(wh, EPS)) +
+ *   colsum(W) . rowsum(H) - sum_{x > EPS} x; every scalar is accumulated in float64.
+ * The sparse products are ganmf_pure_svd's kernel, the Gram matrices its fp32 MFMA product; the row solvers, the sampled products and
+ * the reductions are ganmf_amd/csrc/nmf_rows.hpp.  No atomics, fixed summation order: the same bytes on every call.  Blocking.  Pad
+ * columns stay zero.
+ *   Errors: -1 with nothing enqueued for num_factors > GANMF_NMF_MAX_FACTORS, a side that has not been uploaded, sides with different
+ *   numbers of stored entries, a data-parallel handle, an unknown beta_loss, n_iter < 0, a row of perms that is not a permutation. */
+#define GANMF_NMF_MAX_FACTORS 270
+#define GANMF_NMF_FROBENIUS 0
+#define GANMF_NMF_KULLBACK_LEIBLER 1
+int ganmf_nmf_mu(ganmf_handle* h, int beta_loss, int n_iter, int update_H, double* error);
+int ganmf_nmf_cd(ganmf_handle* h, const int32_t* perms, int n_iter, int update_H, double* violation);
+int ganmf_nmf_error(ganmf_handle* h, int beta_loss, double* error);
 
 /* Item-based nearest neighbours on the device (KNN/ItemKNNCFRecommender.py; Base/Similarity/Compute_Similarity_Python.py:209-384,
  * which the reference runs in pure Python when its Cython extension is absent).  All three entries need a GANMF_MODEL_ITEMSIM handle.
