@@ -48,6 +48,7 @@
 #include "svd_rows.hpp"
 #include "nmf_rows.hpp"
 #include "itemknn_rows.hpp"
+#include "userknn_rows.hpp"
 #include "p3_rows.hpp"
 #include "level_sched.hpp"
 #include "slim_bpr.hpp"
@@ -90,6 +91,7 @@ extern "C" {
 #include "lib/abi_svd.inc"
 #include "lib/abi_nmf.inc"
 #include "lib/abi_itemknn.inc"
+#include "lib/abi_userknn.inc"
 #include "lib/abi_p3.inc"
 #include "lib/abi_slim.inc"
 #include "lib/abi_mf_sgd.inc"

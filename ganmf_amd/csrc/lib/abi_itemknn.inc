@@ -24,7 +24,10 @@ static int itemsim_ready(ganmf_handle* h, const char* who, int transposed) {
   return 0;
 }
 
+static int usersim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W, int ldw);      // (abi_userknn.inc)
+
 static int itemsim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W, int ldw) {
+  if (h->knn_user) return usersim_product(h, ids_dev, n, W, ldw);      // a held user matrix: W[users] . URM
   KnnScoreP p{};
   const AlsSide& s = h->als[0];
   p.r_indptr = s.indptr; p.r_items = s.indices; p.r_val = s.conf;
@@ -74,7 +77,7 @@ static int itemsim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W
 // in between leaves "no matrix" (knn_nnz < 0), whatever has been allocated by then (the next drop or the handle's end frees it).
 static void itemsim_drop(ganmf_handle* h) {
   hipFree(h->knn_indptr); hipFree(h->knn_nbr); hipFree(h->knn_val);
-  h->knn_indptr = nullptr; h->knn_nbr = nullptr; h->knn_val = nullptr; h->knn_nnz = -1;
+  h->knn_indptr = nullptr; h->knn_nbr = nullptr; h->knn_val = nullptr; h->knn_nnz = -1; h->knn_user = 0;
 }
 
 // ---- what the fits share (ganmf_itemknn_fit, ganmf_p3_fit, ganmf_slim_bpr_finish) --------------------------------------------------
@@ -127,16 +130,17 @@ static SimRowPlan itemsim_row_plan(int n) {
   return r;
 }
 
-// What the two row builders read (SimRowP: side 1, the slab, the plan's row, the picks); returns the dynamic LDS of their launch:
+// What the two row builders read (SimRowP: the side whose n rows are compared over their m columns -- side 1 with (N, U) for the item
+// models, side 0 with (U, N) for ganmf_userknn_fit --, the slab, the plan's row, the picks); returns the dynamic LDS of their launch:
 // the slab, and behind it the row where the plan keeps it in LDS.
-static size_t itemsim_row_args(ganmf_handle* h, int k, const SimRowPlan& plan, const SimPicks& t, SimRowP* p) {
-  const AlsSide& s = h->als[1];
+static size_t itemsim_row_args(ganmf_handle* h, int side, int n, int m, int k, const SimRowPlan& plan, const SimPicks& t, SimRowP* p) {
+  const AlsSide& s = h->als[side];
   p->c_indptr = s.indptr; p->c_users = s.indices; p->c_val = s.conf;
-  p->n_items = h->N; p->n_users = h->U; p->topk = k;
-  p->slab = std::min(KNN_SLAB, round_up(h->U, 64));
+  p->n_items = n; p->n_users = m; p->topk = k;
+  p->slab = std::min(KNN_SLAB, round_up(m, 64));
   p->row_lds = plan.row_lds; p->row_glob = t.row; p->ld_row = plan.ld_row;
   p->out_idx = t.idx; p->out_val = t.val; p->out_cnt = t.cnt;
-  return ((size_t)p->slab + (plan.row_lds ? (size_t)h->N : 0)) * sizeof(float);
+  return ((size_t)p->slab + (plan.row_lds ? (size_t)n : 0)) * sizeof(float);
 }
 
 // [n] counts from the device (enqueued behind the kernel that wrote them) to an indptr on the host
@@ -162,12 +166,11 @@ static int itemsim_alloc(const int64_t* ip, int n, long long** indptr, int** idx
   return 0;
 }
 
-// The picks of a pass (k per item in their layout, at most `most` stored) to a compact matrix, ids ascending inside an item: the
-// counts read back, the indptr formed and checked, the matrix allocated, itemknn_pack_kernel.  Into temporaries between two passes,
-// into the handle for the result.
-static int itemsim_compact(ganmf_handle* h, const char* who, const SimPicks& t, int k, long long most, long long** indptr, int** idx,
+// The picks of a pass (k per item of the n in their layout, at most `most` stored) to a compact [n, n] matrix, ids ascending inside an
+// item: the counts read back, the indptr formed and checked, the matrix allocated, itemknn_pack_kernel.  Into temporaries between two
+// passes, into the handle for the result.
+static int itemsim_compact(ganmf_handle* h, const char* who, int n, const SimPicks& t, int k, long long most, long long** indptr, int** idx,
                            float** val, long long* nnz) {
-  const int n = h->N;
   std::vector<int64_t> ip;
   TRY(itemsim_indptr(h, who, t.cnt, n, most, ip));
   *nnz = ip[(size_t)n];
@@ -181,8 +184,7 @@ static int itemsim_compact(ganmf_handle* h, const char* who, const SimPicks& t, 
 
 // The column pass (p3_columns_kernel): the ck largest non-zeros of every column of R, bit copies, into the picks.  The dense column
 // lives where the plan puts a row, and the grid is the plan's: min(n, 8192) workgroups with the column in LDS, at most 512 above.
-static int itemsim_columns(ganmf_handle* h, const SimCsr& R, int ck, const SimRowPlan& plan, const SimPicks& t) {
-  const int n = h->N;
+static int itemsim_columns(ganmf_handle* h, int n, const SimCsr& R, int ck, const SimRowPlan& plan, const SimPicks& t) {
   P3ColP p{};
   p.r_indptr = R.indptr; p.r_idx = R.idx; p.r_val = R.val;
   p.n_items = n; p.topk = ck;
@@ -223,6 +225,7 @@ int ganmf_itemknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float*
   if (!h || !indptr) return fail(-1, "%s: null argument", who);
   TRY(itemsim_handle(h, who));
   if (h->knn_nnz < 0) return fail(-1, "%s: the handle holds no item similarity matrix", who);
+  if (h->knn_user) return fail(-1, "%s: the handle holds a user similarity matrix (ganmf_userknn_get reads it)", who);
   if (h->knn_nnz > 0 && (!indices || !data)) return fail(-1, "%s: null argument", who);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
@@ -267,7 +270,7 @@ int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
   if (kind == KNN_PRODUCT) TRY(upload_floats(&den.b, den_b, n));
   p.den_a = den.a; p.den_b = den.b;
   TRY(t.alloc(n, k, plan.row_floats()));
-  const size_t shmem = itemsim_row_args(h, k, plan, t, &p);
+  const size_t shmem = itemsim_row_args(h, 1, n, h->U, k, plan, t, &p);
   TRY(allow_lds((const void*)itemknn_fit_kernel, shmem));
   {      // every workgroup walks the whole matrix once per slab of its item
     Scope sc(h, T_KNN_FIT, 2.0 * n * (double)s.nnz, 8.0 * n * (double)s.nnz);
@@ -275,7 +278,7 @@ int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
     HIP_TRY(hipGetLastError());
   }
   long long nnz = 0;
-  TRY(itemsim_compact(h, who, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
   HIP_TRY(hipStreamSynchronize(h->st));
   h->knn_nnz = nnz;
   *nnz_out = nnz;

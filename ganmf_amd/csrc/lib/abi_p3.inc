@@ -33,13 +33,13 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
   {
     P3RowP p{};
     p.row_scale = scale.a; p.col_scale = scale.b;
-    const size_t shmem = itemsim_row_args(h, k, plan, t, &p);
+    const size_t shmem = itemsim_row_args(h, 1, n, h->U, k, plan, t, &p);
     TRY(allow_lds((const void*)p3_rows_kernel, shmem));
     Scope sc(h, T_P3_ROWS, 2.0 * n * (double)s.nnz, 8.0 * n * (double)s.nnz);      // every workgroup walks the whole matrix once per slab
     GANMF_LAUNCH(p3_rows_kernel, dim3(plan.grid), dim3(KNN_THREADS), shmem, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  TRY(itemsim_compact(h, who, t, k, k, &R.indptr, &R.idx, &R.val, &R.nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, &R.indptr, &R.idx, &R.val, &R.nnz));
   if (normalize) {
     Scope sc(h, T_P3_NORMALIZE, 2.0 * (double)R.nnz, 12.0 * (double)R.nnz);
     GANMF_LAUNCH(p3_normalize_kernel, dim3((unsigned)n), dim3(64), 0, h->st, (const long long*)R.indptr, R.val, n);
@@ -49,8 +49,8 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
   // ---- column pass: the col_topk largest of every column of R; col_topk = 0: R transposed ----
   long long nnz = 0;
   if (ck > 0) {
-    TRY(itemsim_columns(h, R, ck, plan, t));
-    TRY(itemsim_compact(h, who, t, ck, ck, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
+    TRY(itemsim_columns(h, n, R, ck, plan, t));
+    TRY(itemsim_compact(h, who, n, t, ck, ck, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
   } else {
     HIP_TRY(hipMemsetAsync(t.cnt, 0, (size_t)n * sizeof(int), h->st));
     if (R.nnz > 0) {

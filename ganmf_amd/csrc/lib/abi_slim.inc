@@ -208,11 +208,11 @@ int ganmf_slim_bpr_finish(ganmf_handle* h, int32_t topk, int64_t* nnz_out) {
     GANMF_LAUNCH(slim_rows_kernel, dim3(grid), dim3(SLIM_THREADS), 0, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  TRY(itemsim_compact(h, who, t, k, k, &R.indptr, &R.idx, &R.val, &R.nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, &R.indptr, &R.idx, &R.val, &R.nnz));
   // ---- similarityMatrixTopK: the k largest non-zeros of every column (p3_columns_kernel, bit copies) ----
-  TRY(itemsim_columns(h, R, k, plan, t));
+  TRY(itemsim_columns(h, n, R, k, plan, t));
   long long nnz = 0;
-  TRY(itemsim_compact(h, who, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
   HIP_TRY(hipStreamSynchronize(h->st));
   h->knn_nnz = nnz;
   *nnz_out = nnz;

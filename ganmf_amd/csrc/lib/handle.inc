@@ -342,11 +342,14 @@ struct ganmf_handle {
   int* als_bad = nullptr;
   // GANMF_MODEL_ITEMSIM (itemknn_rows.hpp): the item similarity matrix W by target item -- column i of the reference's W_sparse is
   // knn_nbr / knn_val [knn_indptr[i], knn_indptr[i + 1]) -- from ganmf_itemknn_fit or ganmf_set_item_similarity; knn_dense: the dense
-  // profiles [rows, ld] of the scoring route for catalogues above one workgroup's LDS, grown on demand
+  // profiles [rows, ld] of the scoring route for catalogues above one workgroup's LDS, grown on demand.  The one held matrix may
+  // instead be a USER similarity (knn_user = 1; userknn_rows.hpp): W_sparse [U, U] by row -- row u is knn_nbr / knn_val
+  // [knn_indptr[u], knn_indptr[u + 1]) -- from ganmf_userknn_fit or ganmf_set_user_similarity
   long long* knn_indptr = nullptr;
   int* knn_nbr = nullptr;
   float* knn_val = nullptr;
   int64_t knn_nnz = -1;      // -1: no matrix held
+  int knn_user = 0;          // the held matrix: 0 item x item by target item, 1 user x user by row
   float* knn_dense = nullptr;
   size_t knn_dense_cap = 0;
   SlimState slim;                                   // ganmf_slim_bpr_* (slim_bpr.hpp)

@@ -431,6 +431,20 @@ class Engine:
         self._knn_nnz = int(nnz.value)
         return self._knn_nnz
 
+    def userknn_fit(self, kind, topk, shrink=0.0, p0=1.0, p1=1.0, den_a=None, den_b=None):
+        """The user similarity matrix from side 0 of set_confidence (the weighted URM, users x items), left on the device by row
+        (ganmf_userknn_fit): itemknn_fit with the sides exchanged, den_a / den_b the per-USER float32 terms.  Returns the number
+        of stored similarities."""
+        a = None if den_a is None else np.ascontiguousarray(den_a, dtype=np.float32).ravel()
+        b = None if den_b is None else np.ascontiguousarray(den_b, dtype=np.float32).ravel()
+        assert all(v is None or v.size == self.num_users for v in (a, b))
+        nnz = C.c_int64(0)
+        L.check(self.lib.ganmf_userknn_fit(self.h, int(kind), int(topk), float(shrink), float(p0), float(p1),
+                                           _f32p(a) if a is not None else None, _f32p(b) if b is not None else None,
+                                           C.byref(nnz)), "ganmf_userknn_fit")
+        self._knn_nnz = int(nnz.value)
+        return self._knn_nnz
+
     def p3_fit(self, topk, row_scale, col_scale=None, normalize=False, col_topk=None):
         """The P3alpha / RP3beta matrix from the uploads of set_confidence -- side 0 the URM the scores are formed from, side 1 the
         transition weights Pui^alpha by item -- left on the device (ganmf_p3_fit): row_scale [num_items] = (1 / deg_i)^alpha,
@@ -800,6 +814,37 @@ class Engine:
         data = np.ascontiguousarray(W.data, dtype=np.float32)
         L.check(self.lib.ganmf_set_item_similarity(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices), _f32p(data),
                                                    self.num_items), "ganmf_set_item_similarity")
+        self._knn_nnz = int(indptr[-1])
+
+    def user_similarity(self):
+        """The held user similarity matrix as the reference lays W_sparse out (ganmf_userknn_get): scipy CSR float32
+        [num_users, num_users], row u = the users whose profiles user u's scores sum, ascending."""
+        import scipy.sparse as sps
+        n = self.num_users
+        nnz = getattr(self, "_knn_nnz", None)
+        if nnz is None:
+            raise L.GanmfError("user_similarity: the engine holds no user similarity matrix")
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        indices = np.zeros(max(nnz, 1), dtype=np.int32)
+        data = np.zeros(max(nnz, 1), dtype=np.float32)
+        L.check(self.lib.ganmf_userknn_get(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices), _f32p(data)),
+                "ganmf_userknn_get")
+        return sps.csr_matrix((data[:nnz], indices[:nnz], indptr), shape=(n, n))
+
+    def set_user_similarity(self, W_sparse):
+        """Uploads a user similarity matrix in the reference's layout ([num_users, num_users], scores = W_sparse[users] . URM), any
+        scipy format (ganmf_set_user_similarity): rows ascending, duplicates summed."""
+        import scipy.sparse as sps
+        W = sps.csr_matrix(W_sparse, dtype=np.float32)
+        if W.shape != (self.num_users, self.num_users):
+            raise ValueError("set_user_similarity: W_sparse must be %d x %d, given %r" % (self.num_users, self.num_users, W.shape))
+        W.sum_duplicates()
+        W.sort_indices()
+        indptr = np.ascontiguousarray(W.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(W.indices, dtype=np.int32)
+        data = np.ascontiguousarray(W.data, dtype=np.float32)
+        L.check(self.lib.ganmf_set_user_similarity(self.h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(indices), _f32p(data),
+                                                   self.num_users), "ganmf_set_user_similarity")
         self._knn_nnz = int(indptr[-1])
 
     def snapshot_best(self):

@@ -59,11 +59,16 @@ class SimilarityModelMixin(object):
             raise RuntimeError("{}: model has no device state; call fit() or loadModel() first".format(self.RECOMMENDER_NAME))
 
     # ---- the similarity matrix (Base/BaseSimilarityMatrixRecommender.py:16-30) --------------------
+    # item x item, scores = URM_train[users] . W_sparse; a user-based model (UserKNN.py) sets this to "user": user x user, scores =
+    # W_sparse[users] . URM_train
+    _similarity_of = "item"
+
     @property
     def W_sparse(self):
-        """scipy CSR float32 [n_items, n_items], rows = neighbour, columns = item: the reference's layout"""
+        """scipy CSR float32 [n_items, n_items], rows = neighbour, columns = item: the reference's layout (a user-based model:
+        [n_users, n_users], row u = the users whose profiles user u's scores sum)"""
         self._require_engine()
-        return self.engine.item_similarity()
+        return self.engine.user_similarity() if self._similarity_of == "user" else self.engine.item_similarity()
 
     # ---- what a similarity-matrix model does not have ---------------------------------------------
     honours_items_to_compute = True
@@ -107,7 +112,11 @@ class SimilarityModelMixin(object):
             if kinds.get("W_sparse") != "sps.spmatrix":
                 raise ValueError("{}: the saved model holds no sparse W_sparse".format(self.RECOMMENDER_NAME))
             W = sps.load_npz(io.BytesIO(z.read(files["W_sparse"])))
-        if W.shape != (self.n_items, self.n_items):
-            raise ValueError("{}: the saved W_sparse is {}, URM_train has {} items".format(self.RECOMMENDER_NAME, W.shape, self.n_items))
+        n = self.n_users if self._similarity_of == "user" else self.n_items
+        if W.shape != (n, n):
+            raise ValueError("{}: the saved W_sparse is {}, URM_train has {} {}s".format(self.RECOMMENDER_NAME, W.shape, n, self._similarity_of))
         self._build()
-        self.engine.set_item_similarity(W)
+        if self._similarity_of == "user":
+            self.engine.set_user_similarity(W)
+        else:
+            self.engine.set_item_similarity(W)

@@ -565,6 +565,36 @@ int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
 int ganmf_itemknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float* data);
 int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_items);
 
+/* User-based nearest neighbours on the device (KNN/UserKNNCFRecommender.py; Base/BaseSimilarityMatrixRecommender.py:95-117: scores =
+ * W_sparse[users] . URM_train).  All three entries need a GANMF_MODEL_ITEMSIM handle.  Such a handle holds at most ONE similarity
+ * matrix and records whether it is item x item (above) or user x user; every fit and upload, of either kind, drops the held one.
+ * ganmf_userknn_fit: ganmf_itemknn_fit with the two sides of the URM exchanged -- for every user i, w_j = sum over the items of
+ *   x_i. x_j. for every user j, w_i = 0, the kind's value, the min(topk, num_users) largest kept where not zero -- with the same kinds,
+ *   the same selection (ties to the smaller user id) and the same kernel, which reads side 0 (users x items, canonical) in place of
+ *   side 1; side 1 is not read.  den_a / den_b are per USER, [num_users] (the row norms, row counts or their powers).  The by-target
+ *   result (column i of the reference's W_sparse = the kept neighbours of user i) is then turned into rows INSIDE the call, on the
+ *   host: read back, a stable counting sort by the stored neighbour (columns visited in ascending order, so every row ascends),
+ *   uploaded -- at most num_users * topk entries; the reference does the same conversion in scipy.  The handle then holds W BY ROW:
+ *   row u = the users v with W_sparse[u, v] stored, ascending.  A row is NOT bounded by topk: a user who is in many top-k lists has a
+ *   long row.  *nnz receives the number of stored entries.  Blocking.  Same bytes on every call.
+ *   Errors as ganmf_itemknn_fit's (-1, nothing enqueued, the held matrix dropped only once every check has passed), with side 0 the
+ *   one side that must be uploaded and canonical.
+ * ganmf_userknn_get: the held W to the caller as CSR by row: indptr [num_users + 1], indices / data [nnz].  An error (-1) while the
+ *   handle holds an item matrix; ganmf_itemknn_get is an error while it holds a user matrix.
+ * ganmf_set_user_similarity: uploads W_sparse [n_users, n_users] as CSR by row (a saved model); checks as ganmf_set_item_similarity:
+ *   monotone indptr from 0, indices in [0, n_users), n_users the handle's num_users, weights finite.  The chain below runs in stored
+ *   order: upload rows with ascending indices for scores that equal a fitted model's.
+ * Scores while a user matrix is held: out[r, i] = sum over the stored v of row ids[r] of W[ids[r], v] x[v, i], x side 0: for every
+ *   item ONE fp32 FMA chain over the neighbours in stored order that starts at 0; exactly 0 for an item no neighbour rated (and for a
+ *   user without neighbours).  No floating-point atomics; a user's scores depend on that user's row of W and on x alone, not on the
+ *   batch or the user's place in it.  One workgroup per scored row keeps the row's accumulator in LDS (catalogues up to 32 768 items;
+ *   wider ones accumulate in the row of the output itself), each wave owning a contiguous range of items.  Seen mask, score filter,
+ *   top-k and every evaluation entry run on these scores unchanged.  transposed = 1 is an error (-1). */
+int ganmf_userknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, float p0, float p1, const float* den_a, const float* den_b,
+                      int64_t* nnz);
+int ganmf_userknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float* data);
+int ganmf_set_user_similarity(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_users);
+
 /* The graph-based item models P3alpha and RP3beta on the device (GraphBased/P3alphaRecommender.py:52-141, RP3betaRecommender.py:
  * 49-151): a three-step random walk item -> user -> item, W = Piu^alpha . Pui^alpha with Pui the URM with every user row divided by
  * its L1 norm and Piu ones at the stored entries of the URM's transpose, every item row divided by its stored count deg_i.  Needs a
