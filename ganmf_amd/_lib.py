@@ -50,7 +50,7 @@ SYMBOLS = [
     "ganmf_set_tensor", "ganmf_get_tensor", "ganmf_tensor_shape", "ganmf_get_adam_powers",
     "ganmf_set_adam_powers", "ganmf_train_epoch", "ganmf_train_epoch_ragged", "ganmf_train_step", "ganmf_scores",
     "ganmf_set_seen_csr", "ganmf_set_score_filter", "ganmf_recommend", "ganmf_set_test_csr", "ganmf_evaluate", "ganmf_set_test_ratings", "ganmf_set_eval_item_weights", "ganmf_evaluate_full", "ganmf_set_candidates_csr", "ganmf_recommend_candidates", "ganmf_evaluate_candidates", "ganmf_evaluate_groups", "ganmf_set_items_to_ignore", "ganmf_set_item_diversity", "ganmf_evaluate_diversity", "ganmf_score_similarity", "ganmf_set_discriminate_block", "ganmf_discriminate", "ganmf_als_set_confidence", "ganmf_als_half_sweep", "ganmf_pure_svd", "ganmf_nmf_mu", "ganmf_nmf_cd", "ganmf_nmf_error", "ganmf_itemknn_fit", "ganmf_itemknn_get", "ganmf_set_item_similarity", "ganmf_userknn_fit", "ganmf_userknn_get", "ganmf_set_user_similarity", "ganmf_p3_fit", "ganmf_slim_bpr_init", "ganmf_slim_bpr_draw", "ganmf_slim_bpr_run", "ganmf_slim_bpr_epochs", "ganmf_slim_bpr_finish", "ganmf_slim_bpr_get_state", "ganmf_mf_sgd_init", "ganmf_mf_sgd_draw", "ganmf_mf_sgd_run", "ganmf_mf_sgd_epochs", "ganmf_mf_sgd_publish", "ganmf_mf_sgd_get_state", "ganmf_mf_sgd_set_state", "ganmf_cfgan_init", "ganmf_cfgan_draw_masks", "ganmf_cfgan_set_masks", "ganmf_cfgan_get_masks", "ganmf_cfgan_step", "ganmf_cfgan_epoch", "ganmf_caae_init", "ganmf_caae_cdf", "ganmf_caae_draw_perm", "ganmf_caae_draw_negatives", "ganmf_caae_draw_batch", "ganmf_caae_get_draws", "ganmf_caae_d_step", "ganmf_caae_g_step", "ganmf_caae_epoch", "ganmf_snapshot_best", "ganmf_restore_best", "ganmf_profile_enable", "ganmf_profile_read", "ganmf_stream_timer",
-    "ganmf_bench_scores", "ganmf_gemm_f32", "ganmf_gemm_f32_ex", "ganmf_crc32c", "ganmf_device_count", "ganmf_abi_version", "ganmf_last_error",
+    "ganmf_bench_scores", "ganmf_gemm_f32", "ganmf_gemm_f32_ex", "ganmf_crc32c", "ganmf_device_count", "ganmf_live_device_bytes", "ganmf_abi_version", "ganmf_last_error",
 ]
 
 
@@ -195,6 +195,7 @@ def load_library():
         "ganmf_gemm_f32_ex": (C.c_int, [C.c_int, f32p, f32p, f32p, i64, i64, i64, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_int, f32p, P(C.c_int32), i64, C.c_int, f32p]),
         "ganmf_device_count": (C.c_int, []),
+        "ganmf_live_device_bytes": (i64, []),
         "ganmf_abi_version": (C.c_int, []),
         "ganmf_last_error": (C.c_char_p, []),
     }

@@ -66,6 +66,7 @@ namespace {
 #include "lib/base.inc"
 }  // namespace
 
+#include "lib/devmem.inc"
 #include "lib/handle.inc"
 
 namespace {

@@ -17,17 +17,9 @@ int ganmf_als_set_confidence(ganmf_handle* h, int side, const int64_t* indptr, c
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   AlsSide& s = h->als[side];
-  hipFree(s.indptr); hipFree(s.indices); hipFree(s.conf);
-  s = AlsSide{};
-  HIP_TRY(hipMalloc((void**)&s.indptr, (size_t)(n_rows + 1) * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&s.indices, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&s.conf, (size_t)std::max<int64_t>(nnz, 1) * sizeof(float)));
-  HIP_TRY(hipMemcpy(s.indptr, indptr, (size_t)(n_rows + 1) * sizeof(long long), hipMemcpyHostToDevice));
-  if (nnz) {
-    HIP_TRY(hipMemcpy(s.indices, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s.conf, conf, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
-  }
-  s.rows = n_rows; s.nnz = nnz;
+  s.canonical = false; s.conf.reset();
+  TRY(s.upload(indptr, indices, n_rows, n_cols));
+  TRY(s.upload_values(s.conf, conf));
   s.canonical = true;
   for (int64_t r = 0; r < n_rows && s.canonical; ++r)
     for (int64_t j = indptr[r] + 1; j < indptr[r + 1]; ++j)
@@ -51,8 +43,8 @@ int ganmf_als_half_sweep(ganmf_handle* h, int side, float reg) {
   Tensor& Yt = side == 0 ? h->V : h->Ue;      // held fixed
   Tensor& Xt = side == 0 ? h->Ue : h->V;      // solved
   const int n_fixed = Yt.rows, n_rows = Xt.rows, ld = h->ldk;
-  if (!h->als_G) TRY(dalloc(&h->als_G, (size_t)ld * ld));
-  if (!h->als_bad) TRY(dalloc((float**)&h->als_bad, (size_t)std::max(h->U, h->N) + 1));
+  if (!h->als_G) TRY(h->als_G.alloc((size_t)ld * ld, true));
+  if (!h->als_bad) TRY(h->als_bad.alloc((size_t)std::max(h->U, h->N) + 1, true));
   ++h->param_version;
   {      // G = Y^T Y on the fp32 MFMA whatever the handle's training arithmetic is (split along K by the planner)
     GemmP g{};

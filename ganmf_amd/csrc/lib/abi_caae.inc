@@ -22,36 +22,36 @@ int ganmf_caae_init(ganmf_handle* h, int32_t g_units, int32_t g_layers, int32_t 
   c.words = (N + 31) / 32;
   for (ProfileMlp& gn : c.gen) TRY(mlp_alloc(h, gn, g_units, g_layers, ACT_SIGMOID, ACT_SIGMOID, m_batch));
   TRY(alloc_tensor(c.bias, 1, N, false, 1));
-  TRY(dalloc((float**)&c.k_rows, (size_t)U));
+  TRY(c.k_rows.alloc((size_t)U, true));
   HIP_TRY(hipMemcpy(c.k_rows, k_rows, (size_t)U * sizeof(int), hipMemcpyHostToDevice));
-  TRY(dalloc(&c.cdf[0], (size_t)U * h->ldN));
-  TRY(dalloc(&c.cdf[1], (size_t)U * h->ldN));
-  TRY(dalloc(&c.lse_all, (size_t)U));
-  TRY(dalloc((float**)&c.xt, (size_t)3 * d_bsize));
-  TRY(dalloc((float**)&c.first, (size_t)U + N));
+  TRY(c.cdf[0].alloc((size_t)U * h->ldN, true));
+  TRY(c.cdf[1].alloc((size_t)U * h->ldN, true));
+  TRY(c.lse_all.alloc((size_t)U, true));
+  TRY(c.xt.alloc((size_t)3 * d_bsize, true));
+  TRY(c.first.alloc((size_t)U + N, true));
   HIP_TRY(hipMemset(c.first, 0x7f, ((size_t)U + N) * sizeof(int)));
   HIP_TRY(hipDeviceSynchronize());
-  TRY(dalloc((float**)&c.xu, (size_t)m_batch));
-  TRY(dalloc((float**)&c.xi, (size_t)m_batch * n_s));
-  TRY(dalloc((float**)&c.xn, (size_t)m_batch * c.words));
-  TRY(dalloc(&c.Pg, (size_t)d_bsize * h->ldk));
-  TRY(dalloc(&c.Qi, (size_t)d_bsize * h->ldk));
-  TRY(dalloc(&c.Qj, (size_t)d_bsize * h->ldk));
-  TRY(dalloc(&c.coef, (size_t)d_bsize));
-  TRY(dalloc(&c.lt, (size_t)d_bsize));
-  TRY(dalloc(&c.rt, (size_t)3 * d_bsize));      // rt, then the gathered biases [2 d_bsize]
-  TRY(dalloc(&c.C, (size_t)m_batch * h->ldN));
-  TRY(dalloc(&c.R, (size_t)m_batch * h->ldN));
-  TRY(dalloc(&c.Rp, (size_t)m_batch * h->ldN));
-  TRY(dalloc(&c.cdfb, (size_t)m_batch * h->ldN));
-  TRY(dalloc(&c.dz, (size_t)m_batch * h->ldN));
-  TRY(dalloc(&c.dh0, (size_t)m_batch * c.gen[0].ldg));
-  TRY(dalloc(&c.dh1, (size_t)m_batch * c.gen[0].ldg));
-  TRY(dalloc(&c.lse, (size_t)m_batch));
-  TRY(dalloc(&c.reward, (size_t)m_batch * n_s));
-  TRY(dalloc(&c.la, (size_t)m_batch));
-  TRY(dalloc(&c.ae, (size_t)m_batch));
-  TRY(dalloc(&c.sq, (size_t)(g_layers + 1) * CFGAN_SQ_BLOCKS));
+  TRY(c.xu.alloc((size_t)m_batch, true));
+  TRY(c.xi.alloc((size_t)m_batch * n_s, true));
+  TRY(c.xn.alloc((size_t)m_batch * c.words, true));
+  TRY(c.Pg.alloc((size_t)d_bsize * h->ldk, true));
+  TRY(c.Qi.alloc((size_t)d_bsize * h->ldk, true));
+  TRY(c.Qj.alloc((size_t)d_bsize * h->ldk, true));
+  TRY(c.coef.alloc((size_t)d_bsize, true));
+  TRY(c.lt.alloc((size_t)d_bsize, true));
+  TRY(c.rt.alloc((size_t)3 * d_bsize, true));      // rt, then the gathered biases [2 d_bsize]
+  TRY(c.C.alloc((size_t)m_batch * h->ldN, true));
+  TRY(c.R.alloc((size_t)m_batch * h->ldN, true));
+  TRY(c.Rp.alloc((size_t)m_batch * h->ldN, true));
+  TRY(c.cdfb.alloc((size_t)m_batch * h->ldN, true));
+  TRY(c.dz.alloc((size_t)m_batch * h->ldN, true));
+  TRY(c.dh0.alloc((size_t)m_batch * c.gen[0].ldg, true));
+  TRY(c.dh1.alloc((size_t)m_batch * c.gen[0].ldg, true));
+  TRY(c.lse.alloc((size_t)m_batch, true));
+  TRY(c.reward.alloc((size_t)m_batch * n_s, true));
+  TRY(c.la.alloc((size_t)m_batch, true));
+  TRY(c.ae.alloc((size_t)m_batch, true));
+  TRY(c.sq.alloc((size_t)(g_layers + 1) * CFGAN_SQ_BLOCKS, true));
   c.ready = true;
   ++h->param_version;
   return 0;
@@ -60,20 +60,15 @@ int ganmf_caae_init(ganmf_handle* h, int32_t g_units, int32_t g_layers, int32_t 
 // the recorded draws' slots: `passes` discriminator passes and `steps` steps of either generator
 static int caae_slots(ganmf_handle* h, int passes, int steps) {
   CaaeState& c = h->ca;
-  const size_t nn = (size_t)std::max<long long>(h->nnz, 1);
-  if ((size_t)passes * 2 * nn > c.neg_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(c.neg); c.neg = nullptr; c.neg_cap = 0;
-    TRY(dalloc((float**)&c.neg, (size_t)passes * 2 * nn));
-    c.neg_cap = (size_t)passes * 2 * nn;
-  }
+  const size_t nn = (size_t)std::max<long long>(h->urm.nnz, 1);
+  TRY(c.neg.grow(h->st, (size_t)passes * 2 * nn, true));
   if (steps > c.step_slots) {
     HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(c.users); hipFree(c.nu); hipFree(c.items);
-    c.users = nullptr; c.nu = nullptr; c.items = nullptr; c.step_slots = 0;
-    TRY(dalloc((float**)&c.users, (size_t)2 * steps * c.Bm));
-    TRY(dalloc((float**)&c.nu, (size_t)steps * c.Bm * c.words));
-    TRY(dalloc((float**)&c.items, (size_t)2 * steps * c.Bm * c.n_s));
+    c.users.reset(); c.nu.reset(); c.items.reset();
+    c.step_slots = 0;
+    TRY(c.users.alloc((size_t)2 * steps * c.Bm, true));
+    TRY(c.nu.alloc((size_t)steps * c.Bm * c.words, true));
+    TRY(c.items.alloc((size_t)2 * steps * c.Bm * c.n_s, true));
     c.step_slots = steps;
   }
   return 0;
@@ -104,7 +99,7 @@ int ganmf_caae_cdf(ganmf_handle* h, int which, const int32_t* users, int32_t n, 
   HIP_TRY(hipStreamSynchronize(h->st));
   HIP_TRY(hipMemcpy(ud, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
   TRY(mlp_forward_rows(h, c.gen[which], ud, 0, n, c.R, h->ldN));
-  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(n), dim3(256), 0, h->st, c.R, h->ldN, N, c.cdfb, h->ldN, c.lse);
+  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(n), dim3(256), 0, h->st, c.R.get(), h->ldN, N, c.cdfb.get(), h->ldN, c.lse.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->st));
   if (cdf_out) HIP_TRY(hipMemcpy2D(cdf_out, (size_t)N * 4, c.cdfb, (size_t)h->ldN * 4, (size_t)N * 4, (size_t)n, hipMemcpyDeviceToHost));
@@ -119,7 +114,7 @@ int ganmf_caae_draw_perm(ganmf_handle* h, int64_t epoch, int32_t* out) {
   HIP_TRY(hipSetDevice(h->dev));
   TRY(caae_draw_perm(h, epoch));
   HIP_TRY(hipStreamSynchronize(h->st));
-  if (out && h->nnz) HIP_TRY(hipMemcpy(out, h->ca.perm, (size_t)h->nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (out && h->urm.nnz) HIP_TRY(hipMemcpy(out, h->ca.perm, (size_t)h->urm.nnz * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -133,7 +128,7 @@ int ganmf_caae_draw_negatives(ganmf_handle* h, int64_t epoch, int32_t pass, int 
   TRY(caae_slots(h, 1, 0));
   TRY(caae_draw_neg(h, epoch, pass, which, h->ca.neg));
   HIP_TRY(hipStreamSynchronize(h->st));
-  if (out && h->nnz) HIP_TRY(hipMemcpy(out, h->ca.neg, (size_t)h->nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (out && h->urm.nnz) HIP_TRY(hipMemcpy(out, h->ca.neg, (size_t)h->urm.nnz * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -205,7 +200,7 @@ int ganmf_caae_d_step(ganmf_handle* h, const int32_t* users, const int32_t* pos_
       return fail(-1, "%s: triple %d (%d, %d, %d) out of range", who, t, users[t], pos_items[t], neg_items[t]);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(grow_losses(h, h->ca.loss_dev, h->ca.loss_cap, 1));
+  TRY(h->ca.loss_dev.grow(h->st, 1, true));
   HIP_TRY(hipStreamSynchronize(h->st));
   const int32_t* src[3] = {users, pos_items, neg_items};
   for (int q = 0; q < 3; ++q) HIP_TRY(hipMemcpy(c.xt + (size_t)q * c.d_bsize, src[q], (size_t)count * sizeof(int), hipMemcpyHostToDevice));
@@ -229,7 +224,7 @@ int ganmf_caae_g_step(ganmf_handle* h, int which, const int32_t* users, const ui
     if (items[t] < 0 || items[t] >= h->N) return fail(-1, "%s: item %d out of range", who, items[t]);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(grow_losses(h, h->ca.loss_dev, h->ca.loss_cap, 1));
+  TRY(h->ca.loss_dev.grow(h->st, 1, true));
   HIP_TRY(hipStreamSynchronize(h->st));
   int* ud = c.xu;
   int* id = c.xi;
@@ -254,13 +249,13 @@ int ganmf_caae_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g_
   TRY(model_ready(h, who, GANMF_MODEL_CAAE, true));
   if (d_steps < 0 || g_steps < 0 || gpr_steps < 0 || epoch < 0) return fail(-1, "%s: negative argument", who);
   CaaeState& c = h->ca;
-  const long long nnz = h->nnz;
+  const long long nnz = h->urm.nnz;
   const size_t slices = (size_t)((nnz + c.d_bsize - 1) / c.d_bsize);
   const size_t nd = (size_t)d_steps * slices * 2, ng = (size_t)g_steps, np = (size_t)gpr_steps;
   if ((nd && !d_losses) || (ng && !g_losses) || (np && !gpr_losses)) return fail(-1, "%s: null loss buffer", who);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(grow_losses(h, c.loss_dev, c.loss_cap, nd + ng + np + 1));
+  TRY(c.loss_dev.grow(h->st, nd + ng + np + 1, true));
   TRY(caae_prepare(h));
   TRY(caae_slots(h, d_steps, std::max(1, std::max(g_steps, gpr_steps))));
   c.rec_nnz = nnz; c.rec_passes = d_steps; c.rec_steps[0] = g_steps; c.rec_steps[1] = gpr_steps;

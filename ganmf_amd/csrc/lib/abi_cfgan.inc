@@ -24,17 +24,17 @@ int ganmf_cfgan_init(ganmf_handle* h, int32_t g_nodes, int32_t g_layers, int g_a
   c.zr_coef = zr_coefficient; c.seed = seed;
   c.ldx = round_up(2 * N + 2, LD_ALIGN); c.words = (N + 31) / 32;
   TRY(mlp_alloc(h, c.gen, g_nodes, g_layers, g_act, -1, Bm));
-  TRY(dalloc(&c.C, (size_t)Bm * h->ldN));
-  TRY(dalloc(&c.fake, (size_t)Bm * h->ldN));
-  TRY(dalloc(&c.dfake, (size_t)Bm * h->ldN));
-  TRY(dalloc(&c.DX, (size_t)2 * Bm * c.ldx));
-  TRY(dalloc(&c.dh0, (size_t)Bm * c.gen.ldg));
-  TRY(dalloc(&c.dh1, (size_t)Bm * c.gen.ldg));
-  TRY(dalloc(&c.zr_part, (size_t)Bm));
-  TRY(dalloc(&c.loss_rows, (size_t)2 * Bm));
-  TRY(dalloc(&c.sq, (size_t)(std::max(h->L, g_layers) + 1) * CFGAN_SQ_BLOCKS));
-  TRY(dalloc((float**)&c.planes, (size_t)2 * U * c.words));
-  TRY(dalloc((float**)&c.k_rows, (size_t)U));
+  TRY(c.C.alloc((size_t)Bm * h->ldN, true));
+  TRY(c.fake.alloc((size_t)Bm * h->ldN, true));
+  TRY(c.dfake.alloc((size_t)Bm * h->ldN, true));
+  TRY(c.DX.alloc((size_t)2 * Bm * c.ldx, true));
+  TRY(c.dh0.alloc((size_t)Bm * c.gen.ldg, true));
+  TRY(c.dh1.alloc((size_t)Bm * c.gen.ldg, true));
+  TRY(c.zr_part.alloc((size_t)Bm, true));
+  TRY(c.loss_rows.alloc((size_t)2 * Bm, true));
+  TRY(c.sq.alloc((size_t)(std::max(h->L, g_layers) + 1) * CFGAN_SQ_BLOCKS, true));
+  TRY(c.planes.alloc((size_t)2 * U * c.words, true));
+  TRY(c.k_rows.alloc((size_t)U, true));
   HIP_TRY(hipMemcpy(c.k_rows, k_rows, (size_t)U * sizeof(int), hipMemcpyHostToDevice));
   c.ready = true;
   ++h->param_version;
@@ -43,7 +43,7 @@ int ganmf_cfgan_init(ganmf_handle* h, int32_t g_nodes, int32_t g_layers, int g_a
 
 static int cfgan_draw(ganmf_handle* h, int64_t epoch) {
   CfganState& c = h->cf;
-  CfganMaskP p{h->indptr, h->indices, c.k_rows, h->U, h->N, c.words, c.seed, (unsigned long long)epoch, c.planes,
+  CfganMaskP p{h->urm.indptr, h->urm.indices, c.k_rows, h->U, h->N, c.words, c.seed, (unsigned long long)epoch, c.planes,
                c.scheme == GANMF_CFGAN_PM ? CFGAN_PLANE_PM : CFGAN_PLANE_ZR};
   GANMF_LAUNCH(cfgan_masks_kernel, dim3(h->U, c.scheme == GANMF_CFGAN_ZP ? 2 : 1), dim3(256), 0, h->st, p);
   HIP_TRY(hipGetLastError());
@@ -91,7 +91,7 @@ int ganmf_cfgan_step(ganmf_handle* h, int kind, int64_t row0, int32_t nrows, flo
     return fail(-1, "%s: rows [%lld, %lld) of %d, at most %d per step", who, (long long)row0, (long long)row0 + nrows, h->U, h->cf.Bm);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(grow_losses(h, h->cf.loss_dev, h->cf.loss_cap, 1));
+  TRY(h->cf.loss_dev.grow(h->st, 1, true));
   TRY(cfgan_step(h, kind, (int)row0, nrows, h->cf.loss_dev));
   float l = 0.f;
   HIP_TRY(hipMemcpyAsync(&l, h->cf.loss_dev, sizeof(float), hipMemcpyDeviceToHost, h->st));
@@ -110,7 +110,7 @@ int ganmf_cfgan_epoch(ganmf_handle* h, int64_t epoch, int32_t d_steps, int32_t g
   if ((nd && !d_losses) || (ng && !g_losses)) return fail(-1, "%s: null loss buffer", who);
   HIP_TRY(hipSetDevice(h->dev));
   ++h->param_version;
-  TRY(grow_losses(h, c.loss_dev, c.loss_cap, nd + ng + 1));
+  TRY(c.loss_dev.grow(h->st, nd + ng + 1, true));
   if (draw) TRY(cfgan_draw(h, epoch));
   float* out = c.loss_dev;
   for (int pass = 0; pass < d_steps; ++pass)

@@ -39,6 +39,8 @@ int ganmf_device_count(void) {
   return n;
 }
 
+int64_t ganmf_live_device_bytes(void) { return (int64_t)g_live_device_bytes.load(); }
+
 static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h);
 
 int ganmf_create(const ganmf_cfg* cfg, ganmf_handle** out) {
@@ -156,7 +158,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
   if (!sim && !cfgan) {
     TRY(alloc_tensor(h->Ue, U, k, false, 1));      // rows of U belong to their rank: never communicated
     TRY(alloc_tensor(h->V, N, k, true, world));
-    TRY(dalloc(&h->V_alt, h->V.cap));
+    TRY(h->V_alt.alloc(h->V.cap, true));
   }
   if (mf) {
   } else if (cfgan) {
@@ -165,7 +167,7 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
     TRY(alloc_tensor(h->We, N + 1, e, false, world));   // We_ext: row N = encoder bias
     TRY(alloc_tensor(h->Wd, e + 1, N, false, world, h->ldN));   // Wd_ext: row e = decoder bias; shares the leading dimension of the [.., N] work buffers
     h->gD_elems = h->We.cap + h->Wd.cap;
-    TRY(dalloc(&h->gD, h->gD_elems));
+    TRY(h->gD.alloc(h->gD_elems, true));
     h->We.g = h->gD;
     h->Wd.g = h->We.g + h->We.cap;
   } else {
@@ -180,47 +182,47 @@ static int create_impl(const ganmf_cfg* cfg, ganmf_handle* h) {
     }
     TRY(alloc_tensor(h->Wo, 1, e + 1, false, world));
     h->gD_elems += h->Wo.cap;
-    TRY(dalloc(&h->gD, h->gD_elems));
+    TRY(h->gD.alloc(h->gD_elems, true));
     float* gp = h->gD;
     for (int l = 0; l < h->L; ++l) { h->Wl[l].g = gp; gp += h->Wl[l].cap; }
     h->Wo.g = gp;
   }
-  TRY(dalloc(&h->zero_page, 2048 + 64));   // 8 KiB: one 32-byte line per lane of a workgroup
-  TRY(dalloc((float**)&h->perm, (size_t)3 * U));
+  TRY(h->zero_page.alloc(2048 + 64, true));   // 8 KiB: one 32-byte line per lane of a workgroup
+  TRY(h->perm.alloc((size_t)3 * U, true));
   h->pos = h->perm + U;
   h->pos_step = h->perm + 2 * (size_t)U;
   if (!mf && !cfgan) {      // minibatch work buffers of the adversarial step
-    TRY(dalloc(&h->XF, (size_t)2 * B * h->ldN));
-    h->XF_own = h->XF;
-    TRY(dalloc(&h->Ub, (size_t)B * h->ldk));
-    h->Ub_own = h->Ub;
-    TRY(dalloc(&h->dF, (size_t)B * h->ldN));
-    TRY(dalloc(&h->gUb, (size_t)B * h->ldk));
-    h->gUb_own = h->gUb;
+    TRY(h->XF_own.alloc((size_t)2 * B * h->ldN, true));
+    h->XF = h->XF_own;
+    TRY(h->Ub_own.alloc((size_t)B * h->ldk, true));
+    h->Ub = h->Ub_own;
+    TRY(h->dF.alloc((size_t)B * h->ldN, true));
+    TRY(h->gUb_own.alloc((size_t)B * h->ldk, true));
+    h->gUb = h->gUb_own;
     // bias-folding ones columns: XF[:, N] = 1 (and E[:, e] = 1 / a_l[:, e] = 1) for every row; epilogues never store there
     std::vector<float> ones((size_t)2 * B, 1.0f);
     HIP_TRY(hipMemcpy2D(h->XF + N, (size_t)h->ldN * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
     if (!dis) {
-      TRY(dalloc(&h->E, (size_t)2 * B * h->lde));
-      TRY(dalloc(&h->Es, (size_t)2 * B * h->lde));
-      TRY(dalloc(&h->Dl, (size_t)2 * B * h->ldN));
-      TRY(dalloc(&h->dE, (size_t)2 * B * h->lde));
+      TRY(h->E.alloc((size_t)2 * B * h->lde, true));
+      TRY(h->Es.alloc((size_t)2 * B * h->lde, true));
+      TRY(h->Dl.alloc((size_t)2 * B * h->ldN, true));
+      TRY(h->dE.alloc((size_t)2 * B * h->lde, true));
       HIP_TRY(hipMemcpy2D(h->E + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
     } else {
-      h->Al.resize(h->L, nullptr);
+      h->Al.resize(h->L);
       for (int l = 0; l < h->L; ++l) {
-        TRY(dalloc(&h->Al[l], (size_t)2 * B * h->lde));
+        TRY(h->Al[l].alloc((size_t)2 * B * h->lde, true));
         HIP_TRY(hipMemcpy2D(h->Al[l] + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
       }
-      TRY(dalloc(&h->dz0, (size_t)2 * B * h->lde));
-      TRY(dalloc(&h->dz1, (size_t)2 * B * h->lde));
-      TRY(dalloc(&h->dlogit, (size_t)2 * B));
+      TRY(h->dz0.alloc((size_t)2 * B * h->lde, true));
+      TRY(h->dz1.alloc((size_t)2 * B * h->lde, true));
+      TRY(h->dlogit.alloc((size_t)2 * B, true));
     }
   }
-  TRY(dalloc(&h->rs, (size_t)2 * B));
+  TRY(h->rs.alloc((size_t)2 * B, true));
   h->tab_cap = (int)(U / std::max(B, 1)) + 2;
-  TRY(dalloc(&h->scal, (size_t)S_TAB + 4 * (size_t)h->tab_cap));
-  TRY(dalloc(&h->sqp, (size_t)2 * std::max(GEMM_RED_GRID, ((B + 63) / 64) * ((N + 63) / 64)) + 16));
+  TRY(h->scal.alloc((size_t)S_TAB + 4 * (size_t)h->tab_cap, true));
+  TRY(h->sqp.alloc((size_t)2 * std::max(GEMM_RED_GRID, ((B + 63) / 64) * ((N + 63) / 64)) + 16, true));
   {
     auto t64 = [](int a, int b) { return ((a + 63) / 64) * ((b + 63) / 64); };
     h->reg_cap = std::max({ADAM_GRID, (int)GEMM_RED_GRID, t64(N + 2, e), t64(e + 1, N), t64(N, k), t64(B, N), t64(B, e)});
@@ -244,41 +246,6 @@ int ganmf_destroy(ganmf_handle* h) {
     h->local->failed = true;            // a group does not outlive any of its members
     h->local->cv.notify_all();
   }
-  free_tensor(h->We, false); free_tensor(h->Wd, false); hipFree(h->zero_page); hipFree(h->Es);
-  for (auto& t : h->Wl) free_tensor(t, false);
-  free_tensor(h->Wo, false);
-  for (float* a : h->Al) hipFree(a);
-  hipFree(h->dz0); hipFree(h->dz1); hipFree(h->dlogit);
-  free_tensor(h->Ue, false); free_tensor(h->V, true); hipFree(h->V_alt);
-  hipFree(h->gD); hipFree(h->indptr); hipFree(h->indices); hipFree(h->data); hipFree(h->perm);
-  hipFree(h->csc_colptr); hipFree(h->csc_rowidx); hipFree(h->csc_val); hipFree(h->sp_rows);
-  if (h->stage_i) hipHostFree(h->stage_i);
-  if (h->stage_f) hipHostFree(h->stage_f);
-  hipFree(h->test_indptr); hipFree(h->test_indices); hipFree(h->test_gain); hipFree(h->eval_buf);
-  hipFree(h->cand_indptr); hipFree(h->cand_indices);
-  hipFree(h->test_rating); hipFree(h->eval_w); hipFree(h->eval_rmse); hipFree(h->eval_counts); hipFree(h->eval_grp);
-  hipFree(h->XF_own); hipFree(h->XF_pass); hipFree(h->Ub_pass); hipFree(h->Ub_own); hipFree(h->Ub_sched); hipFree(h->lazy_tab);
-  for (auto& ch : h->lazy_chunks) hipFree(ch.first);
-  if (h->lazy_stage) hipHostFree(h->lazy_stage);
-  h->lazy_chunks.clear();
-  hipFree(h->E); hipFree(h->Dl); hipFree(h->dE); hipFree(h->dF); hipFree(h->gUb_own);
-  hipFree(h->slab); hipFree(h->rs); hipFree(h->scal); hipFree(h->sqp);
-  hipFree(h->seen_indptr); hipFree(h->seen_indices); hipFree(h->item_mask); hipFree(h->topk_items); hipFree(h->topk_vals); hipFree(h->sc_ids);
-  hipFree(h->colbuf); hipFree(h->parts_all); hipFree(h->sc_rows); hipFree(h->sc_out); hipFree(h->sc_pa); hipFree(h->sc_pb);
-  hipFree(h->sim_mat); hipFree(h->sim_pool); hipFree(h->sim_part); hipFree(h->sim_zero);
-  hipFree(h->rank_mask); hipFree(h->div_mat);
-  for (AlsSide& s : h->als) { hipFree(s.indptr); hipFree(s.indices); hipFree(s.conf); }
-  hipFree(h->als_G); hipFree(h->als_bad);
-  hipFree(h->knn_indptr); hipFree(h->knn_nbr); hipFree(h->knn_val); hipFree(h->knn_dense);
-  hipFree(h->slim.S); hipFree(h->slim.st0); hipFree(h->slim.st1); profiles_drop(h->slim.profiles);
-  hipFree(h->mfs.P); hipFree(h->mfs.terms); profiles_drop(h->mfs.profiles);
-  hipFree(h->svd_P[0]); hipFree(h->svd_P[1]); hipFree(h->svd_G); hipFree(h->svd_X); hipFree(h->svd_Wl);
-  hipFree(h->svd_lam); hipFree(h->svd_flag);
-  hipFree(h->nmf_den); hipFree(h->nmf_num); hipFree(h->nmf_G); hipFree(h->nmf_q); hipFree(h->nmf_vec); hipFree(h->nmf_rowd); hipFree(h->nmf_part);
-  hipFree(h->nmf_scal); hipFree(h->nmf_perm); hipFree(h->nmf_rowidx); hipFree(h->nmf_errp);
-  hipFree(h->dr_ids); hipFree(h->dr_X); hipFree(h->dr_Ub); hipFree(h->dr_E); hipFree(h->dr_A); hipFree(h->dr_part); hipFree(h->dr_val);
-  cfgan_free(h);
-  caae_free(h);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   if (h->st2) hipStreamSynchronize(h->st2);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -290,8 +257,7 @@ int ganmf_destroy(ganmf_handle* h) {
   if (h->ev_wd) hipEventDestroy(h->ev_wd);
   if (h->st2) hipStreamDestroy(h->st2);
   if (h->st) hipStreamDestroy(h->st);
-  hipFree(h->slab2);
-  delete h;
+  delete h;      // the members free what they own: every stream was drained above
   return 0;
 }
 
@@ -409,17 +375,11 @@ int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* ind
     nnz = (int64_t)c_indices.size();
   }
   HIP_TRY(hipSetDevice(h->dev));
-  if (h->indptr) { hipFree(h->indptr); hipFree(h->indices); hipFree(h->data); h->indptr = nullptr; }
-  HIP_TRY(hipMalloc((void**)&h->indptr, (n_rows + 1) * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&h->indices, std::max<int64_t>(nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&h->data, std::max<int64_t>(nnz, 1) * sizeof(float)));
-  HIP_TRY(hipMemcpy(h->indptr, indptr, (n_rows + 1) * sizeof(long long), hipMemcpyHostToDevice));
-  if (nnz) {
-    HIP_TRY(hipMemcpy(h->indices, indices, nnz * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->data, data, nnz * sizeof(float), hipMemcpyHostToDevice));
-  }
-  h->nnz = nnz;
-  h->has_urm = true;
+  // what is held goes first, the facts beside it are set last: a failure anywhere leaves "no URM" (and no CSC twin)
+  h->has_urm = false; h->sparse_g = false; h->sparse_d = false;
+  h->data.reset(); h->csc.drop(); h->csc_val.reset();
+  TRY(h->urm.upload(indptr, indices, n_rows, n_cols));
+  TRY(h->urm.upload_values(h->data, data));
   h->ca.iu_src = nullptr;      // CAAE: the users of the stored interactions are formed again from this matrix (caae_prepare)
   // SURVEY 8(f)-3: below 0.5 % density (LastFM: 0.22 %) the generator step reads the real rows as CSR (GANMF only;
   // DisGANMF feeds the rows themselves to its discriminator).  GANMF_SPARSE = 0 / 1 overrides.
@@ -438,8 +398,6 @@ int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* ind
   if (h->debug_plan)      // (tests assert on the path the planner took, not only on the numbers it produced)
     fprintf(stderr, "[ganmf urm] set_urm_csr %lldx%lld nnz=%lld%s density %.5f -> sparse_g %d sparse_d %d\n", (long long)n_rows,
             (long long)n_cols, (long long)nnz, canonical ? "" : " (made canonical)", density, (int)h->sparse_g, (int)h->sparse_d);
-  hipFree(h->csc_colptr); hipFree(h->csc_rowidx); hipFree(h->csc_val);
-  h->csc_colptr = nullptr; h->csc_rowidx = nullptr; h->csc_val = nullptr;
   if (h->sparse_d) {      // counting sort by column; rows ascend inside a column because the CSR rows are walked in order
     std::vector<long long> colptr((size_t)n_cols + 1, 0);
     for (int64_t j = 0; j < nnz; ++j) ++colptr[(size_t)indices[j] + 1];
@@ -452,14 +410,13 @@ int ganmf_set_urm_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* ind
         const long long at = fill[indices[j]]++;
         rowidx[at] = (int)r; val[at] = data[j];
       }
-    HIP_TRY(hipMalloc((void**)&h->csc_colptr, (size_t)(n_cols + 1) * sizeof(long long)));
-    HIP_TRY(hipMalloc((void**)&h->csc_rowidx, rowidx.size() * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&h->csc_val, val.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->csc_colptr, colptr.data(), (size_t)(n_cols + 1) * sizeof(long long), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->csc_rowidx, rowidx.data(), rowidx.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->csc_val, val.data(), val.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (!h->sp_rows) TRY(dalloc(&h->sp_rows, (size_t)(h->N + CSC_BIAS_PARTS) * h->lde));
+    int rc = h->csc.upload(colptr.data(), rowidx.data(), n_cols, n_rows);
+    if (!rc) rc = h->csc.upload_values(h->csc_val, val.data());
+    if (!rc && !h->sp_rows) rc = h->sp_rows.alloc((size_t)(h->N + CSC_BIAS_PARTS) * h->lde, true);
+    if (rc) { h->urm.drop(); h->data.reset(); h->csc.drop(); h->csc_val.reset(); h->sparse_g = h->sparse_d = false; return rc; }
   }
+  if (!h->sparse_d) h->sp_rows.reset();      // (scratch of the sparse discriminator step only)
+  h->has_urm = true;
   return 0;
 }
 

@@ -25,8 +25,8 @@ static int discriminate_block(ganmf_handle* h, const int* ids_dev, int nb, int g
   const int cols_grid = (nb + 255) / 256;
   if (generated) {      // X[b, :] = U[ids[b]] . V^T, unfiltered (GANMF.py:82-83)
     const long long total = (long long)nb * (h->ldk / 4);
-    GANMF_LAUNCH(gather_rows_kernel, dim3((int)std::min<long long>(2048, (total + 255) / 256)), dim3(256), 0, h->st, h->Ue.p, h->ldk,
-                 ids_dev, nb, h->dr_Ub);
+    GANMF_LAUNCH(gather_rows_kernel, dim3((int)std::min<long long>(2048, (total + 255) / 256)), dim3(256), 0, h->st, h->Ue.p.get(), h->ldk,
+                 ids_dev, nb, h->dr_Ub.get());
     HIP_TRY(hipGetLastError());
     GemmP g{};
     g.A = h->dr_Ub; g.lda = h->ldk; g.B = h->V.p; g.ldb = h->ldk;
@@ -34,11 +34,11 @@ static int discriminate_block(ganmf_handle* h, const int* ids_dev, int nb, int g
     TRY(run_gemm(h, T_GEMM_GEN, T_RED_GEN, g, false, false, nullptr, 0, 0, &ft));
   } else if (dis) {     // DisGANMF feeds the rows themselves to its layers: the block is expanded on the device
     Scope s(h, T_DENSIFY, 0, 4.0 * nb * h->ldN);
-    GANMF_LAUNCH(disc_densify_kernel, dim3(nb), dim3(256), 0, h->st, h->indptr, h->indices, h->data, ids_dev, h->dr_X, h->ldN);
+    GANMF_LAUNCH(disc_densify_kernel, dim3(nb), dim3(256), 0, h->st, h->urm.indptr.get(), h->urm.indices.get(), h->data.get(), ids_dev, h->dr_X.get(), h->ldN);
     HIP_TRY(hipGetLastError());
   }
   if (generated || dis) {      // the ones column of the input block and DisGANMF's float(uid) column
-    GANMF_LAUNCH(disc_cols_kernel, dim3(cols_grid), dim3(256), 0, h->st, h->dr_X, h->ldN, nb, N, dis ? N + 1 : -1, ids_dev,
+    GANMF_LAUNCH(disc_cols_kernel, dim3(cols_grid), dim3(256), 0, h->st, h->dr_X.get(), h->ldN, nb, N, dis ? N + 1 : -1, ids_dev,
                  (int)h->cfg.row_offset);
     HIP_TRY(hipGetLastError());
   }
@@ -66,18 +66,18 @@ static int discriminate_block(ganmf_handle* h, const int* ids_dev, int nb, int g
     *feat_out = in;
     if (want_value) {      // logit = [a | 1] . wo_ext (DisGANMF.py:63)
       Scope s(h, T_DIS_HEAD, 2.0 * nb * (e + 1), 4.0 * nb * (e + 1));
-      GANMF_LAUNCH(disc_logit_kernel, dim3((nb + 3) / 4), dim3(256), 0, h->st, in, h->lde, e + 1, h->Wo.p, nb, h->dr_val);
+      GANMF_LAUNCH(disc_logit_kernel, dim3((nb + 3) / 4), dim3(256), 0, h->st, in, h->lde, e + 1, h->Wo.p.get(), nb, h->dr_val.get());
       HIP_TRY(hipGetLastError());
     }
     return 0;
   }
   // GANMF: E = x . We + be (GANMF.py:64-65) -- a CSR row-sum for stored rows, the encode product for generated ones
-  GANMF_LAUNCH(disc_cols_kernel, dim3(cols_grid), dim3(256), 0, h->st, h->dr_E, h->lde, nb, e, -1, ids_dev, 0);
+  GANMF_LAUNCH(disc_cols_kernel, dim3(cols_grid), dim3(256), 0, h->st, h->dr_E.get(), h->lde, nb, e, -1, ids_dev, 0);
   HIP_TRY(hipGetLastError());
   if (!generated) {
-    Scope s(h, T_DENSIFY, 0, 4.0 * nb * e + 4.0 * (double)h->nnz / std::max(h->U, 1) * nb * e);
-    GANMF_LAUNCH(csr_encode_rows_kernel, dim3(nb), dim3(256), 0, h->st, h->indptr, h->indices, h->data, ids_dev, h->We.p, h->lde, N, e,
-                 h->dr_E);
+    Scope s(h, T_DENSIFY, 0, 4.0 * nb * e + 4.0 * (double)h->urm.nnz / std::max(h->U, 1) * nb * e);
+    GANMF_LAUNCH(csr_encode_rows_kernel, dim3(nb), dim3(256), 0, h->st, h->urm.indptr.get(), h->urm.indices.get(), h->data.get(), ids_dev, h->We.p.get(), h->lde, N, e,
+                 h->dr_E.get());
     HIP_TRY(hipGetLastError());
   } else {
     GemmP g{};
@@ -96,14 +96,14 @@ static int discriminate_block(ganmf_handle* h, const int* ids_dev, int nb, int g
     g.tiles_m = (nb + ROWSQ_TILE - 1) / ROWSQ_TILE; g.tiles_n = (N + ROWSQ_TILE - 1) / ROWSQ_TILE;
     g.epi.kind = EPI_SUB_AUX_SQ; g.epi.gram_partials = h->dr_part;
     if (generated) { g.epi.aux = h->dr_X; g.epi.ldaux = h->ldN; }
-    else { g.epi.csr_indptr = h->indptr; g.epi.csr_indices = h->indices; g.epi.csr_data = h->data; g.epi.csr_rows = ids_dev; }
+    else { g.epi.csr_indptr = h->urm.indptr; g.epi.csr_indices = h->urm.indices; g.epi.csr_data = h->data; g.epi.csr_rows = ids_dev; }
     {
       Scope s(h, T_GEMM_DEC, gemm_flops(g.M, g.N, g.K), 4.0 * ((double)nb * (e + 1) + (double)(e + 1) * N + (generated ? (double)nb * N : 0.0)));
       GANMF_LAUNCH(rowsq_bf16x3_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(256), 0, h->st, g);
       HIP_TRY(hipGetLastError());
     }
     Scope s(h, T_RED_DEC, (double)nb * g.tiles_n, 8.0 * nb * (g.tiles_n + 1));
-    GANMF_LAUNCH(rowsq_finish_kernel, dim3(cols_grid), dim3(256), 0, h->st, h->dr_part, nb, g.tiles_n, N, h->dr_val);
+    GANMF_LAUNCH(rowsq_finish_kernel, dim3(cols_grid), dim3(256), 0, h->st, h->dr_part.get(), nb, g.tiles_n, N, h->dr_val.get());
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -134,8 +134,8 @@ int ganmf_discriminate(ganmf_handle* h, const int32_t* rows, int64_t n, int gene
   int64_t blk = n;
   if (h->disc_block > 0) blk = std::min(blk, h->disc_block);
   {
-    const size_t have = sizeof(float) * ((need_x ? h->dr_X_cap : 0) + (generated ? h->dr_Ub_cap : 0) + h->dr_E_cap + (dis ? h->dr_A_cap : 0)) +
-                        sizeof(double) * ((dis ? 0 : h->dr_part_cap) + h->dr_val_cap);
+    const size_t have = sizeof(float) * ((need_x ? h->dr_X.cap : 0) + (generated ? h->dr_Ub.cap : 0) + h->dr_E.cap + (dis ? h->dr_A.cap : 0)) +
+                        sizeof(double) * ((dis ? 0 : h->dr_part.cap) + h->dr_val.cap);
     if ((size_t)blk * row_bytes > have) {      // (buffers that already hold the block were admitted by an earlier call)
       size_t free_b = 0, total_b = 0;
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return fail(-2, "%s: hipMemGetInfo failed", who);
@@ -144,13 +144,13 @@ int ganmf_discriminate(ganmf_handle* h, const int32_t* rows, int64_t n, int gene
       blk = std::min(blk, fit);
     }
   }
-  TRY(grow_device(h, (void**)&h->dr_ids, &h->dr_ids_cap, (size_t)n, sizeof(int)));
-  if (need_x) TRY(grow_device(h, (void**)&h->dr_X, &h->dr_X_cap, (size_t)blk * h->ldN, sizeof(float), true));
-  if (generated) TRY(grow_device(h, (void**)&h->dr_Ub, &h->dr_Ub_cap, (size_t)blk * h->ldk, sizeof(float), true));
-  TRY(grow_device(h, (void**)&h->dr_E, &h->dr_E_cap, (size_t)blk * h->lde, sizeof(float), true));
-  if (dis) TRY(grow_device(h, (void**)&h->dr_A, &h->dr_A_cap, (size_t)blk * h->lde, sizeof(float), true));
-  if (!dis && value) TRY(grow_device(h, (void**)&h->dr_part, &h->dr_part_cap, (size_t)blk * tiles_n, sizeof(double)));
-  if (value) TRY(grow_device(h, (void**)&h->dr_val, &h->dr_val_cap, (size_t)blk, sizeof(double)));
+  TRY(h->dr_ids.grow(h->st, (size_t)n, false));
+  if (need_x) TRY(h->dr_X.grow(h->st, (size_t)blk * h->ldN, true));
+  if (generated) TRY(h->dr_Ub.grow(h->st, (size_t)blk * h->ldk, true));
+  TRY(h->dr_E.grow(h->st, (size_t)blk * h->lde, true));
+  if (dis) TRY(h->dr_A.grow(h->st, (size_t)blk * h->lde, true));
+  if (!dis && value) TRY(h->dr_part.grow(h->st, (size_t)blk * tiles_n, false));
+  if (value) TRY(h->dr_val.grow(h->st, (size_t)blk, false));
   int rc = 0;
   hipError_t err = hipMemcpyAsync(h->dr_ids, rows, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->st);
   for (int64_t at = 0; at < n && rc == 0 && err == hipSuccess; at += blk) {

@@ -31,13 +31,13 @@ static int itemsim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W
   KnnScoreP p{};
   const AlsSide& s = h->als[0];
   p.r_indptr = s.indptr; p.r_items = s.indices; p.r_val = s.conf;
-  p.w_indptr = h->knn_indptr; p.w_nbr = h->knn_nbr; p.w_val = h->knn_val;
+  p.w_indptr = h->knn.indptr; p.w_nbr = h->knn.indices; p.w_val = h->knn.val;
   p.ids = ids_dev; p.n = (int)n; p.n_items = W; p.out = h->sc_out; p.ldo = ldw;
   const bool lds = W <= KNN_SCORE_LDS;
   const int G = !lds ? 4 : 8 * W <= KNN_SCORE_GROUP ? 8 : 4 * W <= KNN_SCORE_GROUP ? 4 : 2 * W <= KNN_SCORE_GROUP ? 2 : 1;
   if (!lds) {      // dense profiles in global memory, whole groups of rows
     const size_t rows = (size_t)round_up((int)n, 8);
-    TRY(grow_device(h, (void**)&h->knn_dense, &h->knn_dense_cap, rows * ldw, sizeof(float)));
+    TRY(h->knn_dense.grow(h->st, rows * ldw, false));
     HIP_TRY(hipMemsetAsync(h->knn_dense, 0, rows * ldw * sizeof(float), h->st));
     p.dense = h->knn_dense; p.ldd = ldw;
     GANMF_LAUNCH(itemknn_densify_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, p);
@@ -74,43 +74,31 @@ static int itemsim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W
 }
 
 // The held matrix is dropped.  Every fit and upload drops first and sets h->knn_nnz LAST, behind its final synchronise: any failure
-// in between leaves "no matrix" (knn_nnz < 0), whatever has been allocated by then (the next drop or the handle's end frees it).
+// in between leaves "no matrix" (knn_nnz < 0) and an empty holder.
 static void itemsim_drop(ganmf_handle* h) {
-  hipFree(h->knn_indptr); hipFree(h->knn_nbr); hipFree(h->knn_val);
-  h->knn_indptr = nullptr; h->knn_nbr = nullptr; h->knn_val = nullptr; h->knn_nnz = -1; h->knn_user = 0;
+  h->knn.drop();
+  h->knn_nnz = -1; h->knn_user = 0;
 }
 
 // ---- what the fits share (ganmf_itemknn_fit, ganmf_p3_fit, ganmf_slim_bpr_finish) --------------------------------------------------
 // The picks of one selection pass -- [n, k] ids and values in descending order of value, [n] counts -- and the private rows of the
 // global route, released on every way out.
 struct SimPicks {
-  int *idx = nullptr, *cnt = nullptr;
-  float *val = nullptr, *row = nullptr;
+  DevBuf<int> idx, cnt;
+  DevBuf<float> val, row;
   int alloc(int n, int k, size_t row_floats) {
-    if (row_floats) HIP_TRY(hipMalloc((void**)&row, row_floats * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&idx, (size_t)n * k * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&val, (size_t)n * k * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&cnt, (size_t)n * sizeof(int)));
+    if (row_floats) TRY(row.alloc(row_floats, false));
+    TRY(idx.alloc((size_t)n * k, false));
+    TRY(val.alloc((size_t)n * k, false));
+    TRY(cnt.alloc((size_t)n, false));
     return 0;
   }
-  ~SimPicks() { hipFree(idx); hipFree(cnt); hipFree(val); hipFree(row); }
 };
-// a compact matrix between two passes (R of ganmf_p3_fit and of ganmf_slim_bpr_finish)
-struct SimCsr {
-  long long* indptr = nullptr;
-  int* idx = nullptr;
-  float* val = nullptr;
-  long long nnz = 0;
-  ~SimCsr() { hipFree(indptr); hipFree(idx); hipFree(val); }
-};
-// host vectors of a fit on the device, released on every way out
-struct SimFloats {
-  float *a = nullptr, *b = nullptr;
-  ~SimFloats() { hipFree(a); hipFree(b); }
-};
-static int upload_floats(float** dst, const float* src, int n) {
-  HIP_TRY(hipMalloc((void**)dst, (size_t)n * sizeof(float)));
-  HIP_TRY(hipMemcpy(*dst, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+// host vectors of a fit on the device, released on every way out (the compact matrix between two passes is a SimCsr, handle.inc)
+struct SimFloats { DevBuf<float> a, b; };
+static int upload_floats(DevBuf<float>& dst, const float* src, int n) {
+  TRY(dst.alloc((size_t)n, false));
+  HIP_TRY(hipMemcpy(dst, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -157,27 +145,21 @@ static int itemsim_indptr(ganmf_handle* h, const char* who, const int* cnt_dev, 
 }
 
 // the three arrays of a compact [n, n] matrix (one element where it is empty), its indptr uploaded
-static int itemsim_alloc(const int64_t* ip, int n, long long** indptr, int** idx, float** val) {
-  const size_t room = (size_t)std::max<int64_t>(ip[n], 1);
-  HIP_TRY(hipMalloc((void**)indptr, (size_t)(n + 1) * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)idx, room * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)val, room * sizeof(float)));
-  HIP_TRY(hipMemcpy(*indptr, ip, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice));
-  return 0;
+static int itemsim_alloc(const int64_t* ip, int n, SimCsr& m) {
+  TRY(m.upload(ip, nullptr, n, n));
+  return m.upload_values(m.val, (const float*)nullptr);
 }
 
 // The picks of a pass (k per item of the n in their layout, at most `most` stored) to a compact [n, n] matrix, ids ascending inside an
 // item: the counts read back, the indptr formed and checked, the matrix allocated, itemknn_pack_kernel.  Into temporaries between two
 // passes, into the handle for the result.
-static int itemsim_compact(ganmf_handle* h, const char* who, int n, const SimPicks& t, int k, long long most, long long** indptr, int** idx,
-                           float** val, long long* nnz) {
+static int itemsim_compact(ganmf_handle* h, const char* who, int n, const SimPicks& t, int k, long long most, SimCsr& m) {
   std::vector<int64_t> ip;
   TRY(itemsim_indptr(h, who, t.cnt, n, most, ip));
-  *nnz = ip[(size_t)n];
-  TRY(itemsim_alloc(ip.data(), n, indptr, idx, val));
-  Scope sc(h, T_KNN_PACK, 0.0, 16.0 * (double)*nnz);
+  TRY(itemsim_alloc(ip.data(), n, m));
+  Scope sc(h, T_KNN_PACK, 0.0, 16.0 * (double)m.nnz);
   GANMF_LAUNCH(itemknn_pack_kernel, dim3((unsigned)n), dim3(KNN_THREADS), 0, h->st, (const int*)t.idx, (const float*)t.val,
-               (const int*)t.cnt, k, (const long long*)*indptr, *idx, *val);
+               (const int*)t.cnt, k, (const long long*)m.indptr, m.indices.get(), m.val.get());
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -186,7 +168,7 @@ static int itemsim_compact(ganmf_handle* h, const char* who, int n, const SimPic
 // lives where the plan puts a row, and the grid is the plan's: min(n, 8192) workgroups with the column in LDS, at most 512 above.
 static int itemsim_columns(ganmf_handle* h, int n, const SimCsr& R, int ck, const SimRowPlan& plan, const SimPicks& t) {
   P3ColP p{};
-  p.r_indptr = R.indptr; p.r_idx = R.idx; p.r_val = R.val;
+  p.r_indptr = R.indptr; p.r_idx = R.indices; p.r_val = R.val;
   p.n_items = n; p.topk = ck;
   p.row_lds = plan.row_lds; p.row_glob = t.row; p.ld_row = plan.ld_row;
   p.out_idx = t.idx; p.out_val = t.val; p.out_cnt = t.cnt;
@@ -211,11 +193,8 @@ int ganmf_set_item_similarity(ganmf_handle* h, const int64_t* indptr, const int3
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   itemsim_drop(h);
-  TRY(itemsim_alloc(indptr, (int)n_items, &h->knn_indptr, &h->knn_nbr, &h->knn_val));
-  if (nnz) {
-    HIP_TRY(hipMemcpy(h->knn_nbr, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->knn_val, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
-  }
+  TRY(h->knn.upload(indptr, indices, n_items, n_items));
+  TRY(h->knn.upload_values(h->knn.val, data));
   h->knn_nnz = nnz;
   return 0;
 }
@@ -229,10 +208,10 @@ int ganmf_itemknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float*
   if (h->knn_nnz > 0 && (!indices || !data)) return fail(-1, "%s: null argument", who);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  HIP_TRY(hipMemcpy(indptr, h->knn_indptr, (size_t)(h->N + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(indptr, h->knn.indptr, (size_t)(h->N + 1) * sizeof(long long), hipMemcpyDeviceToHost));
   if (h->knn_nnz > 0) {
-    HIP_TRY(hipMemcpy(indices, h->knn_nbr, (size_t)h->knn_nnz * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(data, h->knn_val, (size_t)h->knn_nnz * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(indices, h->knn.indices, (size_t)h->knn_nnz * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(data, h->knn.val, (size_t)h->knn_nnz * sizeof(float), hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -266,8 +245,8 @@ int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
   const SimRowPlan plan = itemsim_row_plan(n);
   KnnFitP p{};
   p.kind = kind; p.s = (float)((double)shrink + 1e-6); p.shrink = shrink; p.p0 = p0; p.p1 = p1;
-  if (kind <= KNN_TVERSKY) TRY(upload_floats(&den.a, den_a, n));
-  if (kind == KNN_PRODUCT) TRY(upload_floats(&den.b, den_b, n));
+  if (kind <= KNN_TVERSKY) TRY(upload_floats(den.a, den_a, n));
+  if (kind == KNN_PRODUCT) TRY(upload_floats(den.b, den_b, n));
   p.den_a = den.a; p.den_b = den.b;
   TRY(t.alloc(n, k, plan.row_floats()));
   const size_t shmem = itemsim_row_args(h, 1, n, h->U, k, plan, t, &p);
@@ -277,10 +256,9 @@ int ganmf_itemknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
     GANMF_LAUNCH(itemknn_fit_kernel, dim3(plan.grid), dim3(KNN_THREADS), shmem, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  long long nnz = 0;
-  TRY(itemsim_compact(h, who, n, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, h->knn));
   HIP_TRY(hipStreamSynchronize(h->st));
-  h->knn_nnz = nnz;
-  *nnz_out = nnz;
+  h->knn_nnz = h->knn.nnz;
+  *nnz_out = h->knn.nnz;
   return 0;
 }

@@ -7,7 +7,6 @@ static_assert(MF_SGD_BPR == GANMF_MF_SGD_BPR && MF_SGD_FUNK == GANMF_MF_SGD_FUNK
 
 static void mf_sgd_drop(ganmf_handle* h) {
   MfSgdState& s = h->mfs;
-  hipFree(s.P); hipFree(s.terms); profiles_drop(s.profiles);
   s = MfSgdState();
 }
 
@@ -70,10 +69,10 @@ int ganmf_mf_sgd_init(ganmf_handle* h, int algorithm, int use_bias, int sgd_mode
 
   mf_sgd_drop(h);
   MfSgdState& s = h->mfs;
-  s.profiles = profiles;
+  s.profiles = std::move(profiles);
   s.k = k;
   s.block = (size_t)U * k + (size_t)n * k + (size_t)U + (size_t)n + 1;
-  if (int rc = named_alloc(who, "the factors, the biases and their optimiser state (float64)", (void**)&s.P, 3 * s.block * sizeof(double))) {
+  if (int rc = s.P.alloc(who, "the factors, the biases and their optimiser state (float64)", 3 * s.block)) {
     mf_sgd_drop(h);
     return rc;
   }
@@ -107,12 +106,9 @@ static int mf_sgd_run_device(ganmf_handle* h, const char* who, SampleList& t, co
   const bool levelled = route != GANMF_MF_SGD_SEQUENTIAL;
   if (n_levels) *n_levels = 0;
   if (n == 0) return 0;
-  if (s.terms_cap < (size_t)batch_size) {
+  if (s.terms.cap < (size_t)batch_size) {
     HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(s.terms);
-    s.terms = nullptr; s.terms_cap = 0;
-    TRY(named_alloc(who, "the per-sample terms of a batch", (void**)&s.terms, (size_t)batch_size * sizeof(double)));
-    s.terms_cap = (size_t)batch_size;
+    TRY(s.terms.alloc(who, "the per-sample terms of a batch", (size_t)batch_size));
   }
   MfSgdP p{};
   mf_sgd_block(h, 0, &p.W, &p.H, &p.ub, &p.ib, &p.gb);

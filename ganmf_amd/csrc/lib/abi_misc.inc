@@ -85,22 +85,23 @@ static int gemm_f32_entry(int device, const float* A, const float* B, float* C, 
   const int ar = a_kmajor ? K : (a_gather ? (int)a_rows : M), ac = a_kmajor ? M : K;
   const int br = b_kmajor ? K : N, bc = b_kmajor ? N : K;
   const int lda = round_up(ac, LD_ALIGN), ldb = round_up(bc, LD_ALIGN), ldc = round_up((int)N, LD_ALIGN);
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr, *slab = nullptr, *zp = nullptr, *dIds = nullptr, *dMom = nullptr, *dAlpha = nullptr;
-  TRY(dalloc(&zp, 2048 + 64));
-  TRY(dalloc(&dA, (size_t)ar * lda)); TRY(dalloc(&dB, (size_t)br * ldb)); TRY(dalloc(&dC, (size_t)M * ldc));
+  DevBuf<float> dA, dB, dC, slab, zp, dMom, dAlpha;      // (freed on every return)
+  DevBuf<int> dIds;
+  TRY(zp.alloc(2048 + 64, true));
+  TRY(dA.alloc((size_t)ar * lda, true)); TRY(dB.alloc((size_t)br * ldb, true)); TRY(dC.alloc((size_t)M * ldc, true));
   HIP_TRY(hipMemcpy2D(dA, (size_t)lda * 4, A, (size_t)ac * 4, (size_t)ac * 4, ar, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy2D(dB, (size_t)ldb * 4, B, (size_t)bc * 4, (size_t)bc * 4, br, hipMemcpyHostToDevice));
   GemmP g{};
   g.A = dA; g.lda = lda; g.B = dB; g.ldb = ldb; g.C = dC; g.ldc = ldc;
   g.M = (int)M; g.N = (int)N; g.K = (int)K; g.nbatch = 1; g.epi.kind = EPI_STORE; g.zero_page = zp; g.c_pad_writable = 1;
   if (a_gather) {
-    TRY(dalloc(&dIds, (size_t)M));
+    TRY(dIds.alloc((size_t)M, true));
     HIP_TRY(hipMemcpy(dIds, a_gather, (size_t)M * 4, hipMemcpyHostToDevice));
-    g.a_gather = reinterpret_cast<const int*>(dIds);
+    g.a_gather = dIds;
   }
-  if (adam_m) {      // theta (= C), m, v start at zero (dalloc clears)
+  if (adam_m) {      // theta (= C), m, v start at zero (the allocation clears)
     const float alpha = 1e-3f;
-    TRY(dalloc(&dMom, 2 * (size_t)M * ldc)); TRY(dalloc(&dAlpha, 64));
+    TRY(dMom.alloc(2 * (size_t)M * ldc, true)); TRY(dAlpha.alloc(64, true));
     HIP_TRY(hipMemcpy(dAlpha, &alpha, 4, hipMemcpyHostToDevice));
     g.epi.kind = EPI_ADAM; g.epi.adam_theta = dC; g.epi.adam_m = dMom; g.epi.adam_v = dMom + (size_t)M * ldc;
     g.epi.adam_alpha = dAlpha; g.epi.adam_reg = 0.f;
@@ -129,7 +130,7 @@ static int gemm_f32_entry(int device, const float* A, const float* B, float* C, 
   if (a_gather && !(pl.tile == 64 && pl.kg == 4 && !pl.persist && !pl.skinny && !pl.skinny_n && !pl.wide32))
     return fail(-1, "ganmf_gemm_f32_ex: a row list needs a 16-wave 64 x 64 plan (tile = 64, GANMF_TUNE kg=4,ring=3)");
   const size_t slab_elems = gemm_slab_elems(pl, g.M, ldc, 1);
-  if (slab_elems) TRY(dalloc(&slab, slab_elems));
+  if (slab_elems) TRY(slab.alloc(slab_elems, true));
   hipStream_t st = nullptr;
   HIP_TRY(gemm_run(st, g, a_kmajor, b_kmajor, pl, slab, slab_elems));
   HIP_TRY(hipDeviceSynchronize());
@@ -147,8 +148,6 @@ static int gemm_f32_entry(int device, const float* A, const float* B, float* C, 
   }
   HIP_TRY(hipMemcpy2D(C, (size_t)N * 4, dC, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
   if (adam_m) HIP_TRY(hipMemcpy2D(adam_m, (size_t)N * 4, dMom, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
-  hipFree(dA); hipFree(dB); hipFree(dC); hipFree(zp); hipFree(dIds); hipFree(dMom); hipFree(dAlpha);
-  if (slab) hipFree(slab);
   return 0;
 }
 

@@ -21,34 +21,21 @@ static int nmf_gate(ganmf_handle* h, const char* who) {
 
 static int nmf_ensure(ganmf_handle* h, size_t n_scal, size_t n_perm) {
   const size_t rows = (size_t)std::max(h->U, h->N), ld = (size_t)h->ldk, nnz = (size_t)h->als[0].nnz;
-  if (!h->nmf_num) TRY(dalloc(&h->nmf_num, rows * ld));
-  if (!h->nmf_den) TRY(dalloc(&h->nmf_den, rows * ld));
-  if (!h->nmf_G) TRY(dalloc(&h->nmf_G, 2 * ld * ld));
-  if (!h->nmf_vec) TRY(dalloc(&h->nmf_vec, 2 * ld));
-  if (!h->nmf_rowd) TRY(dalloc((float**)&h->nmf_rowd, 2 * (2 * rows)));
-  if (!h->nmf_part) TRY(dalloc((float**)&h->nmf_part, 2 * (size_t)NMF_PARTS));
-  if (nnz > h->nmf_q_cap || !h->nmf_q) {
+  if (!h->nmf_num) TRY(h->nmf_num.alloc(rows * ld, true));
+  if (!h->nmf_den) TRY(h->nmf_den.alloc(rows * ld, true));
+  if (!h->nmf_G) TRY(h->nmf_G.alloc(2 * ld * ld, true));
+  if (!h->nmf_vec) TRY(h->nmf_vec.alloc(2 * ld, true));
+  if (!h->nmf_rowd) TRY(h->nmf_rowd.alloc(2 * rows, true));
+  if (!h->nmf_part) TRY(h->nmf_part.alloc((size_t)NMF_PARTS, true));
+  if (nnz > h->nmf_q.cap || !h->nmf_errp) {      // three arrays by nnz: nmf_errp, allocated last, says that all three are there
     HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->nmf_q); h->nmf_q = nullptr; h->nmf_q_cap = 0;
-    hipFree(h->nmf_rowidx); h->nmf_rowidx = nullptr;
-    hipFree(h->nmf_errp); h->nmf_errp = nullptr;
-    TRY(dalloc(&h->nmf_q, nnz));
-    TRY(dalloc((float**)&h->nmf_rowidx, 2 * nnz));
-    TRY(dalloc((float**)&h->nmf_errp, 2 * (2 * ((nnz + NMF_SAMP_CHUNK - 1) / NMF_SAMP_CHUNK))));
-    h->nmf_q_cap = nnz;
+    h->nmf_errp.reset();
+    TRY(h->nmf_q.alloc(nnz, true));
+    TRY(h->nmf_rowidx.alloc(2 * nnz, true));
+    TRY(h->nmf_errp.alloc(2 * ((nnz + NMF_SAMP_CHUNK - 1) / NMF_SAMP_CHUNK), true));
   }
-  if (n_scal > h->nmf_scal_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->nmf_scal); h->nmf_scal = nullptr; h->nmf_scal_cap = 0;
-    TRY(dalloc((float**)&h->nmf_scal, 2 * n_scal));
-    h->nmf_scal_cap = n_scal;
-  }
-  if (n_perm > h->nmf_perm_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->nmf_perm); h->nmf_perm = nullptr; h->nmf_perm_cap = 0;
-    TRY(dalloc((float**)&h->nmf_perm, n_perm));
-    h->nmf_perm_cap = n_perm;
-  }
+  TRY(h->nmf_scal.grow(h->st, n_scal, true));
+  TRY(h->nmf_perm.grow(h->st, n_perm, true));
   return 0;
 }
 
@@ -106,7 +93,7 @@ static int nmf_sum(ganmf_handle* h, const double* in, long long n, int stride, d
 static int nmf_dot(ganmf_handle* h, const float* A, int lda, const float* B, int ldb, int rows, int cols, long long total, double* out) {
   {
     Scope sc(h, T_NMF_REDUCE, 2.0 * total, 8.0 * total);
-    GANMF_LAUNCH(nmf_dot_kernel, dim3(NMF_PARTS), dim3(NMF_THREADS), 0, h->st, A, lda, B, ldb, rows, cols, total, h->nmf_part);
+    GANMF_LAUNCH(nmf_dot_kernel, dim3(NMF_PARTS), dim3(NMF_THREADS), 0, h->st, A, lda, B, ldb, rows, cols, total, h->nmf_part.get());
     HIP_TRY(hipGetLastError());
   }
   return nmf_sum(h, h->nmf_part, NMF_PARTS, 1, out, 0);
@@ -141,7 +128,7 @@ static int nmf_rowidx_build(ganmf_handle* h) {
     const AlsSide& s = h->als[side];
     if (s.rows == 0 || s.nnz == 0) continue;
     Scope sc(h, T_NMF_SAMPLED, 0, 4.0 * s.nnz);
-    GANMF_LAUNCH(nmf_rowidx_kernel, dim3((unsigned)((s.rows + 3) / 4)), dim3(NMF_THREADS), 0, h->st, s.indptr, (int)s.rows,
+    GANMF_LAUNCH(nmf_rowidx_kernel, dim3((unsigned)((s.rows + 3) / 4)), dim3(NMF_THREADS), 0, h->st, s.indptr.get(), (int)s.rows,
                  h->nmf_rowidx + (size_t)side * s.nnz);
     HIP_TRY(hipGetLastError());
   }

@@ -24,8 +24,8 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
   SimPicks t;
   SimCsr R;
   const AlsSide& s = h->als[1];
-  TRY(upload_floats(&scale.a, row_scale, n));
-  if (col_scale) TRY(upload_floats(&scale.b, col_scale, n));
+  TRY(upload_floats(scale.a, row_scale, n));
+  if (col_scale) TRY(upload_floats(scale.b, col_scale, n));
   const SimRowPlan plan = itemsim_row_plan(n);      // (both passes)
   TRY(t.alloc(n, std::max(k, ck), plan.row_floats()));
 
@@ -39,10 +39,10 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
     GANMF_LAUNCH(p3_rows_kernel, dim3(plan.grid), dim3(KNN_THREADS), shmem, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  TRY(itemsim_compact(h, who, n, t, k, k, &R.indptr, &R.idx, &R.val, &R.nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, R));
   if (normalize) {
     Scope sc(h, T_P3_NORMALIZE, 2.0 * (double)R.nnz, 12.0 * (double)R.nnz);
-    GANMF_LAUNCH(p3_normalize_kernel, dim3((unsigned)n), dim3(64), 0, h->st, (const long long*)R.indptr, R.val, n);
+    GANMF_LAUNCH(p3_normalize_kernel, dim3((unsigned)n), dim3(64), 0, h->st, (const long long*)R.indptr, R.val.get(), n);
     HIP_TRY(hipGetLastError());
   }
 
@@ -50,24 +50,25 @@ int ganmf_p3_fit(ganmf_handle* h, int32_t topk, int32_t col_topk, int normalize,
   long long nnz = 0;
   if (ck > 0) {
     TRY(itemsim_columns(h, n, R, ck, plan, t));
-    TRY(itemsim_compact(h, who, n, t, ck, ck, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
+    TRY(itemsim_compact(h, who, n, t, ck, ck, h->knn));
+    nnz = h->knn.nnz;
   } else {
     HIP_TRY(hipMemsetAsync(t.cnt, 0, (size_t)n * sizeof(int), h->st));
     if (R.nnz > 0) {
       const unsigned blocks = (unsigned)std::min<long long>((R.nnz + KNN_THREADS - 1) / KNN_THREADS, 4096);
       Scope sc(h, T_P3_COLUMNS, 0.0, 8.0 * (double)R.nnz);
-      GANMF_LAUNCH(p3_count_kernel, dim3(blocks), dim3(KNN_THREADS), 0, h->st, (const int*)R.idx, R.nnz, t.cnt);
+      GANMF_LAUNCH(p3_count_kernel, dim3(blocks), dim3(KNN_THREADS), 0, h->st, (const int*)R.indices, R.nnz, t.cnt.get());
       HIP_TRY(hipGetLastError());
     }
     std::vector<int64_t> ip;
     TRY(itemsim_indptr(h, who, t.cnt, n, n, ip));
     nnz = ip[(size_t)n];
     if (nnz != R.nnz) return fail(-2, "%s: the transposed matrix counts %lld entries of %lld", who, nnz, R.nnz);
-    TRY(itemsim_alloc(ip.data(), n, &h->knn_indptr, &h->knn_nbr, &h->knn_val));
+    TRY(itemsim_alloc(ip.data(), n, h->knn));
     if (nnz > 0) {
       Scope sc(h, T_P3_COLUMNS, 0.0, 16.0 * (double)n * n);
-      GANMF_LAUNCH(p3_transpose_kernel, dim3(plan.grid), dim3(KNN_THREADS), 0, h->st, (const long long*)R.indptr, (const int*)R.idx,
-                   (const float*)R.val, n, (const long long*)h->knn_indptr, h->knn_nbr, h->knn_val);
+      GANMF_LAUNCH(p3_transpose_kernel, dim3(plan.grid), dim3(KNN_THREADS), 0, h->st, (const long long*)R.indptr, (const int*)R.indices,
+                   (const float*)R.val, n, (const long long*)h->knn.indptr, h->knn.indices.get(), h->knn.val.get());
       HIP_TRY(hipGetLastError());
     }
   }

@@ -1,19 +1,6 @@
 // abi_score.inc -- C ABI: scores, score filter, seen / test matrices, recommend, evaluate, scoring bench
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
-// A grow-on-demand buffer of the handle: at least `need` elements of `elem_bytes` behind *buf, *cap the elements it holds.  The stream
-// is drained before a buffer that enqueued work may still use is freed.  zeroed: through dalloc (float elements, zero-filled, at
-// least four of them, the device synchronised).  A failed allocation leaves a null pointer and cap 0.
-static int grow_device(ganmf_handle* h, void** buf, size_t* cap, size_t need, size_t elem_bytes, bool zeroed = false) {
-  if (need <= *cap) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(*buf); *buf = nullptr; *cap = 0;
-  if (zeroed) TRY(dalloc((float**)buf, need));
-  else HIP_TRY(hipMalloc(buf, need * elem_bytes));
-  *cap = need;
-  return 0;
-}
-
 // The scoring product itself: out[n, ldw] = rows[ids] . cols^T.  Many-tile shapes under the fp32-accurate default arithmetic take
 // the pre-split persistent kernel (gemm_bf16p.hpp): both factors are split ONCE into their three bf16 planes (the gather of the
 // scored rows rides in that pass), then one persistent launch; everything else goes through the planner (run_gemm).
@@ -25,8 +12,8 @@ static int score_product(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
   if (presplit) {
     const int mpad = round_up((int)n, BF16P_TILE), npad = round_up(W, BF16P_TILE), kp2 = round_up(h->k, BF16P_BK) / 2;
     const size_t need_a = (size_t)3 * mpad * kp2, need_b = (size_t)3 * npad * kp2;
-    TRY(grow_device(h, (void**)&h->sc_pa, &h->sc_pa_cap, need_a, sizeof(unsigned)));
-    TRY(grow_device(h, (void**)&h->sc_pb, &h->sc_pb_cap, need_b, sizeof(unsigned)));
+    TRY(h->sc_pa.grow(h->st, need_a, false));
+    TRY(h->sc_pb.grow(h->st, need_b, false));
     const double fl = gemm_flops((double)n, W, h->k);
     Scope s(h, T_SCORE_GEMM, fl, gemm_bytes((double)n, W, h->k));
     if (gemm_only) {      // (ganmf_bench_scores: operands prepared by the call before)
@@ -45,11 +32,11 @@ static int score_product(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
     HIP_TRY(gemm_bf16p_launch(h->st, h->sc_pa, mpad, h->sc_pb, npad, kp2, h->sc_out, ldw, (int)n, W));
     return 0;
   }
-  TRY(grow_device(h, (void**)&h->sc_rows, &h->sc_rows_cap, (size_t)n * h->ldk, sizeof(float), true));
+  TRY(h->sc_rows.grow(h->st, (size_t)n * h->ldk, true));
   if (!gemm_only) {
     const long long total = (long long)n * (h->ldk / 4);
     GANMF_LAUNCH(gather_rows_kernel, dim3((int)std::min<long long>(2048, (total + 255) / 256)), dim3(256), 0,
-                       h->st, rowsT.p, h->ldk, ids_dev, (int)n, h->sc_rows);
+                       h->st, rowsT.p.get(), h->ldk, ids_dev, (int)n, h->sc_rows.get());
     HIP_TRY(hipGetLastError());
   }
   GemmP g{};
@@ -69,28 +56,28 @@ static int scores_device(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
   if (h->cfg.model == GANMF_MODEL_ITEMSIM) {      // same [n, ldw] buffer and padding as the GEMM path: everything downstream is unchanged
     TRY(itemsim_ready(h, "scores", transposed));
     const int W = h->N, ldw = round_up(W, LD_ALIGN);
-    TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
+    TRY(h->sc_out.grow(h->st, (size_t)n * ldw, true));
     TRY(itemsim_product(h, ids_dev, n, W, ldw));
     *out_dev = h->sc_out; *width = W; *ld_out = ldw;
     return 0;
   }
   if (h->cfg.model == GANMF_MODEL_CFGAN) {      // the third source (step_cfgan.inc): the generator's output for the rows, or rows of its transpose
     const int W = transposed ? h->U : h->N, ldw = round_up(W, LD_ALIGN);
-    TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
+    TRY(h->sc_out.grow(h->st, (size_t)n * ldw, true));
     TRY(cfgan_scores(h, ids_dev, n, transposed, h->sc_out, ldw));
     *out_dev = h->sc_out; *width = W; *ld_out = ldw;
     return 0;
   }
   if (h->cfg.model == GANMF_MODEL_CAAE) {      // the fourth source (step_caae.inc): sigmoid(G(profile)) of the rows
     const int W = h->N, ldw = round_up(W, LD_ALIGN);
-    TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
+    TRY(h->sc_out.grow(h->st, (size_t)n * ldw, true));
     TRY(caae_scores(h, ids_dev, n, transposed, h->sc_out, ldw));
     *out_dev = h->sc_out; *width = W; *ld_out = ldw;
     return 0;
   }
   Tensor& colsT = transposed ? h->Ue : h->V;   // the other factor
   const int W = colsT.rows, ldw = round_up(W, LD_ALIGN);
-  TRY(grow_device(h, (void**)&h->sc_out, &h->sc_out_cap, (size_t)n * ldw, sizeof(float), true));
+  TRY(h->sc_out.grow(h->st, (size_t)n * ldw, true));
   TRY(score_product(h, ids_dev, n, transposed, W, ldw));
   *out_dev = h->sc_out; *width = W; *ld_out = ldw;
   return 0;
@@ -99,7 +86,7 @@ static int scores_device(ganmf_handle* h, const int* ids_dev, int64_t n, int tra
 // device copy of an id list in the handle's reusable buffer (scores / recommend are called once per 1000-user
 // block by the evaluators: no allocation per call)
 static int upload_ids(ganmf_handle* h, const int32_t* ids, int64_t n, int** out) {
-  TRY(grow_device(h, (void**)&h->sc_ids, &h->sc_ids_cap, (size_t)n, sizeof(int)));
+  TRY(h->sc_ids.grow(h->st, (size_t)n, false));
   HIP_TRY(hipMemcpyAsync(h->sc_ids, ids, n * sizeof(int), hipMemcpyHostToDevice, h->st));
   *out = h->sc_ids;
   return 0;
@@ -114,9 +101,9 @@ static int score_filter_args(ganmf_handle* h, const char* who, int W, int limit,
     *mask = h->item_mask;
   }
   if (h->mask_cold) {
-    if (!h->seen_indptr || h->seen_rows != limit || h->seen_cols != W)
+    if (!h->seen.indptr || h->seen.rows != limit || h->seen.cols != W)
       return fail(-1, "%s: masking cold rows needs ganmf_set_seen_csr with a %d x %d matrix", who, limit, W);
-    *cold = h->seen_indptr;
+    *cold = h->seen.indptr;
   }
   return 0;
 }
@@ -139,7 +126,7 @@ static int refresh_rank_mask(ganmf_handle* h) {
   if (h->item_mask_w > 0) keep = h->filter_host;
   for (size_t i = 0; i < wmax; ++i)
     if (h->ignore_host[i]) keep[i] = 0;
-  TRY(grow_device(h, (void**)&h->rank_mask, &h->rank_mask_cap, wmax, 1));
+  TRY(h->rank_mask.grow(h->st, wmax, false));
   HIP_TRY(hipMemcpy(h->rank_mask, keep.data(), wmax, hipMemcpyHostToDevice));
   return 0;
 }
@@ -163,7 +150,7 @@ int ganmf_set_score_filter(ganmf_handle* h, const int32_t* items, int64_t n_item
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
   if (n_items > 0) {
-    TRY(grow_device(h, (void**)&h->item_mask, &h->item_mask_cap, (size_t)wmax, 1));
+    TRY(h->item_mask.grow(h->st, (size_t)wmax, false));
     std::vector<unsigned char> m((size_t)wmax, 0);
     for (int64_t i = 0; i < n_items; ++i) m[(size_t)items[i]] = 1;
     HIP_TRY(hipMemcpy(h->item_mask, m.data(), m.size(), hipMemcpyHostToDevice));
@@ -243,16 +230,9 @@ static int check_csr(const char* who, const int64_t* indptr, const int32_t* indi
 int ganmf_set_seen_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols) {
   if (!h || !indptr) return fail(-1, "ganmf_set_seen_csr: null argument");
   TRY(check_csr("ganmf_set_seen_csr", indptr, indices, n_rows, n_cols, false, false));
-  const int64_t nnz = indptr[n_rows];
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  if (h->seen_indptr) { hipFree(h->seen_indptr); hipFree(h->seen_indices); h->seen_indptr = nullptr; h->seen_indices = nullptr; }
-  HIP_TRY(hipMalloc((void**)&h->seen_indptr, (n_rows + 1) * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&h->seen_indices, std::max<int64_t>(nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMemcpy(h->seen_indptr, indptr, (n_rows + 1) * sizeof(long long), hipMemcpyHostToDevice));
-  if (nnz) HIP_TRY(hipMemcpy(h->seen_indices, indices, nnz * sizeof(int), hipMemcpyHostToDevice));
-  h->seen_rows = n_rows; h->seen_cols = n_cols;
-  return 0;
+  return h->seen.upload(indptr, indices, n_rows, n_cols);
 }
 
 // a launch with `shmem` bytes of dynamic LDS: past the 48 KiB every kernel may ask for, the kernel has to be told first
@@ -273,10 +253,10 @@ static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_
   if (cand) TRY(not_cfgan(h, who));
   TRY(itemsim_ready(h, who, transposed));
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
-  if (cand && !h->cand_indptr) return fail(-1, "%s: no candidate matrix (ganmf_set_candidates_csr)", who);
-  if (cand && (h->cand_rows != limit || h->cand_cols != W))
-    return fail(-1, "%s: the candidate matrix is %lld x %lld, transposed = %d needs %d x %d", who, (long long)h->cand_rows,
-                (long long)h->cand_cols, transposed, limit, W);
+  if (cand && !h->cand.indptr) return fail(-1, "%s: no candidate matrix (ganmf_set_candidates_csr)", who);
+  if (cand && (h->cand.rows != limit || h->cand.cols != W))
+    return fail(-1, "%s: the candidate matrix is %lld x %lld, transposed = %d needs %d x %d", who, (long long)h->cand.rows,
+                (long long)h->cand.cols, transposed, limit, W);
   if (cutoff < 1 || cutoff > W || cutoff > GANMF_RECOMMEND_MAX_CUTOFF)
     return fail(-1, "%s: cutoff %d out of range [1,%d]", who, cutoff, std::min(W, GANMF_RECOMMEND_MAX_CUTOFF));
   long long longest = 0;      // (candidate lists of the rows asked for)
@@ -288,7 +268,7 @@ static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_
       return fail(-1, "%s: row %d has %lld candidates, at most %d (GANMF_CANDIDATES_MAX_PER_ROW)", who, ids[i], len, CAND_MAX_PER_ROW);
     longest = std::max(longest, len);
   }
-  if (remove_seen && (!h->seen_indptr || h->seen_rows != limit || h->seen_cols != W))
+  if (remove_seen && (!h->seen.indptr || h->seen.rows != limit || h->seen.cols != W))
     return fail(-1, "%s: remove_seen needs ganmf_set_seen_csr with a %d x %d matrix", who, limit, W);
   const unsigned char* fmask; const long long* fcold;
   TRY(score_filter_args(h, who, W, limit, &fmask, &fcold));
@@ -300,23 +280,21 @@ static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_
   HIP_TRY(hipSetDevice(h->dev));
   int* ids_dev = nullptr;
   TRY(upload_ids(h, ids, n, &ids_dev));
-  {   // the two top-k buffers under their one cap: published once both hold n * cutoff
+  {   // the two top-k buffers: the count is published (topk_vals.cap) once both hold n * cutoff
     const size_t need = (size_t)n * cutoff;
-    size_t cap_items = h->topk_cap, cap_vals = h->topk_cap;
-    if (need > h->topk_cap) h->topk_cap = 0;
-    TRY(grow_device(h, (void**)&h->topk_items, &cap_items, need, sizeof(int)));
-    TRY(grow_device(h, (void**)&h->topk_vals, &cap_vals, need, sizeof(float)));
-    h->topk_cap = cap_items;
+    if (need > h->topk_vals.cap) h->topk_vals.reset();      // (topk_vals grows last: its cap is what both hold)
+    TRY(h->topk_items.grow(h->st, need, false));
+    TRY(h->topk_vals.grow(h->st, need, false));
   }
-  const long long* seen_indptr = remove_seen ? h->seen_indptr : nullptr;
+  const long long* seen_indptr = remove_seen ? h->seen.indptr : nullptr;
   if (cand) {
     Tensor& rowsT = transposed ? h->V : h->Ue;
     Tensor& colsT = transposed ? h->Ue : h->V;
     CandP p{};
     p.cap = cand_cap;
     p.rows = rowsT.p; p.cols = colsT.p; p.ld = h->ldk; p.k = h->k; p.ids = ids_dev;
-    p.c_indptr = h->cand_indptr; p.c_indices = h->cand_indices;
-    p.seen_indptr = seen_indptr; p.seen_indices = h->seen_indices;
+    p.c_indptr = h->cand.indptr; p.c_indices = h->cand.indices;
+    p.seen_indptr = seen_indptr; p.seen_indices = h->seen.indices;
     p.item_mask = fmask; p.cold_indptr = fcold; p.cutoff = cutoff;
     p.out_items = h->topk_items; p.out_vals = h->topk_vals;
     TRY(allow_lds(rmse ? reinterpret_cast<const void*>(cand_topk_rmse_kernel) : reinterpret_cast<const void*>(cand_topk_kernel), cand_shmem));
@@ -329,11 +307,11 @@ static int rank_device(ganmf_handle* h, const char* who, bool cand, const int32_
     const size_t shmem = Wd <= lds_cap ? (size_t)Wd * sizeof(float) : 0;
     TRY(allow_lds(rmse ? reinterpret_cast<const void*>(mask_topk_rmse_kernel) : reinterpret_cast<const void*>(mask_topk_kernel), shmem));
     if (rmse)
-      GANMF_LAUNCH(mask_topk_rmse_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev, seen_indptr, h->seen_indices,
-                   (int)cutoff, lds_cap, h->topk_items, h->topk_vals, fmask, fcold, *rmse);
+      GANMF_LAUNCH(mask_topk_rmse_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev, seen_indptr, h->seen.indices.get(),
+                   (int)cutoff, lds_cap, h->topk_items.get(), h->topk_vals.get(), fmask, fcold, *rmse);
     else
-      GANMF_LAUNCH(mask_topk_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev, seen_indptr, h->seen_indices,
-                   (int)cutoff, lds_cap, h->topk_items, h->topk_vals, fmask, fcold);
+      GANMF_LAUNCH(mask_topk_kernel, dim3((int)n), dim3(256), shmem, h->st, od, ldw, Wd, ids_dev, seen_indptr, h->seen.indices.get(),
+                   (int)cutoff, lds_cap, h->topk_items.get(), h->topk_vals.get(), fmask, fcold);
   }
   HIP_TRY(hipGetLastError());
   if (ids_dev_out) *ids_dev_out = ids_dev;
@@ -363,8 +341,7 @@ int ganmf_set_candidates_csr(ganmf_handle* h, const int64_t* indptr, const int32
   if (indptr) TRY(check_csr("ganmf_set_candidates_csr", indptr, indices, n_rows, n_cols, true, false));
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(h->cand_indptr); hipFree(h->cand_indices);
-  h->cand_indptr = nullptr; h->cand_indices = nullptr; h->cand_rows = h->cand_cols = 0;
+  h->cand.drop();
   h->cand_indptr_host.clear();
   if (!indptr) return 0;
   // canonical rows (columns ascending, a repeated column kept once), as ganmf_set_urm_csr makes the training matrix canonical
@@ -378,12 +355,8 @@ int ganmf_set_candidates_csr(ganmf_handle* h, const int64_t* indptr, const int32
     ix.erase(std::unique(ix.begin() + at, ix.end()), ix.end());
     ip[(size_t)r + 1] = (long long)ix.size();
   }
-  HIP_TRY(hipMalloc((void**)&h->cand_indptr, ip.size() * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&h->cand_indices, std::max<size_t>(ix.size(), 1) * sizeof(int)));
-  HIP_TRY(hipMemcpy(h->cand_indptr, ip.data(), ip.size() * sizeof(long long), hipMemcpyHostToDevice));
-  if (!ix.empty()) HIP_TRY(hipMemcpy(h->cand_indices, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice));
+  TRY(h->cand.upload(ip.data(), ix.data(), n_rows, n_cols));      // a failed upload leaves "no candidate matrix"
   h->cand_indptr_host.swap(ip);
-  h->cand_rows = n_rows; h->cand_cols = n_cols;     // set last: a failed upload leaves "no candidate matrix"
   return 0;
 }
 
@@ -400,33 +373,22 @@ int ganmf_set_test_csr(ganmf_handle* h, const int64_t* indptr, const int32_t* in
                        int64_t n_cols) {
   if (!h || !indptr || (!indices && indptr[n_rows] > 0) || (!gains && indptr[n_rows] > 0)) return fail(-1, "ganmf_set_test_csr: null argument");
   TRY(check_csr("ganmf_set_test_csr", indptr, indices, n_rows, n_cols, true, true));
-  const int64_t nnz = indptr[n_rows];
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(h->test_indptr); hipFree(h->test_indices); hipFree(h->test_gain);
-  h->test_indptr = nullptr; h->test_indices = nullptr; h->test_gain = nullptr; h->test_rows = h->test_cols = 0;
-  hipFree(h->test_rating); h->test_rating = nullptr; h->test_rating_ok = false; h->test_nnz = nnz;
-  HIP_TRY(hipMalloc((void**)&h->test_indptr, (size_t)(n_rows + 1) * sizeof(long long)));
-  HIP_TRY(hipMalloc((void**)&h->test_indices, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&h->test_gain, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
-  static_assert(sizeof(long long) == sizeof(int64_t), "indptr width");
-  HIP_TRY(hipMemcpy(h->test_indptr, indptr, (size_t)(n_rows + 1) * sizeof(long long), hipMemcpyHostToDevice));
-  if (nnz > 0) {
-    HIP_TRY(hipMemcpy(h->test_indices, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->test_gain, gains, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-  }
-  h->test_rows = n_rows; h->test_cols = n_cols;
-  return 0;
+  h->test_gain.reset();
+  h->test_rating.reset(); h->test_rating_ok = false;      // the ratings belong to the matrix they were set for
+  TRY(h->test.upload(indptr, indices, n_rows, n_cols));
+  return h->test.upload_values(h->test_gain, gains);
 }
 
 int ganmf_set_test_ratings(ganmf_handle* h, const float* ratings, int64_t nnz) {
   if (!h || (nnz > 0 && !ratings)) return fail(-1, "ganmf_set_test_ratings: null argument");
-  if (!h->test_indptr) return fail(-1, "ganmf_set_test_ratings: needs ganmf_set_test_csr first");
-  if (nnz != h->test_nnz) return fail(-1, "ganmf_set_test_ratings: %lld ratings for a test matrix of %lld entries", (long long)nnz, (long long)h->test_nnz);
+  if (!h->test.indptr) return fail(-1, "ganmf_set_test_ratings: needs ganmf_set_test_csr first");
+  if (nnz != h->test.nnz) return fail(-1, "ganmf_set_test_ratings: %lld ratings for a test matrix of %lld entries", (long long)nnz, (long long)h->test.nnz);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(h->test_rating); h->test_rating = nullptr; h->test_rating_ok = false;
-  HIP_TRY(hipMalloc((void**)&h->test_rating, (size_t)std::max<int64_t>(nnz, 1) * sizeof(float)));
+  h->test_rating.reset(); h->test_rating_ok = false;
+  TRY(h->test_rating.alloc((size_t)std::max<int64_t>(nnz, 1), false));
   if (nnz > 0) HIP_TRY(hipMemcpy(h->test_rating, ratings, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
   h->test_rating_ok = true;
   return 0;
@@ -437,8 +399,8 @@ int ganmf_set_eval_item_weights(ganmf_handle* h, const double* novelty, const do
   if (width < 1 || width > std::max(h->U, h->N)) return fail(-1, "ganmf_set_eval_item_weights: width %lld out of range", (long long)width);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(h->eval_w); h->eval_w = nullptr; h->eval_w_width = 0;
-  HIP_TRY(hipMalloc((void**)&h->eval_w, (size_t)2 * width * sizeof(double)));
+  h->eval_w_width = 0;
+  TRY(h->eval_w.alloc((size_t)2 * width, false));
   HIP_TRY(hipMemcpy(h->eval_w, novelty, (size_t)width * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->eval_w + width, popularity, (size_t)width * sizeof(double), hipMemcpyHostToDevice));
   h->eval_w_width = width;
@@ -458,7 +420,7 @@ static int eval_prepare(ganmf_handle* h, const char* who, bool cand, bool full, 
   if (n_cutoffs < 1 || n_cutoffs > GANMF_EVAL_MAX_CUTOFFS) return fail(-1, "%s: 1..%d cut-offs per call", who, GANMF_EVAL_MAX_CUTOFFS);
   if (n < 1 || n > (1 << 30)) return fail(-1, "%s: n out of range", who);
   const int limit = transposed ? h->N : h->U, W = transposed ? h->U : h->N;
-  if (!h->test_indptr || h->test_rows != limit || h->test_cols != W)
+  if (!h->test.indptr || h->test.rows != limit || h->test.cols != W)
     return fail(-1, "%s: needs ganmf_set_test_csr with a %d x %d matrix", who, limit, W);
   if (full && !h->test_rating_ok) return fail(-1, "%s: needs ganmf_set_test_ratings for the current test matrix", who);
   if (full && h->eval_w_width != W) return fail(-1, "%s: needs ganmf_set_eval_item_weights of width %d", who, W);
@@ -469,13 +431,13 @@ static int eval_prepare(ganmf_handle* h, const char* who, bool cand, bool full, 
   }
   HIP_TRY(hipSetDevice(h->dev));
   if (full) {
-    TRY(grow_device(h, (void**)&h->eval_rmse, &h->eval_rmse_cap, (size_t)n, sizeof(float)));
-    TRY(grow_device(h, (void**)&h->eval_counts, &h->eval_counts_cap, (size_t)n_cutoffs * W, sizeof(unsigned)));
+    TRY(h->eval_rmse.grow(h->st, (size_t)n, false));
+    TRY(h->eval_counts.grow(h->st, (size_t)n_cutoffs * W, false));
   }
-  const RmseP rp{h->test_indptr, h->test_indices, h->test_rating, h->eval_rmse};
+  const RmseP rp{h->test.indptr, h->test.indices, h->test_rating, h->eval_rmse};
   int* ids_dev = nullptr;
   TRY(rank_device(h, who, cand, ids, n, transposed, K, remove_seen, &ids_dev, full ? &rp : nullptr));
-  TRY(grow_device(h, (void**)&h->eval_buf, &h->eval_cap, (size_t)K + (size_t)n * K + tail, sizeof(double)));
+  TRY(h->eval_buf.grow(h->st, (size_t)K + (size_t)n * K + tail, false));
   c->K = K; c->W = W;
   c->d_disc = h->eval_buf;
   c->d_ideal = c->d_disc + K;
@@ -485,7 +447,7 @@ static int eval_prepare(ganmf_handle* h, const char* who, bool cand, bool full, 
   EvalP& p = c->p;
   p = EvalP{};
   p.items = h->topk_items; p.K = K; p.n = (int)n; p.ids = ids_dev;
-  p.t_indptr = h->test_indptr; p.t_indices = h->test_indices; p.t_gain = h->test_gain;
+  p.t_indptr = h->test.indptr; p.t_indices = h->test.indices; p.t_gain = h->test_gain;
   p.disc = c->d_disc; p.ideal_cum = c->d_ideal; p.ncut = n_cutoffs; p.partials = nullptr;
   for (int i = 0; i < n_cutoffs; ++i) p.cutoffs[i] = cutoffs[i];
   return 0;
@@ -584,7 +546,7 @@ int ganmf_evaluate_groups(ganmf_handle* h, const int32_t* ids, int64_t n, int tr
   const size_t n_user = (size_t)n * ncol, n_sum = (size_t)G * ncol;
   EvalCall c;
   TRY(eval_prepare(h, who, candidates != 0, false, ids, n, transposed, remove_seen, cutoffs, n_cutoffs, disc, ideal_cum, n_user + n_sum, &c));
-  TRY(grow_device(h, (void**)&h->eval_grp, &h->eval_grp_cap, G > 0 ? members.size() + begin.size() : 0, sizeof(int)));
+  TRY(h->eval_grp.grow(h->st, G > 0 ? members.size() + begin.size() : 0, false));
   double* d_user = c.d_tail;
   double* d_sum = d_user + n_user;
   {
@@ -619,14 +581,14 @@ int ganmf_set_item_diversity(ganmf_handle* h, const float* matrix, int64_t width
   if (matrix && (width < 1 || width > std::max(h->U, h->N))) return fail(-1, "%s: width %lld out of range", who, (long long)width);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(h->div_mat); h->div_mat = nullptr; h->div_w = 0;
+  h->div_mat.reset(); h->div_w = 0;
   if (!matrix) return 0;
   const size_t bytes = (size_t)width * (size_t)width * sizeof(float);
   size_t free_b = 0, total_b = 0;     // never more than a quarter of the free device memory (the rule of ganmf_score_similarity)
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4)
     return fail(-1, "%s: out of memory budget: a %lld x %lld matrix needs %.1f MB, over a quarter of the %.1f MB free", who,
                 (long long)width, (long long)width, bytes / 1048576.0, free_b / 1048576.0);
-  HIP_TRY(hipMalloc((void**)&h->div_mat, bytes));
+  TRY(h->div_mat.alloc((size_t)width * (size_t)width, false));
   HIP_TRY(hipMemcpy(h->div_mat, matrix, bytes, hipMemcpyHostToDevice));
   h->div_w = width;                   // set last: a failed upload leaves "no matrix"
   return 0;
@@ -652,7 +614,7 @@ int ganmf_evaluate_diversity(ganmf_handle* h, const int32_t* ids, int64_t n, int
   TRY(rank_device(h, who, candidates != 0, ids, n, transposed, K, remove_seen, nullptr, nullptr));     // (refuses K over the limit)
   const int grid = (int)((n + 255) / 256);
   const size_t n_user = (size_t)n * n_cutoffs, n_part = (size_t)grid * n_cutoffs;
-  TRY(grow_device(h, (void**)&h->eval_buf, &h->eval_cap, n_user + n_part, sizeof(double)));
+  TRY(h->eval_buf.grow(h->st, n_user + n_part, false));
   double* d_user = h->eval_buf;
   double* d_part = d_user + n_user;
   p.items = h->topk_items; p.K = K; p.D = h->div_mat; p.W = W; p.ncut = n_cutoffs; p.out = d_user;
@@ -732,26 +694,26 @@ int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int t
   HIP_TRY(hipSetDevice(h->dev));
   {   // never more than a quarter of the free device memory for what this call adds to the handle (the rule of the pass buffers)
     size_t grow = 0, free_b = 0, total_b = 0;
-    if (need_out > h->sc_out_cap) grow += (need_out - h->sc_out_cap) * sizeof(float);
-    if (need_mat > h->sim_mat_cap) grow += (need_mat - h->sim_mat_cap) * sizeof(float);
-    if (need_pool > h->sim_pool_cap) grow += (need_pool - h->sim_pool_cap) * sizeof(float);
-    if ((size_t)2 * tiles > h->sim_part_cap) grow += ((size_t)2 * tiles - h->sim_part_cap) * sizeof(double);
+    if (need_out > h->sc_out.cap) grow += (need_out - h->sc_out.cap) * sizeof(float);
+    if (need_mat > h->sim_mat.cap) grow += (need_mat - h->sim_mat.cap) * sizeof(float);
+    if (need_pool > h->sim_pool.cap) grow += (need_pool - h->sim_pool.cap) * sizeof(float);
+    if ((size_t)2 * tiles > h->sim_part.cap) grow += ((size_t)2 * tiles - h->sim_part.cap) * sizeof(double);
     if (grow > 0 && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow > free_b / 4))
       return fail(-1, "%s: %lld rows%s need %.1f MB more device memory, over a quarter of the %.1f MB free", who, (long long)n,
                   want_mat ? " with their similarity matrix" : "", grow / 1048576.0, free_b / 1048576.0);
   }
   int* ids_dev = nullptr;
   TRY(upload_ids(h, ids, n, &ids_dev));
-  TRY(grow_device(h, (void**)&h->sim_mat, &h->sim_mat_cap, need_mat, sizeof(float)));
-  TRY(grow_device(h, (void**)&h->sim_pool, &h->sim_pool_cap, need_pool, sizeof(float)));
-  TRY(grow_device(h, (void**)&h->sim_part, &h->sim_part_cap, (size_t)2 * tiles, sizeof(double)));
-  TRY(grow_device(h, (void**)&h->sim_zero, &h->sim_zero_cap, (size_t)n, sizeof(int)));
+  TRY(h->sim_mat.grow(h->st, need_mat, false));
+  TRY(h->sim_pool.grow(h->st, need_pool, false));
+  TRY(h->sim_part.grow(h->st, (size_t)2 * tiles, false));
+  TRY(h->sim_zero.grow(h->st, (size_t)n, false));
   float* sd = nullptr; int Wd = 0, ldd = 0;
   int rc = scores_device(h, ids_dev, n, transposed, &sd, &Wd, &ldd);      // unfiltered: a -inf has no cosine
   if (rc) { hipStreamSynchronize(h->st); return rc; }
   {
     Scope s(h, T_SIM_AUX, 3.0 * n * W, 8.0 * n * ldw);
-    GANMF_LAUNCH(sim_normalize_kernel, dim3((int)n), dim3(256), 0, h->st, sd, ldd, Wd, h->sim_zero);
+    GANMF_LAUNCH(sim_normalize_kernel, dim3((int)n), dim3(256), 0, h->st, sd, ldd, Wd, h->sim_zero.get());
     HIP_TRY(hipGetLastError());
   }
   {
@@ -776,7 +738,7 @@ int ganmf_score_similarity(ganmf_handle* h, const int32_t* ids, int64_t n, int t
   if (e == hipSuccess && pooled) {
     {
       Scope s(h, T_SIM_AUX, (double)n * n, 4.0 * n * n);
-      GANMF_LAUNCH(sim_pool_kernel, dim3((unsigned)(pool * pool)), dim3(256), 0, h->st, h->sim_mat, ldn, (int)n, (int)pool, h->sim_pool);
+      GANMF_LAUNCH(sim_pool_kernel, dim3((unsigned)(pool * pool)), dim3(256), 0, h->st, h->sim_mat.get(), ldn, (int)n, (int)pool, h->sim_pool.get());
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(pooled, h->sim_pool, need_pool * sizeof(float), hipMemcpyDeviceToHost, h->st);

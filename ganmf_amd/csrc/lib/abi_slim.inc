@@ -4,7 +4,6 @@
 
 static void slim_drop(ganmf_handle* h) {
   SlimState& s = h->slim;
-  hipFree(s.S); hipFree(s.st0); hipFree(s.st1); profiles_drop(s.profiles);
   s = SlimState();
 }
 
@@ -39,11 +38,11 @@ int ganmf_slim_bpr_init(ganmf_handle* h, int symmetric, int sgd_mode, double lea
 
   slim_drop(h);
   SlimState& s = h->slim;
-  s.profiles = profiles;
+  s.profiles = std::move(profiles);
   s.cells = symmetric ? (size_t)n * ((size_t)n + 1) / 2 : (size_t)n * (size_t)n;
-  int rc = named_alloc(who, symmetric ? "S (one float64 per unordered item pair)" : "S (float64, items x items)", (void**)&s.S, s.cells * sizeof(double));
-  if (!rc) rc = named_alloc(who, "the optimiser state", (void**)&s.st0, (size_t)n * sizeof(double));
-  if (!rc) rc = named_alloc(who, "the optimiser state", (void**)&s.st1, (size_t)n * sizeof(double));
+  int rc = s.S.alloc(who, symmetric ? "S (one float64 per unordered item pair)" : "S (float64, items x items)", s.cells);
+  if (!rc) rc = s.st0.alloc(who, "the optimiser state", (size_t)n);
+  if (!rc) rc = s.st1.alloc(who, "the optimiser state", (size_t)n);
   if (rc) { slim_drop(h); return rc; }
   hipError_t e = hipMemset(s.S, 0, s.cells * sizeof(double));
   if (e == hipSuccess) e = hipMemset(s.st0, 0, (size_t)n * sizeof(double));
@@ -67,7 +66,7 @@ static int slim_run_device(ganmf_handle* h, const char* who, SampleList& t, cons
   if (n_levels) *n_levels = 0;
   if (n == 0) return 0;
   SlimP p{};
-  p.indptr = s.profiles.indptr; p.items = s.profiles.items; p.S = s.S; p.st0 = s.st0; p.st1 = s.st1;
+  p.indptr = s.profiles.indptr; p.items = s.profiles.indices; p.S = s.S; p.st0 = s.st0; p.st1 = s.st1;
   p.n_items = h->N; p.symmetric = s.symmetric; p.sgd = s.sgd;
   p.lr = s.lr; p.li = s.li; p.lj = s.lj; p.gamma = s.gamma; p.b1 = s.b1; p.b2 = s.b2;
   p.users = t.users; p.pos = t.pos; p.neg = t.neg;
@@ -80,7 +79,7 @@ static int slim_run_device(ganmf_handle* h, const char* who, SampleList& t, cons
       b1p *= s.b1;
       b2p *= s.b2;
     }
-    TRY(named_alloc(who, "the beta powers", (void**)&t.pows, pows.size() * sizeof(double)));
+    TRY(t.pows.alloc(who, "the beta powers", pows.size()));
     HIP_TRY(hipMemcpyAsync(t.pows, pows.data(), pows.size() * sizeof(double), hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));      // (pows leaves scope)
     p.pows = t.pows;
@@ -172,11 +171,6 @@ int ganmf_slim_bpr_epochs(ganmf_handle* h, int64_t n_epochs, int mode, int64_t* 
   return 0;
 }
 
-struct SlimFinishTmp {
-  double* rows = nullptr;
-  ~SlimFinishTmp() { hipFree(rows); }
-};
-
 int ganmf_slim_bpr_finish(ganmf_handle* h, int32_t topk, int64_t* nnz_out) {
   const char* who = "ganmf_slim_bpr_finish";
   if (!h || !nnz_out) return fail(-1, "%s: null argument", who);
@@ -191,31 +185,30 @@ int ganmf_slim_bpr_finish(ganmf_handle* h, int32_t topk, int64_t* nnz_out) {
   const SlimState& s = h->slim;
   SimPicks t;
   SimCsr R;
-  SlimFinishTmp d;
+  DevBuf<double> rows;      // the private float64 rows of slim_rows_kernel
   // slim_rows_kernel keeps its float64 row in global memory whatever n: at most 512 workgroups.  The column pass takes the plan of the
   // other fits as it is: min(n, 8192) workgroups with the column in LDS, above KNN_ROW_LDS the same 512 with a private float row each.
   const SimRowPlan plan = itemsim_row_plan(n);
   const unsigned grid = (unsigned)std::min(n, 512);
-  TRY(named_alloc(who, "the private float64 rows", (void**)&d.rows, (size_t)grid * n * sizeof(double)));
+  TRY(rows.alloc(who, "the private float64 rows", (size_t)grid * n));
   TRY(t.alloc(n, k, plan.row_floats()));
   // ---- get_S: the diagonal, then the top-k of every float64 row, rounded to float32 ----
-  GANMF_LAUNCH(slim_zero_diag_kernel, dim3((unsigned)((n + SLIM_THREADS - 1) / SLIM_THREADS)), dim3(SLIM_THREADS), 0, h->st, s.S, n, s.symmetric);
+  GANMF_LAUNCH(slim_zero_diag_kernel, dim3((unsigned)((n + SLIM_THREADS - 1) / SLIM_THREADS)), dim3(SLIM_THREADS), 0, h->st, s.S.get(), n, s.symmetric);
   HIP_TRY(hipGetLastError());
   {
     SlimRowP p{};
-    p.S = s.S; p.n_items = n; p.symmetric = s.symmetric; p.topk = k; p.rows = d.rows;
+    p.S = s.S; p.n_items = n; p.symmetric = s.symmetric; p.topk = k; p.rows = rows;
     p.out_idx = t.idx; p.out_val = t.val; p.out_cnt = t.cnt;
     GANMF_LAUNCH(slim_rows_kernel, dim3(grid), dim3(SLIM_THREADS), 0, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  TRY(itemsim_compact(h, who, n, t, k, k, &R.indptr, &R.idx, &R.val, &R.nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, R));
   // ---- similarityMatrixTopK: the k largest non-zeros of every column (p3_columns_kernel, bit copies) ----
   TRY(itemsim_columns(h, n, R, k, plan, t));
-  long long nnz = 0;
-  TRY(itemsim_compact(h, who, n, t, k, k, &h->knn_indptr, &h->knn_nbr, &h->knn_val, &nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, h->knn));
   HIP_TRY(hipStreamSynchronize(h->st));
-  h->knn_nnz = nnz;
-  *nnz_out = nnz;
+  h->knn_nnz = h->knn.nnz;
+  *nnz_out = h->knn.nnz;
   return 0;
 }
 

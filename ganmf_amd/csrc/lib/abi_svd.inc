@@ -6,18 +6,15 @@ static int svd_ensure(ganmf_handle* h, int ldl) {
   const size_t rows = (size_t)std::max(h->U, h->N);
   if (h->svd_ldl >= ldl) return 0;
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(h->svd_P[0]); hipFree(h->svd_P[1]); hipFree(h->svd_G); hipFree(h->svd_X); hipFree(h->svd_Wl);
-  hipFree(h->svd_lam); hipFree(h->svd_flag);
-  h->svd_P[0] = h->svd_P[1] = h->svd_G = h->svd_X = h->svd_Wl = h->svd_lam = nullptr;
-  h->svd_flag = nullptr;
+  h->svd_P[0].reset(); h->svd_P[1].reset(); h->svd_G.reset(); h->svd_X.reset(); h->svd_Wl.reset(); h->svd_lam.reset(); h->svd_flag.reset();
   h->svd_ldl = 0;
-  TRY(dalloc(&h->svd_P[0], rows * ldl));
-  TRY(dalloc(&h->svd_P[1], rows * ldl));
-  TRY(dalloc(&h->svd_G, (size_t)ldl * ldl));
-  TRY(dalloc(&h->svd_X, (size_t)ldl * ldl));
-  TRY(dalloc(&h->svd_Wl, (size_t)ldl * h->ldk));
-  TRY(dalloc(&h->svd_lam, (size_t)ldl + h->ldk));
-  TRY(dalloc((float**)&h->svd_flag, 4));
+  TRY(h->svd_P[0].alloc(rows * ldl, true));
+  TRY(h->svd_P[1].alloc(rows * ldl, true));
+  TRY(h->svd_G.alloc((size_t)ldl * ldl, true));
+  TRY(h->svd_X.alloc((size_t)ldl * ldl, true));
+  TRY(h->svd_Wl.alloc((size_t)ldl * h->ldk, true));
+  TRY(h->svd_lam.alloc((size_t)ldl + h->ldk, true));
+  TRY(h->svd_flag.alloc(4, true));
   h->svd_ldl = ldl;
   return 0;
 }

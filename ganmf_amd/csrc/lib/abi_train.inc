@@ -99,7 +99,7 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
       h->front_staged = false; h->x_staged = false; h->XF = h->XF_own; h->d_alpha = S_ALPHA_D;
       if (h->lazy_pass) lazy_pass_abort(h);
       if (g_opened_early) {
-        GANMF_LAUNCH(restore_g_powers_kernel, dim3(1), dim3(64), 0, h->st, h->scal);
+        GANMF_LAUNCH(restore_g_powers_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get());
         (void)hipGetLastError();
       }
     }
@@ -116,7 +116,7 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
   for (int p = 0; p < d_steps; ++p) {
     const int tab = S_TAB + (p & 1) * h->tab_cap;      // (passes alternate tables: a side-lane update of the pass before may still read its slot)
     if (staged && p > 0) {      // (the first pass's table was written by stage_pass's row-expansion launch)
-      GANMF_LAUNCH(open_steps_kernel, dim3(1), dim3(64), 0, h->st, h->scal, 0, tab, (int)nfull, h->cfg.d_lr);
+      GANMF_LAUNCH(open_steps_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get(), 0, tab, (int)nfull, h->cfg.d_lr);
       HIP_TRY(hipGetLastError());
     }
     for (int64_t i = 0; i < per_pass; ++i, ++idx) {
@@ -158,10 +158,10 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
     if (h->cfg.model == GANMF_MODEL_DISGANMF) TRY(allreduce(h, h->d_parts, (size_t)nd * 4));
     else {
       const int grid = (int)std::min<int64_t>(256, (nd + 255) / 256);
-      GANMF_LAUNCH(col_copy_kernel, dim3(grid), dim3(256), 0, h->st, h->d_parts, h->colbuf, (long long)nd, 2, 1);
+      GANMF_LAUNCH(col_copy_kernel, dim3(grid), dim3(256), 0, h->st, h->d_parts, h->colbuf.get(), (long long)nd, 2, 1);
       HIP_TRY(hipGetLastError());
       TRY(allreduce(h, h->colbuf, (size_t)nd));
-      GANMF_LAUNCH(col_copy_kernel, dim3(grid), dim3(256), 0, h->st, h->d_parts, h->colbuf, (long long)nd, 2, 0);
+      GANMF_LAUNCH(col_copy_kernel, dim3(grid), dim3(256), 0, h->st, h->d_parts, h->colbuf.get(), (long long)nd, 2, 0);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -170,7 +170,8 @@ int ganmf_train_epoch_ragged(ganmf_handle* h, const int32_t* perm, int64_t n, in
   TRY(ensure_stage(h, 0, ndp + ngp));
   HIP_TRY(hipMemcpyAsync(h->stage_f, h->d_parts, (ndp + ngp) * sizeof(float), hipMemcpyDeviceToHost, h->st));   // d_parts | g_parts, contiguous
   HIP_TRY(hipStreamSynchronize(h->st));
-  const std::vector<float> dp(h->stage_f, h->stage_f + ndp), gp(h->stage_f + ndp, h->stage_f + ndp + ngp);
+  const float* const sf = h->stage_f;
+  const std::vector<float> dp(sf, sf + ndp), gp(sf + ndp, sf + ndp + ngp);
   finish_losses(h, dp, gp, bglob, nd, ng, per_pass, d_losses, g_losses);
   return 0;
 }

@@ -7,7 +7,7 @@ static int usersim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W
   UserKnnScoreP p{};
   const AlsSide& s = h->als[0];
   p.r_indptr = s.indptr; p.r_items = s.indices; p.r_val = s.conf;
-  p.w_indptr = h->knn_indptr; p.w_nbr = h->knn_nbr; p.w_val = h->knn_val;
+  p.w_indptr = h->knn.indptr; p.w_nbr = h->knn.indices; p.w_val = h->knn.val;
   p.ids = ids_dev; p.n = (int)n; p.n_items = W; p.out = h->sc_out; p.ldo = ldw;
   p.acc_lds = W <= KNN_SCORE_LDS ? 1 : 0;
   const size_t shmem = p.acc_lds ? (size_t)W * sizeof(float) : 0;
@@ -23,11 +23,8 @@ static int usersim_product(ganmf_handle* h, const int* ids_dev, int64_t n, int W
 // the three arrays of a [n_users, n_users] matrix by row into the handle: dropped first, valid last
 static int usersim_hold(ganmf_handle* h, const int64_t* indptr, const int32_t* indices, const float* data, int n) {
   const int64_t nnz = indptr[n];
-  TRY(itemsim_alloc(indptr, n, &h->knn_indptr, &h->knn_nbr, &h->knn_val));
-  if (nnz) {
-    HIP_TRY(hipMemcpy(h->knn_nbr, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->knn_val, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
-  }
+  TRY(h->knn.upload(indptr, indices, n, n));
+  TRY(h->knn.upload_values(h->knn.val, data));
   HIP_TRY(hipStreamSynchronize(h->st));
   h->knn_user = 1;
   h->knn_nnz = nnz;
@@ -59,10 +56,10 @@ int ganmf_userknn_get(ganmf_handle* h, int64_t* indptr, int32_t* indices, float*
   if (h->knn_nnz > 0 && (!indices || !data)) return fail(-1, "%s: null argument", who);
   HIP_TRY(hipSetDevice(h->dev));
   HIP_TRY(hipStreamSynchronize(h->st));
-  HIP_TRY(hipMemcpy(indptr, h->knn_indptr, (size_t)(h->U + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(indptr, h->knn.indptr, (size_t)(h->U + 1) * sizeof(long long), hipMemcpyDeviceToHost));
   if (h->knn_nnz > 0) {
-    HIP_TRY(hipMemcpy(indices, h->knn_nbr, (size_t)h->knn_nnz * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(data, h->knn_val, (size_t)h->knn_nnz * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(indices, h->knn.indices, (size_t)h->knn_nnz * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(data, h->knn.val, (size_t)h->knn_nnz * sizeof(float), hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -93,8 +90,8 @@ int ganmf_userknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
   const SimRowPlan plan = itemsim_row_plan(n);
   KnnFitP p{};
   p.kind = kind; p.s = (float)((double)shrink + 1e-6); p.shrink = shrink; p.p0 = p0; p.p1 = p1;
-  if (kind <= KNN_TVERSKY) TRY(upload_floats(&den.a, den_a, n));
-  if (kind == KNN_PRODUCT) TRY(upload_floats(&den.b, den_b, n));
+  if (kind <= KNN_TVERSKY) TRY(upload_floats(den.a, den_a, n));
+  if (kind == KNN_PRODUCT) TRY(upload_floats(den.b, den_b, n));
   p.den_a = den.a; p.den_b = den.b;
   TRY(t.alloc(n, k, plan.row_floats()));
   const size_t shmem = itemsim_row_args(h, 0, n, h->N, k, plan, t, &p);      // the rows of side 0 compared over the items
@@ -104,7 +101,7 @@ int ganmf_userknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
     GANMF_LAUNCH(itemknn_fit_kernel, dim3(plan.grid), dim3(KNN_THREADS), shmem, h->st, p);
     HIP_TRY(hipGetLastError());
   }
-  TRY(itemsim_compact(h, who, n, t, k, k, &C.indptr, &C.idx, &C.val, &C.nnz));
+  TRY(itemsim_compact(h, who, n, t, k, k, C));
   HIP_TRY(hipStreamSynchronize(h->st));
   // ---- by target user -> by row, on the host: a stable counting sort by the stored neighbour.  Columns are visited in ascending
   // order, so every row ascends.  (At most n * k entries; a row has no bound of its own.) ----
@@ -114,7 +111,7 @@ int ganmf_userknn_fit(ganmf_handle* h, int kind, int32_t topk, float shrink, flo
   std::vector<float> cv(std::max<size_t>(nnz, 1)), rv(std::max<size_t>(nnz, 1));
   HIP_TRY(hipMemcpy(cp.data(), C.indptr, ((size_t)n + 1) * sizeof(long long), hipMemcpyDeviceToHost));
   if (nnz) {
-    HIP_TRY(hipMemcpy(cj.data(), C.idx, nnz * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cj.data(), C.indices, nnz * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(cv.data(), C.val, nnz * sizeof(float), hipMemcpyDeviceToHost));
   }
   if (cp[0] != 0 || cp[(size_t)n] != (int64_t)nnz) return fail(-2, "%s: the compact matrix came back with a bad indptr", who);

@@ -1,4 +1,4 @@
-// base.inc -- errors, environment knobs, tensors, profile classes (inside the anonymous namespace)
+// base.inc -- errors, environment knobs, profile classes (inside the anonymous namespace)
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
 thread_local std::string g_err;
@@ -73,14 +73,6 @@ constexpr int ADAM_GRID = 1024;
 // GEMMs run 10 % faster there than on the fp32 MFMA, +2.7 % steps/s) with 32-deep K-tiles -- 24 KiB of LDS per workgroup: six co-resident
 // workgroups hide the theta / m / v round trip of each other (33.6 / 28.8 us against 37.2 / 32.0 at 64)
 constexpr int FUSED_MODE = MFMA_BF16X3, FUSED_TILE = 64, FUSED_BK = 32;
-
-struct Tensor {
-  int rows = 0, cols = 0, ld = 0;
-  float *p = nullptr, *m = nullptr, *v = nullptr, *best = nullptr, *g = nullptr;
-  size_t cap = 0;          // allocated elements: padded() rounded up to world_size equal slices of a multiple of 64 floats
-  size_t padded() const { return (size_t)rows * ld; }
-  size_t count() const { return (size_t)rows * cols; }
-};
 
 // profiling: kernel classes
 enum Tag : int {

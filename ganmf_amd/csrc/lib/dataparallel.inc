@@ -138,7 +138,7 @@ int adam_dense(ganmf_handle* h, int tag, Tensor& t, const float* g, int alpha_id
   const long long n4 = (long long)count / 4;
   hipStream_t st = lane ? h->st2 : h->st;
   Scope s(h, tag, 0, 28.0 * count, st);
-  GANMF_LAUNCH(adam_dense_kernel, dim3(ADAM_GRID), dim3(256), 0, st, t.p + off, t.m + off, t.v + off, g + off, n4, h->scal,
+  GANMF_LAUNCH(adam_dense_kernel, dim3(ADAM_GRID), dim3(256), 0, st, t.p + off, t.m + off, t.v + off, g + off, n4, h->scal.get(),
                      alpha_idx, reg, sq);
   HIP_TRY(hipGetLastError());
   return 0;

@@ -51,34 +51,20 @@ int arenas_finish(ganmf_handle* h, int64_t nd, int64_t ng) {
 
 // pinned host staging (ints: permutation | inverse permutation; floats: loss parts), grown on demand
 int ensure_stage(ganmf_handle* h, size_t n_int, size_t n_float) {
-  if (n_int > h->stage_i_cap) {
-    if (h->stage_i) hipHostFree(h->stage_i);
-    h->stage_i = nullptr; h->stage_i_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&h->stage_i, n_int * sizeof(int), hipHostMallocDefault));
-    h->stage_i_cap = n_int;
-  }
-  if (n_float > h->stage_f_cap) {
-    if (h->stage_f) hipHostFree(h->stage_f);
-    h->stage_f = nullptr; h->stage_f_cap = 0;
-    const size_t want = n_float + n_float / 2 + 256;
-    HIP_TRY(hipHostMalloc((void**)&h->stage_f, want * sizeof(float), hipHostMallocDefault));
-    h->stage_f_cap = want;
-  }
+  if (n_int > h->stage_i.cap) TRY(h->stage_i.alloc(n_int, false));
+  if (n_float > h->stage_f.cap) TRY(h->stage_f.alloc(n_float + n_float / 2 + 256, false));
   return 0;
 }
 
 int ensure_parts(ganmf_handle* h, int64_t steps) {
-  if (steps <= h->parts_cap) return 0;
+  if (steps <= (int64_t)h->colbuf.cap) return 0;      // (colbuf, allocated last, holds one float per step of room)
   HIP_TRY(hipStreamSynchronize(h->st));
-  // capacity is only published once every buffer of the new size exists: a failing dalloc leaves cap 0 and null
-  // pointers, so the next call allocates again instead of running on freed memory
-  hipFree(h->parts_all); hipFree(h->colbuf);
-  h->parts_all = h->d_parts = h->g_parts = h->d_arena = h->g_arena = h->colbuf = nullptr;
-  h->parts_cap = 0;
+  // a failing allocation leaves colbuf empty and null views, so the next call allocates again instead of running on freed memory
+  h->parts_all.reset(); h->colbuf.reset();
+  h->d_parts = h->g_parts = h->d_arena = h->g_arena = nullptr;
   const int64_t cap = steps + 64;
-  TRY(dalloc(&h->parts_all, (size_t)cap * 2 * (4 + arena_stride(h))));
-  TRY(dalloc(&h->colbuf, (size_t)cap));
-  h->parts_cap = cap;
+  TRY(h->parts_all.alloc((size_t)cap * 2 * (4 + arena_stride(h)), true));
+  TRY(h->colbuf.alloc((size_t)cap, true));
   return 0;
 }
 

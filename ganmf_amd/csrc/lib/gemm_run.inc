@@ -2,17 +2,10 @@
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
 int ensure_slab(ganmf_handle* h, size_t elems, int lane) {
-  float*& slab = lane ? h->slab2 : h->slab;
-  size_t& cap = lane ? h->slab2_elems : h->slab_elems;
-  if (elems <= cap) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
+  DevBuf<float>& slab = lane ? h->slab2 : h->slab;
+  if (elems <= slab.cap) return 0;
   HIP_TRY(hipStreamSynchronize(h->st2));
-  if (slab) hipFree(slab);
-  slab = nullptr; cap = 0;
-  const size_t want = elems + elems / 4 + 1024;
-  TRY(dalloc(&slab, want));
-  cap = want;
-  return 0;
+  return slab.grow(h->st, elems + elems / 4 + 1024, true);
 }
 
 // One logical GEMM of the step: plan (tile / ring / split-K), launch, and when split the reduce
@@ -59,9 +52,10 @@ int run_gemm(ganmf_handle* h, int tag_gemm, int tag_red, GemmP g, bool akm, bool
   const bool deferred = defer && pl.nsplit > 1 && g.epi.kind == EPI_STORE && g.nbatch == 1 &&
                         reduce_groups((long long)g.M * ((g.N + 3) >> 2), pl.nsplit) == 1;
   const int slab_lane = deferred ? 1 : lane;
-  if (pl.nsplit > 1) TRY(ensure_slab(h, gemm_slab_elems(pl, g.M, g.ldc, g.nbatch), slab_lane));
-  float* slab = slab_lane ? h->slab2 : h->slab;
-  const size_t slab_elems = slab_lane ? h->slab2_elems : h->slab_elems;
+  const bool lent = slab_lane && h->slab2_lent;      // (gen_update's lazy pass: a block of the pass arena stands in for slab2)
+  if (pl.nsplit > 1 && !lent) TRY(ensure_slab(h, gemm_slab_elems(pl, g.M, g.ldc, g.nbatch), slab_lane));
+  float* slab = lent ? h->slab2_lent : slab_lane ? h->slab2.get() : h->slab.get();
+  const size_t slab_elems = lent ? h->slab2_lent_elems : slab_lane ? h->slab2.cap : h->slab.cap;
   const bool wants_sq = g.epi.sq_partials != nullptr;
   const int nredg = GEMM_RED_GRID;      // blocks (and partials) of a stand-alone slab sum
   const int sqc = !wants_sq ? 0 : (pl.nsplit > 1 ? nredg : pl.sq_count);

@@ -1,6 +1,17 @@
 // handle.inc -- the loopback communicator's group state and struct ganmf_handle
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
+// A parameter with its Adam moments and best-snapshot twin.  g is a view: a slice of the handle's gD for the tensors whose gradients
+// are reduced together, or the tensor's own g_own (alloc_tensor's grad_separate).
+struct Tensor {
+  int rows = 0, cols = 0, ld = 0;
+  DevBuf<float> p, m, v, best, g_own;
+  float* g = nullptr;
+  size_t cap = 0;          // allocated elements: padded() rounded up to world_size equal slices of a multiple of 64 floats
+  size_t padded() const { return (size_t)rows * ld; }
+  size_t count() const { return (size_t)rows * cols; }
+};
+
 // ---- in-process loopback communicator: group state (see allreduce_local) ----
 constexpr int LOCAL_MAX_WORLD = 8;
 struct LocalPtrs { float* p[LOCAL_MAX_WORLD]; };
@@ -33,23 +44,23 @@ struct LocalGroup {
 
 // one side of the handle's weighted sparse matrix (ganmf_als_set_confidence): CSR over that side's rows -- the ALS confidences, or
 // the URM itself for ganmf_pure_svd
-struct AlsSide {
-  long long* indptr = nullptr;
-  int* indices = nullptr;
-  float* conf = nullptr;
-  int64_t rows = 0, nnz = 0;
+struct AlsSide : DevCsr {
+  DevBuf<float> conf;
   bool canonical = false;      // every row's columns ascend without repeats (what the GANMF_MODEL_ITEMSIM entries need)
+};
+
+// a compact similarity matrix with its values: the one a GANMF_MODEL_ITEMSIM handle holds, and the temporaries between two passes of a fit
+struct SimCsr : DevCsr {
+  DevBuf<float> val;
+  void drop() { DevCsr::drop(); val.reset(); }
 };
 
 // The profiles an SGD trainer draws its samples from, on the device (profiles_upload / profiles_drop of lib/sgd_train.inc; draw_kernel):
 // users x items in CSR with ascending items, the stored values where the trainer reads them, and the users with 0 < |profile| < n_items
-struct SampleProfiles {
-  long long* indptr = nullptr;
-  int* items = nullptr;
-  double* ratings = nullptr;      // FunkSVD's; else null
-  int* eligible = nullptr;        // [n_eligible] ascending
+struct SampleProfiles : DevCsr {
+  DevBuf<double> ratings;         // FunkSVD's; else null
+  DevBuf<int> eligible;           // [n_eligible] ascending
   int n_eligible = 0;
-  int64_t nnz = 0;
 };
 
 // SLIM-BPR training state of a GANMF_MODEL_ITEMSIM handle (ganmf_slim_bpr_init; slim_bpr.hpp): S and the optimiser state in float64,
@@ -62,7 +73,7 @@ struct SlimState {
   uint64_t seed = 0;
   int64_t epoch = 0;
   size_t cells = 0;
-  double *S = nullptr, *st0 = nullptr, *st1 = nullptr;
+  DevBuf<double> S, st0, st1;
   SampleProfiles profiles;
 };
 
@@ -78,10 +89,9 @@ struct MfSgdState {
   uint64_t seed = 0;
   int64_t epoch = 0;
   size_t block = 0;
-  double* P = nullptr;
+  DevBuf<double> P;
   SampleProfiles profiles;
-  double* terms = nullptr;
-  size_t terms_cap = 0;
+  DevBuf<double> terms;
 };
 
 // The generator CFGAN and CAAE share (profile_mlp.inc): an MLP from a dense profile row [N] through Lg hidden layers of g units back to
@@ -91,9 +101,9 @@ struct ProfileMlp {
   int out_act = -1;                         // activation of the output layer (-1: none; CAAE: the sigmoid)
   std::vector<Tensor> Gl;        // l = 0: [N + 1, g] (row N the bias); l > 0: [g + 1, g]
   Tensor Go;                     // [g + 1, N] (row g the bias), leading dimension ldN
-  std::vector<float*> Hl;        // hidden outputs of a training batch [rows, ldg] with the ones column at g
+  std::vector<DevBuf<float>> Hl;       // hidden outputs of a training batch [rows, ldg] with the ones column at g
   // scratch of a block of sc_rows scored rows: dense profiles, two hidden blocks (the layers alternate), one output block
-  float *sc_C = nullptr, *sc_H0 = nullptr, *sc_H1 = nullptr, *sc_F = nullptr;
+  DevBuf<float> sc_C, sc_H0, sc_H1, sc_F;
   size_t sc_rows = 0;
   std::vector<Tensor*> tensors() {
     std::vector<Tensor*> v;
@@ -112,12 +122,11 @@ struct CfganState {
   float zr_coef = 0.f;
   uint64_t seed = 0;
   ProfileMlp gen;
-  float *C = nullptr, *fake = nullptr, *dfake = nullptr, *DX = nullptr, *dh0 = nullptr, *dh1 = nullptr;
-  float *zr_part = nullptr, *loss_rows = nullptr, *sq = nullptr, *loss_dev = nullptr;
-  size_t loss_cap = 0;
-  unsigned* planes = nullptr;    // [2][U][words]: CFGAN_PLANE_ZR, CFGAN_PLANE_PM
-  int* k_rows = nullptr;         // [U]
-  float* cache = nullptr;        // item-mode scoring: the transposed G(all rows) [N, ld(U)] as of cache_version
+  DevBuf<float> C, fake, dfake, DX, dh0, dh1;
+  DevBuf<float> zr_part, loss_rows, sq, loss_dev;
+  DevBuf<unsigned> planes;       // [2][U][words]: CFGAN_PLANE_ZR, CFGAN_PLANE_PM
+  DevBuf<int> k_rows;            // [U]
+  DevBuf<float> cache;           // item-mode scoring: the transposed G(all rows) [N, ld(U)] as of cache_version
   long long cache_version = -1;
 };
 
@@ -131,32 +140,29 @@ struct CaaeState {
   uint64_t seed = 0;
   ProfileMlp gen[2];
   Tensor bias;                   // disc_item_bias [1, N]
-  int* k_rows = nullptr;         // [U] size of Nu per user
+  DevBuf<int> k_rows;            // [U] size of Nu per user
   // the epoch's state: both CDFs [U, ldN], the user of every stored interaction, the shuffled order and its triples
-  float* cdf[2] = {nullptr, nullptr};
-  int* iu = nullptr;             // [nnz] row of CSR position e
+  DevBuf<float> cdf[2];
+  DevBuf<int> iu;                // [nnz] row of CSR position e
   const void* iu_src = nullptr;  // the indptr it was formed from
-  int *perm = nullptr, *tu = nullptr, *ti = nullptr;      // [nnz]: CSR position, user and item of every position of the shuffled order
-  long long order_cap = 0;
+  DevBuf<int> perm, tu, ti;      // [nnz]: CSR position, user and item of every position of the shuffled order
   // recorded draws of the last epoch, per pass / step slot (ganmf_caae_get_draws)
-  int* neg = nullptr;            // [passes][2][nnz]
-  size_t neg_cap = 0;
-  int* users = nullptr;          // [2][steps][Bm]
-  unsigned* nu = nullptr;        // [steps][Bm * words]
-  int* items = nullptr;          // [2][steps][Bm * n_s]
+  DevBuf<int> neg;               // [passes][2][nnz]
+  DevBuf<int> users;             // [2][steps][Bm]
+  DevBuf<unsigned> nu;           // [steps][Bm * words]
+  DevBuf<int> items;             // [2][steps][Bm * n_s]
   int step_slots = 0, rec_passes = 0, rec_steps[2] = {0, 0};
   long long rec_nnz = 0;
   // explicit triples of a single D-step, the gathered rows and per-triple values of the step in flight
-  int* xt = nullptr;             // [3][d_bsize]
-  int* first = nullptr;          // [U + N] CaaeDP::first: 0x7f7f7f7f between steps
-  int *xu = nullptr, *xi = nullptr;      // [Bm], [Bm * n_s]: users and policy items of a single step or draw entry
-  unsigned* xn = nullptr;        // [Bm * words]: its Nu planes
-  float *Pg = nullptr, *Qi = nullptr, *Qj = nullptr, *coef = nullptr, *lt = nullptr, *rt = nullptr;
+  DevBuf<int> xt;                // [3][d_bsize]
+  DevBuf<int> first;             // [U + N] CaaeDP::first: 0x7f7f7f7f between steps
+  DevBuf<int> xu, xi;            // [Bm], [Bm * n_s]: users and policy items of a single step or draw entry
+  DevBuf<unsigned> xn;           // [Bm * words]: its Nu planes
+  DevBuf<float> Pg, Qi, Qj, coef, lt, rt;
   // generator step: profiles, outputs of G and G', batch CDF, d loss / d z of the output layer, hidden gradients, per-row parts
-  float *C = nullptr, *R = nullptr, *Rp = nullptr, *cdfb = nullptr, *dz = nullptr, *dh0 = nullptr, *dh1 = nullptr;
-  float *lse = nullptr, *reward = nullptr, *la = nullptr, *ae = nullptr, *sq = nullptr, *loss_dev = nullptr;
-  size_t loss_cap = 0;
-  float* lse_all = nullptr;      // [U] log sum exp(r) of the all-users CDF pass
+  DevBuf<float> C, R, Rp, cdfb, dz, dh0, dh1;
+  DevBuf<float> lse, reward, la, ae, sq, loss_dev;
+  DevBuf<float> lse_all;         // [U] log sum exp(r) of the all-users CDF pass
 };
 
 struct ganmf_handle {
@@ -173,40 +179,37 @@ struct ganmf_handle {
   int L = 0, act = 0;
   std::vector<Tensor> Wl;   // l = 0: [N+2, e] rows 0..N-1 profile weights, row N bias, row N+1 the float(uid) weight; l > 0: [e+1, e]
   Tensor Wo;                // [1, e+1]: output kernel (e) then output bias
-  std::vector<float*> Al;   // layer outputs [2B, lde] with the ones column at e
-  float *dz0 = nullptr, *dz1 = nullptr, *dlogit = nullptr;
+  std::vector<DevBuf<float>> Al;   // layer outputs [2B, lde] with the ones column at e
+  DevBuf<float> dz0, dz1, dlogit;
   Tensor We, Wd, Ue, V;   // We = We_ext [N+1, e] (row N = encoder bias), Wd = Wd_ext [e+1, N] (row e = decoder bias)
-  float* gD = nullptr;  // contiguous [gWe_ext | gWd_ext] (one all-reduce)
+  DevBuf<float> gD;     // contiguous [gWe_ext | gWd_ext] (one all-reduce)
   size_t gD_elems = 0;
   // CSR
-  long long* indptr = nullptr;
-  int* indices = nullptr;
-  float* data = nullptr;
-  long long nnz = 0;
+  DevCsr urm;
+  DevBuf<float> data;
   bool has_urm = false;
   bool sparse_g = false;   // SURVEY 8(f)-3: generator steps take the real rows' encodings from a CSR row-sum (no densify of X)
   bool sparse_d = false;   //               discriminator steps too: Er from the CSR rows, X subtracted from the reconstruction through a CSR
                            //               lookup in the decode epilogue, X^T.dE_r added to the encoder gradient from the CSC matrix
-  long long* csc_colptr = nullptr;   // CSC form of the same matrix (sparse_d): column j = the rows that store item j, ascending
-  int* csc_rowidx = nullptr;
-  float* csc_val = nullptr;
-  float* sp_rows = nullptr;          // [N + CSC_BIAS_PARTS, lde]: X^T . dE_r of the step in flight (csc_rows_kernel)
+  DevCsr csc;                        // CSC form of the same matrix (sparse_d): column j = the rows that store item j, ascending
+  DevBuf<float> csc_val;
+  DevBuf<float> sp_rows;             // [N + CSC_BIAS_PARTS, lde]: X^T . dE_r of the step in flight (csc_rows_kernel)
   // epoch schedule
-  int* perm = nullptr;      // [2U] device: the epoch's permutation, then (pos = perm + U) its inverse
+  DevBuf<int> perm;         // [3U] device: the epoch's permutation, then (pos = perm + U) its inverse, then pos_step
+  PinnedBuf<int> stage_i;   // pinned host staging (ensure_stage)
+  PinnedBuf<float> stage_f;
+  // Views into buffers owned elsewhere, never freed: pos, pos_step (perm), XF (XF_own or a block of XF_pass), Ub / gUb (Ub_own /
+  // gUb_own, Ub_sched or a lazy chunk), d_parts / g_parts / d_arena / g_arena (parts_all), dis_slot (an arena), Tensor::g
   int* pos = nullptr;
-  int* stage_i = nullptr;   // pinned host staging (ensure_stage)
-  float* stage_f = nullptr;
-  size_t stage_i_cap = 0, stage_f_cap = 0;
+  float *XF = nullptr, *Ub = nullptr, *gUb = nullptr;
   // minibatch work buffers
-  float *XF = nullptr, *Ub = nullptr, *E = nullptr, *Es = nullptr, *Dl = nullptr, *dE = nullptr, *dF = nullptr, *gUb = nullptr;
+  DevBuf<float> E, Es, Dl, dE, dF;
   // staged discriminator pass (stage_pass, step_ganmf.inc): U and V are frozen for the whole pass (GANMF.py:176-189), so the CSR row
   // expansion and the generator product of ALL its full minibatches run once, in front of it, into one [real ; generated] block of 2B rows
   // per minibatch; XF then points at the block of the step in flight (XF_own: the handle's own 2B-row buffer)
-  float* XF_own = nullptr;
-  float* XF_pass = nullptr;
-  size_t XF_pass_elems = 0;
-  float* Ub_pass = nullptr;              // U rows of the pass in schedule order (only when the generator product does not gather them itself)
-  size_t Ub_pass_elems = 0;
+  DevBuf<float> XF_own;
+  DevBuf<float> XF_pass;
+  DevBuf<float> Ub_pass;                 // U rows of the pass in schedule order (only when the generator product does not gather them itself)
   bool skinny = true;                    // GANMF_TUNE=skinny=0: K <= 64 products stay on the tiled MFMA kernels
   int bf16w = 1;                         // GANMF_TUNE=bf16w=0: products that would run as two K slices per 64 x 64 tile stay that way (2: the 64 x 32 kernel wherever eligible)
   bool skinny_n = true;                  // GANMF_TUNE=skinny_n=0: N <= 32 products behind a long K stay on the tiled MFMA kernels
@@ -219,28 +222,25 @@ struct ganmf_handle {
   bool lazy_rows = true;                 // GANMF_TUNE=lazy_rows=0: adam_rows_kernel over all rows in every generator step
   bool lazy_pass = false;                // the generator step in flight belongs to such a pass
   int g_alpha = S_ALPHA_G;               // scalar slot holding lr_t of the generator step in flight
-  float* Ub_own = nullptr;               // the handle's own [B, ldk] minibatch embeddings (Ub points into Ub_sched during a lazy pass)
-  float* gUb_own = nullptr;
-  float* Ub_sched = nullptr;             // [n, ldk] embeddings of the scheduled rows as their step will read them
-  size_t Ub_sched_elems = 0;
+  DevBuf<float> Ub_own;                  // the handle's own [B, ldk] minibatch embeddings (Ub points into Ub_sched during a lazy pass)
+  DevBuf<float> gUb_own;
+  DevBuf<float> Ub_sched;                // [n, ldk] embeddings of the scheduled rows as their step will read them
   int* pos_step = nullptr;               // [U] device: step index of every schedule position (perm + 2U)
-  std::vector<std::pair<float*, size_t>> lazy_chunks;      // gUb (slabs) of every step of the pass: bump-allocated, kept across passes
+  std::vector<DevBuf<float>> lazy_chunks;      // gUb (slabs) of every step of the pass: bump-allocated, kept across passes
   size_t lazy_chunk = 0, lazy_used = 0;
   std::vector<LazyStep> lazy_steps;
   int lazy_step = 0;                     // index of the generator step in flight within its pass
-  LazyStep* lazy_stage = nullptr;        // pinned host staging of the table, two halves (passes alternate)
-  size_t lazy_stage_cap = 0;
-  LazyStep* lazy_tab = nullptr;          // device copy of lazy_steps
-  size_t lazy_tab_cap = 0;
-  float* zero_page = nullptr;
-  float* slab = nullptr;
-  size_t slab_elems = 0;
-  float* slab2 = nullptr;                // split-K workspace of the side lane
-  size_t slab2_elems = 0;
+  PinnedBuf<LazyStep> lazy_stage;        // pinned host staging of the table, two halves (passes alternate)
+  DevBuf<LazyStep> lazy_tab;             // device copy of lazy_steps
+  DevBuf<float> zero_page;
+  DevBuf<float> slab;
+  DevBuf<float> slab2;                   // split-K workspace of the side lane
+  float* slab2_lent = nullptr;           // view: a block of the pass arena that stands in for slab2 during one run_gemm (gen_update)
+  size_t slab2_lent_elems = 0;
   int x3kg = 7;                   // GANMF_X3KG bits: 16-wave split-bf16 loop for the plans of the 16-wave fp32 ring kernel (1 NT, 2 K-major B), 4: its one-piece form for bf16 / fp16 plans
-  float* rs = nullptr;
-  float* scal = nullptr;
-  float *sqp = nullptr;  // [2][max_tiles]
+  DevBuf<float> rs;
+  DevBuf<float> scal;
+  DevBuf<float> sqp;     // [2][max_tiles]
   int sqp_stride = 0;
   int reg_cap = 0;
   bool dis_colsum_pending = false;      // this discriminator step's column sums (ColSumP dis_colsum) ride in the layer-0 gradient GEMM's launch (dis_d_step)
@@ -254,21 +254,17 @@ struct ganmf_handle {
   int multi = 31;         // combined launches (gemm_multi.hpp), bit 0: generator GEMM + CSR row expansion, bit 1: gUb + gV,
                           // bit 2: slab sum of dE inside the gWd launch, bit 3 (with bit 2): d_coef inside the dE launch,
                           // bit 4 (with bit 2): gWd + gWe in one launch behind a stand-alone slab sum of dE (GANMF_MULTI)
-  float* V_alt = nullptr; // second parameter buffer of item_embeddings: the fused gV update is written there while gUb
+  DevBuf<float> V_alt;   // second parameter buffer of item_embeddings: the fused gV update is written there while gUb
                           // still reads the old V in the same launch; swapped with V.p after the launch
   bool dis_fuse_hidden = true;   // DisGANMF: also for the hidden layers l > 0 (GANMF_DIS_FUSE_HIDDEN)
-  float* parts_all = nullptr;                    // ONE allocation: [d_parts | g_parts | d_arena | g_arena], packed per call (parts_begin)
+  DevBuf<float> parts_all;                       // ONE allocation: [d_parts | g_parts | d_arena | g_arena], packed per call (parts_begin)
   float *d_parts = nullptr, *g_parts = nullptr;  // [steps][4]
-  float* colbuf = nullptr;                       // [cap] one column of d_parts on its way through an all-reduce
+  DevBuf<float> colbuf;                          // [cap] one column of d_parts on its way through an all-reduce
   float *d_arena = nullptr, *g_arena = nullptr;  // [cap][4][reg_cap] per-step block partials (GANMF), reduced once per epoch
-  int64_t parts_cap = 0;
   // recommend(): URM_train in evaluation orientation for the seen-item mask, top-k outputs
-  long long* seen_indptr = nullptr;
-  int* seen_indices = nullptr;
-  int64_t seen_rows = 0, seen_cols = 0;
+  DevCsr seen;
   // score filter (ganmf_set_score_filter): byte per score column (1 = computed), and whether cold rows are masked
-  unsigned char* item_mask = nullptr;
-  size_t item_mask_cap = 0;
+  DevBuf<unsigned char> item_mask;
   int64_t item_mask_w = 0;             // 0: no item filter; else one past the largest listed item
   bool mask_cold = false;
   // ignore list (ganmf_set_items_to_ignore): byte per score column (1 = ignored) on the host, beside the host copy of the score filter's
@@ -276,82 +272,63 @@ struct ganmf_handle {
   // ignored -- formed by whichever of the two setters ran last.  ganmf_scores keeps reading item_mask.
   std::vector<unsigned char> filter_host, ignore_host;
   int64_t ignore_w = 0;                // 0: no ignore list; else one past the largest ignored item
-  unsigned char* rank_mask = nullptr;
-  size_t rank_mask_cap = 0;
-  int* topk_items = nullptr;
-  float* topk_vals = nullptr;
-  size_t topk_cap = 0;
+  DevBuf<unsigned char> rank_mask;
+  DevBuf<int> topk_items;          // the two top-k outputs hold the same count: topk_vals is grown last, so its cap is what both hold
+  DevBuf<float> topk_vals;
   // ganmf_set_item_diversity: the [div_w, div_w] item diversity matrix of ganmf_evaluate_diversity, resident until replaced
-  float* div_mat = nullptr;
+  DevBuf<float> div_mat;
   int64_t div_w = 0;
   // ganmf_evaluate(): URM_test in evaluation orientation (sorted rows) with the DCG gains, work buffers
-  long long* test_indptr = nullptr;
-  int* test_indices = nullptr;
-  double* test_gain = nullptr;
-  int64_t test_rows = 0, test_cols = 0;
-  double* eval_buf = nullptr;      // disc | ideal_cum | block partials
-  size_t eval_cap = 0;
+  DevCsr test;
+  DevBuf<double> test_gain;
+  DevBuf<double> eval_buf;         // disc | ideal_cum | block partials
   // ganmf_evaluate_full(): rating per stored test entry (dropped by every ganmf_set_test_csr), the two per-item weights of the
   // evaluation width, and work buffers (per-row RMSE, [n_cutoffs, W] counts)
-  int64_t test_nnz = 0;
-  float* test_rating = nullptr;
+  DevBuf<float> test_rating;
   bool test_rating_ok = false;
-  double* eval_w = nullptr;        // novelty | popularity, eval_w_width each
+  DevBuf<double> eval_w;           // novelty | popularity, eval_w_width each
   int64_t eval_w_width = 0;
-  float* eval_rmse = nullptr;
-  size_t eval_rmse_cap = 0;
-  unsigned* eval_counts = nullptr;
-  size_t eval_counts_cap = 0;
+  DevBuf<float> eval_rmse;
+  DevBuf<unsigned> eval_counts;
   // ganmf_evaluate_groups(): members of every group | their begin offsets (the per-user values and the group sums live in eval_buf)
-  int* eval_grp = nullptr;
-  size_t eval_grp_cap = 0;
+  DevBuf<int> eval_grp;
   // ganmf_set_candidates_csr: per-row candidate lists (evaluation orientation, rows sorted and unique) for cand_topk_kernel;
   // the host keeps the row pointers to size a launch's LDS and to refuse a row over GANMF_CANDIDATES_MAX_PER_ROW without launching
-  long long* cand_indptr = nullptr;
-  int* cand_indices = nullptr;
+  DevCsr cand;
   std::vector<long long> cand_indptr_host;
-  int64_t cand_rows = 0, cand_cols = 0;
   // scoring scratch
-  int* sc_ids = nullptr;
-  size_t sc_ids_cap = 0;
-  float *sc_rows = nullptr, *sc_out = nullptr;
-  size_t sc_rows_cap = 0, sc_out_cap = 0;
-  unsigned *sc_pa = nullptr, *sc_pb = nullptr;      // bf16 x 3 planes of the scored rows / of the other factor (gemm_bf16p.hpp)
-  size_t sc_pa_cap = 0, sc_pb_cap = 0;
+  DevBuf<int> sc_ids;
+  DevBuf<float> sc_rows, sc_out;
+  DevBuf<unsigned> sc_pa, sc_pb;                    // bf16 x 3 planes of the scored rows / of the other factor (gemm_bf16p.hpp)
   const float* sc_pb_src = nullptr;                 // what sc_pb holds: the planes of this parameter buffer ...
   long long sc_pb_version = -1, param_version = 0;  // ... as of this parameter version (bumped by training, set_tensor, restore_best)
   int sc_pb_rows = 0;
   // ganmf_score_similarity (gram_stats.hpp): the similarity matrix [n, ld(n)] (only when the matrix or its block means are asked for), the
   // block means, the per-tile (sum d, sum d^2) pairs and the zero-row flags; grown on demand.  The normalised rows live in sc_out.
-  float *sim_mat = nullptr, *sim_pool = nullptr;
-  double* sim_part = nullptr;
-  int* sim_zero = nullptr;
-  size_t sim_mat_cap = 0, sim_pool_cap = 0, sim_part_cap = 0, sim_zero_cap = 0;
+  DevBuf<float> sim_mat, sim_pool;
+  DevBuf<double> sim_part;
+  DevBuf<int> sim_zero;
   // ganmf_discriminate (disc_rows.hpp): block buffers of its own, grown on demand -- the ids, the input block [blk, ldN] (generated rows,
   // or DisGANMF's expanded rows), the gathered embeddings [blk, ldk], the codes / layer outputs [blk, lde] (two: the layers alternate), the
   // per-(row, column tile) partials and the values.  The step's buffers, the staged-pass state and the beta powers are never touched.
-  int* dr_ids = nullptr;
-  float *dr_X = nullptr, *dr_Ub = nullptr, *dr_E = nullptr, *dr_A = nullptr;
-  double *dr_part = nullptr, *dr_val = nullptr;
-  size_t dr_ids_cap = 0, dr_X_cap = 0, dr_Ub_cap = 0, dr_E_cap = 0, dr_A_cap = 0, dr_part_cap = 0, dr_val_cap = 0;
+  DevBuf<int> dr_ids;
+  DevBuf<float> dr_X, dr_Ub, dr_E, dr_A;
+  DevBuf<double> dr_part, dr_val;
   int64_t disc_block = 0;                           // ganmf_set_discriminate_block: rows per block of the call's loop (0: a quarter of the free memory)
   // ganmf_als_half_sweep (als_rows.hpp): the confidence matrix in both orientations, G = Y^T Y [k, ldk], and the failure words
   // [1 + max(U, N)] (word 0: any row of the call, word 1 + u: row u)
   AlsSide als[2];
-  float* als_G = nullptr;
-  int* als_bad = nullptr;
+  DevBuf<float> als_G;
+  DevBuf<int> als_bad;
   // GANMF_MODEL_ITEMSIM (itemknn_rows.hpp): the item similarity matrix W by target item -- column i of the reference's W_sparse is
   // knn_nbr / knn_val [knn_indptr[i], knn_indptr[i + 1]) -- from ganmf_itemknn_fit or ganmf_set_item_similarity; knn_dense: the dense
   // profiles [rows, ld] of the scoring route for catalogues above one workgroup's LDS, grown on demand.  The one held matrix may
   // instead be a USER similarity (knn_user = 1; userknn_rows.hpp): W_sparse [U, U] by row -- row u is knn_nbr / knn_val
   // [knn_indptr[u], knn_indptr[u + 1]) -- from ganmf_userknn_fit or ganmf_set_user_similarity
-  long long* knn_indptr = nullptr;
-  int* knn_nbr = nullptr;
-  float* knn_val = nullptr;
+  SimCsr knn;                // knn.indices, knn.val: knn_nbr, knn_val of the comment above
   int64_t knn_nnz = -1;      // -1: no matrix held
   int knn_user = 0;          // the held matrix: 0 item x item by target item, 1 user x user by row
-  float* knn_dense = nullptr;
-  size_t knn_dense_cap = 0;
+  DevBuf<float> knn_dense;
   SlimState slim;                                   // ganmf_slim_bpr_* (slim_bpr.hpp)
   MfSgdState mfs;                                   // ganmf_mf_sgd_* (mf_sgd.hpp)
   CfganState cf;                                    // ganmf_cfgan_* (cfgan_masks.hpp, cfgan_rows.hpp)
@@ -359,18 +336,17 @@ struct ganmf_handle {
   // ganmf_pure_svd (svd_rows.hpp): the two panels [max(U, N), svd_ldl] the iteration alternates between, the Gram matrix and the
   // inverse Cholesky factor [svd_ldl, svd_ldl], the [svd_ldl, ldk] matrix W of the final products, lambda [svd_ldl] | sigma [ldk],
   // and the failure words (SvdCholP::flag).  Allocated by the first call, regrown by a call with a wider n_random.
-  float* svd_P[2] = {nullptr, nullptr};
-  float *svd_G = nullptr, *svd_X = nullptr, *svd_Wl = nullptr, *svd_lam = nullptr;
-  int* svd_flag = nullptr;
+  DevBuf<float> svd_P[2];
+  DevBuf<float> svd_G, svd_X, svd_Wl, svd_lam;
+  DevBuf<int> svd_flag;
   int svd_ldl = 0;
   // ganmf_nmf_* (nmf_rows.hpp): the denominator and numerator panels [max(U, N), ldk], the Gram matrices of both factors [2][ldk, ldk], the value
   // array of the sampled products [nnz], the two column-sum vectors [2][ldk], the per-row float64 values [2 max(U, N)], the partial
   // sums [NMF_PARTS], the scalars [4 + iterations] and the permutations of a call; allocated by the first call, grown on demand
-  float *nmf_den = nullptr, *nmf_num = nullptr, *nmf_G = nullptr, *nmf_q = nullptr, *nmf_vec = nullptr;
-  double *nmf_rowd = nullptr, *nmf_part = nullptr, *nmf_scal = nullptr;
-  int *nmf_perm = nullptr, *nmf_rowidx = nullptr;      // nmf_rowidx [2][nnz]: the row of every CSR position of both sides
-  double* nmf_errp = nullptr;                          // [chunks, 2] divergence sums of nmf_sampled_kernel
-  size_t nmf_q_cap = 0, nmf_scal_cap = 0, nmf_perm_cap = 0;
+  DevBuf<float> nmf_den, nmf_num, nmf_G, nmf_q, nmf_vec;
+  DevBuf<double> nmf_rowd, nmf_part, nmf_scal;
+  DevBuf<int> nmf_perm, nmf_rowidx;                    // nmf_rowidx [2][nnz]: the row of every CSR position of both sides
+  DevBuf<double> nmf_errp;                             // [chunks, 2] divergence sums of nmf_sampled_kernel
   int gram_arith = 1;                               // GANMF_TUNE gram: 1 (default, the faster one measured) the exact three-way bf16 split, 0 the plain fp32 MFMA body
   bool score_presplit = true;                       // GANMF_SCORE_PRESPLIT: many-tile scoring products on the pre-split persistent kernel
   // RCCL

@@ -4,10 +4,10 @@
 // Every dense product goes through run_gemm under the handle's planner.
 
 // a block [rows, ldg] of hidden outputs: zero, with the ones column at g
-int mlp_hidden_block(const ProfileMlp& m, float** p, size_t rows) {
-  TRY(dalloc(p, rows * m.ldg));
+int mlp_hidden_block(const ProfileMlp& m, DevBuf<float>& p, size_t rows) {
+  TRY(p.alloc(rows * m.ldg, true));
   std::vector<float> ones(rows, 1.0f);
-  HIP_TRY(hipMemcpy2D(*p + m.g, (size_t)m.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy2D(p + m.g, (size_t)m.ldg * 4, ones.data(), 4, 4, rows, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -17,29 +17,22 @@ int mlp_alloc(ganmf_handle* h, ProfileMlp& m, int g, int Lg, int act, int out_ac
   m.Gl.resize(Lg);
   for (int l = 0; l < Lg; ++l) TRY(alloc_tensor(m.Gl[l], l == 0 ? h->N + 1 : g + 1, g, true, 1));
   TRY(alloc_tensor(m.Go, g + 1, h->N, true, 1, h->ldN));
-  m.Hl.assign(Lg, nullptr);
-  for (int l = 0; l < Lg; ++l) TRY(mlp_hidden_block(m, &m.Hl[l], (size_t)rows));
+  m.Hl.clear();
+  m.Hl.resize(Lg);
+  for (int l = 0; l < Lg; ++l) TRY(mlp_hidden_block(m, m.Hl[l], (size_t)rows));
   return 0;
-}
-
-void mlp_free(ProfileMlp& m) {
-  for (auto& t : m.Gl) free_tensor(t, true);
-  free_tensor(m.Go, true);
-  for (float* a : m.Hl) hipFree(a);
-  hipFree(m.sc_C); hipFree(m.sc_H0); hipFree(m.sc_H1); hipFree(m.sc_F);
-  m = ProfileMlp{};
 }
 
 // the scratch blocks for `rows` rows
 int mlp_scratch(ganmf_handle* h, ProfileMlp& m, size_t rows) {
   if (rows <= m.sc_rows) return 0;
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(m.sc_C); hipFree(m.sc_H0); hipFree(m.sc_H1); hipFree(m.sc_F);
-  m.sc_C = m.sc_H0 = m.sc_H1 = m.sc_F = nullptr; m.sc_rows = 0;
-  TRY(dalloc(&m.sc_C, rows * h->ldN));
-  TRY(mlp_hidden_block(m, &m.sc_H0, rows));
-  TRY(mlp_hidden_block(m, &m.sc_H1, rows));
-  TRY(dalloc(&m.sc_F, rows * h->ldN));
+  m.sc_C.reset(); m.sc_H0.reset(); m.sc_H1.reset(); m.sc_F.reset();
+  m.sc_rows = 0;
+  TRY(m.sc_C.alloc(rows * h->ldN, true));
+  TRY(mlp_hidden_block(m, m.sc_H0, rows));
+  TRY(mlp_hidden_block(m, m.sc_H1, rows));
+  TRY(m.sc_F.alloc(rows * h->ldN, true));
   m.sc_rows = rows;
   return 0;
 }
@@ -64,23 +57,22 @@ int mlp_forward(ganmf_handle* h, const ProfileMlp& m, const float* X, int nb, fl
 // out[i, :] = M(profile of row ids[i]) for n rows of the URM (ids_dev == nullptr: rows row0 ..).  C != nullptr: a training batch -- the
 // dense profiles into C [n, ldN], the hidden outputs into the model's own blocks Hl; else through the model's scratch blocks
 int mlp_forward_rows(ganmf_handle* h, ProfileMlp& m, const int* ids_dev, int row0, int n, float* out, int ldo, float* C = nullptr) {
-  float* const* H = m.Hl.data();
-  std::vector<float*> scratch;
+  std::vector<float*> scratch(m.Hl.begin(), m.Hl.end());      // the hidden blocks as plain pointers
   if (!C) {
+    scratch.clear();
     TRY(mlp_scratch(h, m, (size_t)n));
     C = m.sc_C;
     for (int l = 0; l < m.Lg; ++l) scratch.push_back((l & 1) ? m.sc_H1 : m.sc_H0);
-    H = scratch.data();
   }
-  GANMF_LAUNCH(cfgan_densify_kernel, dim3(n), dim3(256), 0, h->st, h->indptr, h->indices, h->data, ids_dev, row0, h->N, C, h->ldN);
+  GANMF_LAUNCH(cfgan_densify_kernel, dim3(n), dim3(256), 0, h->st, h->urm.indptr.get(), h->urm.indices.get(), h->data.get(), ids_dev, row0, h->N, C, h->ldN);
   HIP_TRY(hipGetLastError());
-  return mlp_forward(h, m, C, n, H, out, ldo);
+  return mlp_forward(h, m, C, n, scratch.data(), out, ldo);
 }
 
 // sq[t * CFGAN_SQ_BLOCKS ..] = the block partials of sum(theta^2) of tensor t
 int sumsq_tensors(ganmf_handle* h, const std::vector<Tensor*>& ts, float* sq) {
   for (size_t t = 0; t < ts.size(); ++t)
-    GANMF_LAUNCH(cfgan_sumsq_kernel, dim3(CFGAN_SQ_BLOCKS), dim3(256), 0, h->st, ts[t]->p, (long long)(ts[t]->padded() / 4), sq + t * CFGAN_SQ_BLOCKS);
+    GANMF_LAUNCH(cfgan_sumsq_kernel, dim3(CFGAN_SQ_BLOCKS), dim3(256), 0, h->st, ts[t]->p.get(), (long long)(ts[t]->padded() / 4), sq + t * CFGAN_SQ_BLOCKS);
   HIP_TRY(hipGetLastError());
   return 0;
 }

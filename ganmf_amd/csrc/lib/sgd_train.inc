@@ -1,4 +1,4 @@
-// sgd_train.inc -- what the SGD trainers (abi_slim.inc, abi_mf_sgd.inc) share on the host: the named allocator, the profiles on the
+// sgd_train.inc -- what the SGD trainers (abi_slim.inc, abi_mf_sgd.inc) share on the host: the profiles on the
 // device, the sample list with its draw, its checks and its copies, and the level order (counter_draw.hpp, level_sched.hpp).
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
@@ -10,22 +10,8 @@ static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int3
 
 constexpr int64_t SGD_MAX_SAMPLES = (int64_t)1 << 30;
 
-// hipMalloc whose failure names the bytes asked for (and is cleared: the handle stays usable)
-static int named_alloc(const char* who, const char* what, void** p, size_t bytes) {
-  const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 8));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return fail(-2, "%s: out of memory: %s needs %llu bytes (%s)", who, what, (unsigned long long)bytes, hipGetErrorString(e));
-  }
-  return 0;
-}
-
 // ---- the profiles -----------------------------------------------------------------------------------------------------------------
-static void profiles_drop(SampleProfiles& pr) {
-  hipFree(pr.indptr); hipFree(pr.items); hipFree(pr.ratings); hipFree(pr.eligible);
-  pr = SampleProfiles();
-}
+static void profiles_drop(SampleProfiles& pr) { pr = SampleProfiles(); }
 
 // into an object that holds nothing, from host CSR (h_indptr != null; ratings optional) or from the device CSR (dev_indptr, dev_items)
 static int profiles_upload(SampleProfiles& pr, const char* who, int n_users, int n_items, const int64_t* h_indptr, const int32_t* h_indices,
@@ -43,37 +29,30 @@ static int profiles_upload(SampleProfiles& pr, const char* who, int n_users, int
     if (len > 0 && len < n_items) users.push_back(u);
   }
   if (users.empty()) return fail(-1, "%s: no user has a profile that is neither empty nor full: there is nothing to sample", who);
-  const size_t n = (size_t)h_indptr[n_users];
-  int rc = named_alloc(who, "the profiles", (void**)&pr.indptr, ((size_t)n_users + 1) * sizeof(long long));
-  if (!rc) rc = named_alloc(who, "the profiles", (void**)&pr.items, n * sizeof(int));
-  if (!rc && h_ratings) rc = named_alloc(who, "the profiles", (void**)&pr.ratings, n * sizeof(double));
-  if (!rc) rc = named_alloc(who, "the eligible users", (void**)&pr.eligible, users.size() * sizeof(int));
+  int rc = pr.upload(h_indptr, from_device ? dev_items : h_indices, n_users, n_items, from_device, who, "the profiles");
+  if (!rc && h_ratings) rc = pr.upload_values(pr.ratings, h_ratings, false, who, "the profiles");
+  if (!rc) rc = pr.eligible.alloc(who, "the eligible users", users.size());
+  if (!rc) {
+    const hipError_t e = hipMemcpy(pr.eligible, users.data(), users.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(-2, "%s: %s", who, hipGetErrorString(e));
+  }
   if (rc) { profiles_drop(pr); return rc; }
-  hipError_t e = hipMemcpy(pr.indptr, h_indptr, ((size_t)n_users + 1) * sizeof(long long), hipMemcpyHostToDevice);
-  if (e == hipSuccess && n)
-    e = from_device ? hipMemcpy(pr.items, dev_items, n * sizeof(int), hipMemcpyDeviceToDevice)
-                    : hipMemcpy(pr.items, h_indices, n * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess && n && h_ratings) e = hipMemcpy(pr.ratings, h_ratings, n * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(pr.eligible, users.data(), users.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { profiles_drop(pr); return fail(-2, "%s: %s", who, hipGetErrorString(e)); }
   pr.n_eligible = (int)users.size();
-  pr.nnz = (int64_t)n;
   return 0;
 }
 
 // ---- the sample list on the device --------------------------------------------------------------------------------------------------
 struct SampleList {
-  int *users = nullptr, *pos = nullptr, *neg = nullptr;      // neg: the BPR trainers'
-  double* rating = nullptr;                                   // FunkSVD's
-  double* pows = nullptr;                                     // SLIM-BPR under Adam: the beta powers of every sample
-  long long* order = nullptr;                                 // the levelled route: list positions sorted by level
-  ~SampleList() { hipFree(users); hipFree(pos); hipFree(neg); hipFree(rating); hipFree(pows); hipFree(order); }
+  DevBuf<int> users, pos, neg;      // neg: the BPR trainers'
+  DevBuf<double> rating;            // FunkSVD's
+  DevBuf<double> pows;              // SLIM-BPR under Adam: the beta powers of every sample
+  DevBuf<long long> order;          // the levelled route: list positions sorted by level
 
   int alloc(const char* who, int64_t n, bool rated) {
-    TRY(named_alloc(who, "the samples", (void**)&users, (size_t)n * sizeof(int)));
-    TRY(named_alloc(who, "the samples", (void**)&pos, (size_t)n * sizeof(int)));
-    if (rated) TRY(named_alloc(who, "the samples", (void**)&rating, (size_t)n * sizeof(double)));
-    else TRY(named_alloc(who, "the samples", (void**)&neg, (size_t)n * sizeof(int)));
+    TRY(users.alloc(who, "the samples", (size_t)n));
+    TRY(pos.alloc(who, "the samples", (size_t)n));
+    if (rated) TRY(rating.alloc(who, "the samples", (size_t)n));
+    else TRY(neg.alloc(who, "the samples", (size_t)n));
     return 0;
   }
   // host arrays in (h_rating != null: a rated list, else h_neg); done when it returns: the caller's arrays may change
@@ -106,7 +85,7 @@ struct SampleList {
   }
   // enqueued: `sorted` has to live until the stream is synchronised
   int upload_order(const char* who, hipStream_t st, const std::vector<int64_t>& sorted) {
-    TRY(named_alloc(who, "the level order", (void**)&order, sorted.size() * sizeof(long long)));
+    TRY(order.alloc(who, "the level order", sorted.size()));
     HIP_TRY(hipMemcpyAsync(order, sorted.data(), sorted.size() * sizeof(long long), hipMemcpyHostToDevice, st));
     return 0;
   }
@@ -123,7 +102,7 @@ static int sample_count(const char* who, int64_t n_epochs, int64_t per, int64_t*
 static int sample_draw(ganmf_handle* h, const SampleProfiles& pr, bool rated, double quota, uint64_t seed, int64_t epoch, int64_t per,
                        int64_t n, SampleList& t) {
   DrawP p{};
-  p.indptr = pr.indptr; p.items = pr.items; p.ratings = pr.ratings; p.eligible = pr.eligible;
+  p.indptr = pr.indptr; p.items = pr.indices; p.ratings = pr.ratings; p.eligible = pr.eligible;
   p.n_users = h->U; p.n_items = h->N; p.n_eligible = pr.n_eligible; p.rated = rated ? 1 : 0; p.quota = quota;
   p.seed = seed; p.epoch0 = epoch; p.per_epoch = per; p.n = n;
   p.users = t.users; p.pos = t.pos; p.neg = t.neg; p.rating = t.rating;

@@ -8,18 +8,6 @@
 // theta -= lr * (g + beta * theta).  Products that read a parameter run before the kernel that updates it.  sum(theta^2) of the loss is
 // taken at the head of the step, at the pre-update parameters like every other term of the reported loss.
 // =================================================================================================
-void caae_free(ganmf_handle* h) {
-  CaaeState& c = h->ca;
-  for (ProfileMlp& g : c.gen) mlp_free(g);
-  free_tensor(c.bias, false);
-  hipFree(c.k_rows); hipFree(c.cdf[0]); hipFree(c.cdf[1]); hipFree(c.iu); hipFree(c.perm); hipFree(c.tu); hipFree(c.ti);
-  hipFree(c.neg); hipFree(c.users); hipFree(c.nu); hipFree(c.items); hipFree(c.xt); hipFree(c.first); hipFree(c.xu); hipFree(c.xi); hipFree(c.xn);
-  hipFree(c.Pg); hipFree(c.Qi); hipFree(c.Qj); hipFree(c.coef); hipFree(c.lt); hipFree(c.rt);
-  hipFree(c.C); hipFree(c.R); hipFree(c.Rp); hipFree(c.cdfb); hipFree(c.dz); hipFree(c.dh0); hipFree(c.dh1);
-  hipFree(c.lse); hipFree(c.reward); hipFree(c.la); hipFree(c.ae); hipFree(c.sq); hipFree(c.loss_dev); hipFree(c.lse_all);
-  c = CaaeState{};
-}
-
 // The fourth score source behind scores_device: out[i, :] = sigmoid(G(profile of ids[i])) -- the sigmoid applied, as CAAE.py:391 returns it
 int caae_scores(ganmf_handle* h, const int* ids_dev, int64_t n, int transposed, float* out, int ldw) {
   if (!h->ca.ready) return fail(-1, "scores: ganmf_caae_init has not been called on this GANMF_MODEL_CAAE handle");
@@ -39,7 +27,7 @@ int caae_cdf_all(ganmf_handle* h, int which) {
   for (int r0 = 0; r0 < U; r0 += blk) {
     const int nb = std::min(blk, U - r0);
     TRY(mlp_forward_rows(h, gn, nullptr, r0, nb, gn.sc_F, h->ldN));
-    GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, gn.sc_F, h->ldN, h->N, c.cdf[which] + (size_t)r0 * h->ldN, h->ldN,
+    GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, gn.sc_F.get(), h->ldN, h->N, c.cdf[which] + (size_t)r0 * h->ldN, h->ldN,
                  c.lse_all + r0);
     HIP_TRY(hipGetLastError());
   }
@@ -49,18 +37,18 @@ int caae_cdf_all(ganmf_handle* h, int which) {
 // iu (the user of every CSR position) and the shuffled-order buffers for the URM held now
 int caae_prepare(ganmf_handle* h) {
   CaaeState& c = h->ca;
-  if (c.iu_src == (const void*)h->indptr && c.order_cap >= h->nnz) return 0;
+  if (c.iu_src == (const void*)h->urm.indptr && (long long)c.ti.cap >= h->urm.nnz) return 0;      // (ti is allocated last)
   HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(c.iu); hipFree(c.perm); hipFree(c.tu); hipFree(c.ti);
-  c.iu = c.perm = c.tu = c.ti = nullptr; c.order_cap = 0; c.iu_src = nullptr;
-  const size_t n = (size_t)std::max<long long>(h->nnz, 1);
-  TRY(dalloc((float**)&c.iu, n));
-  TRY(dalloc((float**)&c.perm, n));
-  TRY(dalloc((float**)&c.tu, n));
-  TRY(dalloc((float**)&c.ti, n));
-  GANMF_LAUNCH(caae_rows_of_kernel, dim3(h->U), dim3(256), 0, h->st, h->indptr, h->U, c.iu);
+  c.iu.reset(); c.perm.reset(); c.tu.reset(); c.ti.reset();
+  c.iu_src = nullptr;
+  const size_t n = (size_t)std::max<long long>(h->urm.nnz, 1);
+  TRY(c.iu.alloc(n, true));
+  TRY(c.perm.alloc(n, true));
+  TRY(c.tu.alloc(n, true));
+  TRY(c.ti.alloc(n, true));
+  GANMF_LAUNCH(caae_rows_of_kernel, dim3(h->U), dim3(256), 0, h->st, h->urm.indptr.get(), h->U, c.iu.get());
   HIP_TRY(hipGetLastError());
-  c.order_cap = h->nnz; c.iu_src = (const void*)h->indptr;
+  c.iu_src = (const void*)h->urm.indptr;
   return 0;
 }
 
@@ -70,9 +58,9 @@ inline int caae_grid(long long n) { return (int)std::max<long long>(1, std::min<
 int caae_draw_perm(ganmf_handle* h, int64_t epoch) {
   CaaeState& c = h->ca;
   TRY(caae_prepare(h));
-  if (h->nnz == 0) return 0;
-  GANMF_LAUNCH(caae_perm_kernel, dim3(caae_grid(h->nnz)), dim3(256), 0, h->st, caae_base(c.seed, (unsigned long long)epoch, CAAE_S_PERM, 0),
-               h->nnz, c.iu, h->indices, c.perm, c.tu, c.ti);
+  if (h->urm.nnz == 0) return 0;
+  GANMF_LAUNCH(caae_perm_kernel, dim3(caae_grid(h->urm.nnz)), dim3(256), 0, h->st, caae_base(c.seed, (unsigned long long)epoch, CAAE_S_PERM, 0),
+               h->urm.nnz, c.iu.get(), h->urm.indices.get(), c.perm.get(), c.tu.get(), c.ti.get());
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -80,9 +68,9 @@ int caae_draw_perm(ganmf_handle* h, int64_t epoch) {
 // (b) one negative per position from the resident CDF of generator `which`
 int caae_draw_neg(ganmf_handle* h, int64_t epoch, int pass, int which, int* out) {
   CaaeState& c = h->ca;
-  if (h->nnz == 0) return 0;
-  GANMF_LAUNCH(caae_cdf_draw_kernel, dim3(caae_grid(h->nnz)), dim3(256), 0, h->st,
-               caae_base(c.seed, (unsigned long long)epoch, CAAE_S_NEG + which, (unsigned long long)pass), h->nnz, c.tu, 1, c.cdf[which], h->ldN, h->N, out);
+  if (h->urm.nnz == 0) return 0;
+  GANMF_LAUNCH(caae_cdf_draw_kernel, dim3(caae_grid(h->urm.nnz)), dim3(256), 0, h->st,
+               caae_base(c.seed, (unsigned long long)epoch, CAAE_S_NEG + which, (unsigned long long)pass), h->urm.nnz, c.tu.get(), 1, c.cdf[which].get(), h->ldN, h->N, out);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -106,7 +94,7 @@ int caae_batch_forward(ganmf_handle* h, int which, const int* users_dev, float* 
 int caae_draw_nu(ganmf_handle* h, int64_t epoch, int step, const int* users_dev, unsigned* planes) {
   CaaeState& c = h->ca;
   TRY(caae_batch_forward(h, 1, users_dev, c.Rp));
-  CaaeNuP p{h->indptr, h->indices, users_dev, c.k_rows, c.Rp, h->ldN, h->N, c.words,
+  CaaeNuP p{h->urm.indptr, h->urm.indices, users_dev, c.k_rows, c.Rp, h->ldN, h->N, c.words,
             caae_base(c.seed, (unsigned long long)epoch, CAAE_S_NU, (unsigned long long)step), planes};
   GANMF_LAUNCH(caae_nu_kernel, dim3(c.Bm), dim3(256), 0, h->st, p);
   HIP_TRY(hipGetLastError());
@@ -117,11 +105,11 @@ int caae_draw_nu(ganmf_handle* h, int64_t epoch, int step, const int* users_dev,
 int caae_draw_items(ganmf_handle* h, int64_t epoch, int which, int step, const int* users_dev, int* items) {
   CaaeState& c = h->ca;
   TRY(caae_batch_forward(h, which, users_dev, c.R));
-  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(c.Bm), dim3(256), 0, h->st, c.R, h->ldN, h->N, c.cdfb, h->ldN, c.lse);
+  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(c.Bm), dim3(256), 0, h->st, c.R.get(), h->ldN, h->N, c.cdfb.get(), h->ldN, c.lse.get());
   HIP_TRY(hipGetLastError());
   const long long n = (long long)c.Bm * c.n_s;
   GANMF_LAUNCH(caae_cdf_draw_kernel, dim3(caae_grid(n)), dim3(256), 0, h->st,
-               caae_base(c.seed, (unsigned long long)epoch, CAAE_S_ITEMS + which, (unsigned long long)step), n, (const int*)nullptr, c.n_s, c.cdfb,
+               caae_base(c.seed, (unsigned long long)epoch, CAAE_S_ITEMS + which, (unsigned long long)step), n, (const int*)nullptr, c.n_s, c.cdfb.get(),
                h->ldN, h->N, items);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -133,7 +121,7 @@ int caae_d_step(ganmf_handle* h, const int* tu, const int* ti, const int* tj, in
   CaaeDP p{tu, ti, tj, cnt, h->k, h->ldk, h->Ue.p, h->V.p, c.bias.p, c.Pg, c.Qi, c.Qj, c.coef, c.lt, c.rt, c.rt + c.d_bsize, c.first, h->U, c.lr, c.beta};
   GANMF_LAUNCH(caae_d_coef_kernel, dim3((cnt + 3) / 4), dim3(256), 0, h->st, p);
   HIP_TRY(hipGetLastError());
-  GANMF_LAUNCH(cfgan_loss_kernel, dim3(1), dim3(256), 0, h->st, c.lt, (const float*)nullptr, cnt, c.rt, cnt, c.beta, (const float*)nullptr, 0.f, loss_dev);
+  GANMF_LAUNCH(cfgan_loss_kernel, dim3(1), dim3(256), 0, h->st, c.lt.get(), (const float*)nullptr, cnt, c.rt.get(), cnt, c.beta, (const float*)nullptr, 0.f, loss_dev);
   HIP_TRY(hipGetLastError());
   GANMF_LAUNCH(caae_d_update_kernel, dim3((3 * cnt + 3) / 4), dim3(256), 0, h->st, p);
   HIP_TRY(hipGetLastError());
@@ -158,16 +146,16 @@ int caae_g_step(ganmf_handle* h, int which, const int* users_dev, const unsigned
   const std::vector<Tensor*> mine = gn.tensors();
   if (c.beta != 0.f) TRY(sumsq_tensors(h, mine, c.sq));
   TRY(caae_batch_forward(h, which, users_dev, c.R));
-  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, c.R, h->ldN, N, (float*)nullptr, h->ldN, c.lse);
+  GANMF_LAUNCH(caae_cdf_rows_kernel, dim3(nb), dim3(256), 0, h->st, c.R.get(), h->ldN, N, (float*)nullptr, h->ldN, c.lse.get());
   HIP_TRY(hipGetLastError());
   const long long nd = (long long)nb * c.n_s;
-  GANMF_LAUNCH(caae_reward_kernel, dim3((int)((nd + 3) / 4)), dim3(256), 0, h->st, users_dev, items_dev, nb, c.n_s, h->Ue.p, h->V.p, c.bias.p,
-               h->k, h->ldk, which == 0 ? 1.0f : -1.0f, c.reward);
+  GANMF_LAUNCH(caae_reward_kernel, dim3((int)((nd + 3) / 4)), dim3(256), 0, h->st, users_dev, items_dev, nb, c.n_s, h->Ue.p.get(), h->V.p.get(), c.bias.p.get(),
+               h->k, h->ldk, which == 0 ? 1.0f : -1.0f, c.reward.get());
   HIP_TRY(hipGetLastError());
   CaaePolP pp{c.R, c.C, which == 0 ? nu_dev : (const unsigned*)nullptr, items_dev, c.reward, c.lse, c.dz, c.la, c.ae, h->ldN, N, c.words, c.n_s, pc, ac};
   GANMF_LAUNCH(caae_policy_kernel, dim3(nb), dim3(256), 0, h->st, pp);
   HIP_TRY(hipGetLastError());
-  GANMF_LAUNCH(caae_g_loss_kernel, dim3(1), dim3(256), 0, h->st, c.la, c.ae, nb, pc, ac, c.beta != 0.f ? c.sq : (const float*)nullptr,
+  GANMF_LAUNCH(caae_g_loss_kernel, dim3(1), dim3(256), 0, h->st, c.la.get(), c.ae.get(), nb, pc, ac, c.beta != 0.f ? c.sq : (const float*)nullptr,
                (int)mine.size() * CFGAN_SQ_BLOCKS, c.beta, loss_dev);
   HIP_TRY(hipGetLastError());
   // backward, top down: every product reads the pre-step parameters; the updates follow
@@ -176,7 +164,7 @@ int caae_g_step(ganmf_handle* h, int which, const int* users_dev, const unsigned
   }));
   for (Tensor* t : mine) {
     const long long n4 = (long long)(t->padded() / 4);
-    GANMF_LAUNCH(caae_sgd_kernel, dim3(caae_grid(n4)), dim3(256), 0, h->st, t->p, t->g, n4, c.lr, c.beta);
+    GANMF_LAUNCH(caae_sgd_kernel, dim3(caae_grid(n4)), dim3(256), 0, h->st, t->p.get(), t->g, n4, c.lr, c.beta);
   }
   HIP_TRY(hipGetLastError());
   return 0;

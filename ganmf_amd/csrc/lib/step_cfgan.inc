@@ -14,27 +14,17 @@ int cfgan_create(ganmf_handle* h) {
   h->L = h->cfg.d_layers; h->act = h->cfg.d_act;
   h->Wl.resize(h->L);
   for (int l = 0; l < h->L; ++l) TRY(alloc_tensor(h->Wl[l], l == 0 ? 2 * N + 1 : e + 1, e, true, 1));
-  TRY(alloc_tensor(h->Wo, 1, e + 1, true, 1));      // (every CFGAN tensor owns its gradient buffer: free_tensor(.., true))
-  h->Al.resize(h->L, nullptr);
+  TRY(alloc_tensor(h->Wo, 1, e + 1, true, 1));      // (every CFGAN tensor owns its gradient buffer)
+  h->Al.resize(h->L);
   std::vector<float> ones((size_t)2 * B, 1.0f);
   for (int l = 0; l < h->L; ++l) {
-    TRY(dalloc(&h->Al[l], (size_t)2 * B * h->lde));
+    TRY(h->Al[l].alloc((size_t)2 * B * h->lde, true));
     HIP_TRY(hipMemcpy2D(h->Al[l] + e, (size_t)h->lde * 4, ones.data(), 4, 4, (size_t)2 * B, hipMemcpyHostToDevice));
   }
-  TRY(dalloc(&h->dz0, (size_t)2 * B * h->lde));
-  TRY(dalloc(&h->dz1, (size_t)2 * B * h->lde));
-  TRY(dalloc(&h->dlogit, (size_t)2 * B));
+  TRY(h->dz0.alloc((size_t)2 * B * h->lde, true));
+  TRY(h->dz1.alloc((size_t)2 * B * h->lde, true));
+  TRY(h->dlogit.alloc((size_t)2 * B, true));
   return 0;
-}
-
-void cfgan_free(ganmf_handle* h) {
-  CfganState& c = h->cf;
-  mlp_free(c.gen);
-  if (h->cfg.model == GANMF_MODEL_CFGAN) { for (auto& t : h->Wl) hipFree(t.g); hipFree(h->Wo.g); }
-  hipFree(c.C); hipFree(c.fake); hipFree(c.dfake); hipFree(c.DX); hipFree(c.dh0); hipFree(c.dh1);
-  hipFree(c.zr_part); hipFree(c.loss_rows); hipFree(c.sq); hipFree(c.loss_dev); hipFree(c.planes); hipFree(c.k_rows);
-  hipFree(c.cache);
-  c = CfganState{};
 }
 
 // gW = A_ext^T . dz over `nrows` rows, TF-Adam in the epilogue (the plan DisGANMF's weight gradients run on)
@@ -63,7 +53,7 @@ int cfgan_step(ganmf_handle* h, int kind, int row0, int nb, float* loss_dev) {
   std::vector<Tensor*> mine;
   if (gstep) mine = c.gen.tensors();
   else { for (auto& t : h->Wl) mine.push_back(&t); mine.push_back(&h->Wo); }
-  GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal, kind, alpha, gstep ? h->cfg.g_lr : h->cfg.d_lr);
+  GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get(), kind, alpha, gstep ? h->cfg.g_lr : h->cfg.d_lr);
   HIP_TRY(hipGetLastError());
   if (reg != 0.f) TRY(sumsq_tensors(h, mine, c.sq));
   // rows, generator, masked rows into the discriminator's input block
@@ -86,14 +76,14 @@ int cfgan_step(ganmf_handle* h, int kind, int row0, int nb, float* loss_dev) {
   float* la = c.loss_rows;
   float* lb = c.loss_rows + c.Bm;
   // rows < nb carry label 1: the real half of a D-step, and ALL rows of a G-step (CFGAN.py:164: the generator wants its rows called real)
-  GANMF_LAUNCH(dis_head_kernel, dim3((M + 3) / 4), dim3(256), 0, h->st, feat, h->lde, e + 1, h->Wo.p, 0, M, nb, 1.0f / (float)nb, h->dlogit, la, lb);
+  GANMF_LAUNCH(dis_head_kernel, dim3((M + 3) / 4), dim3(256), 0, h->st, feat, h->lde, e + 1, h->Wo.p.get(), 0, M, nb, 1.0f / (float)nb, h->dlogit.get(), la, lb);
   HIP_TRY(hipGetLastError());
   GANMF_LAUNCH(cfgan_loss_kernel, dim3(1), dim3(256), 0, h->st, la, gstep ? (const float*)nullptr : lb, nb,
                reg != 0.f ? c.sq : (const float*)nullptr, (int)mine.size() * CFGAN_SQ_BLOCKS, reg, zr ? c.zr_part : (const float*)nullptr, c.zr_coef, loss_dev);
   HIP_TRY(hipGetLastError());
-  GANMF_LAUNCH(dis_dz_top_kernel, dim3(dis_dz_top_blocks(e)), dim3(DZ_COLS * DZ_GROUPS), 0, h->st, feat, h->lde, e, h->Wo.p, h->dlogit,
-               0, M, 0, 0.f, h->act, h->dz0, (float*)nullptr, (float*)nullptr, gstep ? (float*)nullptr : h->Wo.p, h->Wo.m, h->Wo.v,
-               h->scal, alpha, reg, (float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  GANMF_LAUNCH(dis_dz_top_kernel, dim3(dis_dz_top_blocks(e)), dim3(DZ_COLS * DZ_GROUPS), 0, h->st, feat, h->lde, e, h->Wo.p.get(), h->dlogit.get(),
+               0, M, 0, 0.f, h->act, h->dz0.get(), (float*)nullptr, (float*)nullptr, gstep ? (float*)nullptr : h->Wo.p, h->Wo.m.get(), h->Wo.v.get(),
+               h->scal.get(), alpha, reg, (float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   HIP_TRY(hipGetLastError());
   // hidden layers, top down: the product that reads W_l (backward) in front of the one that updates it
   float* cur = h->dz0;
@@ -123,19 +113,19 @@ int cfgan_scores(ganmf_handle* h, const int* ids_dev, int64_t n, int transposed,
   if (!transposed) return mlp_forward_rows(h, c.gen, ids_dev, 0, (int)n, out, ldw);
   const int ldu = round_up(U, LD_ALIGN);      // == ldw
   if (c.cache_version != h->param_version || !c.cache) {
-    if (!c.cache) TRY(dalloc(&c.cache, (size_t)N * ldu));
+    if (!c.cache) TRY(c.cache.alloc((size_t)N * ldu, true));
     const int blk = std::min(U, 1024);
     TRY(mlp_scratch(h, c.gen, (size_t)blk));      // grown here: sc_F is named as the output below, before mlp_forward_rows would grow it
     for (int r0 = 0; r0 < U; r0 += blk) {
       const int nb = std::min(blk, U - r0);
       TRY(mlp_forward_rows(h, c.gen, nullptr, r0, nb, c.gen.sc_F, h->ldN));
-      GANMF_LAUNCH(cfgan_transpose_kernel, dim3((N + 31) / 32, (nb + 31) / 32), dim3(256), 0, h->st, c.gen.sc_F, h->ldN, nb, N, c.cache, ldu, r0);
+      GANMF_LAUNCH(cfgan_transpose_kernel, dim3((N + 31) / 32, (nb + 31) / 32), dim3(256), 0, h->st, c.gen.sc_F.get(), h->ldN, nb, N, c.cache.get(), ldu, r0);
       HIP_TRY(hipGetLastError());
     }
     c.cache_version = h->param_version;
   }
   const long long total = (long long)n * (ldu / 4);
-  GANMF_LAUNCH(gather_rows_kernel, dim3((int)std::min<long long>(2048, (total + 255) / 256)), dim3(256), 0, h->st, c.cache, ldu, ids_dev, (int)n, out);
+  GANMF_LAUNCH(gather_rows_kernel, dim3((int)std::min<long long>(2048, (total + 255) / 256)), dim3(256), 0, h->st, c.cache.get(), ldu, ids_dev, (int)n, out);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -117,7 +117,7 @@ int dis_backprop_hidden(ganmf_handle* h, int row0, int nrows, bool param_grads, 
         const bool regD = h->cfg.d_reg != 0.f;
         GANMF_LAUNCH(dis_uid_grad_kernel, dim3(nblk), dim3(64 * UIDG_GROUPS), 0, h->st, h->XF, h->ldN, N + 1, cur, h->lde,
                            nrows, e, h->Wl[0].g + ro, apply ? h->Wl[0].p + ro : nullptr, h->Wl[0].m + ro, h->Wl[0].v + ro,
-                           h->scal, h->d_alpha, h->cfg.d_reg,
+                           h->scal.get(), h->d_alpha, h->cfg.d_reg,
                            (apply && regD) ? h->dis_slot + (size_t)4 * h->dis_cap + h->dis_regn[0] : nullptr);
         HIP_TRY(hipGetLastError());
         if (apply && regD) h->dis_regn[0] += nblk;
@@ -183,11 +183,11 @@ int dis_d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float
       Scope s(h, T_DIS_HEAD, 0, 4.0 * 2 * nb * e * 3);
       if (!head_done)
       GANMF_LAUNCH(dis_head_kernel, dim3((2 * nb + 3) / 4), dim3(256), 0, h->st, feat, h->lde, e + 1,
-                         h->Wo.p, 0, 2 * nb, nb, inv_b, h->dlogit, h->dis_slot, h->dis_slot + h->dis_cap);
+                         h->Wo.p.get(), 0, 2 * nb, nb, inv_b, h->dlogit.get(), h->dis_slot, h->dis_slot + h->dis_cap);
       const size_t ro = (size_t)(h->N + 1) * h->lde;      // the float(uid) row of W_0_ext
       GANMF_LAUNCH(dis_dz_top_kernel, dim3(ntop), dim3(DZ_COLS * DZ_GROUPS), 0, h->st, feat, h->lde, e,
-                         h->Wo.p, h->dlogit, 0, 2 * nb, 0, 0.f, h->act, h->dz0, h->Wo.g, (float*)nullptr,
-                         fuse_wo ? h->Wo.p : nullptr, h->Wo.m, h->Wo.v, h->scal, h->d_alpha, h->cfg.d_reg,
+                         h->Wo.p.get(), h->dlogit.get(), 0, 2 * nb, 0, 0.f, h->act, h->dz0.get(), h->Wo.g, (float*)nullptr,
+                         fuse_wo ? h->Wo.p : nullptr, h->Wo.m.get(), h->Wo.v.get(), h->scal.get(), h->d_alpha, h->cfg.d_reg,
                          (fuse_wo && h->cfg.d_reg != 0.f) ? h->dis_slot + (size_t)(4 + h->L) * h->dis_cap : nullptr,
                          uid_top ? (const float*)(h->XF + (h->N + 1)) : (const float*)nullptr, h->ldN,
                          uid_top ? h->Wl[0].p + ro : (float*)nullptr, uid_top ? h->Wl[0].m + ro : (float*)nullptr,
@@ -200,7 +200,7 @@ int dis_d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float
     TRY(dis_backprop_hidden(h, 0, 2 * nb, true, b_global, &dz0));
     if (h->dis_colsum_pending) return fail(-1, "dis_d_step: the column sums of the backward top were not launched");
   } else {
-    GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal, 0, h->d_alpha, h->cfg.d_lr);
+    GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get(), 0, h->d_alpha, h->cfg.d_lr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(h->gD, 0, h->gD_elems * sizeof(float), h->st));
   }
@@ -238,13 +238,13 @@ int dis_g_step(ganmf_handle* h, const int* rows_dev, int nb, int start, int b_gl
     {  // generator loss = loss_fake + alpha * FM  (DisGANMF.py:135-136): generated rows only, label 0
       Scope s(h, T_DIS_HEAD, 0, 4.0 * 2 * nb * e * 3);
       if (!head_done)
-      GANMF_LAUNCH(dis_head_kernel, dim3((nb + 3) / 4), dim3(256), 0, h->st, feat, h->lde, e + 1, h->Wo.p,
-                         nb, nb, nb, inv_b, h->dlogit, (float*)nullptr, h->dis_slot);      // generated rows only -> seg 0
+      GANMF_LAUNCH(dis_head_kernel, dim3((nb + 3) / 4), dim3(256), 0, h->st, feat, h->lde, e + 1, h->Wo.p.get(),
+                         nb, nb, nb, inv_b, h->dlogit.get(), (float*)nullptr, h->dis_slot);      // generated rows only -> seg 0
       fmn = (head_done && head.pair_off > 0) ? nb : dis_dz_top_blocks(e);
       if (!(head_done && head.pair_off > 0))
-      GANMF_LAUNCH(dis_dz_top_kernel, dim3(fmn), dim3(DZ_COLS * DZ_GROUPS), 0, h->st, feat, h->lde, e, h->Wo.p, h->dlogit,
-                         nb, nb, nb, fmc, h->act, h->dz0, (float*)nullptr, h->dis_slot + h->dis_cap, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                         h->scal, 0, 0.f, (float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+      GANMF_LAUNCH(dis_dz_top_kernel, dim3(fmn), dim3(DZ_COLS * DZ_GROUPS), 0, h->st, feat, h->lde, e, h->Wo.p.get(), h->dlogit.get(),
+                         nb, nb, nb, fmc, h->act, h->dz0.get(), (float*)nullptr, h->dis_slot + h->dis_cap, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                         h->scal.get(), 0, 0.f, (float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
       HIP_TRY(hipGetLastError());
     }
     float* dz0;
@@ -257,7 +257,7 @@ int dis_g_step(ganmf_handle* h, const int* rows_dev, int nb, int start, int b_gl
       TRY(run_gemm(h, T_GEMM_DF, T_RED_DF, g, false, false));
     }
   } else {
-    if (!h->lazy_pass) GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal, 1, h->g_alpha, h->cfg.g_lr);
+    if (!h->lazy_pass) GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get(), 1, h->g_alpha, h->cfg.g_lr);
     HIP_TRY(hipGetLastError());
   }
   const bool reg = h->cfg.g_reg != 0.f;

@@ -39,10 +39,10 @@ bool stage_pass_plan(ganmf_handle* h, int64_t nfull, GemmPlan* pl, bool* front) 
   *pl = generator_plan(h, h->B, front);
   if (!*front && (pl->persist || pl->nsplit != 1)) return false;      // (only one-launch forms are replayed as batches)
   const size_t need = (size_t)nfull * 2 * h->B * h->ldN;
-  if (need > h->XF_pass_elems) {      // grown on demand; never more than a quarter of the free device memory
+  if (need > h->XF_pass.cap) {      // grown on demand; never more than a quarter of the free device memory
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-    if ((need - h->XF_pass_elems) * sizeof(float) > free_b / 4) return false;
+    if ((need - h->XF_pass.cap) * sizeof(float) > free_b / 4) return false;
   }
   return true;
 }
@@ -55,10 +55,10 @@ bool stage_pass_plan(ganmf_handle* h, int64_t nfull, GemmPlan* pl, bool* front) 
 // with a NaN bit pattern in a pad column would reach user_embeddings' pads and from there F = Ub . V^T; tests/test_gpu_multi_launch.py
 // poisons the allocator to see this).
 static bool lazy_chunk_alloc(ganmf_handle* h, size_t elems) {
-  float* p = nullptr;
-  if (hipMalloc((void**)&p, elems * sizeof(float)) != hipSuccess) return false;
-  if (hipMemsetAsync(p, 0, elems * sizeof(float), h->st) != hipSuccess) { hipFree(p); return false; }
-  h->lazy_chunks.emplace_back(p, elems);
+  DevBuf<float> chunk;
+  if (chunk.alloc(elems, false) != 0) return false;
+  if (hipMemsetAsync(chunk, 0, elems * sizeof(float), h->st) != hipSuccess) return false;
+  h->lazy_chunks.push_back(std::move(chunk));
   return true;
 }
 // (best effort = a failure must leave no trace: neither HIP's sticky last-error, which the next launch check of the same call would
@@ -82,24 +82,18 @@ void prealloc_pass_buffers(ganmf_handle* h, bool ragged) {      // (ragged: the 
   bool front = false;
   if (!ragged && stage_pass_plan(h, nfull, &pl, &front)) {
     const size_t need = (size_t)nfull * 2 * h->B * h->ldN;
-    if (need > h->XF_pass_elems) {
-      hipFree(h->XF_pass); h->XF_pass = nullptr; h->XF_pass_elems = 0;
-      if (dalloc(&h->XF_pass, need) == 0) h->XF_pass_elems = need;
-      else h->XF_pass = nullptr;
+    if (need > h->XF_pass.cap) {
+      (void)h->XF_pass.alloc(need, true);
     }
     const size_t need_u = front ? 0 : (size_t)nfull * h->B * h->ldk;
-    if (need_u > h->Ub_pass_elems && fits_quarter_of_free((need_u - h->Ub_pass_elems) * sizeof(float))) {
-      hipFree(h->Ub_pass); h->Ub_pass = nullptr; h->Ub_pass_elems = 0;
-      if (dalloc(&h->Ub_pass, need_u) == 0) h->Ub_pass_elems = need_u;
-      else h->Ub_pass = nullptr;
+    if (need_u > h->Ub_pass.cap && fits_quarter_of_free((need_u - h->Ub_pass.cap) * sizeof(float))) {
+      (void)h->Ub_pass.alloc(need_u, true);
     }
   }
   if (h->lazy_rows && h->cfg.g_reg == 0.f) {
     const size_t need = (size_t)h->U * h->ldk;
-    if (need > h->Ub_sched_elems && fits_quarter_of_free((need - h->Ub_sched_elems) * sizeof(float))) {
-      hipFree(h->Ub_sched); h->Ub_sched = nullptr; h->Ub_sched_elems = 0;
-      if (dalloc(&h->Ub_sched, need) == 0) h->Ub_sched_elems = need;
-      else h->Ub_sched = nullptr;
+    if (need > h->Ub_sched.cap && fits_quarter_of_free((need - h->Ub_sched.cap) * sizeof(float))) {
+      (void)h->Ub_sched.alloc(need, true);
     }
     // the arena of a pass's gUb slabs (here: sixteen slabs per step, at most 512 MiB; more is added when a pass needs it) and its tables
     if (h->lazy_chunks.empty()) {
@@ -107,9 +101,8 @@ void prealloc_pass_buffers(ganmf_handle* h, bool ragged) {      // (ragged: the 
       if (fits_quarter_of_free(want * sizeof(float))) lazy_chunk_alloc(h, want);
     }
     const size_t T = (size_t)nfull + 2;
-    if (2 * T > h->lazy_stage_cap && hipHostMalloc((void**)&h->lazy_stage, 2 * (T + 16) * sizeof(LazyStep), hipHostMallocDefault) == hipSuccess)
-      h->lazy_stage_cap = 2 * (T + 16);
-    if (2 * T > h->lazy_tab_cap && hipMalloc((void**)&h->lazy_tab, 2 * (T + 16) * sizeof(LazyStep)) == hipSuccess) h->lazy_tab_cap = 2 * (T + 16);
+    if (2 * T > h->lazy_stage.cap) (void)h->lazy_stage.alloc(2 * (T + 16), false);
+    if (2 * T > h->lazy_tab.cap) (void)h->lazy_tab.alloc(2 * (T + 16), false);
   }
 }
 
@@ -123,23 +116,15 @@ int stage_pass(ganmf_handle* h, const int* rows_dev, int64_t nfull, const GemmPl
                bool* g_opened, bool gen = true) {
   const int N = h->N, k = h->k, B = h->B;
   const size_t need = (size_t)nfull * 2 * B * h->ldN;
-  if (need > h->XF_pass_elems) {
-    HIP_TRY(hipStreamSynchronize(h->st));
+  if (need > h->XF_pass.cap) {
     HIP_TRY(hipStreamSynchronize(h->st2));
-    hipFree(h->XF_pass); h->XF_pass = nullptr; h->XF_pass_elems = 0;
-    TRY(dalloc(&h->XF_pass, need));      // (zeroed: the padding columns of the generated rows are never written)
-    h->XF_pass_elems = need;
+    TRY(h->XF_pass.grow(h->st, need, true));      // (zeroed: the padding columns of the generated rows are never written)
   }
   const size_t need_u = (front || !gen) ? 0 : (size_t)nfull * B * h->ldk;
-  if (need_u > h->Ub_pass_elems) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->Ub_pass); h->Ub_pass = nullptr; h->Ub_pass_elems = 0;
-    TRY(dalloc(&h->Ub_pass, need_u));
-    h->Ub_pass_elems = need_u;
-  }
+  TRY(h->Ub_pass.grow(h->st, need_u, true));
   const int rows = (int)(nfull * B);
   {
-    DensP d{h->indptr, h->indices, h->data, rows_dev, rows, N, h->XF_pass, h->ldN, h->Ue.p, h->ldk, (front || !gen) ? nullptr : h->Ub_pass,
+    DensP d{h->urm.indptr, h->urm.indices, h->data, rows_dev, rows, N, h->XF_pass, h->ldN, h->Ue.p, h->ldk, (front || !gen) ? nullptr : h->Ub_pass,
             h->scal, 0, 0, 0.f, uid_col, row_offset};
     d.stage_b = B;
     d.open_d_slot = S_TAB; d.open_d_count = gen ? (int)nfull : 0; d.lr_d = h->cfg.d_lr;
@@ -180,7 +165,7 @@ int rows_and_generator(ganmf_handle* h, const int* rows_dev, int nb, int which, 
   // generator pass with the per-pass update of U (lazy_pass_begin): Ub already points at this minibatch's embeddings as of this step,
   // lr_t of the step has its table slot
   const bool lazy = which == 1 && h->lazy_pass;
-  DensP d{h->indptr, h->indices, h->data, rows_dev, nb, N, h->XF, h->ldN, h->Ue.p, h->ldk, lazy ? nullptr : h->Ub, h->scal, which,
+  DensP d{h->urm.indptr, h->urm.indices, h->data, rows_dev, nb, N, h->XF, h->ldN, h->Ue.p, h->ldk, lazy ? nullptr : h->Ub, h->scal, which,
           lazy ? -1 : aslot, which ? h->cfg.g_lr : h->cfg.d_lr, uid_col, row_offset};
   GemmP g{};
   g.A = h->Ub; g.lda = h->ldk; g.B = h->V.p; g.ldb = h->ldk;
@@ -228,9 +213,9 @@ int step_front(ganmf_handle* h, const int* rows_dev, int nb, int which) {
     // sparse regime: Er from the CSR rows, X never materialised, the encode GEMM runs on the generated half only
     TRY(dp_join(h, PEND_WE));
     {
-      Scope s(h, T_DENSIFY, 0, 4.0 * nb * (2 * k + e) + 4.0 * (double)h->nnz / std::max(h->U, 1) * nb * e);
-      GANMF_LAUNCH(sparse_front_kernel, dim3(nb), dim3(256), 0, h->st, h->indptr, h->indices, h->data, rows_dev, nb, N,
-                         h->XF, h->ldN, h->Ue.p, h->ldk, lazy ? nullptr : h->Ub, h->scal, which, lazy ? -1 : aslot, which ? h->cfg.g_lr : h->cfg.d_lr, h->We.p, h->lde, e, h->E);
+      Scope s(h, T_DENSIFY, 0, 4.0 * nb * (2 * k + e) + 4.0 * (double)h->urm.nnz / std::max(h->U, 1) * nb * e);
+      GANMF_LAUNCH(sparse_front_kernel, dim3(nb), dim3(256), 0, h->st, h->urm.indptr.get(), h->urm.indices.get(), h->data.get(), rows_dev, nb, N,
+                         h->XF, h->ldN, h->Ue.p.get(), h->ldk, lazy ? nullptr : h->Ub, h->scal.get(), which, lazy ? -1 : aslot, which ? h->cfg.g_lr : h->cfg.d_lr, h->We.p.get(), h->lde, e, h->E.get());
       HIP_TRY(hipGetLastError());
     }
     {
@@ -284,7 +269,7 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
       g.epi.kind = EPI_SUB_AUX_SQ; g.epi.aux = h->XF; g.epi.ldaux = h->ldN;
       g.epi.aux_batch_stride = (long long)nb * h->ldN; g.epi.sq_partials = h->sqp;
       if (h->sparse_d) {      // the real rows were never expanded: X[m, n] is looked up in the CSR rows of the batch
-        g.epi.csr_indptr = h->indptr; g.epi.csr_indices = h->indices; g.epi.csr_data = h->data; g.epi.csr_rows = rows_dev;
+        g.epi.csr_indptr = h->urm.indptr; g.epi.csr_indices = h->urm.indices; g.epi.csr_data = h->data; g.epi.csr_rows = rows_dev;
       }
       // [real ; generated] are contiguous in E, XF and Dl: with whole 64-row tiles per path the two batches are ONE product of
       // 2.nb rows, whose list order (tile row fastest) puts the four row tiles of a tile column next to each other on one XCD --
@@ -308,7 +293,7 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
     }
   } else {
     // rank out of rows: still open the optimizer step and contribute zeros to the collectives
-    GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal, 0, aslot, h->cfg.d_lr);
+    GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get(), 0, aslot, h->cfg.d_lr);
     HIP_TRY(hipGetLastError());
   }
   if (dist) {
@@ -379,9 +364,9 @@ int d_step(ganmf_handle* h, const int* rows_dev, int nb, int b_global, float* pa
     };
     auto sparse_rows = [&]() -> int {      // S = X^T . dE_r (+ the bias parts): dE must be final
       if (!h->sparse_d) return 0;
-      Scope s(h, T_DENSIFY, 0, 4.0 * ((double)h->nnz / std::max(h->U, 1) * nb * e + 2.0 * (N + CSC_BIAS_PARTS) * e));
-      GANMF_LAUNCH(csc_rows_kernel, dim3(N + CSC_BIAS_PARTS), dim3(256), 0, h->st, h->csc_colptr, h->csc_rowidx, h->csc_val,
-                   h->pos, start, nb, N, h->dE, h->lde, e, h->sp_rows);
+      Scope s(h, T_DENSIFY, 0, 4.0 * ((double)h->urm.nnz / std::max(h->U, 1) * nb * e + 2.0 * (N + CSC_BIAS_PARTS) * e));
+      GANMF_LAUNCH(csc_rows_kernel, dim3(N + CSC_BIAS_PARTS), dim3(256), 0, h->st, h->csc.indptr.get(), h->csc.indices.get(), h->csc_val.get(),
+                   h->pos, start, nb, N, h->dE.get(), h->lde, e, h->sp_rows.get());
       HIP_TRY(hipGetLastError());
       return 0;
     };
@@ -528,7 +513,7 @@ bool lazy_pass_ok(const ganmf_handle* h, int64_t per_pass, int64_t n) {
   const GemmPlan pl = gemm_plan(h->B, h->k, h->N, 1, false, h->tune);
   const size_t per_step = (size_t)(std::max(pl.nsplit, 1) + 1) * h->B * h->ldk + 128;
   size_t have = 0;
-  for (const auto& ch : h->lazy_chunks) have += ch.second;
+  for (const auto& ch : h->lazy_chunks) have += ch.cap;
   const size_t need = (size_t)per_pass * per_step;
   if (need <= have) return true;
   size_t free_b = 0, total_b = 0;
@@ -538,13 +523,13 @@ bool lazy_pass_ok(const ganmf_handle* h, int64_t per_pass, int64_t n) {
 // a block of the pass arena (64-float aligned); chunks are kept for the passes to come
 int lazy_block(ganmf_handle* h, size_t elems, float** out) {
   elems = (elems + 63) / 64 * 64;
-  while (h->lazy_chunk < h->lazy_chunks.size() && h->lazy_used + elems > h->lazy_chunks[h->lazy_chunk].second) { ++h->lazy_chunk; h->lazy_used = 0; }
+  while (h->lazy_chunk < h->lazy_chunks.size() && h->lazy_used + elems > h->lazy_chunks[h->lazy_chunk].cap) { ++h->lazy_chunk; h->lazy_used = 0; }
   if (h->lazy_chunk == h->lazy_chunks.size()) {
     const size_t want = std::max<size_t>(elems, (size_t)16 << 20);      // 64 MiB chunks, zeroed (lazy_chunk_alloc)
     if (!lazy_chunk_alloc(h, want)) HIP_TRY(hipErrorOutOfMemory);
     h->lazy_used = 0;
   }
-  *out = h->lazy_chunks[h->lazy_chunk].first + h->lazy_used;
+  *out = h->lazy_chunks[h->lazy_chunk] + h->lazy_used;
   h->lazy_used += elems;
   return 0;
 }
@@ -553,24 +538,21 @@ void lazy_pass_abort(ganmf_handle* h) {
 }
 int lazy_pass_begin(ganmf_handle* h, int p, int64_t per_pass, int64_t n, bool opened) {      // opened: lr_t of the pass's steps is in its table already (stage_pass)
   const size_t need = (size_t)n * h->ldk;
-  if (need > h->Ub_sched_elems) {
-    HIP_TRY(hipStreamSynchronize(h->st));
+  if (need > h->Ub_sched.cap) {
     HIP_TRY(hipStreamSynchronize(h->st2));
-    hipFree(h->Ub_sched); h->Ub_sched = nullptr; h->Ub_sched_elems = 0;
-    TRY(dalloc(&h->Ub_sched, need));
-    h->Ub_sched_elems = need;
+    TRY(h->Ub_sched.grow(h->st, need, true));
   }
   const int tab = lazy_tab_slot(h, p);
   if (!opened) {
-    GANMF_LAUNCH(open_steps_kernel, dim3(1), dim3(64), 0, h->st, h->scal, 1, tab, (int)per_pass, h->cfg.g_lr);
+    GANMF_LAUNCH(open_steps_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get(), 1, tab, (int)per_pass, h->cfg.g_lr);
     HIP_TRY(hipGetLastError());
   }
   {
     Scope s(h, T_ADAM_U, 0, 16.0 * n * h->ldk);
     const long long total = (long long)n * (h->ldk / 4);
     const int grid = (int)std::max<long long>(1, std::min<long long>(8192, (total + 255) / 256));
-    GANMF_LAUNCH(adam_rows_advance_kernel, dim3(grid), dim3(256), 0, h->st, h->Ue.p, h->Ue.m, h->Ue.v, h->perm, h->pos_step, (int)n,
-                 h->ldk, h->scal, tab, h->cfg.g_reg, h->Ub_sched);
+    GANMF_LAUNCH(adam_rows_advance_kernel, dim3(grid), dim3(256), 0, h->st, h->Ue.p.get(), h->Ue.m.get(), h->Ue.v.get(), h->perm.get(), h->pos_step, (int)n,
+                 h->ldk, h->scal.get(), tab, h->cfg.g_reg, h->Ub_sched.get());
     HIP_TRY(hipGetLastError());
   }
   h->lazy_steps.assign((size_t)per_pass, LazyStep{nullptr, 0, 1, 0, 0});
@@ -580,22 +562,11 @@ int lazy_pass_begin(ganmf_handle* h, int p, int64_t per_pass, int64_t n, bool op
 }
 int lazy_pass_end(ganmf_handle* h, int p, int64_t per_pass) {
   const size_t T = (size_t)per_pass;
-  if (2 * T > h->lazy_stage_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->lazy_stage) hipHostFree(h->lazy_stage);
-    h->lazy_stage = nullptr; h->lazy_stage_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&h->lazy_stage, 2 * (T + 16) * sizeof(LazyStep), hipHostMallocDefault));
-    h->lazy_stage_cap = 2 * (T + 16);
-  }
-  if (2 * T > h->lazy_tab_cap) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    hipFree(h->lazy_tab); h->lazy_tab = nullptr; h->lazy_tab_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->lazy_tab, 2 * (T + 16) * sizeof(LazyStep)));
-    h->lazy_tab_cap = 2 * (T + 16);
-  }
+  if (2 * T > h->lazy_stage.cap) TRY(h->lazy_stage.grow(h->st, 2 * (T + 16), false));
+  if (2 * T > h->lazy_tab.cap) TRY(h->lazy_tab.grow(h->st, 2 * (T + 16), false));
   if (p >= 2) HIP_TRY(hipStreamSynchronize(h->st));      // the half of the staging table this pass reuses has been copied
-  LazyStep* const host = h->lazy_stage + (size_t)(p & 1) * (h->lazy_stage_cap / 2);
-  LazyStep* const dev = h->lazy_tab + (size_t)(p & 1) * (h->lazy_tab_cap / 2);
+  LazyStep* const host = h->lazy_stage + (size_t)(p & 1) * (h->lazy_stage.cap / 2);
+  LazyStep* const dev = h->lazy_tab + (size_t)(p & 1) * (h->lazy_tab.cap / 2);
   std::copy(h->lazy_steps.begin(), h->lazy_steps.end(), host);
   HIP_TRY(hipMemcpyAsync(dev, host, T * sizeof(LazyStep), hipMemcpyHostToDevice, h->st));
   {
@@ -604,8 +575,8 @@ int lazy_pass_end(ganmf_handle* h, int p, int64_t per_pass) {
     // busy would double the launch)
     const long long total = (long long)h->U * (h->ldk / 4);
     const int grid = (int)std::max<long long>(1, std::min<long long>(8192, (total + 255) / 256));
-    GANMF_LAUNCH(adam_rows_flush_kernel, dim3(grid), dim3(256), 0, h->st, h->Ue.p, h->Ue.m, h->Ue.v, h->pos, h->pos_step, dev,
-                 (int)per_pass, h->U, h->ldk, h->scal, lazy_tab_slot(h, p), h->cfg.g_reg);
+    GANMF_LAUNCH(adam_rows_flush_kernel, dim3(grid), dim3(256), 0, h->st, h->Ue.p.get(), h->Ue.m.get(), h->Ue.v.get(), h->pos, h->pos_step, dev,
+                 (int)per_pass, h->U, h->ldk, h->scal.get(), lazy_tab_slot(h, p), h->cfg.g_reg);
     HIP_TRY(hipGetLastError());
   }
   lazy_pass_abort(h);      // (restores the handle's own minibatch buffers and lr_t slot)
@@ -636,16 +607,14 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
     TRY(lazy_block(h, (size_t)nb * h->ldk, &fin));
     g.C = fin;
     gub = SlabRef{fin, 1, 0};
-    float* const slab2 = h->slab2;
-    const size_t slab2_elems = h->slab2_elems;
     if (pl.nsplit > 1 && h->defer_gub) {
       const size_t elems = gemm_slab_elems(pl, g.M, g.ldc, 1);
       float* blk = nullptr;
       TRY(lazy_block(h, elems, &blk));
-      h->slab2 = blk; h->slab2_elems = elems;      // (run_gemm files deferred slabs in the second workspace)
+      h->slab2_lent = blk; h->slab2_lent_elems = elems;      // (run_gemm files deferred slabs in the second workspace)
     }
     const int rc = run_gemm(h, T_GEMM_GUB, T_RED_GUB, g, false, true, nullptr, 0, 0, nullptr, h->defer_gub ? &gub : nullptr, nullptr, nullptr, &pl);
-    h->slab2 = slab2; h->slab2_elems = slab2_elems;
+    h->slab2_lent = nullptr; h->slab2_lent_elems = 0;
     return rc;
   };
   auto gemm_gV = [&]() -> int {   // gV = dF^T . Ub
@@ -766,8 +735,8 @@ int gen_update(ganmf_handle* h, int nb, int start, int b_global, int* regn_v, fl
     h->lazy_steps[h->lazy_step] = LazyStep{gub.p, gub.split_stride, gub.nsplit, start, nb};
   } else {
     Scope s(h, T_ADAM_U, 0, 24.0 * h->Ue.count());
-    GANMF_LAUNCH(adam_rows_kernel, dim3(ADAM_GRID), dim3(256), 0, h->st, h->Ue.p, h->Ue.m, h->Ue.v, gub.p,
-                       gub.nsplit, gub.split_stride, h->pos, start, nb, h->U, h->ldk, h->scal, h->g_alpha, h->cfg.g_reg,
+    GANMF_LAUNCH(adam_rows_kernel, dim3(ADAM_GRID), dim3(256), 0, h->st, h->Ue.p.get(), h->Ue.m.get(), h->Ue.v.get(), gub.p,
+                       gub.nsplit, gub.split_stride, h->pos, start, nb, h->U, h->ldk, h->scal.get(), h->g_alpha, h->cfg.g_reg,
                        reg ? reg_u : nullptr);
     HIP_TRY(hipGetLastError());
   }
@@ -817,7 +786,7 @@ int g_step(ganmf_handle* h, const int* rows_dev, int nb, int start, int b_global
       TRY(run_gemm(h, T_GEMM_DF, T_RED_DF, g, false, false, nullptr, 4.0 * nb * N));
     }
   } else if (!h->lazy_pass) {      // (a lazy pass opened all its steps at once)
-    GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal, 1, h->g_alpha, h->cfg.g_lr);
+    GANMF_LAUNCH(open_step_kernel, dim3(1), dim3(64), 0, h->st, h->scal.get(), 1, h->g_alpha, h->cfg.g_lr);
     HIP_TRY(hipGetLastError());
   }
   const bool reg = h->cfg.g_reg != 0.f;

@@ -1,4 +1,4 @@
-// support.inc -- profile scopes, allocation, reference-variable views of the folded tensors
+// support.inc -- profile scopes, tensor allocation, reference-variable views of the folded tensors
 // (a fragment of libganmf_hip.so's single translation unit: included by ganmf_hip.hip, in its order)
 
 struct Scope {
@@ -25,30 +25,18 @@ struct Scope {
   }
 };
 
-int dalloc(float** p, size_t elems) {
-  HIP_TRY(hipMalloc((void**)p, std::max<size_t>(elems, 4) * sizeof(float)));
-  HIP_TRY(hipMemset(*p, 0, std::max<size_t>(elems, 4) * sizeof(float)));
-  HIP_TRY(hipDeviceSynchronize());  // the handle's stream does not synchronise with the null stream
-  return 0;
-}
-
 int alloc_tensor(Tensor& t, int rows, int cols, bool grad_separate, int world, int ld = 0) {
   t.rows = rows; t.cols = cols; t.ld = ld ? ld : round_up(cols + 1, LD_ALIGN);
   // data-parallel runs reduce-scatter the gradient, update one slice per rank and all-gather the parameter: every
   // buffer holds world equal slices (the tail past padded() is zero and stays zero: Adam's fixed point)
   const size_t w = (size_t)std::max(world, 1);
   t.cap = ((t.padded() + w - 1) / w + 63) / 64 * 64 * w;
-  TRY(dalloc(&t.p, t.cap));
-  TRY(dalloc(&t.m, t.cap));
-  TRY(dalloc(&t.v, t.cap));
-  TRY(dalloc(&t.best, t.cap));
-  if (grad_separate) TRY(dalloc(&t.g, t.cap));
+  TRY(t.p.alloc(t.cap, true));
+  TRY(t.m.alloc(t.cap, true));
+  TRY(t.v.alloc(t.cap, true));
+  TRY(t.best.alloc(t.cap, true));
+  if (grad_separate) { TRY(t.g_own.alloc(t.cap, true)); t.g = t.g_own; }
   return 0;
-}
-
-void free_tensor(Tensor& t, bool grad_separate) {
-  hipFree(t.p); hipFree(t.m); hipFree(t.v); hipFree(t.best);
-  if (grad_separate) hipFree(t.g);
 }
 
 // GANMF_MODEL_ITEMSIM holds the weighted URM and an item similarity matrix, no tensor at all: the entries that read or write factors,
@@ -77,16 +65,6 @@ int model_ready(ganmf_handle* h, const char* who, int model, bool need_urm) {
   if (!(cfgan ? h->cf.ready : h->ca.ready))
     return fail(-1, "%s: ganmf_%s_init has not been called on this handle", who, cfgan ? "cfgan" : "caae");
   if (need_urm && !h->has_urm) return fail(-1, "%s: ganmf_set_urm_csr has not been called", who);
-  return 0;
-}
-
-// room for n step losses in a model's device buffer
-int grow_losses(ganmf_handle* h, float*& buf, size_t& cap, size_t n) {
-  if (n <= cap) return 0;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  hipFree(buf); buf = nullptr; cap = 0;
-  TRY(dalloc(&buf, n));
-  cap = n;
   return 0;
 }
 

@@ -774,6 +774,10 @@ int ganmf_gemm_f32_ex(int device, const float* A, const float* B, float* C, int6
 uint32_t ganmf_crc32c(uint32_t crc, const void* data, uint64_t n);
 
 int ganmf_device_count(void);
+/* Bytes of device memory the library holds in this process, over all handles and all devices: what every allocation asked for (at
+ * least 16 bytes each), added when it is made and subtracted when it is freed.  Pinned host staging is not counted.  After the last
+ * ganmf_destroy it is back at its value before the first ganmf_create (tests/test_gpu_device_memory.py). */
+int64_t ganmf_live_device_bytes(void);
 int ganmf_abi_version(void);
 const char* ganmf_last_error(void);
 

@@ -112,11 +112,14 @@ def test_engine_create_destroy_does_not_leak():
             eng.recommend(np.arange(300), 5)
             eng.snapshot_best()
             eng.close()
+    from ganmf_amd import _lib as L
+    live0 = L.load_library().ganmf_live_device_bytes()      # the library's own count of what it holds: exact, where the pool's is not
     cycle(40)                                  # warm allocator / RCCL / HIP module state: what earlier tests of the same
     free0 = free_bytes()                       # process left in the runtime's pools settles here, a leak keeps growing
     cycle(40)
     free1 = free_bytes()
     assert free0 - free1 < 8 << 20, "device memory shrank by %.1f MiB over 40 engine lifetimes" % ((free0 - free1) / 2 ** 20)
+    assert L.load_library().ganmf_live_device_bytes() == live0
 
 
 @pytest.mark.parametrize("seed", range(8))
